@@ -12,10 +12,23 @@ timed step's match graph (incl. the pairs at every launch boundary) against the 
 for bit; `ba.parity` = the device's solve against the oracle's (1e-5 relative).
 
   python bench.py --gpus 1 --steps 3 --warmup 1
+  python bench.py --gpus 1 --steps 3 --warmup 1 --full
+  python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs results/outputs
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Output: rank 0 prints one JSON line per sub-line as it finishes ({"line": "<name>", ...}: the other BASELINE.json
+A plain run does only what the headline needs: it builds the S200 descriptors, warms up, times exactly --steps steps
+and prints the headline line (metric, value, unit, higher_is_better, dtype, ms_per_step, the roofline of those steps).
+Everything else — the parity gates against the CPU oracle, the CPU baselines, the BA legs and the sub-lines below —
+runs only with --full; --lines, --ba-solves and --cpu-pairs select among them there.
+
+--dump-outputs DIR writes, after the timed steps, the match graph the LAST timed step left on the device (rank 0's shard
+at N > 1) as DIR/<name>.npy in float32 / float64: pairs (the frame pair of each row), counts (mutual matches per pair),
+offsets (CSR start of each pair's rows in edges, one more row than pairs), edges (query row, train row). If that exceeds
+64 MB, a fixed seeded sample of the pairs is written instead; pair_index always says which rows of the job they are.
+The inputs depend only on the arguments, so two builds can be compared output for output.
+
+Output (--full): rank 0 prints one JSON line per sub-line as it finishes ({"line": "<name>", ...}: the other BASELINE.json
 configurations and the real descriptor shapes, each with its own roofline against the peak of the arithmetic it runs
 on, SURVEY.md §8(d) "Other configs as inputs"; {"line": "ba", ...} is the full bundle-adjustment record) and, LAST,
 the headline line of the contract — kept short (headline + roofline + cpu_baseline + a compact `ba` + one
@@ -66,16 +79,33 @@ def parse():
     ap.add_argument("--kpts", type=int, default=2000)
     ap.add_argument("--dim", type=int, default=256)
     ap.add_argument("--landmarks", type=int, default=50_000)
-    ap.add_argument("--cpu-pairs", type=int, default=-1, help="pairs in the CPU-baseline sample (-1 = 400 per core, 0 = skip)")
-    ap.add_argument("--ba-solves", type=int, default=50, help="timed RefineBA solves of the S200 window per option set (0 = skip BA)")
-    ap.add_argument("--lines", default="auto", help="comma list of sub-lines (see the module docstring), 'all', 'none', or "
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: parity gates, CPU baselines, BA legs, sub-lines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's match graph as DIR/<name>.npy (see the module docstring)")
+    ap.add_argument("--cpu-pairs", type=int, default=None,
+                    help="--full: pairs in the CPU-baseline sample (-1 = 400 per core, the default; 0 = skip)")
+    ap.add_argument("--ba-solves", type=int, default=None,
+                    help="--full: timed RefineBA solves of the S200 window per option set (default 50, 0 = skip BA)")
+    ap.add_argument("--lines", default="auto", help="--full: comma list of sub-lines (see the module docstring), 'all', 'none', or "
                                                     "'auto' = all at N=1, c5_kitti at N>1")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse N > 1 on one GPU)")
     ap.add_argument("--all-on-device", type=int, default=-1, help="rehearsal: put every rank on this device index")
     ap.add_argument("--single-process", action="store_true",
                     help="N GPUs from ONE process through the C-ABI communicator (eacham_comm_*: a context + host thread per device, "
                          "RCCL all-gather) instead of one process per GPU; needs no launcher")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.full:
+        args.cpu_pairs = -1 if args.cpu_pairs is None else args.cpu_pairs
+        args.ba_solves = 50 if args.ba_solves is None else args.ba_solves
+    else:
+        asked = [name for name, on in (("--lines " + args.lines, args.lines not in ("auto", "none", "")),
+                                       (f"--ba-solves {args.ba_solves}", args.ba_solves not in (None, 0)),
+                                       (f"--cpu-pairs {args.cpu_pairs}", args.cpu_pairs not in (None, 0))) if on]
+        if asked:
+            ap.error(f"{', '.join(asked)} asks for what only --full runs")
+        args.cpu_pairs, args.ba_solves, args.lines = 0, 0, "none"
+    return args
 
 
 SOURCE_GROUPS = {"match": ("matcher.hip", "matcher_f32.hip", "context.hip", "context.hpp"),
@@ -149,7 +179,7 @@ def host_cores() -> int:
 class Dist:
     """rank/world + the torch handles every leg needs."""
 
-    def __init__(self, args):
+    def __init__(self, args, one_rank_group: bool = True):
         import torch
         import torch.distributed as dist
         self.torch, self.dist = torch, dist
@@ -172,7 +202,7 @@ class Dist:
                 dist.init_process_group("nccl", device_id=self.dev)
             else:
                 dist.init_process_group(args.backend)
-        elif args.backend == "nccl":
+        elif args.backend == "nccl" and one_rank_group:
             # N = 1: a one-rank RCCL group, so that the device-tensor all-gather of the shard path and its stream
             # join execute on every single-GPU run too (the c5_kitti line gathers through it)
             try:
@@ -207,6 +237,46 @@ class Dist:
         if self.world > 1:
             self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM)
         return float(t.item())
+
+
+def frame_descriptors(scene, n_kpts: int, dim: int):
+    """synth.make_frame_descriptors over all frames, contiguous chunks of frames on a thread pool: a frame's rows depend only
+    on (seed, frame), so the matrices are the same as from one call."""
+    from concurrent.futures import ThreadPoolExecutor
+    from eacham_amd import synth
+    n = scene["T_true"].shape[0]
+    k = max(1, min(16, host_cores(), n))
+    chunks = [range(n * i // k, n * (i + 1) // k) for i in range(k)]
+    with ThreadPoolExecutor(k) as ex:
+        parts = list(ex.map(lambda fr: synth.make_frame_descriptors(scene, n_kpts, dim, frames=fr)[0], chunks))
+    return [d for p in parts for d in p]
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname: str, pairs, counts, offsets, q, t):
+    """--dump-outputs: one match graph (CSR over `pairs`, as eacham_match_all_pairs_dev / eacham_comm_match_fetch return
+    it) as DIR/<name>.npy. Indices are below 2^24 and exact in float32; offsets are float64. Over DUMP_LIMIT_BYTES a fixed
+    seeded sample of the pairs is kept, with offsets rebuilt over the sample."""
+    pairs = np.asarray(pairs).reshape(-1, 2)
+    counts = np.asarray(counts[:len(pairs)], dtype=np.int64)
+    offsets = np.asarray(offsets[:len(pairs) + 1], dtype=np.int64)
+    idx = np.arange(len(pairs), dtype=np.int64)
+    per_pair = 2 * 4 + 4 + 8 + 8      # pairs, counts, offsets, pair_index
+    size = len(idx) * per_pair + int(counts.sum()) * 2 * 4
+    if size > DUMP_LIMIT_BYTES:
+        keep = int(len(idx) * DUMP_LIMIT_BYTES / size * 0.9)
+        idx = np.sort(np.random.default_rng(0).choice(len(idx), keep, replace=False))
+    c = counts[idx]
+    starts = offsets[idx]
+    new_off = np.concatenate([[0], np.cumsum(c)])
+    rows = np.repeat(starts - new_off[:-1], c) + np.arange(int(new_off[-1]), dtype=np.int64)
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in (("pairs", pairs[idx].astype(np.float32)), ("counts", c.astype(np.float32)),
+                    ("offsets", new_off.astype(np.float64)), ("pair_index", idx.astype(np.float64)),
+                    ("edges", np.stack([np.asarray(q)[rows], np.asarray(t)[rows]], axis=1).astype(np.float32))):
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def run_matching(D: Dist, descs, kind: str, steps: int, warmup: int, gather_at_one: bool = False):
@@ -624,6 +694,8 @@ def main_single_process(args):
         c.sync()
     elapsed = time.perf_counter() - t0
     counts, offsets, q, t = comm.match_fetch()   # outside the timed region: the host copy of device 0's graph
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, pairs, counts, offsets, q, t)
     n = np.array([d.shape[0] for d in descs], dtype=np.float64)
     ops = 2.0 * args.dim * float(np.mean(n)) ** 2 * len(pairs) * args.steps
     achieved = ops / elapsed / 1e12
@@ -711,23 +783,27 @@ def main():
     # parent that holds contexts of its own, every one of the child's microsecond launches pays for two processes sharing the
     # device (284-298 frames/s inside the bench against 320 alone). Its line is emitted at its place further down.
     early_loop = sfm_loop_line() if "c3_sfm_loop" in lines and env_rank == 0 else None
-    D = Dist(args)
+    D = Dist(args, one_rank_group=args.full)
     from eacham_amd import HipContext, synth, ba
 
     # ---- headline: S200 matching, identical inputs on every rank ----------------------------
     scene = synth.make_scene(args.frames, args.landmarks, 10)
-    descs, _ = synth.make_frame_descriptors(scene, args.kpts, args.dim)
+    descs = frame_descriptors(scene, args.kpts, args.dim)
     head, r = matching_line(D, descs, "i8", args.dim, args.steps, args.warmup,
                             f"S200 matching: {args.frames} frames x {args.kpts} kpts x {args.dim}-D, "
                             f"{len(synth.all_pairs(args.frames))} unordered pairs (both directions + mutual check)",
-                            sweep_kernel(args.dim), parity_pairs=0 if (D.world == 1 and args.cpu_pairs != 0) else 48)
+                            sweep_kernel(args.dim),
+                            parity_pairs=0 if (not args.full or (D.world == 1 and args.cpu_pairs != 0)) else 48)
+    if args.dump_outputs and D.rank == 0:
+        g = r["graph"]
+        dump_outputs(args.dump_outputs, g["pairs"], g["counts"], g["offsets"], g["edges"][:, 0], g["edges"][:, 1])
     if args.kpts == 2000 and args.dim == 256:
         head["roofline"]["traffic"], head["roofline"]["traffic_source"] = measured_traffic("eacham::" + sweep_kernel(256))
     else:
         head["roofline"]["traffic_source"] = "not the profiled workload"
 
     sub = {}
-    ctx = HipContext(D.local)  # BA legs
+    ctx = HipContext(D.local) if args.full else None  # BA legs
     ba_out = None
     if args.ba_solves > 0:
         ba_out = bench_ba(D, ctx, scene, args.ba_solves, ba.OptimizerConfig.refine_ba(), "S200 RefineBA")
@@ -883,7 +959,8 @@ def main():
                         if "pairs_checked" in v["parity"] else v["parity"]
                 out["lines"][name] = c
         print(json.dumps(out), flush=True)
-    ctx.close()
+    if ctx is not None:
+        ctx.close()
     if D.world > 1:
         D.dist.barrier()
     if D.has_group:

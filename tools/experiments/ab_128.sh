@@ -8,5 +8,5 @@ for rep in 1 2; do
 done
 for lib in "$@"; do
   echo -n "$lib lines: "
-  EACHAM_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --steps 3 --warmup 1 --cpu-pairs 0 --ba-solves 0 --lines c5_kitti,c5_kitti_long 2>&1 | grep -oE '"line": "[a-z0-9_]+"|"value": [0-9.]+' | head -6 | tr '\n' ' '; echo
+  EACHAM_HIP_LIB=$PWD/$lib timeout -k 10 300 python bench.py --full --steps 3 --warmup 1 --cpu-pairs 0 --ba-solves 0 --lines c5_kitti,c5_kitti_long 2>&1 | grep -oE '"line": "[a-z0-9_]+"|"value": [0-9.]+' | head -6 | tr '\n' ' '; echo
 done

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """usage: tools/pmc_sq_json.py [tiles] [round] [prefix] [kernel] [suffix] [dim]
 Builds profiles/<round>_pmc_sq_<kernel>.json (kernel defaults to match_sweep_kernel) from the three SQ counter passes of tools/pmc.sh
-(gpurun_out/<prefix>_a, _b, _c; defaults r01, sq): mean per dispatch of the LARGEST-grid launch of that kernel + the
+(results/<prefix>_a, _b, _c, or EACHAM_OUT_DIR; defaults r01, sq): mean per dispatch of the LARGEST-grid launch of that kernel + the
 derived fractions quoted in DESIGN.md (formulas in the `derived_from` field)."""
 import collections, csv, glob, json, os, sys
 
@@ -13,7 +13,7 @@ kernel = sys.argv[4] if len(sys.argv) > 4 else "match_sweep_kernel"
 suffix = sys.argv[5] if len(sys.argv) > 5 else ""      # e.g. _d128: profiles/<round>_pmc_sq_<kernel>_d128.json
 dim = sys.argv[6] if len(sys.argv) > 6 else "256"
 for d in (prefix + "_a", prefix + "_b", prefix + "_c"):
-    for fn in glob.glob(os.path.join(root, "gpurun_out", d, "**", "*counter_collection.csv"), recursive=True):
+    for fn in glob.glob(os.path.join(root, os.environ.get("EACHAM_OUT_DIR", "results"), d, "**", "*counter_collection.csv"), recursive=True):
         with open(fn) as f:
             for row in csv.DictReader(f):
                 if kernel in row["Kernel_Name"]:

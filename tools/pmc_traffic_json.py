@@ -11,11 +11,11 @@ sys.path.insert(0, root)
 import bench  # noqa: E402
 
 out = collections.defaultdict(dict)
-tag = sys.argv[1] if len(sys.argv) > 1 else "r03a"          # gpurun_out/<tag>_fetch, <tag>_write (tools/prof.sh <tag>)
+tag = sys.argv[1] if len(sys.argv) > 1 else "r03a"          # results/<tag>_fetch, <tag>_write (tools/prof.sh <tag>)
 rnd = sys.argv[2] if len(sys.argv) > 2 else "r03"           # profiles/<rnd>_pmc_*.json
 for counter, d in (("FETCH_SIZE", tag + "_fetch"), ("WRITE_SIZE", tag + "_write")):
     acc = collections.defaultdict(list)
-    for fn in glob.glob(os.path.join(root, "gpurun_out", d, "**", "*counter_collection.csv"), recursive=True):
+    for fn in glob.glob(os.path.join(root, os.environ.get("EACHAM_OUT_DIR", "results"), d, "**", "*counter_collection.csv"), recursive=True):
         with open(fn) as f:
             for row in csv.DictReader(f):
                 if row["Counter_Name"] != counter:
