@@ -4207,11 +4207,13 @@ __global__ __launch_bounds__(TPB) void prep_grp_records(const GrpCounters* __res
 
 // One workgroup per group: ba_groups.hpp step 3-4. The group's entries are generated as 64-bit words
 //   block key << 31 | emission index << 18 | r1 << 9 | r2        (rows <= 511, <= 8192 entries)
+// (the 9-bit row fields bound a group to 511 rows, the host form's multiple of 4 to 508: the largest EACHAM_BA_GROUP_ROWS
+// that context.hip accepts, so that both forms of the construction build groups at every size the switch can select)
 // and sorted by a bitonic network in LDS (the word order IS (block key, emission index)); runs, slices, lanes, segments and
 // chunks follow from scans over the sorted list. PASS 0 only counts ({chunks, uint4-rows, segments} -> counts[g]); PASS 1, given
 // the scanned bases, writes the chunk table, the entries, the lane records and the (key, where) list of the segments.
 constexpr int GE_THREADS = 256;
-constexpr int GE_MAXE = 8192;   // most entries of a group the kernel is ever asked for (rows <= 512)
+constexpr int GE_MAXE = 8192;   // most entries of a group the kernel is ever asked for (rows <= 508)
 template <class T>
 __device__ __forceinline__ T ge_block_scan(T v, T* lds, T* total) {  // exclusive scan over the workgroup, GE_THREADS values
     const int tid = threadIdx.x;

@@ -1,6 +1,7 @@
 """GPU: the HIP bundle adjuster (through the C-ABI) against the CPU oracle.
 Tolerance (north_star): camera poses / landmark positions within 1e-5 relative; the tests ask for
 far tighter agreement wherever fp64 + identical algorithm allow it."""
+import dataclasses
 import os
 
 import numpy as np
@@ -17,6 +18,14 @@ POSE_POINT_RTOL = 1e-5  # north_star tolerance
 
 def rel(a, b):
     return np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300)
+
+
+def backward_error(S, g, x):
+    """Normwise backward error of x as a solution of S x = g, ||S x - g|| / (||S|| ||x|| + ||g||) in infinity norms, evaluated
+    in extended precision: it judges a step by the system alone, whatever algorithm produced it."""
+    S, g, x = (np.asarray(v, dtype=np.longdouble) for v in (S, g, x))
+    r = S @ x - g
+    return float(np.abs(r).max() / (np.abs(S).sum(axis=1).max() * np.abs(x).max() + np.abs(g).max()))
 
 
 def scene_arrays(seed=3, n_cams=6, n_lm=200, k=4, outliers=True, **kw):
@@ -69,26 +78,39 @@ def test_block_boundaries_of_the_reduced_system(hip_ctx, n_cams):
     assert np.isclose(err, erro, rtol=1e-12) and np.isclose(lin, lino, rtol=1e-9)
 
 
-@pytest.mark.parametrize("n_cams,n_lm,k", [(12, 200, 6), (31, 400, 6), (60, 600, 8), (130, 2600, 6)])
+@pytest.mark.parametrize("n_cams,n_lm,k", [(12, 200, 6), (31, 400, 6), (60, 600, 8), (130, 2600, 6), (260, 3900, 6), (400, 6000, 6)])
 def test_every_elimination_order_solves_the_same_system(hip_ctx, n_cams, n_lm, k):
     """The reduced camera system is factorised in tiles of the symbolic pattern, level by level of the elimination
     tree of the chosen camera ordering (ba_plan.hpp; the reference gets COLAMD + multifrontal Cholesky through
     SetCeresDefaults, BundleAdjuster.cpp:182-190). The caller's order (one path: the dense chain), reverse
     Cuthill-McKee, nested dissection (independent subtrees in one launch, several sources per target) and the cost
-    model's choice must all return the step of the oracle; S itself comes back in the caller's order whatever the layout."""
+    model's choice must all return the step of the oracle; S itself comes back in the caller's order whatever the layout.
+    The step's backward error against the oracle's damped system is held to that of the oracle's own step. The helix
+    scenes of 260 and 400 cameras (n = 1565 / 2405) are the deep trees at mid size: a path of 25 / 38 panels in the
+    caller's order, many sources per target tile."""
     sc, A = scene_arrays(seed=30 + n_cams, n_cams=n_cams, n_lm=n_lm, k=k)
     ref = O.ba_step(A, 1e-3, 0)
     assert ref[-1]
-    steps = {}
+    bw_ref = backward_error(ref[0], ref[1], ref[2])
+    steps, plans = {}, {}
     for name in ("natural", "rcm", "nd", "auto"):
         A.ordering = name
+        pb = ba.PreparedBA(hip_ctx, A)
+        plans[name] = pb.plan_info()
+        pb.close()
         S, g, dc, dl, err, lin = ba.debug_step(hip_ctx, A, 1e-3)
+        bw = backward_error(ref[0], ref[1], dc)
+        print(name, plans[name]["panels"], "panels", plans[name]["levels"], "levels: delta_c", rel(dc, ref[2]), "backward error", bw, "oracle", bw_ref)
         assert rel(S, ref[0]) < 1e-11 and rel(g, ref[1]) < 1e-11, name
         assert rel(dc, ref[2]) < 1e-8 and rel(dl, ref[3]) < 1e-8, name
         assert np.isclose(err, ref[4], rtol=1e-12) and np.isclose(lin, ref[5], rtol=1e-9), name
+        assert bw <= 10 * bw_ref, (name, bw, bw_ref)
         steps[name] = dc
     for name in ("rcm", "nd", "auto"):
         assert rel(steps[name], steps["natural"]) < 1e-9
+    if n_cams >= 260:   # the regime is reached: a long path in the caller's order, a lower tree under nested dissection
+        assert plans["natural"]["levels"] == plans["natural"]["panels"] >= 25
+        assert plans["nd"]["levels"] < plans["natural"]["levels"]
 
 
 def test_unknown_ordering_is_rejected(hip_ctx):
@@ -375,13 +397,26 @@ def test_metric_scene_s200(hip_ctx):
     assert np.abs(out.K - sc["K"]).max() < 5.0
 
 
-def test_config4_size_properties(hip_ctx):
-    """BASELINE configs[3]: 500 cams / 100k landmarks / 1M observations (n = 3005: 47 panels in the caller's order,
-    ~59 under nested dissection with an elimination tree 16 levels high). Too large for the oracle to finish in seconds, so
-    the check is by size-independent properties: determinism, a large error drop, recovery of the truth, and
-    agreement of LM and DogLeg on the optimum."""
+@pytest.fixture(scope="module")
+def config4():
+    """BASELINE configs[3]: 500 cams / 100k landmarks / 1M observations, built once for the tests that use it."""
     sc = synth.make_scene(500, 100_000, 10, seed=4)
-    A = ba.BaArrays.from_scene(sc)
+    return sc, ba.BaArrays.from_scene(sc)
+
+
+# The plan of config 4 under each ordering, (panels, levels of the elimination tree): the caller's order is one path of 47
+# panels; nested dissection (also the cost model's choice) lays the same columns out in 71 panels on 19 levels.
+# tests/test_ba_plan.py executes the same analysis on the CPU.
+CONFIG4_PLANS = {"natural": (47, 47), "nd": (71, 19), "auto": (71, 19)}
+
+
+def test_config4_size_properties(hip_ctx, config4):
+    """BASELINE configs[3]: 500 cams / 100k landmarks / 1M observations (n = 3005: 47 panels in the caller's order,
+    71 under nested dissection with an elimination tree 19 levels high). The oracle's dense solve of this size takes a few
+    seconds: the LM and the DogLeg run are held to it with the bars of the smaller scenes (same decisions, trace within
+    1e-6, poses and points within the north-star tolerance and 1e-7), and to the size-independent properties: determinism, a large
+    error drop, recovery of the truth, and agreement of LM and DogLeg on the optimum."""
+    sc, A = config4
     solver = ba.PreparedBA(hip_ctx, A)
     out = solver.run(ba.OptimizerConfig.refine_ba())
     again = solver.run(ba.OptimizerConfig.refine_ba())
@@ -395,6 +430,44 @@ def test_config4_size_properties(hip_ctx):
     assert np.median(err) < 0.35 * np.median(err0), (np.median(err), np.median(err0), err.max())
     assert np.isclose(dl.final_error, out.final_error, rtol=1e-4)
     assert (np.diff(out.trace[out.trace[:, 3] == 1, 1]) < 0).all()   # accepted steps only ever lower the error
+    for got, cfg in ((out, ba.OptimizerConfig.refine_ba()), (dl, ba.OptimizerConfig("DogLeg", 100, 1e-5, 10.0, False))):
+        ref = O.ba_solve(A, cfg)
+        assert got.status == ref.status == 0
+        assert (got.outer_iterations, got.inner_iterations) == (ref.outer_iterations, ref.inner_iterations), cfg.method
+        print(cfg.method, got.outer_iterations, "iterations, relative differences: poses", rel(got.cam_T_wc, ref.cam_T_wc), "points",
+              rel(got.points, ref.points), "trace", (np.abs(got.trace[:, :2] - ref.trace[:, :2]) / np.abs(ref.trace[:, :2])).max())
+        assert np.array_equal(got.trace[:, 3:], ref.trace[:, 3:]) and np.allclose(got.trace[:, :2], ref.trace[:, :2], rtol=1e-6), cfg.method
+        assert rel(got.cam_T_wc, ref.cam_T_wc) < POSE_POINT_RTOL and rel(got.points, ref.points) < POSE_POINT_RTOL, cfg.method
+        assert rel(got.cam_T_wc, ref.cam_T_wc) < 1e-7 and rel(got.points, ref.points) < 1e-7, cfg.method   # (1e-14 measured)
+
+
+def test_config4_damped_step_under_every_ordering(hip_ctx, config4):
+    """One damped step of config 4 in the regime the level schedule is built for (dozens of panels, a tree 19 to 47 levels
+    high, many sources per target tile): the caller's order, nested dissection and the cost model's choice against the
+    oracle's dense Cholesky, with the bars of the small sizes, and the backward error of the camera step against the system
+    the oracle factorises held to that of the oracle's own step."""
+    sc, A = config4
+    So, go, dco, dlo, erro, lino, ok = O.ba_step(A, 1e-3, 0)
+    assert ok
+    bw_ref = backward_error(So, go, dco)
+    steps = {}
+    for name, (panels, levels) in CONFIG4_PLANS.items():
+        B = dataclasses.replace(A, ordering=name)
+        pb = ba.PreparedBA(hip_ctx, B)
+        info = pb.plan_info()
+        pb.close()
+        S, g, dc, dl, err, lin = ba.debug_step(hip_ctx, B, 1e-3)
+        bw = backward_error(So, go, dc)
+        print(name, info["panels"], "panels", info["levels"], "levels: S", rel(S, So), "g", rel(g, go), "delta_c", rel(dc, dco),
+              "delta_l", rel(dl, dlo), "backward error", bw, "oracle", bw_ref)
+        assert info["panels"] >= 47 and (info["panels"], info["levels"]) == (panels, levels), (name, info)
+        assert rel(S, So) < 1e-11 and rel(g, go) < 1e-11, name
+        assert rel(dc, dco) < 1e-8 and rel(dl, dlo) < 1e-8, name
+        assert np.isclose(err, erro, rtol=1e-12) and np.isclose(lin, lino, rtol=1e-9), name
+        assert bw <= 10 * bw_ref, (name, bw, bw_ref)
+        steps[name] = dc
+    for name in ("nd", "auto"):
+        assert rel(steps[name], steps["natural"]) < 1e-9
 
 
 def _ctx_with(**env):

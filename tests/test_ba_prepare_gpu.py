@@ -14,24 +14,34 @@ from eacham_amd import HipContext, ba, synth
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module", params=["groups", "pairs"])
-def ctx_pair(request):
-    """(host-built, device-built) contexts under one form of the Schur stage: the landmark groups of csrc/ba_groups.hpp (what the
-    device form builds by default) or the pair lists of rounds 1-4 (what the host form builds by default) — either form of the
-    construction must reproduce either structure."""
-    old = {k: os.environ.get(k) for k in ("EACHAM_BA_PREPARE", "EACHAM_BA_SCHUR")}
+def _ctx_pair_with(**env):
+    """(host-built, device-built) contexts created under the given switches (they are read once, at eacham_ctx_create)."""
+    old = {k: os.environ.get(k) for k in ["EACHAM_BA_PREPARE", *env]}
+    host = None
     try:
-        os.environ["EACHAM_BA_SCHUR"] = request.param
+        os.environ.update(env)
         os.environ["EACHAM_BA_PREPARE"] = "host"
         host = HipContext(0)
         os.environ["EACHAM_BA_PREPARE"] = "device"
-        dev = HipContext(0)
+        return host, HipContext(0)
+    except BaseException:
+        if host is not None:
+            host.close()
+        raise
     finally:
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+@pytest.fixture(scope="module", params=["groups", "pairs"])
+def ctx_pair(request):
+    """(host-built, device-built) contexts under one form of the Schur stage: the landmark groups of csrc/ba_groups.hpp (what the
+    device form builds by default) or the pair lists of rounds 1-4 (what the host form builds by default) — either form of the
+    construction must reproduce either structure."""
+    host, dev = _ctx_pair_with(EACHAM_BA_SCHUR=request.param)
     yield host, dev
     host.close()
     dev.close()
@@ -130,3 +140,59 @@ def test_metric_scene_is_bit_identical_and_reports_its_preparation(ctx_pair):
         pb.close()
     assert infos[0]["panels"] == infos[1]["panels"] and infos[0]["tiles"] == infos[1]["tiles"] and infos[0]["levels"] == infos[1]["levels"]
     print("prepare_us host", infos[0]["prepare_us"], "device", infos[1]["prepare_us"])
+
+
+@pytest.fixture(scope="module")
+def config4_arrays():
+    """BASELINE configs[3]: 500 cameras / 100 000 landmarks / 1 000 000 observations, built once for both forms of the Schur stage."""
+    return ba.BaArrays.from_scene(synth.make_scene(500, 100_000, 10, seed=4))
+
+
+def test_config4_is_bit_identical_and_plans_alike(ctx_pair, config4_arrays):
+    """Config 4, five times the observations of S200: a whole run and the plan of the reduced camera system agree between the forms."""
+    host, dev = ctx_pair
+    out = _same_run(ctx_pair, config4_arrays)
+    assert out.status == 0 and out.outer_iterations >= 2
+    infos = []
+    for ctx in (host, dev):
+        pb = ba.PreparedBA(ctx, config4_arrays)
+        infos.append(pb.plan_info())
+        pb.close()
+    for key in ("panels", "tiles", "levels", "ordering", "tile_updates"):
+        assert infos[0][key] == infos[1][key], (key, infos)
+    print("config 4 prepare_us host", infos[0]["prepare_us"], "device", infos[1]["prepare_us"])
+
+
+def _group_rows(pb):
+    """Rows per landmark group of a prepared problem; 0 when the pair lists serve."""
+    n_groups = len(pb.structure("g_groups")) // 8
+    return len(pb.structure("g_rowinfo")) // (2 * n_groups) if n_groups else 0
+
+
+@pytest.mark.parametrize("rows", [16, 64, 252, 480, 508, 512])
+def test_every_accepted_group_size_builds_the_same_structure(rows):
+    """EACHAM_BA_GROUP_ROWS selects 16 to 508 rows per group (multiples of 4); 508 is the most the device form can pack
+    (9-bit row fields of its entry keys, ba.hip prep_grp_entries). At every accepted size both forms of the construction
+    choose the same structure and build it bit for bit alike; 512 is outside the range and ignored by both (the size the
+    problem selects, 128 rows here, serves). At 16 rows a landmark of 8 observations (9 rows > 16 / 2) fits no group:
+    both forms then take the pair lists."""
+    pair = _ctx_pair_with(EACHAM_BA_SCHUR="groups", EACHAM_BA_GROUP_ROWS=str(rows))
+    try:
+        scenes = [_arrays(19, 12, 300, 6, shuffle=True, pixel_noise=1.5), _arrays(137, 130, 2600, 6, shuffle=True, pixel_noise=1.5)]
+        if rows == 16:
+            scenes.append(_arrays(67, 60, 600, 8, shuffle=True, pixel_noise=1.5))
+        for i, A in enumerate(scenes):
+            want = 0 if i == 2 else rows if rows <= 508 else 128
+            got = []
+            for ctx in pair:
+                pb = ba.PreparedBA(ctx, A)
+                got.append(_group_rows(pb))
+                pb.close()
+            assert got == [want, want], (rows, i, got)
+            _same_step(pair, A)
+        if rows in (16, 512):
+            for A in scenes:
+                _same_run(pair, A)
+    finally:
+        for ctx in pair:
+            ctx.close()
