@@ -3563,32 +3563,126 @@ static int ba_alloc_work_b(eacham_ctx* ctx, eacham_ba_handle* h) {
     if (!h->planning) EACHAM_HIP_TRY(ctx, hipMemsetAsync(D.flags, 0, (N_STATUS + plan.npan) * sizeof(int), ctx->stream));  // (final_sums leaves them cleared)
     return EACHAM_OK;
 }
-#undef TRY
 
-// The structure built by host loops (the round-1..3 form): what a local window of a few thousand observations still uses —
-// a dozen dependent launches and three read-backs cost more than these loops on a problem that small — and the reference
-// the device-built structure is held against bit for bit (EACHAM_BA_PREPARE=host|device forces either form).
-static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_ba_handle** out, bool allow_dense) {
-    if (!P || P->n_cams < 0 || P->n_points < 0 || P->n_obs < 0) return ctx->fail(EACHAM_ERR_INVALID, "bad BA problem");
-    const int nc = P->n_cams, nl = P->n_points, no = P->n_obs;
-    if (no > 0 && (!P->obs_cam || !P->obs_point || !P->obs_uv)) return ctx->fail(EACHAM_ERR_INVALID, "null observation arrays");
-    if ((nc > 0 && (!P->cam_T_wc || !P->cam_fixed)) || (nl > 0 && (!P->points || !P->point_observers)))
-        return ctx->fail(EACHAM_ERR_INVALID, "null camera/point arrays");
-    for (int o = 0; o < no; ++o)
-        if (P->obs_cam[o] >= (uint32_t)nc || P->obs_point[o] >= (uint32_t)nl)
-            return ctx->fail(EACHAM_ERR_INVALID, "observation %d references a camera/point out of range", o);
-    eacham_ba_handle* h = new eacham_ba_handle();
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto us_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
+// ---- what the two constructions of the structure (host loops below, sorts and scans on the device further down) share ----
+
+// Limits of the 32-bit indices. The camera blocks (c <= c') of the pair lists are numbered in an int; the device form also forms
+// `nblk + TPB` for its grids and a thread's block number `blockIdx.x * TPB + threadIdx.x` in an int, hence its smaller bound (half
+// the range: far more headroom than those sums need, kept as it was). The pair entries are indexed by int in both forms.
+static constexpr long long BA_MAX_CAM_BLOCKS_HOST = 0x7fffffffLL;
+static constexpr long long BA_MAX_CAM_BLOCKS_DEVICE = 0x3fffffffLL;
+static constexpr long long BA_MAX_PAIR_ENTRIES = 0x7fffffffLL;
+
+static double us_since(std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); }
+
+// Owns the handle while eacham_ba_prepare builds it; release() hands it to the caller. Leaving with an error instead joins the
+// plan thread of the device form, drains the context's two streams (copies out of the caller's arrays or out of host vectors of
+// the construction may still be in flight), returns the arenas to the pool and deletes the handle. The success path pays none of it.
+struct BaPrepareGuard {
+    eacham_ctx* ctx;
+    eacham_ba_handle* h;
+    std::thread plan_thread;
+    BaPrepareGuard(eacham_ctx* c, eacham_ba_handle* handle) : ctx(c), h(handle) {}
+    ~BaPrepareGuard() {
+        if (plan_thread.joinable()) plan_thread.join();
+        if (!h) return;
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipStreamSynchronize(ctx->stream2);
+        if (h->block >= 0) ctx->ba_pool[h->block].busy = false;
+        if (h->block2 >= 0) ctx->ba_pool[h->block2].busy = false;
+        delete h;
+    }
+    eacham_ba_handle* release() { return std::exchange(h, nullptr); }
+};
+
+// The dimensions and the launch shapes of the per-landmark kernels.
+static void ba_handle_init(const eacham_ctx* ctx, const eacham_ba_problem* P, eacham_ba_handle* h) {
     BaDev& D = h->D;
+    const int nl = P->n_points;
     memset(&D, 0, sizeof(D));
-    D.nc = nc; D.nl = nl; D.no = no; D.n = 6 * nc + 5;
+    D.nc = P->n_cams; D.nl = nl; D.no = P->n_obs; D.n = 6 * P->n_cams + 5;
     D.nz = make_noise();
     D.n_lm_blocks = std::max(1, (nl + TPB - 1) / TPB);
     D.lpl = ctx->ba_lpl_lin > 0 ? ctx->ba_lpl_lin : (nl <= 8192 ? 8 : 2);  // (S200: 45.7 / 40.4 / 41.0 / 45.6 us for 1 / 2 / 4 / 8, tools/ba_lpl_lin.sh)
     D.n_ll_blocks = std::max(1, (int)(((long long)nl * D.lpl + TPB - 1) / TPB));
     D.lpl_step = ctx->ba_lpl_step > 0 ? ctx->ba_lpl_step : (nl <= 8192 ? 8 : 2);
     D.n_step_blocks = std::max(1, (int)(((long long)nl * D.lpl_step + TPB - 1) / TPB));
+}
+
+// The elimination ordering asked for: the problem's, or the context's (EACHAM_BA_ORDERING) where the problem leaves it open.
+static int ba_ordering_hint(eacham_ctx* ctx, const eacham_ba_problem* P, int* hint) {
+    *hint = P->ordering;
+    if (*hint == EACHAM_BA_ORDER_AUTO && ctx->ba_ordering != EACHAM_BA_ORDER_AUTO) *hint = ctx->ba_ordering;
+    if (*hint < EACHAM_BA_ORDER_AUTO || *hint > EACHAM_BA_ORDER_ND) return ctx->fail(EACHAM_ERR_INVALID, "unknown BA ordering %d", *hint);
+    return EACHAM_OK;
+}
+
+// Which form of the Schur stage a context WANTS from a construction form. Host: the landmark groups only when
+// EACHAM_BA_SCHUR=groups, the dense window form only when =dense, else the pair lists. Device: the groups unless =pairs.
+// Whether the wanted form is feasible for the problem is decided where its data is; the pair lists serve when it is not.
+enum BaSchurForm { BA_SCHUR_PAIRS, BA_SCHUR_GROUPS, BA_SCHUR_DENSE };
+static BaSchurForm ba_schur_wanted(const eacham_ctx* ctx, bool device) {
+    if (device) return ctx->ba_schur_mode != 2 ? BA_SCHUR_GROUPS : BA_SCHUR_PAIRS;
+    return ctx->ba_schur_mode == 3 ? BA_SCHUR_DENSE : ctx->ba_schur_mode == 1 ? BA_SCHUR_GROUPS : BA_SCHUR_PAIRS;
+}
+
+// The plan's scalars -> BaDev; its (column, source) pairs in the layout the kernels read (the tables go up with ba_upload_plan).
+static std::vector<int2> ba_plan_to_dev(eacham_ba_handle* h) {
+    const BaPlan& plan = h->plan;
+    BaDev& D = h->D;
+    D.sp_npan = plan.npan; D.sp_ntiles = plan.ntiles; D.sp_posK = plan.posK; D.sp_rhs_row = plan.rhs_row;
+    D.sp_n_pad = (int)plan.pad_cols.size();
+    std::vector<int2> bs_ent(plan.bs_ent.size());
+    for (size_t e = 0; e < bs_ent.size(); ++e) bs_ent[e] = make_int2(plan.bs_ent[e].first, plan.bs_ent[e].second);
+    return bs_ent;
+}
+
+// algorithmic HBM bytes; used by the benchmark's roofline line
+static void ba_traffic_bytes(eacham_ba_handle* h, long long n_entries) {
+    const size_t nc = h->D.nc, nl = h->D.nl, no = h->D.no, n = h->D.n;
+    h->bytes_linearize = no * (24 + 144) + no * 24 + nl * (24 + LMLIN * 8) + nc * (96 + CAMLIN * 8);
+    h->bytes_try = no * (144 * 2 + 144 + 144) + (size_t)n_entries * 8 + nl * (LMLIN * 8 * 3 + 48) + no * 24 + n * n * 8;
+}
+
+// Every device array of a problem is carved out of an arena of the context's pool: `layout`, an allocation sequence of
+// dev_alloc / dev_upload calls, runs twice, first to add up the sizes, then, with an arena of that size in pool slot `*slot`,
+// to hand out the pointers and issue the uploads. `staged` is asked between the passes which byte range [lo, hi) of the arena's
+// uploads is to be sent as ONE copy of a host image (h->stage, which lives as long as the handle) instead of one copy per array;
+// lo == hi: none. An arena that served another problem holds its bytes: nothing may rely on fresh memory being zero (S is cleared
+// by every tryLambda, Lm and the flags by ba_alloc_work_b).
+template <class Layout, class Staged>
+static int ba_arena_layout(eacham_ctx* ctx, eacham_ba_handle* h, int* slot, Layout layout, Staged staged) {
+    h->planning = true;
+    h->arena = nullptr;
+    h->arena_off = 0;
+    TRY(layout());
+    TRY(ba_block_acquire(ctx, h->arena_off, slot));
+    h->arena = (char*)ctx->ba_pool[*slot].dev;
+    h->planning = false;
+    h->arena_off = 0;
+    const std::pair<size_t, size_t> image = staged();
+    h->stage_base = image.first;
+    h->stage.assign(image.second - image.first, 0);
+    int rc = layout();
+    if (!rc && !h->stage.empty() && hipMemcpyAsync(h->arena + h->stage_base, h->stage.data(), h->stage.size(), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = ctx->fail(EACHAM_ERR_HIP, "BA upload failed");
+    if (rc) (void)hipStreamSynchronize(ctx->stream);  // (uploads out of the caller's host vectors may be in flight: those die before the guard acts)
+    return rc;
+}
+
+// The structure built by host loops (the round-1..3 form): what a local window of a few thousand observations still uses —
+// a dozen dependent launches and three read-backs cost more than these loops on a problem that small — and the reference
+// the device-built structure is held against bit for bit (EACHAM_BA_PREPARE=host|device forces either form).
+static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, int hint, eacham_ba_handle** out) {
+    const int nc = P->n_cams, nl = P->n_points, no = P->n_obs;
+    for (int o = 0; o < no; ++o)
+        if (P->obs_cam[o] >= (uint32_t)nc || P->obs_point[o] >= (uint32_t)nl)
+            return ctx->fail(EACHAM_ERR_INVALID, "observation %d references a camera/point out of range", o);
+    eacham_ba_handle* h = new eacham_ba_handle();
+    BaPrepareGuard guard(ctx, h);
+    const auto t_begin = std::chrono::steady_clock::now();
+    BaDev& D = h->D;
+    ba_handle_init(ctx, P, h);
 
     // ---- structure: observations grouped by landmark (stable), then by camera ----
     std::vector<int> lm_ptr(nl + 1, 0);
@@ -3634,20 +3728,18 @@ static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_b
     }
     // ---- the landmark-major structure of the Schur stage (ba_groups.hpp); the pair lists below only when it does not apply ----
     // ---- the dense form for a local window (ba_window.hpp): its structure is these rows and nothing else ----
+    const BaSchurForm wanted = ba_schur_wanted(ctx, false);
     BaWin WN;
-    const bool use_dense = allow_dense && build_window(nc, nl, lm_ptr.data(), obs_cam.data(), obs_uv.data(), WN, ctx->ba_window_rows);
+    const bool use_dense = wanted == BA_SCHUR_DENSE && build_window(nc, nl, lm_ptr.data(), obs_cam.data(), obs_uv.data(), WN, ctx->ba_window_rows);
     BaGroups& GR = h->groups;
-    const bool use_groups = !use_dense && ctx->ba_schur_mode == 1 && build_groups(nc, nl, lm_ptr.data(), obs_cam.data(), obs_uv.data(), GR, ctx->ba_group_rows);
+    const bool use_groups = wanted == BA_SCHUR_GROUPS && build_groups(nc, nl, lm_ptr.data(), obs_cam.data(), obs_uv.data(), GR, ctx->ba_group_rows);
     if (!use_groups) GR = BaGroups();
     // ---- camera-pair lists of the Schur complement: block (c <= c') -> (o, o') pairs, landmark order ----
     // (two passes over every observation pair of every landmark — count, then fill: this loop is most of the host time of
     // preparing a local window, hence the flat 32-bit index arithmetic; entries are written as Et positions directly)
     const bool use_pairs = !use_groups && !use_dense;
     const long long nblk_all = use_pairs ? (long long)nc * (nc + 1) / 2 : 0;
-    if (nblk_all > 0x7fffffffLL) {
-        delete h;
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "too many cameras (%d) for the camera-block index", nc);
-    }
+    if (nblk_all > BA_MAX_CAM_BLOCKS_HOST) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "too many cameras (%d) for the camera-block index", nc);
     std::vector<int> rowoff(std::max(nc, 1));  // block (c, c2 >= c) has index rowoff[c] + c2
     for (int c = 0; c < nc; ++c) rowoff[c] = (int)((long long)c * nc - (long long)c * (c - 1) / 2 - c);
     auto bid = [&](int c, int c2) { return rowoff[c] + c2; };
@@ -3672,10 +3764,7 @@ static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_b
     std::vector<long long> bstart((size_t)nblk_all + 1, 0);
     for (long long b = 0; b < nblk_all; ++b) bstart[b + 1] = bstart[b] + bcount[b + 1];
     const long long n_entries = bstart[nblk_all];
-    if (n_entries > 0x7fffffffLL) {
-        delete h;
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "Schur pair list too large (%lld entries)", n_entries);
-    }
+    if (n_entries > BA_MAX_PAIR_ENTRIES) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "Schur pair list too large (%lld entries)", n_entries);
     std::vector<int2> entries((size_t)n_entries);
     if (use_pairs) {
         std::vector<int> pos((size_t)nblk_all);
@@ -3729,26 +3818,15 @@ static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_b
         if (use_dense)  // every block is kept: the cameras of a window all share landmarks with the current frame
             for (int c = 0; c < nc; ++c)
                 for (int c2 = c + 1; c2 < nc; ++c2) cam_edges.emplace_back(c, c2);
-        int hint = P->ordering;
-        if (hint == EACHAM_BA_ORDER_AUTO && ctx->ba_ordering != EACHAM_BA_ORDER_AUTO) hint = ctx->ba_ordering;
-        if (hint < EACHAM_BA_ORDER_AUTO || hint > EACHAM_BA_ORDER_ND) {
-            delete h;
-            return ctx->fail(EACHAM_ERR_INVALID, "unknown BA ordering %d", hint);
-        }
         try {
             build_ba_plan(nc, cam_edges, hint, h->plan);
         } catch (...) {  // (no exception crosses the C-ABI)
-            delete h;
             return ctx->fail(EACHAM_ERR_HIP, "BA preparation: the analysis of the reduced system ran out of memory or threads");
         }
     }
     h->prep_us[1] = us_since(t_plan);
     const auto t_upload = std::chrono::steady_clock::now();
-    const BaPlan& plan = h->plan;
-    D.sp_npan = plan.npan; D.sp_ntiles = plan.ntiles; D.sp_posK = plan.posK; D.sp_rhs_row = plan.rhs_row;
-    D.sp_n_pad = (int)plan.pad_cols.size();
-    std::vector<int2> bs_ent(plan.bs_ent.size());
-    for (size_t e = 0; e < bs_ent.size(); ++e) bs_ent[e] = make_int2(plan.bs_ent[e].first, plan.bs_ent[e].second);
+    const std::vector<int2> bs_ent = ba_plan_to_dev(h);
 
     // ---- values ----
     std::vector<double> pose(12 * (size_t)nc), lmprior(2 * (size_t)nl), K5(5);
@@ -3762,12 +3840,6 @@ static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_b
     std::vector<double> pts(P->points, P->points + 3 * (size_t)nl);
     std::vector<int> fixed(P->cam_fixed, P->cam_fixed + nc);
 
-    // Every device array of the problem is carved out of one arena: the allocation sequence below runs twice, first
-    // to add up the sizes, then — with an arena of that size taken from the context's pool — to hand out the
-    // pointers and issue the uploads. An arena that served another problem holds its bytes: nothing here may rely on
-    // fresh memory being zero (S is cleared by every tryLambda, Lm and the flags below).
-    int rc = EACHAM_OK;
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
     auto layout = [&]() -> int {
         const double *c_pose0, *c_pt0, *c_K0, *c_lmprior, *c_uv;
         TRY(dev_upload(ctx, h, &c_pose0, pose));
@@ -3794,49 +3866,21 @@ static int ba_prepare_host(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_b
         TRY(dev_upload(ctx, h, &D.blocks, blocks));
         TRY(ba_upload_groups(ctx, h, GR));
         TRY(ba_upload_window(ctx, h, WN));
-        TRY(ba_upload_plan(ctx, h, plan, bs_ent));
+        TRY(ba_upload_plan(ctx, h, h->plan, bs_ent));
         TRY(ba_alloc_work_a(ctx, h));
         TRY(ba_alloc_work_b(ctx, h));
         return EACHAM_OK;
     };
-#undef TRY
-    h->planning = true;
-    h->arena_off = 0;
-    rc = layout();
-    if (!rc) rc = ba_block_acquire(ctx, h->arena_off, &h->block);
-    if (!rc) {
-        h->arena = (char*)ctx->ba_pool[h->block].dev;
-        h->planning = false;
-        h->arena_off = 0;
-        // a local window uploads ~20 arrays of a few KB: one copy of their image instead of 20 (each is a staged,
-        // synchronous-looking call from pageable memory); large problems keep the per-array copies (no second host copy)
-        if (h->upload_end <= ((size_t)4 << 20)) h->stage.assign(h->upload_end, 0);
-        rc = layout();
-        if (!rc && !h->stage.empty())
-            rc = hipMemcpyAsync(h->arena, h->stage.data(), h->stage.size(), hipMemcpyHostToDevice, ctx->stream) == hipSuccess
-                     ? EACHAM_OK : ctx->fail(EACHAM_ERR_HIP, "BA upload failed");
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);  // (uploads from the host vectors may be in flight)
-        if (h->block >= 0) ctx->ba_pool[h->block].busy = false;
-        delete h;
-        return rc;
-    }
+    // a local window uploads ~20 arrays of a few KB: one copy of their image instead of 20 (each is a staged,
+    // synchronous-looking call from pageable memory); large problems keep the per-array copies (no second host copy)
+    TRY(ba_arena_layout(ctx, h, &h->block, layout, [&] { return std::make_pair((size_t)0, h->upload_end <= ((size_t)4 << 20) ? h->upload_end : (size_t)0); }));
     // The per-array copies of a large problem read host vectors that die here: wait for them. A small problem was sent as
     // ONE image out of h->stage, which lives as long as the handle: nothing to wait for (the first kernel of the solve
     // queues behind the copy on the same stream) — 30-40 us of every local-window call.
-    hipError_t e = h->stage.empty() ? hipStreamSynchronize(ctx->stream) : hipSuccess;
-    if (e != hipSuccess) {
-        ctx->ba_pool[h->block].busy = false;
-        delete h;
-        return ctx->fail(EACHAM_ERR_HIP, "BA upload failed: %s", hipGetErrorString(e));
-    }
+    if (h->stage.empty()) EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     h->prep_us[2] = us_since(t_upload);
-    // algorithmic HBM bytes; used by the benchmark's roofline line
-    h->bytes_linearize = (size_t)no * (24 + 144) + (size_t)no * 24 + (size_t)nl * (24 + LMLIN * 8) + (size_t)nc * (96 + CAMLIN * 8);
-    h->bytes_try = (size_t)no * (144 * 2 + 144 + 144) + (size_t)n_entries * 8 + (size_t)nl * (LMLIN * 8 * 3 + 48) +
-                   (size_t)no * 24 + (size_t)D.n * D.n * 8;
-    *out = h;
+    ba_traffic_bytes(h, n_entries);
+    *out = guard.release();
     return EACHAM_OK;
 }
 
@@ -4721,81 +4765,38 @@ static int ba_scratch(eacham_ctx* ctx, int which, size_t bytes, void** out) {
     return EACHAM_OK;
 }
 
-static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_ba_handle** out) {
-    const int nc = P->n_cams, nl = P->n_points, no = P->n_obs;
-    const long long nblk_all = (long long)nc * (nc + 1) / 2;
-    if (nblk_all > 0x3fffffffLL) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "too many cameras (%d) for the camera-block index", nc);
-    const int nblk = (int)nblk_all;
-    eacham_ba_handle* h = new eacham_ba_handle();
-    const auto t_begin = std::chrono::steady_clock::now();
-    auto us_since = [](std::chrono::steady_clock::time_point t0) { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(); };
-    BaDev& D = h->D;
-    memset(&D, 0, sizeof(D));
-    D.nc = nc; D.nl = nl; D.no = no; D.n = 6 * nc + 5;
-    D.nz = make_noise();
-    D.n_lm_blocks = std::max(1, (nl + TPB - 1) / TPB);
-    D.lpl = ctx->ba_lpl_lin > 0 ? ctx->ba_lpl_lin : (nl <= 8192 ? 8 : 2);
-    D.n_ll_blocks = std::max(1, (int)(((long long)nl * D.lpl + TPB - 1) / TPB));
-    D.lpl_step = ctx->ba_lpl_step > 0 ? ctx->ba_lpl_step : (nl <= 8192 ? 8 : 2);
-    D.n_step_blocks = std::max(1, (int)(((long long)nl * D.lpl_step + TPB - 1) / TPB));
-    hipStream_t st = ctx->stream;
-    int rc = EACHAM_OK;
-    std::thread plan_thread;
-    std::vector<unsigned char> adj_h;
-    auto fail = [&](int code) {
-        if (plan_thread.joinable()) plan_thread.join();
-        (void)hipStreamSynchronize(st);
-        (void)hipStreamSynchronize(ctx->stream2);
-        if (h->block >= 0) ctx->ba_pool[h->block].busy = false;
-        if (h->block2 >= 0) ctx->ba_pool[h->block2].busy = false;
-        delete h;
-        return code;
-    };
-#define TRY(x) do { rc = (x); if (rc) return rc; } while (0)
-    const int max_cam_chunks = no / TPB + nc + 1;
-    // ---- arena A: everything whose size follows from (nc, nl, no) ----
+// Scratch buffer `which` of the context, sized and carved by `carve` (a Bump sequence; a null base gives the size only).
+template <class Carve>
+static int ba_scratch_carve(eacham_ctx* ctx, int which, Carve carve) {
+    void* base = nullptr;
+    TRY(ba_scratch(ctx, which, carve(nullptr), &base));
+    (void)carve(base);
+    return EACHAM_OK;
+}
+
+static int bits_for(long long n) { int b = 1; while ((1ll << b) < n) ++b; return b; }
+
+// The device construction, cut into stages at its read-backs: what one stage leaves for a later one lives here, everything else
+// is local to its stage. ba_prepare_device runs the stages in the order they are written in; every launch, copy, event and
+// synchronisation keeps its place on its stream (the overlap of the device work with the plan thread and with the uploads on the
+// second stream is what the call's time rests on: docs/HISTORY.md).
+struct BaDevicePrep {
+    eacham_ctx* const ctx;
+    const eacham_ba_problem* const P;
+    eacham_ba_handle* const h;
+    BaDev& D;
+    const int hint, nc, nl, no, nblk;
+    const hipStream_t st;
+    const unsigned gobs;      // blocks of a launch over the observations
+    const bool try_groups;    // the landmark groups are wanted (ba_schur_wanted) and the problem can be keyed for them
+    const std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
+    // arena A: the structure arrays (BaDev holds most of them as pointers to const)
     int *lm_ptr = nullptr, *cam_ptr = nullptr, *cam_obs = nullptr, *cam_lm = nullptr, *cam_chunk_ptr = nullptr, *obs_pos = nullptr, *pos_cam = nullptr, *fixed = nullptr;
     int2* cam_chunks = nullptr;
     double *lmprior = nullptr, *obs_uv = nullptr, *cam_uv = nullptr;
     unsigned *obs_cam = nullptr, *obs_lm = nullptr;
-    auto layout_a = [&]() -> int {
-        TRY(dev_alloc(ctx, h, &D.pose0, 12 * (size_t)nc));
-        TRY(dev_alloc(ctx, h, &D.pt0, 3 * (size_t)nl));
-        TRY(dev_alloc(ctx, h, &D.K0, 8));
-        TRY(dev_alloc(ctx, h, &lmprior, 2 * (size_t)nl));
-        TRY(dev_alloc(ctx, h, &obs_uv, 2 * (size_t)no));
-        TRY(dev_alloc(ctx, h, &fixed, (size_t)nc));
-        TRY(dev_alloc(ctx, h, &lm_ptr, (size_t)nl + 1));
-        TRY(dev_alloc(ctx, h, &cam_ptr, (size_t)nc + 1));
-        TRY(dev_alloc(ctx, h, &cam_obs, (size_t)no));
-        TRY(dev_alloc(ctx, h, &cam_lm, (size_t)no));
-        TRY(dev_alloc(ctx, h, &cam_chunks, (size_t)max_cam_chunks));
-        TRY(dev_alloc(ctx, h, &cam_chunk_ptr, (size_t)nc + 1));
-        TRY(dev_alloc(ctx, h, &obs_pos, (size_t)no));
-        TRY(dev_alloc(ctx, h, &pos_cam, (size_t)no));
-        TRY(dev_alloc(ctx, h, &cam_uv, 2 * (size_t)no));
-        TRY(dev_alloc(ctx, h, &obs_cam, (size_t)no));
-        TRY(dev_alloc(ctx, h, &obs_lm, (size_t)no));
-        TRY(ba_alloc_work_a(ctx, h));
-        return EACHAM_OK;
-    };
-    h->planning = true;
-    h->arena_off = 0;
-    rc = layout_a();
-    if (!rc) rc = ba_block_acquire(ctx, h->arena_off, &h->block);
-    if (rc) return fail(rc);
-    h->arena = (char*)ctx->ba_pool[h->block].dev;
-    h->planning = false;
-    h->arena_off = 0;
-    rc = layout_a();
-    if (rc) return fail(rc);
-    D.lmprior = lmprior; D.obs_uv = obs_uv; D.fixed = fixed; D.lm_ptr = lm_ptr; D.cam_ptr = cam_ptr; D.cam_obs = cam_obs; D.cam_lm = cam_lm;
-    D.cam_chunks = cam_chunks; D.cam_chunk_ptr = cam_chunk_ptr; D.obs_pos = obs_pos; D.pos_cam = pos_cam; D.cam_uv = cam_uv;
-    D.obs_cam = obs_cam; D.obs_lm = obs_lm;
-    h->pose_init = D.pose0; h->pt_init = D.pt0; h->K_init = D.K0;
-    // ---- scratch 0: the caller's arrays as they are + the temporaries of the observation sorts ----
-    void* s0 = nullptr;
-    uint32_t *raw_cam, *raw_pt, *kA, *kB, *vA, *vB, *kC, *vC;
+    // scratch 0: the caller's arrays as they are + the temporaries of the observation sorts
+    uint32_t *raw_cam, *raw_pt, *kA, *kB, *vA, *vB, *kC, *vC, *lm_order = nullptr;
     double *raw_uv, *raw_T;
     int *raw_obs, *sort_ws, *nchunk, *nchunk_ws;
     long long *pcnt, *poff, *pws;
@@ -4804,160 +4805,214 @@ static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, eacham
     uint32_t *gkA, *gkB, *gvA, *gvB;
     int *gcost, *growsS, *gcostS, *gcstart, *grstart, *gscan_ws, *gsort_ws;
     GrpCounters* gcnt;
-    const bool try_groups = ctx->ba_schur_mode != 2 && nc < 65535 && no > 0;
-    auto carve0 = [&](void* base) {
-        Bump b(base);
-        raw_pt = b.take<uint32_t>(no); raw_cam = b.take<uint32_t>(no); raw_uv = b.take<double>(2 * (size_t)no);
-        raw_T = b.take<double>(16 * (size_t)nc); raw_obs = b.take<int>(nl);
-        kA = b.take<uint32_t>(no); kB = b.take<uint32_t>(no); vA = b.take<uint32_t>(no); vB = b.take<uint32_t>(no);
-        kC = b.take<uint32_t>(no); vC = b.take<uint32_t>(no);   // the camera sort's second pair (the landmark order stays: the late uv gather reads it)
-        sort_ws = b.take<int>(prim::radix_ws_ints(no));
-        nchunk = b.take<int>(nc); nchunk_ws = b.take<int>(prim::scan_ws_elems(nc));
-        pcnt = b.take<long long>(no); poff = b.take<long long>((size_t)no + 1); pws = b.take<long long>(prim::scan_ws_elems(no));
-        cnt = b.take<PrepCounters>(1);
-        adj_dev = b.take<unsigned char>((size_t)nc * nc);
-        // the landmark order of the group structure (ba_groups.hpp): keys, ranks, per-rank rows / costs and their prefixes
-        gkA = b.take<uint32_t>(nl); gkB = b.take<uint32_t>(nl); gvA = b.take<uint32_t>(nl); gvB = b.take<uint32_t>(nl);
-        gcost = b.take<int>(nl); growsS = b.take<int>(nl); gcostS = b.take<int>(nl);
-        gcstart = b.take<int>((size_t)nl + 1); grstart = b.take<int>((size_t)nl + 1); gscan_ws = b.take<int>(prim::scan_ws_elems(nl));
-        gsort_ws = b.take<int>(prim::radix_ws_ints(nl));
-        gcnt = b.take<GrpCounters>(1);
-        return b.off;
-    };
-    rc = ba_scratch(ctx, 0, carve0(nullptr), &s0);
-    if (rc) return fail(rc);
-    (void)carve0(s0);
-#define HIPQ(x) do { if ((x) != hipSuccess) return fail(ctx->fail(EACHAM_ERR_HIP, "%s failed (%s:%d)", #x, __FILE__, __LINE__)); } while (0)
-    HIPQ(hipMemsetAsync(cnt, 0, sizeof(PrepCounters), st));
-    // the landmark ids first: their sort runs while the host stages the rest
-    HIPQ(hipMemcpyAsync(raw_pt, P->obs_point, sizeof(uint32_t) * (size_t)no, hipMemcpyHostToDevice, st));
-    HIPQ(hipMemcpyAsync(raw_cam, P->obs_cam, sizeof(uint32_t) * (size_t)no, hipMemcpyHostToDevice, st));
-    const unsigned gobs = (unsigned)((no + TPB - 1) / TPB);
-    auto bits_for = [](long long n) { int b = 1; while ((1ll << b) < n) ++b; return b; };
-    if (no > 0) prep_keys_lm<<<gobs, TPB, 0, st>>>(no, nc, nl, raw_cam, raw_pt, kA, vA, cnt);
-    const int w_lm = prim::radix_sort_pairs<uint32_t>(st, kA, vA, kB, vB, no, bits_for(std::max(nl, 2)), sort_ws);
-    HIPQ(hipMemcpyAsync(raw_T, P->cam_T_wc, sizeof(double) * 16 * (size_t)nc, hipMemcpyHostToDevice, st));
-    HIPQ(hipMemcpyAsync(raw_obs, P->point_observers, sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, st));
-    HIPQ(hipMemcpyAsync(D.pt0, P->points, sizeof(double) * 3 * (size_t)nl, hipMemcpyHostToDevice, st));
-    HIPQ(hipMemcpyAsync(fixed, P->cam_fixed, sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, st));
-    prep_values<<<(unsigned)((nc + nl + TPB) / TPB), TPB, 0, st>>>(nc, nl, raw_T, raw_obs, D.pose0, lmprior, D.K0, P->K[0], P->K[1], P->K[2], P->K[3]);
-    uint32_t *lm_sorted = w_lm ? kB : kA, *lm_order = w_lm ? vB : vA, *ck = w_lm ? kA : kB, *cv = w_lm ? vA : vB;  // the other pair of buffers feeds the camera sort
-    if (no > 0) {
-        prep_gather_lm<<<(gobs + GATHER_CHUNKS - 1) / GATHER_CHUNKS, TPB, 0, st>>>(no, nl, nc, lm_sorted, lm_order, raw_cam, obs_cam, obs_lm, lm_ptr, ck, cv, cnt);
-    } else {
-        HIPQ(hipMemsetAsync(lm_ptr, 0, sizeof(int) * ((size_t)nl + 1), st));
-        HIPQ(hipMemsetAsync(cam_ptr, 0, sizeof(int) * ((size_t)nc + 1), st));
-    }
-    // the camera graph leaves for the host on the second stream as soon as the landmark grouping exists
-    if (nc > 0) HIPQ(hipMemsetAsync(adj_dev, 0, (size_t)nc * nc, st));
-    if (no > 0 && nc > 0) prep_cam_adjacency<<<gobs, TPB, 0, st>>>(no, nc, obs_cam, obs_lm, lm_ptr, adj_dev);
-    HIPQ(hipEventRecord(ctx->ev_join, st));
-    const int w_cam = prim::radix_sort_pairs<uint32_t>(st, ck, cv, kC, vC, no, bits_for(std::max(nc, 2)), sort_ws);
-    if (no > 0) {
-        const uint32_t *cs = w_cam ? kC : ck, *co = w_cam ? vC : cv;
-        prep_gather_cam<<<gobs, TPB, 0, st>>>(no, nc, cs, co, obs_lm, cam_obs, obs_pos, pos_cam, cam_lm, cam_ptr);
-        if (!try_groups) prep_pair_counts<<<gobs, TPB, 0, st>>>(no, obs_cam, obs_lm, lm_ptr, pcnt);
-    }
     int w_g = 0;
-    if (try_groups) {  // ba_groups.hpp steps 1-2 as far as they go without the group size: order, rows, costs, their prefixes
-        HIPQ(hipMemsetAsync(gcnt, 0, sizeof(GrpCounters), st));
-        const unsigned glm = (unsigned)((nl + TPB - 1) / TPB);
-        prep_grp_keys<<<glm, TPB, 0, st>>>(nl, lm_ptr, obs_cam, gkA, gvA, gcost, gcnt);
-        // (the key interleaves two camera ids: 2 bits_for(nc + 1) bits; landmarks without observations carry the largest key of that width)
-        const int gkey_bits = std::min(32, 2 * bits_for((long long)nc + 1));
-        w_g = prim::radix_sort_pairs<uint32_t>(st, gkA, gvA, gkB, gvB, nl, gkey_bits, gsort_ws);
-        prep_grp_sorted<<<glm, TPB, 0, st>>>(nl, w_g ? gvB : gvA, lm_ptr, gcost, growsS, gcostS);
-        prim::exclusive_scan<int>(st, gcostS, gcstart, nl, gscan_ws, &gcnt->cost_total);
-        prim::exclusive_scan<int>(st, growsS, grstart, nl, gscan_ws, &gcnt->row_total);
-        HIPQ(hipMemcpyAsync(grstart + nl, &gcnt->row_total, sizeof(int), hipMemcpyDeviceToDevice, st));
-    }
-    prep_cam_chunk_counts<<<(unsigned)((nc + TPB) / TPB), TPB, 0, st>>>(nc, cam_ptr, nchunk);
-    prim::exclusive_scan<int>(st, nchunk, cam_chunk_ptr, nc, nchunk_ws, &cnt->n_cam_chunks);
-    HIPQ(hipMemcpyAsync(cam_chunk_ptr + nc, &cnt->n_cam_chunks, sizeof(int), hipMemcpyDeviceToDevice, st));
-    prep_cam_chunk_fill<<<(unsigned)((nc + TPB) / TPB), TPB, 0, st>>>(nc, cam_ptr, cam_chunk_ptr, cam_chunks);
-    if (!try_groups) prim::exclusive_scan<long long>(st, pcnt, poff, no, pws, &cnt->n_entries);
-    // ---- the host's share, beside the device's: ordering, panels, symbolic factor, level schedule (ba_plan.hpp) ----
-    int hint = P->ordering;
-    if (hint == EACHAM_BA_ORDER_AUTO && ctx->ba_ordering != EACHAM_BA_ORDER_AUTO) hint = ctx->ba_ordering;
-    if (hint < EACHAM_BA_ORDER_AUTO || hint > EACHAM_BA_ORDER_ND) return fail(ctx->fail(EACHAM_ERR_INVALID, "unknown BA ordering %d", hint));
-    adj_h.resize((size_t)nc * nc + 1);
-    HIPQ(hipStreamWaitEvent(ctx->stream2, ctx->ev_join, 0));
-    if (nc > 0) HIPQ(hipMemcpyAsync(adj_h.data(), adj_dev, (size_t)nc * nc, hipMemcpyDeviceToHost, ctx->stream2));
-    HIPQ(hipStreamSynchronize(ctx->stream2));
-    // (no HIP call in there, and no exception may leave it: a failed allocation or thread start inside the analysis comes back as
-    // an error code of the call — std::terminate in a process that holds the GPU is not an answer)
-    bool plan_failed = false;
-    auto plan_body = [&, hint]() {
-        try {
-            const auto t_plan = std::chrono::steady_clock::now();
-            std::vector<std::pair<int, int>> cam_edges;
-            for (int c = 0; c < nc; ++c)
-                for (int c2 = c + 1; c2 < nc; ++c2)
-                    if (adj_h[(size_t)c * nc + c2]) cam_edges.emplace_back(c, c2);
-            build_ba_plan(nc, cam_edges, hint, h->plan);
-            h->prep_us[1] = us_since(t_plan);
-        } catch (...) {
-            plan_failed = true;
-        }
-    };
-    try {
-        plan_thread = std::thread(plan_body);
-    } catch (const std::system_error&) {
-        plan_body();  // no thread to be had: the analysis runs here, before the rest of the device work is queued
-    }
-    // ---- the measurements: uploaded on the second stream beside the kernels queued above, gathered behind them ----
-    if (no > 0) {
-        HIPQ(hipMemcpyAsync(raw_uv, P->obs_uv, sizeof(double) * 2 * (size_t)no, hipMemcpyHostToDevice, ctx->stream2));
-        HIPQ(hipEventRecord(ctx->ev_join, ctx->stream2));
-        HIPQ(hipStreamWaitEvent(st, ctx->ev_join, 0));
-        prep_gather_uv<<<gobs, TPB, 0, st>>>(no, lm_order, cam_obs, raw_uv, obs_uv, cam_uv);
-    }
-    // ---- read-back 1: the number of pair entries sizes the next stage ----
-    PrepCounters hc;
-    GrpCounters hg;
-    memset(&hg, 0, sizeof(hg));
-    HIPQ(hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-    if (try_groups) HIPQ(hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
-    HIPQ(hipStreamSynchronize(st));
-    if (hc.bad) return fail(ctx->fail(EACHAM_ERR_INVALID, "an observation references a camera/point out of range"));
-    // the landmark-major structure applies unless a landmark is too heavy for a group (ba_groups.hpp step 2)
-    const long long total_rows = (long long)no + hc.n_used;
-    const int R = ctx->ba_group_rows > 0 ? ctx->ba_group_rows : grp_rows_for(total_rows);
-    const bool use_groups = try_groups && total_rows <= 0x7fffffffLL && R % 4 == 0 && hg.emax <= GRP_ENT_PER_ROW * R && hg.cmax <= R / 2 && std::max(hg.cmax, 4) >= 4;
-    if (try_groups && !use_groups) {  // the pair lists of rounds 1-4 after all: their counts were not taken yet
-        prep_pair_counts<<<gobs, TPB, 0, st>>>(no, obs_cam, obs_lm, lm_ptr, pcnt);
-        prim::exclusive_scan<long long>(st, pcnt, poff, no, pws, &cnt->n_entries);
-        HIPQ(hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-        HIPQ(hipStreamSynchronize(st));
-    }
-    if (use_groups) hc.n_entries = 0;
-    if (hc.n_entries > 0x7fffffffLL) return fail(ctx->fail(EACHAM_ERR_UNSUPPORTED, "Schur pair list too large (%lld entries)", hc.n_entries));
-    const int n_entries = (int)hc.n_entries;
-    h->n_landmarks_used = hc.n_used;
-    D.n_cam_chunks = hc.n_cam_chunks;
-    // ---- scratch 1: expansion, sort by camera block, block / chunk tables (the pair lists: only when the groups do not apply) ----
-    const int max_blocks = (int)std::min<long long>(nblk, (long long)n_entries + nc);
-    const int max_chunks = n_entries / PAIR_CHUNK + max_blocks + 1;
-    void* s1 = nullptr;
-    uint32_t *ekA = nullptr, *ekB = nullptr;
+    // read-back 1 and what follows from it
+    PrepCounters hc{};
+    GrpCounters hg{};
+    int R = 0, n_entries = 0;
+    bool use_groups = false;
+    // the pair lists (scratch 1), until arena B takes them
     int2 *evA = nullptr, *evB = nullptr;
-    int *esort_ws, *bcount, *bfirst, *blast;
-    prim::I3 *bt, *bs, *bws;
     int4 *blocks_tmp = nullptr, *chunks_tmp = nullptr;
     int w_e = 0;
-    if (!use_groups) {
-        auto carve1 = [&](void* base) {
+    // the landmark groups: what the first half (scratch 2) and the second half (scratch 3) staged, until arena B takes it
+    int g_emax = 64, n_items = 0;
+    BaGroup* tg_groups = nullptr;
+    int *tg_lmid = nullptr, *tg_lmrow = nullptr;
+    int2* tg_rowinfo = nullptr;
+    double* tg_uv = nullptr;
+    prim::I3* tg_bases = nullptr;
+    BaChunk* sg_chunks = nullptr;
+    uint32_t *sg_ent = nullptr, *sg_laneinfo = nullptr;
+    int4* sg_blk = nullptr;
+    int* sg_longblk = nullptr;
+    // the plan thread's input and verdict
+    std::vector<unsigned char> adj_h;
+    bool plan_failed = false;
+    BaPrepareGuard guard;  // the LAST member: destroyed first, so that an error return joins the plan thread while what it uses exists
+
+    BaDevicePrep(eacham_ctx* c, const eacham_ba_problem* p, int ordering_hint)
+        : ctx(c), P(p), h(new eacham_ba_handle()), D(h->D), hint(ordering_hint), nc(p->n_cams), nl(p->n_points), no(p->n_obs),
+          nblk((int)((long long)nc * (nc + 1) / 2)), st(c->stream), gobs((unsigned)((no + TPB - 1) / TPB)),
+          try_groups(ba_schur_wanted(c, true) == BA_SCHUR_GROUPS && nc < 65535 && no > 0), guard(c, h) {
+        ba_handle_init(ctx, P, h);
+    }
+
+    // ---- arena A: everything whose size follows from (nc, nl, no); scratch 0 ----
+    int first_arena() {
+        const int max_cam_chunks = no / TPB + nc + 1;
+        auto layout_a = [&]() -> int {
+            TRY(dev_alloc(ctx, h, &D.pose0, 12 * (size_t)nc));
+            TRY(dev_alloc(ctx, h, &D.pt0, 3 * (size_t)nl));
+            TRY(dev_alloc(ctx, h, &D.K0, 8));
+            TRY(dev_alloc(ctx, h, &lmprior, 2 * (size_t)nl));
+            TRY(dev_alloc(ctx, h, &obs_uv, 2 * (size_t)no));
+            TRY(dev_alloc(ctx, h, &fixed, (size_t)nc));
+            TRY(dev_alloc(ctx, h, &lm_ptr, (size_t)nl + 1));
+            TRY(dev_alloc(ctx, h, &cam_ptr, (size_t)nc + 1));
+            TRY(dev_alloc(ctx, h, &cam_obs, (size_t)no));
+            TRY(dev_alloc(ctx, h, &cam_lm, (size_t)no));
+            TRY(dev_alloc(ctx, h, &cam_chunks, (size_t)max_cam_chunks));
+            TRY(dev_alloc(ctx, h, &cam_chunk_ptr, (size_t)nc + 1));
+            TRY(dev_alloc(ctx, h, &obs_pos, (size_t)no));
+            TRY(dev_alloc(ctx, h, &pos_cam, (size_t)no));
+            TRY(dev_alloc(ctx, h, &cam_uv, 2 * (size_t)no));
+            TRY(dev_alloc(ctx, h, &obs_cam, (size_t)no));
+            TRY(dev_alloc(ctx, h, &obs_lm, (size_t)no));
+            TRY(ba_alloc_work_a(ctx, h));
+            return EACHAM_OK;
+        };
+        TRY(ba_arena_layout(ctx, h, &h->block, layout_a, [] { return std::make_pair((size_t)0, (size_t)0); }));
+        D.lmprior = lmprior; D.obs_uv = obs_uv; D.fixed = fixed; D.lm_ptr = lm_ptr; D.cam_ptr = cam_ptr; D.cam_obs = cam_obs; D.cam_lm = cam_lm;
+        D.cam_chunks = cam_chunks; D.cam_chunk_ptr = cam_chunk_ptr; D.obs_pos = obs_pos; D.pos_cam = pos_cam; D.cam_uv = cam_uv;
+        D.obs_cam = obs_cam; D.obs_lm = obs_lm;
+        h->pose_init = D.pose0; h->pt_init = D.pt0; h->K_init = D.K0;
+        return ba_scratch_carve(ctx, 0, [&](void* base) {
+            Bump b(base);
+            raw_pt = b.take<uint32_t>(no); raw_cam = b.take<uint32_t>(no); raw_uv = b.take<double>(2 * (size_t)no);
+            raw_T = b.take<double>(16 * (size_t)nc); raw_obs = b.take<int>(nl);
+            kA = b.take<uint32_t>(no); kB = b.take<uint32_t>(no); vA = b.take<uint32_t>(no); vB = b.take<uint32_t>(no);
+            kC = b.take<uint32_t>(no); vC = b.take<uint32_t>(no);   // the camera sort's second pair (the landmark order stays: the late uv gather reads it)
+            sort_ws = b.take<int>(prim::radix_ws_ints(no));
+            nchunk = b.take<int>(nc); nchunk_ws = b.take<int>(prim::scan_ws_elems(nc));
+            pcnt = b.take<long long>(no); poff = b.take<long long>((size_t)no + 1); pws = b.take<long long>(prim::scan_ws_elems(no));
+            cnt = b.take<PrepCounters>(1);
+            adj_dev = b.take<unsigned char>((size_t)nc * nc);
+            // the landmark order of the group structure (ba_groups.hpp): keys, ranks, per-rank rows / costs and their prefixes
+            gkA = b.take<uint32_t>(nl); gkB = b.take<uint32_t>(nl); gvA = b.take<uint32_t>(nl); gvB = b.take<uint32_t>(nl);
+            gcost = b.take<int>(nl); growsS = b.take<int>(nl); gcostS = b.take<int>(nl);
+            gcstart = b.take<int>((size_t)nl + 1); grstart = b.take<int>((size_t)nl + 1); gscan_ws = b.take<int>(prim::scan_ws_elems(nl));
+            gsort_ws = b.take<int>(prim::radix_ws_ints(nl));
+            gcnt = b.take<GrpCounters>(1);
+            return b.off;
+        });
+    }
+
+    // ---- the uploads; observations grouped by landmark and by camera, the camera graph, the chunk table, the groups' landmark order ----
+    int structure() {
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(cnt, 0, sizeof(PrepCounters), st));
+        // the landmark ids first: their sort runs while the host stages the rest
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(raw_pt, P->obs_point, sizeof(uint32_t) * (size_t)no, hipMemcpyHostToDevice, st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(raw_cam, P->obs_cam, sizeof(uint32_t) * (size_t)no, hipMemcpyHostToDevice, st));
+        if (no > 0) prep_keys_lm<<<gobs, TPB, 0, st>>>(no, nc, nl, raw_cam, raw_pt, kA, vA, cnt);
+        const int w_lm = prim::radix_sort_pairs<uint32_t>(st, kA, vA, kB, vB, no, bits_for(std::max(nl, 2)), sort_ws);
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(raw_T, P->cam_T_wc, sizeof(double) * 16 * (size_t)nc, hipMemcpyHostToDevice, st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(raw_obs, P->point_observers, sizeof(int) * (size_t)nl, hipMemcpyHostToDevice, st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(D.pt0, P->points, sizeof(double) * 3 * (size_t)nl, hipMemcpyHostToDevice, st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fixed, P->cam_fixed, sizeof(int) * (size_t)nc, hipMemcpyHostToDevice, st));
+        prep_values<<<(unsigned)((nc + nl + TPB) / TPB), TPB, 0, st>>>(nc, nl, raw_T, raw_obs, D.pose0, lmprior, D.K0, P->K[0], P->K[1], P->K[2], P->K[3]);
+        uint32_t *lm_sorted = w_lm ? kB : kA, *ck = w_lm ? kA : kB, *cv = w_lm ? vA : vB;  // the other pair of buffers feeds the camera sort
+        lm_order = w_lm ? vB : vA;
+        if (no > 0) {
+            prep_gather_lm<<<(gobs + GATHER_CHUNKS - 1) / GATHER_CHUNKS, TPB, 0, st>>>(no, nl, nc, lm_sorted, lm_order, raw_cam, obs_cam, obs_lm, lm_ptr, ck, cv, cnt);
+        } else {
+            EACHAM_HIP_TRY(ctx, hipMemsetAsync(lm_ptr, 0, sizeof(int) * ((size_t)nl + 1), st));
+            EACHAM_HIP_TRY(ctx, hipMemsetAsync(cam_ptr, 0, sizeof(int) * ((size_t)nc + 1), st));
+        }
+        // the camera graph leaves for the host on the second stream as soon as the landmark grouping exists
+        if (nc > 0) EACHAM_HIP_TRY(ctx, hipMemsetAsync(adj_dev, 0, (size_t)nc * nc, st));
+        if (no > 0 && nc > 0) prep_cam_adjacency<<<gobs, TPB, 0, st>>>(no, nc, obs_cam, obs_lm, lm_ptr, adj_dev);
+        EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st));
+        const int w_cam = prim::radix_sort_pairs<uint32_t>(st, ck, cv, kC, vC, no, bits_for(std::max(nc, 2)), sort_ws);
+        if (no > 0) {
+            const uint32_t *cs = w_cam ? kC : ck, *co = w_cam ? vC : cv;
+            prep_gather_cam<<<gobs, TPB, 0, st>>>(no, nc, cs, co, obs_lm, cam_obs, obs_pos, pos_cam, cam_lm, cam_ptr);
+            if (!try_groups) prep_pair_counts<<<gobs, TPB, 0, st>>>(no, obs_cam, obs_lm, lm_ptr, pcnt);
+        }
+        if (try_groups) {  // ba_groups.hpp steps 1-2 as far as they go without the group size: order, rows, costs, their prefixes
+            EACHAM_HIP_TRY(ctx, hipMemsetAsync(gcnt, 0, sizeof(GrpCounters), st));
+            const unsigned glm = (unsigned)((nl + TPB - 1) / TPB);
+            prep_grp_keys<<<glm, TPB, 0, st>>>(nl, lm_ptr, obs_cam, gkA, gvA, gcost, gcnt);
+            // (the key interleaves two camera ids: 2 bits_for(nc + 1) bits; landmarks without observations carry the largest key of that width)
+            const int gkey_bits = std::min(32, 2 * bits_for((long long)nc + 1));
+            w_g = prim::radix_sort_pairs<uint32_t>(st, gkA, gvA, gkB, gvB, nl, gkey_bits, gsort_ws);
+            prep_grp_sorted<<<glm, TPB, 0, st>>>(nl, w_g ? gvB : gvA, lm_ptr, gcost, growsS, gcostS);
+            prim::exclusive_scan<int>(st, gcostS, gcstart, nl, gscan_ws, &gcnt->cost_total);
+            prim::exclusive_scan<int>(st, growsS, grstart, nl, gscan_ws, &gcnt->row_total);
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(grstart + nl, &gcnt->row_total, sizeof(int), hipMemcpyDeviceToDevice, st));
+        }
+        prep_cam_chunk_counts<<<(unsigned)((nc + TPB) / TPB), TPB, 0, st>>>(nc, cam_ptr, nchunk);
+        prim::exclusive_scan<int>(st, nchunk, cam_chunk_ptr, nc, nchunk_ws, &cnt->n_cam_chunks);
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(cam_chunk_ptr + nc, &cnt->n_cam_chunks, sizeof(int), hipMemcpyDeviceToDevice, st));
+        prep_cam_chunk_fill<<<(unsigned)((nc + TPB) / TPB), TPB, 0, st>>>(nc, cam_ptr, cam_chunk_ptr, cam_chunks);
+        if (!try_groups) prim::exclusive_scan<long long>(st, pcnt, poff, no, pws, &cnt->n_entries);
+        return EACHAM_OK;
+    }
+
+    // ---- the host's share, beside the device's: ordering, panels, symbolic factor, level schedule (ba_plan.hpp) on a thread of its
+    // own; the measurements; read-back 1 and the choice between the landmark groups and the pair lists ----
+    int plan_and_counts() {
+        adj_h.resize((size_t)nc * nc + 1);
+        EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_join, 0));
+        if (nc > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(adj_h.data(), adj_dev, (size_t)nc * nc, hipMemcpyDeviceToHost, ctx->stream2));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream2));
+        // (no HIP call in there, and no exception may leave it: a failed allocation or thread start inside the analysis comes back as
+        // an error code of the call — std::terminate in a process that holds the GPU is not an answer)
+        auto plan_body = [this]() {
+            try {
+                const auto t_plan = std::chrono::steady_clock::now();
+                std::vector<std::pair<int, int>> cam_edges;
+                for (int c = 0; c < nc; ++c)
+                    for (int c2 = c + 1; c2 < nc; ++c2)
+                        if (adj_h[(size_t)c * nc + c2]) cam_edges.emplace_back(c, c2);
+                build_ba_plan(nc, cam_edges, hint, h->plan);
+                h->prep_us[1] = us_since(t_plan);
+            } catch (...) {
+                plan_failed = true;
+            }
+        };
+        try {
+            guard.plan_thread = std::thread(plan_body);
+        } catch (const std::system_error&) {
+            plan_body();  // no thread to be had: the analysis runs here, before the rest of the device work is queued
+        }
+        // ---- the measurements: uploaded on the second stream beside the kernels queued above, gathered behind them ----
+        if (no > 0) {
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(raw_uv, P->obs_uv, sizeof(double) * 2 * (size_t)no, hipMemcpyHostToDevice, ctx->stream2));
+            EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->stream2));
+            EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st, ctx->ev_join, 0));
+            prep_gather_uv<<<gobs, TPB, 0, st>>>(no, lm_order, cam_obs, raw_uv, obs_uv, cam_uv);
+        }
+        // ---- read-back 1: the number of pair entries sizes the next stage ----
+        memset(&hg, 0, sizeof(hg));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+        if (try_groups) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (hc.bad) return ctx->fail(EACHAM_ERR_INVALID, "an observation references a camera/point out of range");
+        // the landmark-major structure applies unless a landmark is too heavy for a group (ba_groups.hpp step 2)
+        const long long total_rows = (long long)no + hc.n_used;
+        R = ctx->ba_group_rows > 0 ? ctx->ba_group_rows : grp_rows_for(total_rows);
+        use_groups = try_groups && total_rows <= 0x7fffffffLL && R % 4 == 0 && hg.emax <= GRP_ENT_PER_ROW * R && hg.cmax <= R / 2 && std::max(hg.cmax, 4) >= 4;
+        if (try_groups && !use_groups) {  // the pair lists of rounds 1-4 after all: their counts were not taken yet
+            prep_pair_counts<<<gobs, TPB, 0, st>>>(no, obs_cam, obs_lm, lm_ptr, pcnt);
+            prim::exclusive_scan<long long>(st, pcnt, poff, no, pws, &cnt->n_entries);
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+            EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+        }
+        if (use_groups) hc.n_entries = 0;
+        if (hc.n_entries > BA_MAX_PAIR_ENTRIES) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "Schur pair list too large (%lld entries)", hc.n_entries);
+        n_entries = (int)hc.n_entries;
+        h->n_landmarks_used = hc.n_used;
+        D.n_cam_chunks = hc.n_cam_chunks;
+        return EACHAM_OK;
+    }
+
+    // ---- scratch 1: expansion, sort by camera block, block / chunk tables (the pair lists: only when the groups do not apply) ----
+    int pair_lists() {
+        const int max_blocks = (int)std::min<long long>(nblk, (long long)n_entries + nc);
+        const int max_chunks = n_entries / PAIR_CHUNK + max_blocks + 1;
+        uint32_t *ekA, *ekB;
+        int *esort_ws, *bcount, *bfirst, *blast;
+        prim::I3 *bt, *bs, *bws;
+        TRY(ba_scratch_carve(ctx, 1, [&](void* base) {
             Bump b(base);
             ekA = b.take<uint32_t>(n_entries); ekB = b.take<uint32_t>(n_entries); evA = b.take<int2>(n_entries); evB = b.take<int2>(n_entries);
             esort_ws = b.take<int>(prim::radix_ws_ints(n_entries));
             bcount = b.take<int>(nblk); bfirst = b.take<int>(2 * (size_t)nblk); blast = bfirst ? bfirst + nblk : nullptr; bt = b.take<prim::I3>(nblk); bs = b.take<prim::I3>(nblk); bws = b.take<prim::I3>(prim::scan_ws_elems(nblk));
             blocks_tmp = b.take<int4>(max_blocks); chunks_tmp = b.take<int4>(max_chunks);
             return b.off;
-        };
-        rc = ba_scratch(ctx, 1, carve1(nullptr), &s1);
-        if (rc) return fail(rc);
-        (void)carve1(s1);
-        HIPQ(hipMemsetAsync(bfirst, 0, sizeof(int) * 2 * (size_t)std::max(nblk, 1), st));
+        }));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(bfirst, 0, sizeof(int) * 2 * (size_t)std::max(nblk, 1), st));
         if (no > 0) prep_expand<<<gobs, TPB, 0, st>>>(no, nc, obs_cam, obs_lm, lm_ptr, obs_pos, poff, ekA, evA);
         w_e = prim::radix_sort_pairs<int2>(st, ekA, evA, ekB, evB, n_entries, bits_for(std::max(nblk, 2)), esort_ws);
         if (n_entries > 0) prep_block_runs<<<(unsigned)((n_entries + TPB - 1) / TPB), TPB, 0, st>>>(n_entries, w_e ? ekB : ekA, bfirst, blast);
@@ -4966,43 +5021,36 @@ static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, eacham
         prim::exclusive_scan<prim::I3>(st, bt, bs, nblk, bws, &cnt->totals);
         if (nblk > 0) prep_block_fill<<<gblk, TPB, 0, st>>>(nc, nblk, bcount, bs, blocks_tmp, chunks_tmp);
         // ---- read-back 2: the table sizes ----
-        HIPQ(hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
-        HIPQ(hipStreamSynchronize(st));
-        if (hc.totals.a != n_entries) return fail(ctx->fail(EACHAM_ERR_HIP, "BA structure build: %d pair entries counted, %d placed", n_entries, hc.totals.a));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hc, cnt, sizeof(hc), hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (hc.totals.a != n_entries) return ctx->fail(EACHAM_ERR_HIP, "BA structure build: %d pair entries counted, %d placed", n_entries, hc.totals.a);
         D.n_blocks = hc.totals.b;
         D.n_chunks = hc.totals.c;
+        return EACHAM_OK;
     }
+
     // ---- the landmark-major structure (ba_groups.hpp steps 2-4 on the device), first half: groups, padded per-group arrays,
     // the counting pass over every group's entries ----
-    const int nu = hc.n_used, LMAXg = R / 4, R0g = R - std::max(hg.cmax, 4) + 1;
-    const int ng_max = use_groups ? hg.cost_total / R0g + 1 : 0;
-    int g_emax = 64;
-    while (g_emax < GRP_ENT_PER_ROW * R) g_emax <<= 1;
-    BaGroup* tg_groups = nullptr;
-    int *tg_lmid = nullptr, *tg_lmrow = nullptr, *tg_lm0 = nullptr;
-    int2* tg_rowinfo = nullptr;
-    double* tg_uv = nullptr;
-    prim::I3 *tg_counts = nullptr, *tg_bases = nullptr, *tg_ws = nullptr;
-    int n_items = 0;
-    if (use_groups) {
-        if (g_emax > GE_MAXE || R > 511) return fail(ctx->fail(EACHAM_ERR_UNSUPPORTED, "group size %d rows is beyond the device construction", R));
-        void* s2 = nullptr;
-        auto carve2 = [&](void* base) {
+    int groups_first() {
+        const int nu = hc.n_used, LMAXg = R / 4, R0g = R - std::max(hg.cmax, 4) + 1;
+        const int ng_max = hg.cost_total / R0g + 1;
+        while (g_emax < GRP_ENT_PER_ROW * R) g_emax <<= 1;
+        if (g_emax > GE_MAXE || R > 511) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "group size %d rows is beyond the device construction", R);
+        int* tg_lm0;
+        prim::I3 *tg_counts, *tg_ws;
+        TRY(ba_scratch_carve(ctx, 2, [&](void* base) {
             Bump b(base);
             tg_groups = b.take<BaGroup>(ng_max); tg_lmid = b.take<int>((size_t)ng_max * LMAXg); tg_lmrow = b.take<int>((size_t)ng_max * LMAXg);
             tg_rowinfo = b.take<int2>((size_t)ng_max * R); tg_uv = b.take<double>(2 * (size_t)ng_max * R);
             tg_lm0 = b.take<int>((size_t)ng_max + 2);
             tg_counts = b.take<prim::I3>(ng_max); tg_bases = b.take<prim::I3>(ng_max); tg_ws = b.take<prim::I3>(prim::scan_ws_elems(ng_max));
             return b.off;
-        };
-        rc = ba_scratch(ctx, 2, carve2(nullptr), &s2);
-        if (rc) return fail(rc);
-        (void)carve2(s2);
-        HIPQ(hipMemsetAsync(tg_groups, 0, sizeof(BaGroup) * (size_t)ng_max, st));
-        HIPQ(hipMemsetAsync(tg_lmid, 0xff, sizeof(int) * (size_t)ng_max * LMAXg, st));
-        HIPQ(hipMemsetAsync(tg_lmrow, 0, sizeof(int) * (size_t)ng_max * LMAXg, st));
-        HIPQ(hipMemsetAsync(tg_rowinfo, 0xff, sizeof(int2) * (size_t)ng_max * R, st));
-        HIPQ(hipMemsetAsync(tg_uv, 0, sizeof(double) * 2 * (size_t)ng_max * R, st));
+        }));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(tg_groups, 0, sizeof(BaGroup) * (size_t)ng_max, st));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(tg_lmid, 0xff, sizeof(int) * (size_t)ng_max * LMAXg, st));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(tg_lmrow, 0, sizeof(int) * (size_t)ng_max * LMAXg, st));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(tg_rowinfo, 0xff, sizeof(int2) * (size_t)ng_max * R, st));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(tg_uv, 0, sizeof(double) * 2 * (size_t)ng_max * R, st));
         const uint32_t* g_sorted = w_g ? gvB : gvA;
         const unsigned gnu = (unsigned)((nu + TPB - 1) / TPB);
         if (nu > 0) {
@@ -5012,60 +5060,50 @@ static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, eacham
         }
         if (hg.any_dup) {  // the general form: sorts every group's entries
             const size_t ge_lds = grp_entries_lds_bytes(g_emax, R);
-            HIPQ(hipFuncSetAttribute((const void*)prep_grp_entries<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
-            HIPQ(hipFuncSetAttribute((const void*)prep_grp_entries<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
             prep_grp_entries<0><<<ng_max, GE_THREADS, ge_lds, st>>>(g_emax, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, tg_counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
         } else {
             const size_t gf_lds = grp_entries_fast_lds_bytes(GRP_ENT_PER_ROW * R, R);
-            HIPQ(hipFuncSetAttribute((const void*)prep_grp_entries_fast<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
-            HIPQ(hipFuncSetAttribute((const void*)prep_grp_entries_fast<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries_fast<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries_fast<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
             prep_grp_entries_fast<0><<<ng_max, GE_THREADS, gf_lds, st>>>(GRP_ENT_PER_ROW * R, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, tg_counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
         }
         prim::exclusive_scan<prim::I3>(st, tg_counts, tg_bases, ng_max, tg_ws, &gcnt->totals);
         // ---- read-back 2: groups, chunks, entry rows, segments ----
-        HIPQ(hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
-        HIPQ(hipStreamSynchronize(st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
         if (nu == 0) hg.ng = 0;
-        if (hg.ng > ng_max) return fail(ctx->fail(EACHAM_ERR_HIP, "BA structure build: %d groups, %d expected at most", hg.ng, ng_max));
+        if (hg.ng > ng_max) return ctx->fail(EACHAM_ERR_HIP, "BA structure build: %d groups, %d expected at most", hg.ng, ng_max);
         D.g_rows = R; D.g_ngroups = hg.ng; D.g_nchunks = hg.totals.a; D.g_nent4 = hg.totals.b; D.g_nparts = hg.totals.c;
         n_items = 2 * nc + 1 + hg.totals.c;
+        return EACHAM_OK;
     }
+
     // ---- second half of the landmark-major structure: the writing pass over the groups, the slots, the block table. It needs the
     // group counters only, not the plan: it runs HERE, beside the host's analysis (which has become the longer of the two: 0.65 ms
     // against 0.45 ms of device work from the camera graph's read-back on S200, 1.5 against 0.9 ms on config 4), into staging buffers;
     // what it produced is copied into the arena once the plan has sized it (the 17 MB of entries: ~10 us device to device). Until the
     // second half of round 5 it waited for the join: 0.3 ms of every S200 call with the device idle. ----
-    BaChunk* sg_chunks = nullptr;
-    uint32_t *sg_ent = nullptr, *sg_laneinfo = nullptr;
-    int4* sg_blk = nullptr;
-    int* sg_longblk = nullptr;
-    if (use_groups) {
+    int groups_second() {
         const int ngf = D.g_ngroups;
-        void* s3 = nullptr;
-        auto carve3 = [&](void* base) {
+        TRY(ba_scratch_carve(ctx, 3, [&](void* base) {
             Bump b(base);
             sg_chunks = b.take<BaChunk>(D.g_nchunks); sg_ent = b.take<uint32_t>(256 * (size_t)D.g_nent4); sg_laneinfo = b.take<uint32_t>(64 * (size_t)D.g_nchunks);
             sg_blk = b.take<int4>(n_items); sg_longblk = b.take<int>((size_t)D.g_nparts / GRP_LONG + 1);
             return b.off;
-        };
-        rc = ba_scratch(ctx, 3, carve3(nullptr), &s3);
-        if (rc) return fail(rc);
-        (void)carve3(s3);
-        void* s1 = nullptr;
+        }));
         uint32_t *ikA, *ikB, *iwA, *iwB;
         int *isort_ws, *blk_first, *longflag, *longpos, *long_ws;
         prim::I3 *ifl, *isc, *iws;
-        auto carve1g = [&](void* base) {
+        TRY(ba_scratch_carve(ctx, 1, [&](void* base) {
             Bump b(base);
             ikA = b.take<uint32_t>(n_items); ikB = b.take<uint32_t>(n_items); iwA = b.take<uint32_t>(n_items); iwB = b.take<uint32_t>(n_items);
             isort_ws = b.take<int>(prim::radix_ws_ints(n_items));
             ifl = b.take<prim::I3>(n_items); isc = b.take<prim::I3>(n_items); iws = b.take<prim::I3>(prim::scan_ws_elems(n_items));
             blk_first = b.take<int>(n_items); longflag = b.take<int>(n_items); longpos = b.take<int>(n_items); long_ws = b.take<int>(prim::scan_ws_elems(n_items));
             return b.off;
-        };
-        rc = ba_scratch(ctx, 1, carve1g(nullptr), &s1);
-        if (rc) return fail(rc);
-        (void)carve1g(s1);
+        }));
         const int n_mand = 2 * nc + 1;
         prep_grp_mandatory<<<(unsigned)((n_mand + TPB - 1) / TPB), TPB, 0, st>>>(nc, ikA, iwA);
         if (ngf > 0) {
@@ -5084,118 +5122,113 @@ static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, eacham
         prim::exclusive_scan<int>(st, longflag, longpos, n_items, long_ws, &gcnt->n_long);
         prep_grp_long<<<git, TPB, 0, st>>>(gcnt, longflag, longpos, sg_longblk);
         // ---- read-back 3: blocks, long blocks ----
-        HIPQ(hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
-        HIPQ(hipStreamSynchronize(st));
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
         D.g_nblk = hg.item_totals.b; D.g_nlong = hg.n_long;
-    }
-    h->prep_us[0] = us_since(t_begin);
-    if (plan_thread.joinable()) plan_thread.join();  // prep_us[1] = the plan's own time; what of it was not hidden behind the device shows in [2]
-    if (plan_failed) return fail(ctx->fail(EACHAM_ERR_HIP, "BA preparation: the analysis of the reduced system ran out of memory or threads"));
-    const auto t_upload = std::chrono::steady_clock::now();
-    const BaPlan& plan = h->plan;
-    D.sp_npan = plan.npan; D.sp_ntiles = plan.ntiles; D.sp_posK = plan.posK; D.sp_rhs_row = plan.rhs_row;
-    D.sp_n_pad = (int)plan.pad_cols.size();
-    std::vector<int2> bs_ent(plan.bs_ent.size());
-    for (size_t e = 0; e < bs_ent.size(); ++e) bs_ent[e] = make_int2(plan.bs_ent[e].first, plan.bs_ent[e].second);
-    // ---- arena B: the pair lists, the plan's tables, what is sized by them ----
-    int2* pair_entries = nullptr;
-    int4 *pair_chunks = nullptr, *blocks = nullptr;
-    BaGroup* fg_groups = nullptr;
-    int *fg_lmid = nullptr, *fg_lmrow = nullptr, *fg_longblk = nullptr;
-    int2* fg_rowinfo = nullptr;
-    double* fg_uv = nullptr;
-    BaChunk* fg_chunks = nullptr;
-    uint32_t *fg_ent = nullptr, *fg_laneinfo = nullptr;
-    int4* fg_blk = nullptr;
-    const int ngf = D.g_ngroups;
-    size_t plan_lo = 0, plan_hi = 0;   // the plan's eleven tables in the arena: sent as ONE copy of their host image
-    auto layout_b = [&]() -> int {
-        TRY(dev_alloc(ctx, h, &pair_entries, (size_t)n_entries));
-        TRY(dev_alloc(ctx, h, &pair_chunks, (size_t)D.n_chunks));
-        TRY(dev_alloc(ctx, h, &blocks, (size_t)D.n_blocks));
-        if (use_groups) {
-            TRY(dev_alloc(ctx, h, &fg_groups, (size_t)ngf));
-            TRY(dev_alloc(ctx, h, &fg_lmid, (size_t)ngf * LMAXg));
-            TRY(dev_alloc(ctx, h, &fg_lmrow, (size_t)ngf * LMAXg));
-            TRY(dev_alloc(ctx, h, &fg_rowinfo, (size_t)ngf * R));
-            TRY(dev_alloc(ctx, h, &fg_uv, 2 * (size_t)ngf * R));
-            TRY(dev_alloc(ctx, h, &fg_chunks, (size_t)D.g_nchunks));
-            TRY(dev_alloc(ctx, h, &fg_ent, 256 * (size_t)D.g_nent4));
-            TRY(dev_alloc(ctx, h, &fg_laneinfo, 64 * (size_t)D.g_nchunks));
-            TRY(dev_alloc(ctx, h, &fg_blk, (size_t)n_items));                      // (blocks <= items)
-            TRY(dev_alloc(ctx, h, &fg_longblk, (size_t)D.g_nparts / GRP_LONG + 1));  // (a long block holds more than GRP_LONG segments)
-        }
-        plan_lo = h->arena_off;
-        TRY(ba_upload_plan(ctx, h, plan, bs_ent));
-        plan_hi = h->arena_off;
-        TRY(ba_alloc_work_b(ctx, h));
         return EACHAM_OK;
-    };
-    char* arena_a = h->arena;
-    const size_t off_a = h->arena_off;
-    h->planning = true;
-    h->arena = nullptr;
-    h->arena_off = 0;
-    rc = layout_b();
-    if (!rc) rc = ba_block_acquire(ctx, h->arena_off, &h->block2);
-    if (rc) return fail(rc);
-    h->arena = (char*)ctx->ba_pool[h->block2].dev;
-    h->planning = false;
-    h->arena_off = 0;
-    h->stage_base = plan_lo;
-    h->stage.assign(plan_hi - plan_lo, 0);
-    rc = layout_b();
-    if (rc) return fail(rc);
-    if (!h->stage.empty()) HIPQ(hipMemcpyAsync(h->arena + h->stage_base, h->stage.data(), h->stage.size(), hipMemcpyHostToDevice, st));
-    (void)arena_a; (void)off_a;
-    if (n_entries > 0) HIPQ(hipMemcpyAsync(pair_entries, w_e ? evB : evA, sizeof(int2) * (size_t)n_entries, hipMemcpyDeviceToDevice, st));
-    if (D.n_chunks > 0) HIPQ(hipMemcpyAsync(pair_chunks, chunks_tmp, sizeof(int4) * (size_t)D.n_chunks, hipMemcpyDeviceToDevice, st));
-    if (D.n_blocks > 0) HIPQ(hipMemcpyAsync(blocks, blocks_tmp, sizeof(int4) * (size_t)D.n_blocks, hipMemcpyDeviceToDevice, st));
-    D.pair_entries = pair_entries; D.pair_chunks = pair_chunks; D.blocks = blocks;
-    if (use_groups) {   // what the two halves staged -> the arena
-        if (ngf > 0) {
-            HIPQ(hipMemcpyAsync(fg_lmid, tg_lmid, sizeof(int) * (size_t)ngf * LMAXg, hipMemcpyDeviceToDevice, st));
-            HIPQ(hipMemcpyAsync(fg_lmrow, tg_lmrow, sizeof(int) * (size_t)ngf * LMAXg, hipMemcpyDeviceToDevice, st));
-            HIPQ(hipMemcpyAsync(fg_rowinfo, tg_rowinfo, sizeof(int2) * (size_t)ngf * R, hipMemcpyDeviceToDevice, st));
-            HIPQ(hipMemcpyAsync(fg_uv, tg_uv, sizeof(double) * 2 * (size_t)ngf * R, hipMemcpyDeviceToDevice, st));
-            HIPQ(hipMemcpyAsync(fg_groups, tg_groups, sizeof(BaGroup) * (size_t)ngf, hipMemcpyDeviceToDevice, st));
-        }
-        if (D.g_nchunks > 0) {
-            HIPQ(hipMemcpyAsync(fg_chunks, sg_chunks, sizeof(BaChunk) * (size_t)D.g_nchunks, hipMemcpyDeviceToDevice, st));
-            HIPQ(hipMemcpyAsync(fg_laneinfo, sg_laneinfo, sizeof(uint32_t) * 64 * (size_t)D.g_nchunks, hipMemcpyDeviceToDevice, st));
-        }
-        if (D.g_nent4 > 0) HIPQ(hipMemcpyAsync(fg_ent, sg_ent, sizeof(uint32_t) * 256 * (size_t)D.g_nent4, hipMemcpyDeviceToDevice, st));
-        if (n_items > 0) HIPQ(hipMemcpyAsync(fg_blk, sg_blk, sizeof(int4) * (size_t)n_items, hipMemcpyDeviceToDevice, st));
-        HIPQ(hipMemcpyAsync(fg_longblk, sg_longblk, sizeof(int) * ((size_t)D.g_nparts / GRP_LONG + 1), hipMemcpyDeviceToDevice, st));
-        D.g_groups = fg_groups; D.g_lmid = fg_lmid; D.g_lmrow = fg_lmrow; D.g_rowinfo = fg_rowinfo; D.g_uv = fg_uv; D.g_chunks = fg_chunks;
-        D.g_ent = fg_ent; D.g_laneinfo = fg_laneinfo; D.g_blk = fg_blk; D.g_longblk = fg_longblk;
     }
-    HIPQ(hipStreamSynchronize(st));  // the plan's tables were copied out of host vectors
-    h->prep_us[2] = us_since(t_upload);
-#undef HIPQ
-#undef TRY
-    h->bytes_linearize = (size_t)no * (24 + 144) + (size_t)no * 24 + (size_t)nl * (24 + LMLIN * 8) + (size_t)nc * (96 + CAMLIN * 8);
-    h->bytes_try = (size_t)no * (144 * 2 + 144 + 144) + (size_t)n_entries * 8 + (size_t)nl * (LMLIN * 8 * 3 + 48) +
-                   (size_t)no * 24 + (size_t)D.n * D.n * 8;
-    *out = h;
+
+    // ---- the join with the plan thread; arena B: the pair lists, the groups, the plan's tables, what is sized by them ----
+    int second_arena() {
+        h->prep_us[0] = us_since(t_begin);
+        if (guard.plan_thread.joinable()) guard.plan_thread.join();  // prep_us[1] = the plan's own time; what of it was not hidden behind the device shows in [2]
+        if (plan_failed) return ctx->fail(EACHAM_ERR_HIP, "BA preparation: the analysis of the reduced system ran out of memory or threads");
+        const auto t_upload = std::chrono::steady_clock::now();
+        const std::vector<int2> bs_ent = ba_plan_to_dev(h);
+        int2* pair_entries = nullptr;
+        int4 *pair_chunks = nullptr, *blocks = nullptr;
+        BaGroup* fg_groups = nullptr;
+        int *fg_lmid = nullptr, *fg_lmrow = nullptr, *fg_longblk = nullptr;
+        int2* fg_rowinfo = nullptr;
+        double* fg_uv = nullptr;
+        BaChunk* fg_chunks = nullptr;
+        uint32_t *fg_ent = nullptr, *fg_laneinfo = nullptr;
+        int4* fg_blk = nullptr;
+        const int ngf = D.g_ngroups, LMAXg = R / 4;
+        size_t plan_lo = 0, plan_hi = 0;   // the plan's eleven tables in the arena: sent as ONE copy of their host image
+        auto layout_b = [&]() -> int {
+            TRY(dev_alloc(ctx, h, &pair_entries, (size_t)n_entries));
+            TRY(dev_alloc(ctx, h, &pair_chunks, (size_t)D.n_chunks));
+            TRY(dev_alloc(ctx, h, &blocks, (size_t)D.n_blocks));
+            if (use_groups) {
+                TRY(dev_alloc(ctx, h, &fg_groups, (size_t)ngf));
+                TRY(dev_alloc(ctx, h, &fg_lmid, (size_t)ngf * LMAXg));
+                TRY(dev_alloc(ctx, h, &fg_lmrow, (size_t)ngf * LMAXg));
+                TRY(dev_alloc(ctx, h, &fg_rowinfo, (size_t)ngf * R));
+                TRY(dev_alloc(ctx, h, &fg_uv, 2 * (size_t)ngf * R));
+                TRY(dev_alloc(ctx, h, &fg_chunks, (size_t)D.g_nchunks));
+                TRY(dev_alloc(ctx, h, &fg_ent, 256 * (size_t)D.g_nent4));
+                TRY(dev_alloc(ctx, h, &fg_laneinfo, 64 * (size_t)D.g_nchunks));
+                TRY(dev_alloc(ctx, h, &fg_blk, (size_t)n_items));                      // (blocks <= items)
+                TRY(dev_alloc(ctx, h, &fg_longblk, (size_t)D.g_nparts / GRP_LONG + 1));  // (a long block holds more than GRP_LONG segments)
+            }
+            plan_lo = h->arena_off;
+            TRY(ba_upload_plan(ctx, h, h->plan, bs_ent));
+            plan_hi = h->arena_off;
+            TRY(ba_alloc_work_b(ctx, h));
+            return EACHAM_OK;
+        };
+        TRY(ba_arena_layout(ctx, h, &h->block2, layout_b, [&] { return std::make_pair(plan_lo, plan_hi); }));
+        if (n_entries > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(pair_entries, w_e ? evB : evA, sizeof(int2) * (size_t)n_entries, hipMemcpyDeviceToDevice, st));
+        if (D.n_chunks > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(pair_chunks, chunks_tmp, sizeof(int4) * (size_t)D.n_chunks, hipMemcpyDeviceToDevice, st));
+        if (D.n_blocks > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(blocks, blocks_tmp, sizeof(int4) * (size_t)D.n_blocks, hipMemcpyDeviceToDevice, st));
+        D.pair_entries = pair_entries; D.pair_chunks = pair_chunks; D.blocks = blocks;
+        if (use_groups) {   // what the two halves staged -> the arena
+            if (ngf > 0) {
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_lmid, tg_lmid, sizeof(int) * (size_t)ngf * LMAXg, hipMemcpyDeviceToDevice, st));
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_lmrow, tg_lmrow, sizeof(int) * (size_t)ngf * LMAXg, hipMemcpyDeviceToDevice, st));
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_rowinfo, tg_rowinfo, sizeof(int2) * (size_t)ngf * R, hipMemcpyDeviceToDevice, st));
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_uv, tg_uv, sizeof(double) * 2 * (size_t)ngf * R, hipMemcpyDeviceToDevice, st));
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_groups, tg_groups, sizeof(BaGroup) * (size_t)ngf, hipMemcpyDeviceToDevice, st));
+            }
+            if (D.g_nchunks > 0) {
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_chunks, sg_chunks, sizeof(BaChunk) * (size_t)D.g_nchunks, hipMemcpyDeviceToDevice, st));
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_laneinfo, sg_laneinfo, sizeof(uint32_t) * 64 * (size_t)D.g_nchunks, hipMemcpyDeviceToDevice, st));
+            }
+            if (D.g_nent4 > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_ent, sg_ent, sizeof(uint32_t) * 256 * (size_t)D.g_nent4, hipMemcpyDeviceToDevice, st));
+            if (n_items > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_blk, sg_blk, sizeof(int4) * (size_t)n_items, hipMemcpyDeviceToDevice, st));
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(fg_longblk, sg_longblk, sizeof(int) * ((size_t)D.g_nparts / GRP_LONG + 1), hipMemcpyDeviceToDevice, st));
+            D.g_groups = fg_groups; D.g_lmid = fg_lmid; D.g_lmrow = fg_lmrow; D.g_rowinfo = fg_rowinfo; D.g_uv = fg_uv; D.g_chunks = fg_chunks;
+            D.g_ent = fg_ent; D.g_laneinfo = fg_laneinfo; D.g_blk = fg_blk; D.g_longblk = fg_longblk;
+        }
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));  // the plan's tables were copied out of host vectors
+        h->prep_us[2] = us_since(t_upload);
+        ba_traffic_bytes(h, n_entries);
+        return EACHAM_OK;
+    }
+};
+
+static int ba_prepare_device(eacham_ctx* ctx, const eacham_ba_problem* P, int hint, eacham_ba_handle** out) {
+    if ((long long)P->n_cams * (P->n_cams + 1) / 2 > BA_MAX_CAM_BLOCKS_DEVICE)
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "too many cameras (%d) for the camera-block index", P->n_cams);
+    BaDevicePrep S(ctx, P, hint);
+    TRY(S.first_arena());
+    TRY(S.structure());
+    TRY(S.plan_and_counts());
+    TRY(S.use_groups ? S.groups_first() : S.pair_lists());
+    if (S.use_groups) TRY(S.groups_second());
+    TRY(S.second_arena());
+    *out = S.guard.release();
     return EACHAM_OK;
 }
 
-static int ba_prepare(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_ba_handle** out, bool lm_direct = false) {
+// One entry for both constructions: the problem and the ordering hint are checked here, once.
+static int ba_prepare(eacham_ctx* ctx, const eacham_ba_problem* P, eacham_ba_handle** out) {
     if (!P || P->n_cams < 0 || P->n_points < 0 || P->n_obs < 0) return ctx->fail(EACHAM_ERR_INVALID, "bad BA problem");
     if (P->n_obs > 0 && (!P->obs_cam || !P->obs_point || !P->obs_uv)) return ctx->fail(EACHAM_ERR_INVALID, "null observation arrays");
     if ((P->n_cams > 0 && (!P->cam_T_wc || !P->cam_fixed)) || (P->n_points > 0 && (!P->points || !P->point_observers)))
         return ctx->fail(EACHAM_ERR_INVALID, "null camera/point arrays");
+    int hint = 0;
+    TRY(ba_ordering_hint(ctx, P, &hint));
     // a local window (the reference's per-frame call, ~10 k observations) is cheaper through the host loops: the device
-    // construction is ~45 dependent launches and three read-backs whatever the size
+    // construction is ~45 dependent launches and three read-backs whatever the size. (Which form of the Schur stage serves:
+    // ba_schur_wanted. The dense form, ba_window.hpp, is a measured alternative, not the default, and carries the direct
+    // Levenberg-Marquardt solve only: on the 19-camera windows of the TUM stand-in its one launch takes 39 us where ba_linearize +
+    // ba_eliminate + ba_schur_pairs take 28, profiles/r05_ba_windows_dense_form.txt.)
     const bool device = ctx->ba_prepare_mode == 2 || (ctx->ba_prepare_mode == 0 && P->n_obs >= 65536);
-    // the dense form of the Schur stage (ba_window.hpp) is a measured alternative, not the default: EACHAM_BA_SCHUR=dense selects it
-    // (it carries the direct Levenberg-Marquardt solve only). On the 19-camera windows of the TUM stand-in its one launch takes
-    // 39 us where ba_linearize + ba_eliminate + ba_schur_pairs take 28 (profiles/r05_ba_windows_dense_form.txt).
-    (void)lm_direct;
-    const bool allow_dense = ctx->ba_schur_mode == 3;
-    return device ? ba_prepare_device(ctx, P, out) : ba_prepare_host(ctx, P, out, allow_dense);
+    return device ? ba_prepare_device(ctx, P, hint, out) : ba_prepare_host(ctx, P, hint, out);
 }
+#undef TRY
 
 static void ba_release(eacham_ctx* ctx, eacham_ba_handle* h) {
     if (!h) return;
@@ -5744,8 +5777,7 @@ int eacham_ba_solve(eacham_ctx* ctx, const eacham_ba_problem* problem, const eac
     std::lock_guard<std::mutex> lock(ctx->mu);
     (void)hipSetDevice(ctx->device);
     eacham_ba_handle* h = nullptr;
-    const bool lm_direct = options && options->method == EACHAM_BA_LM && options->use_preconditioner == 0;
-    int rc = ba_prepare(ctx, problem, &h, lm_direct);
+    int rc = ba_prepare(ctx, problem, &h);
     if (rc) return rc;
     rc = ba_run(ctx, h, options, result);
     ba_release(ctx, h);
