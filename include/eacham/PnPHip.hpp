@@ -33,6 +33,38 @@ struct PnPResult {
     int iterations = 0;           // samples the sequential rule consumed before RANSACUpdateNumIters stopped it
 };
 
+// What one SolvePnPRansac run decided on the way, for whoever wants to replay it (tests): every sample it drew (whole chunks:
+// more than the `iterations` the sequential rule consumed) and the sample whose model won (-1: none).
+struct PnPTrace {
+    std::vector<int32_t> samples;
+    int winner = -1;
+};
+
+namespace pnp_detail {
+
+const int kChunk = 256;   // samples solved and scored per launch
+
+// Samples first .. first + count - 1 of one RANSACPointSetRegistrator::run, count rows of m indices out of n. Sampling::OpenCV
+// continues `rng` (one stream for the whole call: ask for the samples in order); Sampling::Counter is indexed by the global
+// sample number; `given`, when set, is the whole run's list and is read in place of either (rows past its end repeat its last).
+inline std::vector<int32_t> pnp_samples(int n, int m, int first, int count, CvRNG& rng, uint64_t seed, Sampling sampling,
+                                        const std::vector<int32_t>* given = nullptr) {
+    std::vector<int32_t> idx;
+    if (given) {
+        const int rows = (int)(given->size() / m);
+        idx.resize((size_t)count * m);
+        for (int k = 0; k < count; ++k) std::copy_n(&(*given)[(size_t)std::min(first + k, rows - 1) * m], m, &idx[(size_t)k * m]);
+    } else if (sampling == Sampling::OpenCV) {
+        idx.resize((size_t)count * m);
+        for (int k = 0; k < count; ++k) (void)cv_get_subset(rng, n, m, &idx[(size_t)k * m], 10000, [](const int32_t*) { return true; });
+    } else {
+        idx = twoview_detail::draw_samples(n, m, count, seed, first);
+    }
+    return idx;
+}
+
+}  // namespace pnp_detail
+
 inline Vec3 RodriguesFromMatrix(const Mat3& R) {   // rotation matrix -> axis * angle
     const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) * 0.5));
     const double theta = std::acos(c);
@@ -56,13 +88,13 @@ inline Vec3 RodriguesFromMatrix(const Mat3& R) {   // rotation matrix -> axis * 
 // object: n x 3, image: n x 2 (pixels), K9: row-major 3 x 3 (no distortion — the reference passes zeros).
 inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
                                 int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999, uint64_t seed = 1,
-                                Sampling sampling = Sampling::OpenCV) {
+                                Sampling sampling = Sampling::OpenCV, PnPTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
     PnPResult out;
     const int n = (int)(image.size() / 2), m = 5;
-    if (n < m || object.size() != (size_t)3 * n || iterations <= 0) return out;
+    if (n < m || object.size() != (size_t)3 * n || iterations <= 0 || (samples && samples->size() < (size_t)m)) return out;
     const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
     const float thr = reprojectionError * reprojectionError;   // PnPRansacCallback::computeError returns squared pixels
-    const int chunk = 256;
+    const int chunk = pnp_detail::kChunk;
     std::vector<double> models((size_t)chunk * 12), best_model(12, 0.0);
     std::vector<int32_t> okv(chunk), inl(chunk);
     int best_inl = -1, budget = iterations, done = 0;
@@ -72,13 +104,8 @@ inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object,
         // sample s of the whole run is row (s - first) of this chunk: OpenCV's stream is drawn in sample order (a chunk draws ahead
         // of the budget, which only shrinks: the samples the sequential rule consumes are the stream's prefix); the counter-based
         // generator is indexed by the global sample number
-        std::vector<int32_t> idx;
-        if (sampling == Sampling::OpenCV) {
-            idx.resize((size_t)cnt * m);
-            for (int k = 0; k < cnt; ++k) (void)cv_get_subset(rng, n, m, &idx[(size_t)k * m], 10000, [](const int32_t*) { return true; });
-        } else {
-            idx = twoview_detail::draw_samples(n, m, cnt, seed, first);
-        }
+        const std::vector<int32_t> idx = pnp_detail::pnp_samples(n, m, first, cnt, rng, seed, sampling, samples);
+        if (trace) trace->samples.insert(trace->samples.end(), idx.begin(), idx.end());
         ctx.check(eacham_solve_pnp(ctx.get(), n, object.data(), image.data(), K4, m, cnt, idx.data(), models.data(), okv.data()));
         ctx.check(eacham_score_hypotheses(ctx.get(), EACHAM_SCORE_PNP, n, object.data(), image.data(), cnt, models.data(), K4, thr, nullptr,
                                           inl.data(), nullptr));
@@ -87,6 +114,7 @@ inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object,
             if (!okv[k]) continue;
             if (inl[k] > std::max(best_inl, m - 1)) {   // strictly more inliers (and at least a sample's worth) replaces the model
                 best_inl = inl[k];
+                if (trace) trace->winner = first + k;
                 std::copy(&models[(size_t)k * 12], &models[(size_t)k * 12] + 12, best_model.begin());
                 budget = twoview_detail::ransac_update_num_iters(confidence, (double)(n - inl[k]) / n, m, budget);
             }

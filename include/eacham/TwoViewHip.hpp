@@ -129,6 +129,17 @@ struct RobustModel {
     bool ok = false;
 };
 
+// What one lmeds() run decided on the way, for whoever wants to replay it (tests): the minimal samples it used, the winner's
+// place in the flattened candidate list and the sample / root it came from, sigma and the squared-error threshold of the mask,
+// and the winning model as solved (FindHomography refits RobustModel::model afterwards).
+struct LmedsTrace {
+    std::vector<int32_t> samples;
+    int candidates = 0, candidate = -1, sample = -1, root = -1;
+    double sigma = 0.0;
+    float threshold = 0.0f;
+    Mat3 winner{};
+};
+
 // RANSACUpdateNumIters (ptsetreg.cpp): iterations after which a sample of m inliers has been drawn with probability p at
 // outlier ratio ep, capped by maxIters
 inline int ransac_update_num_iters(double p, double ep, int m, int maxIters) {
@@ -173,14 +184,20 @@ inline std::vector<int32_t> lmeds_samples(int n, int m, int iterations, bool hom
 }
 
 inline RobustModel lmeds(Context& ctx, int solve_kind, int score_kind, int m, const std::vector<double>& uv1, const std::vector<double>& uv2,
-                         const double* K4, int maxIters, double confidence, uint64_t seed, Sampling sampling) {
+                         const double* K4, int maxIters, double confidence, uint64_t seed, Sampling sampling, LmedsTrace* trace = nullptr,
+                         const std::vector<int32_t>* given = nullptr) {   // given: the samples to use, in place of drawing them
     RobustModel out;
     const int n = (int)(uv1.size() / 2), maxm = solve_kind == EACHAM_SOLVE_ESSENTIAL5 ? 10 : 1;
     if (n < m || uv2.size() != uv1.size() || maxIters <= 0) return out;
     int iterations = std::min(maxIters, std::max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3));
-    const std::vector<int32_t> idx = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1, uv2, seed, sampling);
+    std::vector<int32_t> idx;
+    if (given)
+        idx.assign(given->begin(), given->begin() + (size_t)m * std::min<size_t>(iterations, given->size() / m));
+    else
+        idx = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1, uv2, seed, sampling);
     iterations = (int)(idx.size() / m);
     out.iterations = iterations;
+    if (trace) trace->samples = idx;
     if (iterations == 0) return out;
     std::vector<double> models((size_t)iterations * maxm * 9);
     std::vector<int32_t> counts(iterations);
@@ -189,6 +206,7 @@ inline RobustModel lmeds(Context& ctx, int solve_kind, int score_kind, int m, co
     for (int s = 0; s < iterations; ++s)
         for (int k = 0; k < counts[s]; ++k) cand.insert(cand.end(), &models[((size_t)s * maxm + k) * 9], &models[((size_t)s * maxm + k) * 9] + 9);
     const int nm = (int)(cand.size() / 9);
+    if (trace) trace->candidates = nm;
     if (nm == 0) return out;
     std::vector<float> med(nm);
     std::vector<int32_t> inl(nm);
@@ -212,18 +230,25 @@ inline RobustModel lmeds(Context& ctx, int solve_kind, int score_kind, int m, co
     for (int i = 0; i < n; ++i) out.mask[i] = err[i] <= thr ? 1 : 0;
     out.inliers = cnt;
     out.ok = true;
+    if (trace) {
+        trace->candidate = best, trace->sigma = sigma, trace->threshold = thr, trace->winner = out.model;
+        for (int s = 0, k = best; s < iterations; k -= counts[s++])
+            if (k < counts[s]) { trace->sample = s, trace->root = k; break; }
+    }
     return out;
 }
 
 }  // namespace twoview_detail
 
+using twoview_detail::LmedsTrace;
 using twoview_detail::RobustModel;
 
 // cv::findEssentialMat(pts1, pts2, focal, pp, LMEDS, prob, threshold, maxIters, mask): pixels in, K4 = fx fy cx cy
 // (the reference passes focal = K(0,0) and pp = (K(0,2), K(1,2)): fx = fy = focal). The model is a unit-norm E.
 inline RobustModel FindEssentialMat(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, const double* K4,
-                                    int maxIters = 1000, uint64_t seed = 12345, double prob = 0.99, Sampling sampling = Sampling::OpenCV) {
-    return twoview_detail::lmeds(ctx, EACHAM_SOLVE_ESSENTIAL5, EACHAM_SCORE_ESSENTIAL, 5, uv1, uv2, K4, maxIters, prob, seed, sampling);
+                                    int maxIters = 1000, uint64_t seed = 12345, double prob = 0.99, Sampling sampling = Sampling::OpenCV,
+                                    LmedsTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
+    return twoview_detail::lmeds(ctx, EACHAM_SOLVE_ESSENTIAL5, EACHAM_SCORE_ESSENTIAL, 5, uv1, uv2, K4, maxIters, prob, seed, sampling, trace, samples);
 }
 // What cv::findHomography does with the inliers of the robust stage (fundam.cpp, "if (result && npoints > 4 ...)"): the
 // normalised DLT over ALL inliers (HomographyEstimatorCallback::runKernel with count = inliers), then at most 10
@@ -281,6 +306,14 @@ inline bool RefitHomography(const std::vector<double>& uv1, const std::vector<do
     int lo = 0;
     for (int k = 1; k < 9; ++k)
         if (LtL[10 * k] < LtL[10 * lo]) lo = k;
+    // a second eigenvalue at rounding level (singular values below 1e-6 of the largest): the points — all on one line, or fewer
+    // than four distinct ones — leave more than one homography, and whichever the eigen-solver picked means nothing
+    double hi = 0.0, next = std::numeric_limits<double>::infinity();
+    for (int k = 0; k < 9; ++k) {
+        hi = std::max(hi, LtL[10 * k]);
+        if (k != lo) next = std::min(next, LtL[10 * k]);
+    }
+    if (!(next > 1e-12 * hi)) return false;
     Mat3 H0;
     for (int k = 0; k < 9; ++k) H0[k] = V[9 * k + lo];
     const Mat3 invHnorm{1.0 / sm[0], 0, cm[0], 0, 1.0 / sm[1], cm[1], 0, 0, 1}, Hnorm2{sM[0], 0, -cM[0] * sM[0], 0, sM[1], -cM[1] * sM[1], 0, 0, 1};
@@ -344,8 +377,10 @@ inline bool RefitHomography(const std::vector<double>& uv1, const std::vector<do
 // cv::findHomography(pts1, pts2, LMEDS, ransacReprojThreshold, mask, maxIters, confidence). The model has H[8] = 1:
 // the LMedS winner refitted on its inliers as above (the mask stays the winner's).
 inline RobustModel FindHomography(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, int maxIters = 100,
-                                  uint64_t seed = 12345, double confidence = 0.999, Sampling sampling = Sampling::OpenCV) {
-    RobustModel r = twoview_detail::lmeds(ctx, EACHAM_SOLVE_HOMOGRAPHY4, EACHAM_SCORE_HOMOGRAPHY, 4, uv1, uv2, nullptr, maxIters, confidence, seed, sampling);
+                                  uint64_t seed = 12345, double confidence = 0.999, Sampling sampling = Sampling::OpenCV,
+                                  LmedsTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
+    RobustModel r = twoview_detail::lmeds(ctx, EACHAM_SOLVE_HOMOGRAPHY4, EACHAM_SCORE_HOMOGRAPHY, 4, uv1, uv2, nullptr, maxIters, confidence, seed,
+                                          sampling, trace, samples);
     if (r.ok && uv1.size() / 2 > 4) {
         Mat3 H;
         if (RefitHomography(uv1, uv2, r.mask, H)) r.model = H;
