@@ -257,20 +257,8 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
         const int v = atoi(b);
         if (v >= 16 && v <= 65536) ctx->match_budget_mb = v;
     }
-    if (const char* l = getenv("EACHAM_BA_LPL_STEP")) {
-        const int v = atoi(l);
-        if (v == 1 || v == 2 || v == 4 || v == 8) ctx->ba_lpl_step = v;
-    }
-    if (const char* l = getenv("EACHAM_BA_LPL_LIN")) {
-        const int v = atoi(l);
-        if (v == 1 || v == 2 || v == 4 || v == 8) ctx->ba_lpl_lin = v;
-    }
     if (const char* m = getenv("EACHAM_BA_PREPARE")) ctx->ba_prepare_mode = !strcmp(m, "host") ? 1 : !strcmp(m, "device") ? 2 : 0;
-    if (const char* m = getenv("EACHAM_BA_SCHUR")) ctx->ba_schur_mode = !strcmp(m, "pairs") ? 2 : !strcmp(m, "groups") ? 1 : !strcmp(m, "dense") ? 3 : 0;
-    if (const char* r = getenv("EACHAM_BA_WINDOW_ROWS")) {
-        const int v = atoi(r);
-        if (v >= 64 && v <= 256 && v % 4 == 0) ctx->ba_window_rows = v;
-    }
+    if (const char* m = getenv("EACHAM_BA_SCHUR")) ctx->ba_schur_mode = !strcmp(m, "pairs") ? 2 : !strcmp(m, "groups") ? 1 : 0;
     if (const char* r = getenv("EACHAM_BA_GROUP_ROWS")) {
         const int v = atoi(r);
         if (v >= 16 && v <= 508 && v % 4 == 0) ctx->ba_group_rows = v;   // (508: see the entry key of prep_grp_entries, ba.hip)
