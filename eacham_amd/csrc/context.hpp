@@ -240,6 +240,17 @@ int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n,
 int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
                   int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
                   int4* stats_dev);
+// How the float path cuts a job into launches and lays one launch's arrays into the workspace (both of its forms, L2 and dot product)
+struct MatchPlanF32 {
+    int row_stride, wb_stride, wgs_per_pair;  // padded rows per frame (max over the resident frames), its 32-row tiles, workgroups per pair
+    int batch;                                // pairs per launch
+    size_t off_rowres, off_colpart, off_matches, total;
+};
+MatchPlanF32 plan_match_f32(const eacham_ctx* ctx, int npairs);
+// matcher_dot.hip
+int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_score, int min_dir, int min_mutual, int mode,
+                  int* counts_dev, long long* offsets_dev, uint2* edges_dev, float* scores_dev, long long edge_cap,
+                  long long* total_dev, int4* stats_dev);
 // matcher.hip
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);
 void launch_compact_edges(eacham_ctx* ctx, int nb, const uint2* matches, const int* counts, const long long* offsets,

@@ -1983,4 +1983,103 @@ int eacham_match_pairs_directed(eacham_ctx* ctx, const int32_t* pairs, int npair
     return match_pairs_host(ctx, pairs, npairs, ratio, 0, 0, 1, counts, offsets, out_q, out_t, cap, out_total, nullptr);
 }
 
+// ---- dot-product form (matcher_dot.hip): host pointers in, CSR over the pairs + scores out ----
+static int match_pairs_dot_host(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
+                                int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score,
+                                int64_t cap, int64_t* out_total, int32_t* stats) {
+    if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
+        return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to the dot-product matcher");
+    int rc = check_pairs_host(ctx, pairs, npairs);
+    if (rc) return rc;
+    if (npairs > 0 && ctx->kind_common != 1)
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are int8");
+    *out_total = 0;
+    if (npairs == 0) {
+        if (offsets) offsets[0] = 0;
+        return EACHAM_OK;
+    }
+    rc = sync_frame_table(ctx);
+    if (rc) return rc;
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t o_pairs = 0;
+    const size_t o_counts = align(o_pairs + (size_t)npairs * 2 * sizeof(int32_t));
+    const size_t o_offsets = align(o_counts + (size_t)npairs * sizeof(int32_t));
+    const size_t o_total = align(o_offsets + (size_t)(npairs + 1) * sizeof(int64_t));
+    const size_t o_stats = align(o_total + sizeof(int64_t));
+    const size_t o_edges = align(o_stats + (size_t)npairs * 4 * sizeof(int32_t));
+    const size_t o_scores = align(o_edges + (size_t)cap * sizeof(uint2));
+    rc = ensure_io(ctx, o_scores + (size_t)cap * sizeof(float));
+    if (rc) return rc;
+    char* io = (char*)ctx->io;
+    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs, pairs, (size_t)npairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    rc = run_match_dot(ctx, (const int2*)(io + o_pairs), npairs, min_score, min_dir, min_mutual, mode, (int*)(io + o_counts),
+                       (long long*)(io + o_offsets), (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
+                       stats ? (int4*)(io + o_stats) : nullptr);
+    if (rc) return rc;
+    long long total = 0;
+    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&total, io + o_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(counts, io + o_counts, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(offsets, io + o_offsets, (size_t)(npairs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
+    if (stats)
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(stats, io + o_stats, (size_t)npairs * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *out_total = total;
+    if (total > cap) return ctx->fail(EACHAM_ERR_CAPACITY, "%lld matches but capacity %lld", total, (long long)cap);
+    if (total > 0) {
+        std::vector<uint2> tmp((size_t)total);
+        EACHAM_HIP_TRY(ctx, hipMemcpy(tmp.data(), io + o_edges, sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost));
+        for (long long k = 0; k < total; ++k) {
+            out_q[k] = tmp[k].x;
+            out_t[k] = tmp[k].y;
+        }
+        if (out_score) EACHAM_HIP_TRY(ctx, hipMemcpy(out_score, io + o_scores, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
+    }
+    return EACHAM_OK;
+}
+
+// Nothing may leave extern "C" (std::vector throws on an absurd capacity): the three entry points run their body through this.
+extern "C++" template <class Body>
+static int dot_entry(eacham_ctx* ctx, Body body) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    try {
+        return body();
+    } catch (const std::exception& e) {
+        return ctx->fail(EACHAM_ERR_INVALID, "dot-product matcher: %s", e.what());
+    } catch (...) {
+        return ctx->fail(EACHAM_ERR_INVALID, "dot-product matcher: unknown exception");
+    }
+}
+
+int eacham_match_pair_dot(eacham_ctx* ctx, int f1, int f2, float min_score, uint32_t* out_q, uint32_t* out_t, float* out_score,
+                          int cap, int* out_count) {
+    return dot_entry(ctx, [&]() -> int {
+        if (!out_count) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+        const int32_t pr[2] = {f1, f2};
+        int32_t count = 0;
+        int64_t offsets[2] = {0, 0}, total = 0;
+        const int rc = match_pairs_dot_host(ctx, pr, 1, min_score, 0, 0, 1, &count, offsets, out_q, out_t, out_score, cap, &total, nullptr);
+        if (rc == EACHAM_OK || rc == EACHAM_ERR_CAPACITY) *out_count = (int)total;
+        return rc;
+    });
+}
+
+int eacham_match_pairs_directed_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int32_t* counts,
+                                    int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap,
+                                    int64_t* out_total) {
+    return dot_entry(ctx, [&]() -> int {
+        return match_pairs_dot_host(ctx, pairs, npairs, min_score, 0, 0, 1, counts, offsets, out_q, out_t, out_score, cap, out_total, nullptr);
+    });
+}
+
+int eacham_match_all_pairs_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
+                               int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap,
+                               int64_t* out_total, int32_t* stats) {
+    return dot_entry(ctx, [&]() -> int {
+        return match_pairs_dot_host(ctx, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
+                                    out_total, stats);
+    });
+}
+
 }  // extern "C"

@@ -309,22 +309,30 @@ int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n,
     return EACHAM_OK;
 }
 
-int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
-                  int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
-                  int4* stats_dev) {
+MatchPlanF32 plan_match_f32(const eacham_ctx* ctx, int npairs) {
     int max_tiles = 4;
     for (const auto& f : ctx->frames)
         if (f.n >= 0) max_tiles = std::max(max_tiles, f.ntiles);
-    const int row_stride = max_tiles * 32, wb_stride = max_tiles;
-    const int wgs_per_pair = (max_tiles + F_WAVES - 1) / F_WAVES;
-    const size_t per_pair = (size_t)row_stride * sizeof(int4) + (size_t)wb_stride * row_stride * sizeof(int4) +
-                            (size_t)row_stride * sizeof(uint2) + sizeof(int);
-    const int batch = (int)std::max<size_t>(1, std::min<size_t>(((size_t)1 << 30) / per_pair, (size_t)npairs));
+    MatchPlanF32 pl;
+    pl.row_stride = max_tiles * 32, pl.wb_stride = max_tiles;
+    pl.wgs_per_pair = (max_tiles + F_WAVES - 1) / F_WAVES;
+    const size_t per_pair = (size_t)pl.row_stride * sizeof(int4) + (size_t)pl.wb_stride * pl.row_stride * sizeof(int4) +
+                            (size_t)pl.row_stride * sizeof(uint2) + sizeof(int);
+    pl.batch = (int)std::max<size_t>(1, std::min<size_t>(((size_t)1 << 30) / per_pair, (size_t)npairs));
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t off_rowres = 0;
-    const size_t off_colpart = align((size_t)batch * row_stride * sizeof(int4));
-    const size_t off_matches = align(off_colpart + (size_t)batch * wb_stride * row_stride * sizeof(int4));
-    const size_t total = align(off_matches + (size_t)batch * row_stride * sizeof(uint2));
+    pl.off_rowres = 0;
+    pl.off_colpart = align((size_t)pl.batch * pl.row_stride * sizeof(int4));
+    pl.off_matches = align(pl.off_colpart + (size_t)pl.batch * pl.wb_stride * pl.row_stride * sizeof(int4));
+    pl.total = align(pl.off_matches + (size_t)pl.batch * pl.row_stride * sizeof(uint2));
+    return pl;
+}
+
+int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
+                  int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
+                  int4* stats_dev) {
+    const MatchPlanF32 pl = plan_match_f32(ctx, npairs);
+    const int row_stride = pl.row_stride, wb_stride = pl.wb_stride, wgs_per_pair = pl.wgs_per_pair, batch = pl.batch;
+    const size_t off_rowres = pl.off_rowres, off_colpart = pl.off_colpart, off_matches = pl.off_matches, total = pl.total;
     int rc = ensure_workspace(ctx, total);
     if (rc) return rc;
     char* ws = (char*)ctx->ws;

@@ -20,6 +20,7 @@ from . import capi
 RATIO = 0.8        # FeatureMatcherFlann.cpp:23 (the ctor's inliersRatio is stored but never used)
 MIN_DIRECTED = 30  # apps/sfm/main.cpp:111  `matches12.size() < 30` -> drop
 MIN_MUTUAL = 30    # apps/sfm/main.cpp:142  `bestMatches12.size() > 30` -> connect
+MIN_SCORE = 0.5    # modules/onnx/lightglue/FeatureMatcherLightglue.cpp:118  `mscores0 > 0.5` -> keep
 
 
 class HipContext:
@@ -162,6 +163,47 @@ class HipContext:
                                                         offsets.ctypes.data, q.ctypes.data, t.ctypes.data, cap, C.byref(total)))
         return [dict(zip(q[offsets[p]:offsets[p + 1]].tolist(), t[offsets[p]:offsets[p + 1]].tolist())) for p in range(npairs)]
 
+    # ---- dot-product similarity (float frames), scores returned ----------------------------
+    def match_pair_dot(self, f1: int, f2: int, min_score: float = MIN_SCORE):
+        """(q, t, scores) of the directed match f1 -> f2: argmax of a.b per row, kept iff the similarity > min_score."""
+        cap = max(self.frame_rows(f1), 1)
+        q = np.empty(cap, dtype=np.uint32)
+        t = np.empty(cap, dtype=np.uint32)
+        s = np.empty(cap, dtype=np.float32)
+        cnt = C.c_int(0)
+        self._check(self._L.eacham_match_pair_dot(self._h, f1, f2, min_score, q.ctypes.data, t.ctypes.data, s.ctypes.data, cap, C.byref(cnt)))
+        return q[:cnt.value].copy(), t[:cnt.value].copy(), s[:cnt.value].copy()
+
+    def _dot_buffers(self, pairs, cap):
+        pairs = np.ascontiguousarray(pairs, dtype=np.int32).reshape(-1, 2)
+        npairs = pairs.shape[0]
+        if cap is None:
+            cap = int(sum(self.frame_rows(int(p[0])) for p in pairs)) if npairs else 0
+        return (pairs, npairs, cap, np.zeros(npairs, dtype=np.int32), np.zeros(npairs + 1, dtype=np.int64),
+                np.empty(max(cap, 1), dtype=np.uint32), np.empty(max(cap, 1), dtype=np.uint32), np.empty(max(cap, 1), dtype=np.float32))
+
+    def match_pairs_directed_dot(self, ordered_pairs, min_score: float = MIN_SCORE, cap: int | None = None):
+        """Every ordered pair (i, j) of the RESIDENT float frames as one directed dot-product match, in one launch sequence.
+        Returns (counts, offsets, q, t, scores): CSR over the pairs."""
+        pairs, npairs, cap, counts, offsets, q, t, s = self._dot_buffers(ordered_pairs, cap)
+        total = C.c_int64(0)
+        self._check(self._L.eacham_match_pairs_directed_dot(self._h, pairs.ctypes.data, npairs, min_score, counts.ctypes.data,
+                                                            offsets.ctypes.data, q.ctypes.data, t.ctypes.data, s.ctypes.data, cap, C.byref(total)))
+        n = total.value
+        return counts, offsets, q[:n].copy(), t[:n].copy(), s[:n].copy()
+
+    def match_all_pairs_dot(self, pairs, min_score: float = MIN_SCORE, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL,
+                            cap: int | None = None, stats: bool = True):
+        """The mutual form (eacham_match_all_pairs_dot). Returns (counts, offsets, q, t, scores, stats)."""
+        pairs, npairs, cap, counts, offsets, q, t, s = self._dot_buffers(pairs, cap)
+        st = np.zeros((npairs, 4), dtype=np.int32) if stats else None
+        total = C.c_int64(0)
+        self._check(self._L.eacham_match_all_pairs_dot(
+            self._h, pairs.ctypes.data, npairs, min_score, min_dir, min_mutual, counts.ctypes.data, offsets.ctypes.data,
+            q.ctypes.data, t.ctypes.data, s.ctypes.data, cap, C.byref(total), st.ctypes.data if stats else None))
+        n = total.value
+        return counts, offsets, q[:n].copy(), t[:n].copy(), s[:n].copy(), st
+
     def match_all_pairs_dev(self, pairs_dev: int, npairs: int, counts_dev: int, offsets_dev: int,
                             edges_dev: int, edge_cap: int, total_dev: int, stats_dev: int = 0,
                             ratio: float = RATIO, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL):
@@ -220,3 +262,29 @@ class FeatureMatcherHip:
     def MatchPairs(self, frames, ordered_pairs) -> list:
         """eacham_match_pairs_directed: every (i, j) of `ordered_pairs` is one Match(frames[i], frames[j])."""
         return self.ctx.match_pairs_directed(frames, ordered_pairs, self.ratio, f32=self._f32)
+
+
+class FeatureMatcherDotHip:
+    """Mirror of eacham::hip::FeatureMatcherDotHip (include/eacham/FeatureMatcherHip.hpp): float descriptors matched by
+    dot-product similarity. `Match(d1, d2)` returns {queryIdx: trainIdx}: with `mutual` the one-to-one matches of the pair
+    (what LightGlue's matches0 are), without it the directed match; `LastScores()` gives {queryIdx: similarity} of that call."""
+
+    def __init__(self, minScore: float = MIN_SCORE, mutual: bool = True, context: HipContext | None = None):
+        self.minScore = minScore
+        self.mutual = mutual
+        self.ctx = context or HipContext()
+        self._scores = {}
+
+    def Match(self, descriptor1: np.ndarray, descriptor2: np.ndarray) -> dict:
+        self.ctx.clear_descriptors()
+        self.ctx.upload_descriptors_f32(0, descriptor1)
+        self.ctx.upload_descriptors_f32(1, descriptor2)
+        if self.mutual:
+            _, _, q, t, s, _ = self.ctx.match_all_pairs_dot([[0, 1]], self.minScore, 0, -1, stats=False)
+        else:
+            q, t, s = self.ctx.match_pair_dot(0, 1, self.minScore)
+        self._scores = dict(zip(q.tolist(), s.tolist()))
+        return dict(zip(q.tolist(), t.tolist()))
+
+    def LastScores(self) -> dict:
+        return self._scores

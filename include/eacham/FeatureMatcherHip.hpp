@@ -406,6 +406,116 @@ inline MatchGraph MatchAllPairs(Context& ctx, const std::vector<DescriptorView>&
     return g;
 }
 
+// ---- dot-product similarity for float descriptors ------------------------------------------------
+// Stands where the reference's LightGlue plug-in matcher stands (modules/onnx/lightglue/FeatureMatcherLightglue.cpp): 256-D float
+// descriptors (feature/Types.h:11-14), a match kept by its score (`mscores0 > 0.5`, :118) and the score handed on. Here the
+// score is the similarity a.b of brute-force matching (eacham_match_*_dot of eacham_hip.h); nothing is normalised.
+//   mutual = true : the one-to-one matches of the pair — q -> t with t the best of q AND q the best of t, both above
+//                   minScore — which is what LightGlue's matches0 are; no 30 / 30 threshold decisions are made;
+//   mutual = false: the directed match q -> argmax_t a_q.b_t.
+// Thread-safe: one shared instance may be called from many threads (apps/sfm/main.cpp:98-109); calls are served one at
+// a time, each uploading its two frames into the instance's own context. Unlike FeatureMatcherHip this adapter neither caches
+// uploads nor combines concurrent callers into one launch sequence; the batch call for a whole stage is MatchAllPairsDot below.
+class FeatureMatcherDotHip : public IFeatureMatcher<DescriptorView> {
+public:
+    using ScoreType = std::unordered_map<unsigned, float>;  // query index -> similarity of its match
+
+    explicit FeatureMatcherDotHip(float minScore = 0.5f, bool mutual = true, int device = 0)
+        : minScore_(minScore), mutual_(mutual), ctx_(device) {}
+
+    MatchType Match(const DescriptorView& d1, const DescriptorView& d2) override { return Match(d1, d2, nullptr); }
+
+    // The scores alongside (the form to use under concurrent callers).
+    MatchType Match(const DescriptorView& d1, const DescriptorView& d2, ScoreType* scores) {
+        std::lock_guard<std::mutex> lk(mu_);
+        const int n1 = d1.rows > 0 ? d1.rows : 0;
+        ctx_.check(eacham_upload_descriptors_f32(ctx_.get(), 0, d1.data, d1.rows, d1.dim));
+        ctx_.check(eacham_upload_descriptors_f32(ctx_.get(), 1, d2.data, d2.rows, d2.dim));
+        std::vector<uint32_t> q((size_t)(n1 > 0 ? n1 : 1)), t(q.size());
+        std::vector<float> s(q.size());
+        int64_t total = 0;
+        if (mutual_) {
+            const int32_t pair[2] = {0, 1};
+            int32_t count = 0;
+            int64_t offsets[2] = {0, 0};
+            ctx_.check(eacham_match_all_pairs_dot(ctx_.get(), pair, 1, minScore_, 0, -1, &count, offsets, q.data(), t.data(), s.data(), n1,
+                                                  &total, nullptr));
+        } else {
+            int count = 0;
+            ctx_.check(eacham_match_pair_dot(ctx_.get(), 0, 1, minScore_, q.data(), t.data(), s.data(), n1, &count));
+            total = count;
+        }
+        MatchType out;
+        out.reserve((size_t)total);
+        last_.clear();
+        for (int64_t k = 0; k < total; ++k) {
+            out.insert({q[k], t[k]});
+            last_.insert({q[k], s[k]});
+        }
+        if (scores) *scores = last_;
+        return out;
+    }
+
+#ifdef EACHAM_HIP_HAVE_OPENCV
+    MatchType Match(const cv::Mat& d1, const cv::Mat& d2) {
+        if (d1.type() != CV_32F || d2.type() != CV_32F || !d1.isContinuous() || !d2.isContinuous())
+            throw std::runtime_error("eacham_hip: descriptors must be continuous CV_32F matrices");
+        return Match(DescriptorView{d1.ptr<float>(), d1.rows, d1.cols}, DescriptorView{d2.ptr<float>(), d2.rows, d2.cols});
+    }
+#endif
+
+    // Scores of the most recent Match() on this instance (a copy). Under concurrent callers "most recent" is whichever call
+    // finished last: use the overload above there.
+    ScoreType LastScores() {
+        std::lock_guard<std::mutex> lk(mu_);
+        return last_;
+    }
+
+    Context& context() { return ctx_; }
+
+private:
+    float minScore_;
+    bool mutual_;
+    Context ctx_;
+    std::mutex mu_;
+    ScoreType last_;
+};
+
+struct MatchGraphDot : MatchGraph {
+    std::vector<float> scores;  // scores[k] = similarity of q[k] -> t[k]
+};
+
+// MatchAllPairs for float descriptors under dot-product similarity: rewrites the context's descriptor store (frame f -> id f),
+// matches every pair in both directions with the mutual check and the thresholds given.
+inline MatchGraphDot MatchAllPairsDot(Context& ctx, const std::vector<DescriptorView>& frames,
+                                      const std::vector<std::pair<unsigned, unsigned>>& pairs, float minScore = 0.5f,
+                                      int minDir = 30, int minMutual = 30) {
+    ctx.store_rewritten();
+    ctx.check(eacham_clear_descriptors(ctx.get()));
+    for (size_t f = 0; f < frames.size(); ++f)
+        ctx.check(eacham_upload_descriptors_f32(ctx.get(), (int)f, frames[f].data, frames[f].rows, frames[f].dim));
+    std::vector<int32_t> flat(2 * pairs.size());
+    int64_t cap = 0;
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        flat[2 * p] = (int32_t)pairs[p].first;
+        flat[2 * p + 1] = (int32_t)pairs[p].second;
+        cap += frames.at(pairs[p].first).rows;
+    }
+    MatchGraphDot g;
+    g.counts.resize(pairs.size());
+    g.offsets.resize(pairs.size() + 1);
+    g.q.resize(cap > 0 ? cap : 1);
+    g.t.resize(g.q.size());
+    g.scores.resize(g.q.size());
+    int64_t total = 0;
+    ctx.check(eacham_match_all_pairs_dot(ctx.get(), flat.data(), (int)pairs.size(), minScore, minDir, minMutual, g.counts.data(),
+                                         g.offsets.data(), g.q.data(), g.t.data(), g.scores.data(), cap, &total, nullptr));
+    g.q.resize(total);
+    g.t.resize(total);
+    g.scores.resize(total);
+    return g;
+}
+
 // ---- view-graph query on the CSR match graph ---------------------------------------------------
 // std::tuple<unsigned, unsigned, unsigned> Graph::GetBestPairForValid(const std::set<unsigned>& excluded)
 //     /root/reference/modules/sfm/data/Graph.h:59-106

@@ -140,6 +140,39 @@ int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int np
  * oracle samples on both sides of every launch boundary of the job of apps/sfm/main.cpp:84-147. */
 int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int32_t* starts, int cap, int* n_batches, int* n_slots);
 
+/* ---- dot-product similarity for float descriptors, scores returned ----------------------------
+ * The brute-force rule for SuperPoint-class descriptors (modules/onnx/lightglue/feature/Types.h:11-14): nearest neighbour
+ * by similarity with a score threshold, where the reference's LightGlue plug-in keeps a match by `mscores0 > 0.5`
+ * (FeatureMatcherLightglue.cpp:118) and hands the score on. For frames uploaded with eacham_upload_descriptors_f32
+ * (any dim 1..256); int8 frames give EACHAM_ERR_UNSUPPORTED, a frame that is not resident EACHAM_ERR_INVALID.
+ *   s(q,t) = a_q . b_t   in fp32, accumulated as the k-ordered fmaf chain from 0 (what the f32 matrix cores produce).
+ *   Nothing is normalised: the caller's values are used as they are.
+ * Directed match f1 -> f2: for each row q, t0 = argmax_t s(q,t), the lower train index on equal similarity; q -> t0 is
+ * kept iff s(q,t0) > min_score (strict). No second neighbour is involved: a train frame of one row is legal, a train
+ * frame of 0 rows gives an empty result. A NaN similarity never compares greater: it never wins and never passes.
+ * Every emitted match k carries out_score[k] = s(q[k], t[k]), bit for bit that chain; out_score may be NULL.
+ * Output sorted by q; *out_count = matches found (EACHAM_ERR_CAPACITY if > cap).
+ * There is no device-pointer form and no sharded form of these calls (the float kind has neither for L2). */
+int eacham_match_pair_dot(eacham_ctx* ctx, int f1, int f2, float min_score,
+                          uint32_t* out_q, uint32_t* out_t, float* out_score, int cap, int* out_count);
+
+/* npairs ORDERED pairs, each one directed dot-product match, in one launch sequence; CSR over the pairs like
+ * eacham_match_pairs_directed, plus the scores. */
+int eacham_match_pairs_directed_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score,
+                                    int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t,
+                                    float* out_score, int64_t cap, int64_t* out_total);
+
+/* The mutual form, same shape as eacham_match_all_pairs: m12, m21 as above; the pair is dropped if |m12| < min_dir or
+ * |m21| < min_dir; mutual = {(q,t) in m12 : m21[t] == q}; the pair is an edge iff |mutual| > min_mutual. counts[p] =
+ * |mutual| for edges, 0 otherwise; CSR over the pairs sorted by q; out_score[k] = s(q[k], t[k]);
+ * stats (may be NULL): npairs x {|m12|, |m21|, |mutual|, edge?1:0}. min_dir = 0 and min_mutual = -1 keep every pair's
+ * one-to-one matches. */
+int eacham_match_all_pairs_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score,
+                               int min_dir, int min_mutual,
+                               int32_t* counts, int64_t* offsets,
+                               uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap, int64_t* out_total,
+                               int32_t* stats);
+
 /* ---- bundle adjustment: RefineBA (modules/sfm/reconstruction/BundleAdjuster.cpp:40-250) --------
  *
  * The caller (the C++ adapter in include/eacham/BundleAdjusterHip.hpp) performs the reference's
