@@ -87,6 +87,8 @@ def lib() -> C.CDLL:
     L.eacham_score_hypotheses.argtypes = [vp, i32, i32, vp, vp, i32, vp, vp, C.c_float, vp, vp, vp]
     L.eacham_solve_minimal.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp, vp, vp]
     L.eacham_solve_pnp.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
+    if hasattr(L, "eacham_lmeds_batch"):  # (absent from older builds selected with EACHAM_HIP_LIB; calling it on one raises AttributeError)
+        L.eacham_lmeds_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     L.eacham_graph_best_pair.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "eacham_graph_create"):
         L.eacham_graph_create.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, C.POINTER(vp)]

@@ -7,7 +7,8 @@
 // reproduces the order a sequential host loop produces, so the device-built structure is bit-identical with the host-built
 // one (tests/test_ba_gpu.py holds them against each other) and two runs are bit-identical with each other.
 //
-// Everything is enqueued on the caller's stream; nothing synchronises. Workspace sizes are given by the *_ws_elems helpers.
+// Everything is enqueued on the caller's stream; nothing synchronises. More than one translation unit includes this file (ba.hip,
+// lmeds_batch.hip): the kernels are templates or static. Workspace sizes are given by the *_ws_elems helpers.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -185,7 +186,7 @@ __device__ __forceinline__ void wave_lds_fence() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-__global__ __launch_bounds__(RS_THREADS) void radix_hist(const uint32_t* __restrict__ keys, int n, int shift, int bits,
+static __global__ __launch_bounds__(RS_THREADS) void radix_hist(const uint32_t* __restrict__ keys, int n, int shift, int bits,
                                                          int nseg, int* __restrict__ hist) {
     __shared__ int cnt[RS_WAVES][1 << RS_MAX_BITS];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;

@@ -1,0 +1,376 @@
+// lmeds_batch.hip — LMedS two-view estimation for a whole LIST of pairs in one call (eacham_lmeds_batch), gfx950.
+//
+// What twoview_detail::lmeds (include/eacham/TwoViewHip.hpp) does for one pair with three blocking calls — solve every minimal
+// sample, score every candidate's median, keep the first smallest, derive the threshold from sigma, classify the points by the
+// winner — runs here for n_problems pairs with no host turn between the stages: the inputs go up once, the results come back
+// once, and the number of launches does not depend on n_problems.
+//
+//   lb_solve_h4 / lb_solve_e5   a wave per sample, SOLVE_WAVES samples per workgroup: the bodies of solve_h4_kernel / solve_e5_kernel
+//                               (solve_dev.hpp) on the sample's own problem, found by a binary search in sample_ptr (and left in
+//                               sample_problem[] for the stages below)
+//   prim::exclusive_scan        of n_models over all samples (devprim.hpp: one launch up to 16 384 samples, three beyond): candidate c
+//                               of the flattened list (sample order, then root order) is root c - first[s] of the sample s with
+//                               first[s] <= c < first[s + 1] — the models stay where the solver wrote them, nothing is copied
+//   lb_score<KIND>              a workgroup per candidate over its own problem's points: score_one, the key transform and the radix
+//                               select of score_kernel (score_dev.hpp), so the medians are the same bits. The number of candidates
+//                               is only known on the device: a fixed grid strides over them. Keys live in LDS up to SC_MAX_LDS
+//                               points (dynamic LDS sized by the largest problem of the call) and in the workgroup's own error row
+//                               beyond it.
+//   lb_select<KIND>             a workgroup per problem: first smallest non-NaN median (strict < over ascending candidate index),
+//                               sigma and the threshold in fp64 in the host's order of operations, then the winner's errors
+//                               against the threshold: the mask bytes and the inlier count.
+#include "context.hpp"
+#include "devprim.hpp"
+#include "score_dev.hpp"
+#include "solve_dev.hpp"
+
+#include <climits>
+
+namespace eacham {
+namespace {
+
+// the largest k in [0, n) with ptr[k] <= v (ptr ascending, ptr[0] <= v)
+template <class T>
+__device__ __forceinline__ int segment_of(const T* __restrict__ ptr, int n, long long v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)ptr[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_h4_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
+                                                                      int n_problems, const double* __restrict__ a, const double* __restrict__ b,
+                                                                      int n_samples, const int* __restrict__ idx, double* __restrict__ models,
+                                                                      int* __restrict__ n_models, int* __restrict__ sample_problem) {
+    __shared__ double LtL[SOLVE_WAVES][81], V[SOLVE_WAVES][81];
+    __shared__ JacRound R[SOLVE_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * SOLVE_WAVES + wave;
+    if (s >= n_samples) return;
+    const int p = segment_of(sample_ptr, n_problems, s);
+    const long long base = point_ptr[p];
+    if (lane == 0) sample_problem[s] = p;
+    if (point_ptr[p + 1] - base < 4) {   // (wave-uniform) a problem without a minimal sample's worth of points has no candidates
+        if (lane == 0) n_models[s] = 0;
+        return;
+    }
+    a += 2 * base, b += 2 * base;
+    double pa[8], pb[8], out[9];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = idx[(size_t)s * 4 + k];
+        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
+        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) out[k] = 0.0;
+    const int n = homography4_wave(pa, pb, out, LtL[wave], V[wave], R[wave]);
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) models[9 * (size_t)s + k] = out[k];
+        n_models[s] = n;
+    }
+}
+
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_e5_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
+                                                                      int n_problems, const double* __restrict__ a, const double* __restrict__ b,
+                                                                      const double* __restrict__ K, int has_K, int n_samples, const int* __restrict__ idx,
+                                                                      double* __restrict__ models, int* __restrict__ n_models,
+                                                                      int* __restrict__ sample_problem) {
+    __shared__ E5Lds lds[SOLVE_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * SOLVE_WAVES + wave;
+    if (s >= n_samples) return;
+    const int p = segment_of(sample_ptr, n_problems, s);
+    const long long base = point_ptr[p];
+    if (lane == 0) sample_problem[s] = p;
+    if (point_ptr[p + 1] - base < 5) {   // (wave-uniform)
+        if (lane == 0) n_models[s] = 0;
+        return;
+    }
+    a += 2 * base, b += 2 * base;
+    double pa[10], pb[10];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) {
+        const int i = idx[(size_t)s * 5 + k];
+        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
+        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
+    }
+    double fx = 1, fy = 1, cx = 0, cy = 0;
+    if (has_K) fx = K[0], fy = K[1], cx = K[2], cy = K[3];
+    double* dst = models + (size_t)s * 90;
+    for (int k = lane; k < 90; k += 64) dst[k] = 0.0;  // (this wave's own stores below follow in program order)
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    const int n = essential5_wave(pa, pb, has_K != 0, fx, fy, cx, cy, dst, lds[wave]);
+    if (lane == 0) n_models[s] = n;
+}
+
+// KIND 0 = essential (Sampson distance, fp64), 1 = homography (transfer error, fp32): score_one's kinds.
+// first[s] = candidates before sample s (the exclusive scan of n_models), *total = all of them; max_models = 10 / 1.
+template <int KIND>
+__global__ __launch_bounds__(SC_BLOCK) void lb_score_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ a,
+                                                            const double* __restrict__ b, const double* __restrict__ Kdev, int normalise,
+                                                            int n_samples, const int* __restrict__ first, const int* __restrict__ total,
+                                                            const int* __restrict__ sample_problem, const double* __restrict__ models,
+                                                            int max_models, float* __restrict__ medians, float* __restrict__ rows,
+                                                            size_t row_stride) {
+    extern __shared__ unsigned keys[];  // [min(largest problem, SC_MAX_LDS)]
+    __shared__ unsigned hist[256], sh[2];
+    double K[4] = {1, 1, 0, 0};
+    if (Kdev) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) K[k] = Kdev[k];
+    }
+    float* erow = rows ? rows + (size_t)blockIdx.x * row_stride : nullptr;
+    const int ncand = *total;
+    for (int c = blockIdx.x; c < ncand; c += gridDim.x) {   // (c, and every barrier below, is uniform over the workgroup)
+        const int s = segment_of(first, n_samples, c);
+        const long long base = point_ptr[sample_problem[s]];
+        const int n = (int)(point_ptr[sample_problem[s] + 1] - base);   // >= 4: the sample was solved
+        const double* pm = models + 9 * ((size_t)s * max_models + (c - first[s]));
+        const double* pa = a + 2 * base;
+        const double* pb = b + 2 * base;
+        double M[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) M[k] = pm[k];
+        const bool keys_in_lds = n <= SC_MAX_LDS;
+        for (int i = threadIdx.x; i < n; i += SC_BLOCK) {
+            const double xa[2] = {pa[2 * (size_t)i], pa[2 * (size_t)i + 1]}, xb[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
+            const float e = score_one<KIND>(xa, xb, M, K, normalise != 0);
+            if (keys_in_lds) keys[i] = fkey(e);
+            else erow[i] = e;
+        }
+        __syncthreads();  // keys / the error row are complete (the row was written by this workgroup: visible after the barrier)
+        auto load = [&](int i) { return keys_in_lds ? keys[i] : fkey(erow[i]); };
+        const unsigned hi = radix_select(load, n, n / 2, hist, sh);
+        float med = fkey_inv(hi);
+        if (n % 2 == 0) {
+            const unsigned lo = radix_select(load, n, n / 2 - 1, hist, sh);
+            med = fmul(fadd(fkey_inv(lo), med), 0.5f);
+        }
+        if (threadIdx.x == 0) medians[c] = med;
+        // (radix_select ends on a barrier: every read of this candidate's keys is done before the next one's are written)
+    }
+}
+
+// sigma of LMeDSPointSetRegistrator::run as the host evaluates `std::max(2.5 * 1.4826 * (1.0 + 5.0 / std::max(n - m, 1)) *
+// std::sqrt((double)median), 0.001)`: the constant product folded, then left to right, every operation rounded on its own.
+__device__ __forceinline__ double lmeds_sigma(float median, int n, int m) {
+    const int d = n - m > 1 ? n - m : 1;
+    const double f = __dadd_rn(1.0, __ddiv_rn(5.0, (double)d));
+    const double s = __dmul_rn(__dmul_rn(2.5 * 1.4826, f), __dsqrt_rn((double)median));
+    return s < 0.001 ? 0.001 : s;
+}
+
+struct Best {
+    float med;
+    int at;   // candidate index in the call's flattened list, -1 = none yet
+};
+// `o` replaces `b` iff it holds a candidate and b does not, or its median is smaller, or equal with the smaller index
+__device__ __forceinline__ Best first_smallest(Best b, Best o) {
+    const bool take = o.at >= 0 && (b.at < 0 || o.med < b.med || (o.med == b.med && o.at < b.at));
+    return take ? o : b;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(SC_BLOCK) void lb_select_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
+                                                             const double* __restrict__ a, const double* __restrict__ b,
+                                                             const double* __restrict__ Kdev, int normalise, int n_samples,
+                                                             const int* __restrict__ first, const int* __restrict__ total,
+                                                             const double* __restrict__ models, int max_models, const float* __restrict__ cmed,
+                                                             double* __restrict__ out_models, float* __restrict__ out_medians,
+                                                             float* __restrict__ out_thresholds, int* __restrict__ out_inliers,
+                                                             unsigned char* __restrict__ out_masks, int* __restrict__ out_winner,
+                                                             int* __restrict__ out_ncand) {
+    constexpr int m = KIND == 0 ? 5 : 4;
+    __shared__ Best wbest[SC_BLOCK / 64];
+    __shared__ int wsum[SC_BLOCK / 64];
+    const int p = blockIdx.x;
+    const long long base = point_ptr[p];
+    const int n = (int)(point_ptr[p + 1] - base);
+    const long long s0 = sample_ptr[p], s1 = sample_ptr[p + 1];
+    const int c0 = s0 < n_samples ? first[s0] : *total, c1 = s1 < n_samples ? first[s1] : *total;
+    Best best{0.f, -1};
+    for (int c = c0 + (int)threadIdx.x; c < c1; c += SC_BLOCK) {   // ascending in every thread: strict < keeps the first
+        const float v = cmed[c];
+        if (v == v && (best.at < 0 || v < best.med)) best = Best{v, c};
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        Best o;
+        o.med = __shfl_down(best.med, off);
+        o.at = __shfl_down(best.at, off);
+        best = first_smallest(best, o);
+    }
+    if ((threadIdx.x & 63) == 0) wbest[threadIdx.x >> 6] = best;
+    __syncthreads();
+    best = wbest[0];
+#pragma unroll
+    for (int w = 1; w < SC_BLOCK / 64; ++w) best = first_smallest(best, wbest[w]);   // (every thread: the same values)
+    const bool none = best.at < 0;
+    double M[9], K[4] = {1, 1, 0, 0};
+    float thr = 0.f;
+    int s = 0;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) M[k] = 0.0;
+    if (!none) {
+        s = segment_of(first, n_samples, best.at);
+        const double* pm = models + 9 * ((size_t)s * max_models + (best.at - first[s]));
+#pragma unroll
+        for (int k = 0; k < 9; ++k) M[k] = pm[k];
+        const double sigma = lmeds_sigma(best.med, n, m);
+        thr = (float)__dmul_rn(sigma, sigma);
+        if (Kdev) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) K[k] = Kdev[k];
+        }
+    }
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out_models[9 * (size_t)p + k] = M[k];
+        out_medians[p] = none ? __uint_as_float(0x7fc00000u) : best.med;
+        out_thresholds[p] = thr;
+        out_winner[3 * (size_t)p] = none ? -1 : best.at - c0;
+        out_winner[3 * (size_t)p + 1] = none ? -1 : s - (int)s0;
+        out_winner[3 * (size_t)p + 2] = none ? -1 : best.at - first[s];
+        out_ncand[p] = c1 - c0;
+    }
+    const double* pa = a + 2 * base;
+    const double* pb = b + 2 * base;
+    int cnt = 0;
+    for (int i = threadIdx.x; i < n; i += SC_BLOCK) {
+        unsigned char in = 0;
+        if (!none) {
+            const double xa[2] = {pa[2 * (size_t)i], pa[2 * (size_t)i + 1]}, xb[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
+            in = score_one<KIND>(xa, xb, M, K, normalise != 0) <= thr;
+        }
+        out_masks[base + i] = in;
+        cnt += in;
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int tot = 0;
+        for (int w = 0; w < SC_BLOCK / 64; ++w) tot += wsum[w];
+        out_inliers[p] = tot;
+    }
+}
+
+constexpr int LB_SCORE_GRID = 4096;      // workgroups striding over the candidates (~2 resident rounds of 256 CUs x 8)
+constexpr int LB_SCORE_GRID_ROWS = 1024; // ... when each carries an error row of the largest problem (> SC_MAX_LDS points)
+
+}  // namespace
+}  // namespace eacham
+
+using namespace eacham;
+
+extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t* point_ptr, const double* a, const double* b,
+                                  const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, double* models, float* medians,
+                                  float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: unknown kind %d", kind);
+    if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: negative number of problems");
+    if (n_problems == 0) return EACHAM_OK;
+    if (!point_ptr || !sample_ptr) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: null offset table");
+    const int P = n_problems, m = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 4 : 5, maxm = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
+    if (point_ptr[0] != 0 || sample_ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: an offset table does not start at 0");
+    for (int p = 0; p < P; ++p)
+        if (point_ptr[p + 1] < point_ptr[p] || sample_ptr[p + 1] < sample_ptr[p])
+            return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: problem %d: offset table not monotone", p);
+    const long long NP = point_ptr[P], S = sample_ptr[P];
+    if (NP > INT_MAX / 2 || S * m > INT_MAX || S * maxm > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "lmeds_batch: %lld points / %lld samples in one call", NP, S);
+    if ((NP > 0 && (!a || !b)) || (S > 0 && !sample_idx)) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: null array");
+    long long max_n = 0;
+    for (int p = 0; p < P; ++p) {
+        const long long n = point_ptr[p + 1] - point_ptr[p];
+        if (n < m) continue;   // its samples are not looked at: the problem gets the "none" record
+        max_n = std::max(max_n, n);
+        for (long long k = sample_ptr[p] * m; k < sample_ptr[p + 1] * m; ++k)
+            if (sample_idx[k] < 0 || sample_idx[k] >= n)
+                return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: problem %d: sample index %d of %lld points", p, (int)sample_idx[k], n);
+    }
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool need_rows = max_n > SC_MAX_LDS;
+    const long long cand_cap = S * maxm;
+    const int score_grid = (int)std::max<long long>(1, std::min<long long>(cand_cap, need_rows ? LB_SCORE_GRID_ROWS : LB_SCORE_GRID));
+    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align(off + bytes); return o; };
+    // the results, then the inputs (each side one contiguous span of the pinned mirror), then what never leaves the device
+    const size_t o_om = take(sizeof(double) * 9 * (size_t)P), o_omed = take(sizeof(float) * (size_t)P), o_othr = take(sizeof(float) * (size_t)P);
+    const size_t o_oinl = take(sizeof(int) * (size_t)P), o_owin = take(sizeof(int) * 3 * (size_t)P), o_onc = take(sizeof(int) * (size_t)P);
+    const size_t o_omask = take((size_t)NP);
+    const size_t o_pp = take(sizeof(int64_t) * ((size_t)P + 1)), o_sp = take(sizeof(int64_t) * ((size_t)P + 1)), o_K = take(sizeof(double) * 4);
+    const size_t o_a = take(sizeof(double) * 2 * (size_t)NP), o_b = take(sizeof(double) * 2 * (size_t)NP);
+    const size_t o_i = take(sizeof(int) * (size_t)S * m);
+    const size_t o_dev = off;
+    const size_t o_m = take(sizeof(double) * 9 * (size_t)cand_cap), o_n = take(sizeof(int) * (size_t)S), o_first = take(sizeof(int) * (size_t)S);
+    const size_t o_sprob = take(sizeof(int) * (size_t)S), o_tot = take(sizeof(int)), o_ws = take(sizeof(int) * prim::scan_ws_elems((size_t)S));
+    const size_t o_cmed = take(sizeof(float) * (size_t)cand_cap);
+    const size_t o_rows = take(need_rows ? sizeof(float) * (size_t)score_grid * (size_t)max_n : 0);
+    if (int rc = ensure_io(ctx, off)) return rc;
+    if (int rc = ensure_io_host(ctx, o_dev)) return rc;
+    char* base = (char*)ctx->io;
+    hipStream_t st = ctx->stream;
+    IoPack io(ctx, st);
+    if (int rc = io.in(o_pp, point_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
+    if (int rc = io.in(o_sp, sample_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
+    if (K)
+        if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
+    if (int rc = io.in(o_a, a, sizeof(double) * 2 * (size_t)NP)) return rc;
+    if (int rc = io.in(o_b, b, sizeof(double) * 2 * (size_t)NP)) return rc;
+    if (int rc = io.in(o_i, sample_idx, sizeof(int) * (size_t)S * m)) return rc;
+    if (int rc = io.flush_in()) return rc;
+    const long long* d_pp = (const long long*)(base + o_pp);
+    const long long* d_sp = (const long long*)(base + o_sp);
+    const double *d_a = (const double*)(base + o_a), *d_b = (const double*)(base + o_b), *d_K = K ? (const double*)(base + o_K) : nullptr;
+    double* d_m = (double*)(base + o_m);
+    int *d_n = (int*)(base + o_n), *d_first = (int*)(base + o_first), *d_sprob = (int*)(base + o_sprob), *d_tot = (int*)(base + o_tot);
+    float* d_cmed = (float*)(base + o_cmed);
+    const int normalise = K && kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
+    {
+        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+        if (S > 0) {
+            const unsigned grid = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
+            if (kind == EACHAM_SOLVE_HOMOGRAPHY4)
+                lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (int)S, (const int*)(base + o_i), d_m, d_n, d_sprob);
+            else
+                lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (const double*)(base + o_K), K ? 1 : 0, (int)S,
+                                                                      (const int*)(base + o_i), d_m, d_n, d_sprob);
+        }
+        prim::exclusive_scan<int>(st, d_n, d_first, (int)S, (int*)(base + o_ws), d_tot);   // (no samples: *total = 0)
+        const size_t smem = sizeof(unsigned) * (size_t)std::max<long long>(1, std::min<long long>(max_n, SC_MAX_LDS));
+#define EACHAM_LB_LAUNCH(KIND)                                                                                                                     \
+    do {                                                                                                                                           \
+        if (S > 0) {                                                                                                                               \
+            if (smem > 48 * 1024)                                                                                                                  \
+                EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)lb_score_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+            lb_score_kernel<KIND><<<score_grid, SC_BLOCK, smem, st>>>(d_pp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_sprob, d_m, maxm, \
+                                                                      d_cmed, need_rows ? (float*)(base + o_rows) : nullptr, (size_t)max_n);       \
+        }                                                                                                                                          \
+        lb_select_kernel<KIND><<<P, SC_BLOCK, 0, st>>>(d_pp, d_sp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_m, maxm, d_cmed,             \
+                                                       (double*)(base + o_om), (float*)(base + o_omed), (float*)(base + o_othr),                   \
+                                                       (int*)(base + o_oinl), (unsigned char*)(base + o_omask), (int*)(base + o_owin),             \
+                                                       (int*)(base + o_onc));                                                                      \
+    } while (0)
+        if (kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_LB_LAUNCH(0);
+        else EACHAM_LB_LAUNCH(1);
+#undef EACHAM_LB_LAUNCH
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    if (int rc = io.out(models, o_om, sizeof(double) * 9 * (size_t)P)) return rc;
+    if (int rc = io.out(medians, o_omed, sizeof(float) * (size_t)P)) return rc;
+    if (int rc = io.out(thresholds, o_othr, sizeof(float) * (size_t)P)) return rc;
+    if (int rc = io.out(inliers, o_oinl, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.out(winner, o_owin, sizeof(int) * 3 * (size_t)P)) return rc;
+    if (int rc = io.out(n_candidates, o_onc, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.out(masks, o_omask, (size_t)NP)) return rc;
+    if (int rc = io.finish()) return rc;
+    return EACHAM_OK;
+}

@@ -20,757 +20,13 @@
 // A sample is ~10^4-10^5 flops of branchy fp64 with kilobytes of private state: latency-bound, no roofline claim; the
 // 1000 / 100 iterations the reference asks for are one launch.
 #include "context.hpp"
+#include "solve_dev.hpp"
 
 #include <algorithm>
 #include <cstdint>
 
 namespace eacham {
 namespace {
-
-__device__ __forceinline__ void wave_sync_lds() {  // a wave's own LDS traffic: order its writes before its reads
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-/* cyclic Jacobi on a symmetric N x N matrix (N <= 12): A is destroyed, V's COLUMNS are the eigenvectors, w the eigenvalues.
- * Small N (3, 4) unrolls completely and stays in registers. */
-template <int N, class MA, class MV>
-__device__ __forceinline__ void jacobi_eig(MA A, MV V, double* w) {
-    constexpr int n = N;
-#pragma unroll
-    for (int i = 0; i < n; ++i)
-#pragma unroll
-        for (int j = 0; j < n; ++j) V[i * n + j] = i == j ? 1.0 : 0.0;
-    auto rotate = [&](int p, int q) {
-        const double apq = A[p * n + q];
-        if (apq == 0.0) return;
-        const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#pragma unroll
-        for (int k = 0; k < n; ++k) {  /* columns p, q */
-            const double akp = A[k * n + p], akq = A[k * n + q];
-            A[k * n + p] = c * akp - s * akq;
-            A[k * n + q] = s * akp + c * akq;
-        }
-#pragma unroll
-        for (int k = 0; k < n; ++k) {  /* rows p, q */
-            const double apk = A[p * n + k], aqk = A[q * n + k];
-            A[p * n + k] = c * apk - s * aqk;
-            A[q * n + k] = s * apk + c * aqk;
-        }
-#pragma unroll
-        for (int k = 0; k < n; ++k) {
-            const double vkp = V[k * n + p], vkq = V[k * n + q];
-            V[k * n + p] = c * vkp - s * vkq;
-            V[k * n + q] = s * vkp + c * vkq;
-        }
-    };
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0, diag = 0.0;
-#pragma unroll
-        for (int p = 0; p < n; ++p) {
-            diag += A[p * n + p] * A[p * n + p];
-#pragma unroll
-            for (int q = p + 1; q < n; ++q) off += A[p * n + q] * A[p * n + q];
-        }
-        if (off <= 1e-60 || off <= 1e-32 * diag) break;
-        if constexpr (N <= 4) {
-#pragma unroll
-            for (int p = 0; p < n - 1; ++p)
-#pragma unroll
-                for (int q = p + 1; q < n; ++q) rotate(p, q);
-        } else {
-            for (int p = 0; p < n - 1; ++p)
-                for (int q = p + 1; q < n; ++q) rotate(p, q);
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < n; ++i) w[i] = A[i * n + i];
-}
-
-/* ---- five-point ---------------------------------------------------------------------------------------------- */
-/* column of the monomial x^ex y^ey z^ez (total degree <= 3) in Nister's elimination order */
-__device__ static int mono_col(int ex, int ey, int ez) {
-    constexpr int8_t order[20][3] = {{3, 0, 0}, {0, 3, 0}, {2, 1, 0}, {1, 2, 0}, {2, 0, 1}, {2, 0, 0}, {0, 2, 1}, {0, 2, 0}, {1, 1, 1}, {1, 1, 0},
-                                        {1, 0, 2}, {1, 0, 1}, {1, 0, 0}, {0, 1, 2}, {0, 1, 1}, {0, 1, 0}, {0, 0, 3}, {0, 0, 2}, {0, 0, 1}, {0, 0, 0}};
-    for (int k = 0; k < 20; ++k)
-        if (order[k][0] == ex && order[k][1] == ey && order[k][2] == ez) return k;
-    return -1;
-}
-
-/* ---- five-point, one WAVE per sample ---------------------------------------------------------------------------------------
- * The arithmetic of essential5 / oracle_essential5 entry by entry, spread over the lanes wherever entries are independent:
- *   null space      the Householder reflections of the 9 x 5 system: a lane per column of Q, a lane per row of P
- *   constraints     the 10 x 20 matrix: an entry per lane (four rounds), each adding ITS monomial's terms in the order of the
- *                   sequential triple loop (a table lists, per monomial, the (a, b, c) factor choices that produce it)
- *   Gauss-Jordan    on one shared copy in LDS: pivot search by every lane (same values), row swap / scale by 20 lanes, the
- *                   180 eliminated entries of a step over the wave
- *   det B(z)        every lane, in registers (a few hundred operations on identical values)
- *   roots           Durand-Kerner in its simultaneous form: root k on lane k, the other iterates by lane shuffles
- *   x, y, polish    a real root per lane: the 3 Gauss-Newton steps read the assembled constraints from LDS
- * Nothing is indexed at run time outside LDS: no scratch. A wave's LDS operations execute in program order; the fences only
- * pin the compiler. */
-struct E5Lds {
-    double A[200], A0[200];  // the constraints as eliminated / as assembled
-    double Q[45], P[81];     // Q^T (9 x 5) and the orthogonal factor
-    double lin[36];          // entry e of E as a linear form in (x, y, z, 1)
-    double poly[11], mon[11];
-    double B[45];            // B(z): [row][column][power of z]
-    unsigned char mcol[64];     // column of the monomial x^ex y^ey z^ez at [16 ex + 4 ey + ez]
-    unsigned char term[20][8];  // per monomial: the (a, b, c) choices of mul3acc that produce it, packed a | b << 2 | c << 4, in loop order
-    unsigned char nterm[20];
-};
-
-__device__ __forceinline__ double readlane_f64(double v, int lane_uniform) {  // the value of lane `lane_uniform` (a wave-uniform index)
-    const long long b = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)b, lane_uniform), hi = __builtin_amdgcn_readlane((int)(b >> 32), lane_uniform);
-    return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
-}
-__device__ __forceinline__ double wave_max_lanes(double v) {  // max over the wave (order-independent)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
-    return v;
-}
-
-__device__ static int essential5_wave(const double* p1, const double* p2, bool has_K, double fx, double fy, double cx, double cy,
-                                      double* __restrict__ Eout /* global: 10 x 9 */, E5Lds& S) {
-    const int lane = threadIdx.x & 63;
-    // ---- the monomial table (lane 0..19: its own monomial) ----
-    if (lane < 20) {
-        int n = 0;
-#pragma unroll
-        for (int a = 0; a < 4; ++a)
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const int ex = (a == 0) + (b == 0) + (c == 0), ey = (a == 1) + (b == 1) + (c == 1), ez = (a == 2) + (b == 2) + (c == 2);
-                    if (mono_col(ex, ey, ez) == lane) S.term[lane][n++] = (unsigned char)(a | (b << 2) | (c << 4));
-                }
-        S.nterm[lane] = (unsigned char)n;
-    }
-    {
-        const int ex = lane >> 4, ey = (lane >> 2) & 3, ez = lane & 3;
-        S.mcol[lane] = ex + ey + ez <= 3 ? (unsigned char)mono_col(ex, ey, ez) : (unsigned char)0;
-    }
-    // ---- Q^T ----
-    if (lane < 5) {
-        const int i = lane;
-        double x1 = p1[2 * i], y1 = p1[2 * i + 1], x2 = p2[2 * i], y2 = p2[2 * i + 1];
-        if (has_K) {
-            x1 = (x1 - cx) / fx; y1 = (y1 - cy) / fy;
-            x2 = (x2 - cx) / fx; y2 = (y2 - cy) / fy;
-        }
-        const double row[9] = {x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, 1.0};
-#pragma unroll
-        for (int k = 0; k < 9; ++k) S.Q[k * 5 + i] = row[k];
-    }
-    for (int e = lane; e < 81; e += 64) S.P[e] = (e / 9 == e % 9) ? 1.0 : 0.0;
-    wave_sync_lds();
-    // ---- Householder QR of Q^T: lanes 0..4 own a column of Q, lanes 16..24 a row of P ----
-    for (int k = 0; k < 5; ++k) {
-        double norm = 0.0;
-        for (int r = k; r < 9; ++r) norm += S.Q[r * 5 + k] * S.Q[r * 5 + k];
-        norm = sqrt(norm);
-        if (!(norm > 0.0)) return 0;  // (wave-uniform)
-        double v[9];
-#pragma unroll
-        for (int r = 0; r < 9; ++r) v[r] = r < k ? 0.0 : S.Q[r * 5 + k];
-        {
-            const double add = S.Q[k * 5 + k] >= 0.0 ? norm : -norm;
-#pragma unroll
-            for (int r = 0; r < 9; ++r)
-                if (r == k) v[r] += add;
-        }
-        double vv = 0.0;
-#pragma unroll
-        for (int r = 0; r < 9; ++r)
-            if (r >= k) vv += v[r] * v[r];
-        if (!(vv > 0.0)) return 0;
-        wave_sync_lds();  // every lane has read column k before anybody rewrites it
-        if (lane < 5 && lane >= k) {  /* Q <- (I - 2 v v^T / vv) Q, column `lane` */
-            const int c = lane;
-            double d = 0.0;
-#pragma unroll
-            for (int r = 0; r < 9; ++r)
-                if (r >= k) d += v[r] * S.Q[r * 5 + c];
-            d = 2.0 * d / vv;
-#pragma unroll
-            for (int r = 0; r < 9; ++r)
-                if (r >= k) S.Q[r * 5 + c] -= d * v[r];
-        }
-        if (lane >= 16 && lane < 25) {  /* P <- P (I - 2 v v^T / vv), row `lane - 16` */
-            const int r = lane - 16;
-            double d = 0.0;
-#pragma unroll
-            for (int c = 0; c < 9; ++c)
-                if (c >= k) d += S.P[r * 9 + c] * v[c];
-            d = 2.0 * d / vv;
-#pragma unroll
-            for (int c = 0; c < 9; ++c)
-                if (c >= k) S.P[r * 9 + c] -= d * v[c];
-        }
-        wave_sync_lds();
-    }
-    if (lane < 36) S.lin[lane] = S.P[(lane >> 2) * 9 + 5 + (lane & 3)];
-    wave_sync_lds();
-    // ---- the ten cubic constraints: entry (row, col) of the 10 x 20 matrix per lane ----
-    for (int e = lane; e < 200; e += 64) {
-        const int row = e / 20, col = e % 20;
-        const int nt = S.nterm[col];
-        double acc = 0.0;
-        auto mul3 = [&](int e1, int e2, int e3, double sgn) {  // acc += the terms of sgn * l(e1) l(e2) l(e3) that fall on monomial `col`
-            for (int t = 0; t < nt; ++t) {
-                const int tc = S.term[col][t];
-                acc += sgn * (S.lin[4 * e1 + (tc & 3)] * S.lin[4 * e2 + ((tc >> 2) & 3)]) * S.lin[4 * e3 + (tc >> 4)];
-            }
-        };
-        if (row == 0) {  /* det E */
-            const int perm[6][3] = {{0, 1, 2}, {1, 2, 0}, {2, 0, 1}, {0, 2, 1}, {1, 0, 2}, {2, 1, 0}};
-#pragma unroll
-            for (int p = 0; p < 6; ++p) mul3(perm[p][0], 3 + perm[p][1], 6 + perm[p][2], p < 3 ? 1.0 : -1.0);
-        } else {         /* 2 E E^T E - tr(E E^T) E */
-            const int i = (row - 1) / 3, j = (row - 1) % 3;
-            for (int k = 0; k < 3; ++k)
-                for (int l = 0; l < 3; ++l) {
-                    mul3(3 * i + l, 3 * k + l, 3 * k + j, 2.0);
-                    mul3(3 * k + l, 3 * k + l, 3 * i + j, -1.0);
-                }
-        }
-        S.A[e] = acc;
-        S.A0[e] = acc;
-    }
-    wave_sync_lds();
-    // ---- Gauss-Jordan, partial pivoting ----
-    for (int col = 0; col < 10; ++col) {
-        int piv = col;
-        for (int r = col + 1; r < 10; ++r)
-            if (fabs(S.A[r * 20 + col]) > fabs(S.A[piv * 20 + col])) piv = r;
-        if (!(fabs(S.A[piv * 20 + col]) > 1e-300)) return 0;  // (wave-uniform)
-        wave_sync_lds();
-        if (piv != col && lane < 20) {
-            const double t = S.A[piv * 20 + lane];
-            S.A[piv * 20 + lane] = S.A[col * 20 + lane];
-            S.A[col * 20 + lane] = t;
-        }
-        wave_sync_lds();
-        const double inv = 1.0 / S.A[col * 20 + col];
-        wave_sync_lds();
-        if (lane < 20) S.A[col * 20 + lane] *= inv;
-        wave_sync_lds();
-        double f[3];
-        int at[3];
-#pragma unroll
-        for (int t = 0; t < 3; ++t) {  // the 9 x 20 entries of the other rows, three per lane: factors first, then the update
-            const int e = lane + 64 * t;
-            int r = e / 20;
-            if (r >= col) ++r;
-            at[t] = e < 180 ? r * 20 + e % 20 : -1;
-            f[t] = e < 180 ? S.A[r * 20 + col] : 0.0;
-        }
-        wave_sync_lds();
-#pragma unroll
-        for (int t = 0; t < 3; ++t)
-            if (at[t] >= 0 && f[t] != 0.0) S.A[at[t]] -= f[t] * S.A[col * 20 + at[t] % 20];
-        wave_sync_lds();
-    }
-    /* B(z): rows k = e - z f, l = g - z h, m = i - z j; entries = polynomials in z (ascending), degrees 3, 3, 4. An entry per lane:
-     * column j of row r reads e[top_j - k] and f[top_j - k + 1] with top = 2, 5, 9 and 3, 3, 4 coefficients of e */
-    if (lane < 45) {
-        const int r = lane / 15, j = (lane % 15) / 5, k = lane % 5;
-        const double* e = S.A + (4 + 2 * r) * 20 + 10;
-        const double* f = S.A + (5 + 2 * r) * 20 + 10;
-        const int top = j == 0 ? 2 : (j == 1 ? 5 : 9), ne = j == 2 ? 4 : 3;
-        double v;
-        if (k == 0) v = e[top];
-        else if (k < ne) v = e[top - k] - f[top - k + 1];
-        else if (k == ne) v = -f[top - k + 1];
-        else v = 0.0;
-        S.B[lane] = v;
-    }
-    wave_sync_lds();
-    /* det B(z) by cofactor expansion along row 0, coefficient k on lane k: for every coefficient the products enter in the order the
-     * sequential polynomial multiplications add them (first factor's power ascending) */
-    if (lane <= 10) {
-        const int k = lane;
-        double pk = 0.0;
-        for (int c0 = 0; c0 < 3; ++c0) {
-            const int c1 = c0 == 0 ? 1 : (c0 == 1 ? 2 : 0), c2 = c0 == 0 ? 2 : (c0 == 1 ? 0 : 1);
-            const int d1 = c1 == 2 ? 4 : 3, d2 = c2 == 2 ? 4 : 3, d0 = c0 == 2 ? 4 : 3;
-            if (k > d0 + d1 + d2) continue;
-            double tk = 0.0;  /* term[k] = sum_i B[0][c0][i] * minor[k - i] */
-            for (int i = 0; i <= d0; ++i) {
-                const int j = k - i;
-                if (j < 0 || j > d1 + d2) continue;
-                double m1 = 0.0, m2 = 0.0;  /* minor[j] = (B[1][c1] B[2][c2] - B[1][c2] B[2][c1])[j] */
-                for (int a = 0; a <= d1; ++a) {
-                    const int b = j - a;
-                    if (b >= 0 && b <= d2) m1 += S.B[15 + 5 * c1 + a] * S.B[30 + 5 * c2 + b];
-                }
-                for (int a = 0; a <= d2; ++a) {
-                    const int b = j - a;
-                    if (b >= 0 && b <= d1) m2 += S.B[15 + 5 * c2 + a] * S.B[30 + 5 * c1 + b];
-                }
-                tk += S.B[5 * c0 + i] * (m1 - m2);
-            }
-            pk += tk;
-        }
-        S.poly[k] = pk;
-    }
-    wave_sync_lds();
-    // ---- the real roots of poly: Durand-Kerner, root k on lane k ----
-    double cmax = 0.0;
-    for (int k = 0; k <= 10; ++k) cmax = fmax(cmax, fabs(S.poly[k]));
-    if (!(cmax > 0.0)) return 0;
-    int deg = 10;
-    while (deg > 0 && fabs(S.poly[deg]) <= 1e-14 * cmax) --deg;
-    if (deg == 0) return 0;
-    const double lead = S.poly[deg];
-    if (lane <= deg) S.mon[lane] = S.poly[lane] / lead;  /* monic */
-    wave_sync_lds();
-    double bound = 0.0;
-    for (int k = 0; k < deg; ++k) bound = fmax(bound, fabs(S.mon[k]));
-    bound += 1.0;
-    double zr = 0.0, zi = 0.0;
-    {
-        double r0 = 1.0;
-        const double a0 = fabs(S.mon[0]);
-        if (a0 > 0.0) {
-            double y = a0 > 1.0 ? a0 : 1.0;
-            for (int it = 0; it < 80; ++it) {
-                double yp = 1.0;
-                for (int j = 0; j < deg - 1; ++j) yp *= y;
-                y = ((deg - 1) * y + a0 / yp) / deg;
-            }
-            r0 = y;
-        }
-        r0 = fmin(fmax(r0, 0.5), bound);
-        double cr = 1.0, ci = 0.0;
-        for (int k = 0; k < deg; ++k) {
-            if (k == lane) zr = r0 * cr, zi = r0 * ci;
-            const double tr = cr * 0.4 - ci * 0.9, ti = cr * 0.9 + ci * 0.4;
-            cr = tr, ci = ti;
-        }
-    }
-    const bool mine = lane < deg;
-#ifndef E5_EXP_DK_SWEEPS
-#define E5_EXP_DK_SWEEPS 200
-#endif
-    // one sweep: this lane's correction from the iterates the sweep starts with. `change <= 1e-11 bound` of the restatement = no
-    // lane's correction above it (a NaN correction is ignored by fmax there and by the comparison here); tolerance and sweep
-    // limit: see the CPU restatement (solve_oracle.c)
-    const double stop = 1e-11 * bound;
-    auto correct = [&](double pr, double pi, double dr, double di) {
-        const double den = dr * dr + di * di;
-        double ch = 0.0;
-        if (mine && den > 0.0) {
-            const double qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
-            zr -= qr;
-            zi -= qi;
-            ch = fabs(qr) + fabs(qi);
-        }
-        return __ballot(ch > stop) == 0ull;
-    };
-    if (deg == 10) {  // the usual case: coefficients in registers, the other iterates by v_readlane with constant lanes
-        double mm[10];
-#pragma unroll
-        for (int j = 0; j < 10; ++j) mm[j] = S.mon[j];
-        for (int it = 0; it < E5_EXP_DK_SWEEPS; ++it) {
-            double pr = 1.0, pi = 0.0;  /* Horner on the monic polynomial */
-#pragma unroll
-            for (int j = 9; j >= 0; --j) {
-                const double tr = pr * zr - pi * zi + mm[j], ti = pr * zi + pi * zr;
-                pr = tr, pi = ti;
-            }
-            double dr = 1.0, di = 0.0;
-#pragma unroll
-            for (int j = 0; j < 10; ++j) {
-                const double zrj = readlane_f64(zr, j), zij = readlane_f64(zi, j);
-                if (j != lane) {
-                    const double ar = zr - zrj, ai = zi - zij;
-                    const double tr = dr * ar - di * ai, ti = dr * ai + di * ar;
-                    dr = tr, di = ti;
-                }
-            }
-            if (correct(pr, pi, dr, di)) break;
-        }
-    } else {
-        for (int it = 0; it < E5_EXP_DK_SWEEPS; ++it) {
-            double pr = 1.0, pi = 0.0;
-            for (int j = deg - 1; j >= 0; --j) {
-                const double mj = S.mon[j];
-                const double tr = pr * zr - pi * zi + mj, ti = pr * zi + pi * zr;
-                pr = tr, pi = ti;
-            }
-            double dr = 1.0, di = 0.0;
-            for (int j = 0; j < deg; ++j) {
-                const double zrj = readlane_f64(zr, j), zij = readlane_f64(zi, j);  // (j is wave-uniform: two v_readlane, no LDS permute)
-                if (j != lane) {
-                    const double ar = zr - zrj, ai = zi - zij;
-                    const double tr = dr * ar - di * ai, ti = dr * ai + di * ar;
-                    dr = tr, di = ti;
-                }
-            }
-            if (correct(pr, pi, dr, di)) break;
-        }
-    }
-    bool real = mine && !(fabs(zi) > 1e-7 * (1.0 + fabs(zr)));
-    double z = zr;
-    if (real)
-        for (int it = 0; it < 4; ++it) {  /* Newton polish on the real polynomial */
-            double p = S.poly[deg], d = 0.0;
-            for (int j = deg - 1; j >= 0; --j) {
-                d = d * z + p;
-                p = p * z + S.poly[j];
-            }
-            if (!(fabs(d) > 0.0)) break;
-            z -= p / d;
-        }
-    // position of this root in the ascending list (the sequential insertion sort is stable)
-    int rank = 0;
-    for (int j = 0; j < deg; ++j) {
-        const double zj = __shfl(z, j);
-        const int rj = __shfl((int)real, j);
-        if (rj && (zj < z || (zj == z && j < lane))) ++rank;
-    }
-    // ---- x, y and the polish, a real root per lane ----
-    bool ok = false;
-    double Ev[9];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Ev[e] = 0.0;
-    if (real) {
-        double b[3][3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int j = 0; j < 3; ++j) {
-                double v = S.B[15 * i + 5 * j + 4];
-#pragma unroll
-                for (int k = 3; k >= 0; --k) v = v * z + S.B[15 * i + 5 * j + k];
-                b[i][j] = v;
-            }
-        /* [x y 1]^T spans the null space of b: two of its rows, the pair with the largest 2 x 2 determinant */
-        const double d01 = b[0][0] * b[1][1] - b[0][1] * b[1][0], d02 = b[0][0] * b[2][1] - b[0][1] * b[2][0], d12 = b[1][0] * b[2][1] - b[1][1] * b[2][0];
-        int bp = 0;
-        double bd = 0.0;
-        if (fabs(d01) > fabs(bd)) bd = d01, bp = 0;
-        if (fabs(d02) > fabs(bd)) bd = d02, bp = 1;
-        if (fabs(d12) > fabs(bd)) bd = d12, bp = 2;
-        if (fabs(bd) > 0.0) {
-            double u0[3], u1[3];  // the two rows chosen
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                u0[c] = bp == 2 ? b[1][c] : b[0][c];
-                u1[c] = bp == 0 ? b[1][c] : b[2][c];
-            }
-            double x = (u0[1] * u1[2] - u0[2] * u1[1]) / bd;
-            double y = (u0[2] * u1[0] - u0[0] * u1[2]) / bd;
-            double zz = z;
-#ifndef E5_EXP_POLISH
-#define E5_EXP_POLISH 3
-#endif
-            for (int it = 0; it < E5_EXP_POLISH; ++it) {  /* three Gauss-Newton steps on the ten constraints themselves, in (x, y, z) */
-                // (rolled loops and powers by selection: unrolled, the 20 monomials and their derivatives are ~100 live registers
-                // per lane and the kernel spills; the monomial's column comes from a 64-byte table)
-                const double x2 = x * x, x3 = x * x * x, y2 = y * y, y3 = y * y * y, z2 = zz * zz, z3 = zz * zz * zz;
-                auto pw = [](double v1, double v2, double v3, int e) { return e == 0 ? 1.0 : (e == 1 ? v1 : (e == 2 ? v2 : v3)); };
-                double JtJ[3][3] = {{0, 0, 0}, {0, 0, 0}, {0, 0, 0}}, Jtr[3] = {0, 0, 0};
-#pragma clang loop unroll(disable)
-                for (int row = 0; row < 10; ++row) {
-                    double rv = 0.0, g0 = 0.0, g1 = 0.0, g2 = 0.0;
-#pragma clang loop unroll(disable)
-                    for (int ex = 0; ex <= 3; ++ex)
-#pragma clang loop unroll(disable)
-                        for (int ey = 0; ex + ey <= 3; ++ey)
-#pragma clang loop unroll(disable)
-                            for (int ez = 0; ex + ey + ez <= 3; ++ez) {
-                                const double cf = S.A0[row * 20 + S.mcol[16 * ex + 4 * ey + ez]];
-                                const double pxe = pw(x, x2, x3, ex), pye = pw(y, y2, y3, ey), pze = pw(zz, z2, z3, ez);
-                                rv += cf * (pxe * pye) * pze;
-                                if (ex) g0 += cf * (ex * pw(x, x2, x3, ex - 1) * pye) * pze;
-                                if (ey) g1 += cf * (pxe * (ey * pw(y, y2, y3, ey - 1))) * pze;
-                                if (ez) g2 += cf * (pxe * pye) * (ez * pw(zz, z2, z3, ez - 1));
-                            }
-                    const double g[3] = {g0, g1, g2};
-#pragma unroll
-                    for (int u = 0; u < 3; ++u) {
-                        Jtr[u] += g[u] * rv;
-#pragma unroll
-                        for (int v = 0; v < 3; ++v) JtJ[u][v] += g[u] * g[v];
-                    }
-                }
-                /* 3 x 3 solve by cofactors */
-                const double c00 = JtJ[1][1] * JtJ[2][2] - JtJ[1][2] * JtJ[2][1], c01 = JtJ[1][2] * JtJ[2][0] - JtJ[1][0] * JtJ[2][2],
-                             c02 = JtJ[1][0] * JtJ[2][1] - JtJ[1][1] * JtJ[2][0];
-                const double dt = JtJ[0][0] * c00 + JtJ[0][1] * c01 + JtJ[0][2] * c02;
-                if (!(fabs(dt) > 0.0)) break;
-                const double c10 = JtJ[0][2] * JtJ[2][1] - JtJ[0][1] * JtJ[2][2], c11 = JtJ[0][0] * JtJ[2][2] - JtJ[0][2] * JtJ[2][0],
-                             c12 = JtJ[0][1] * JtJ[2][0] - JtJ[0][0] * JtJ[2][1];
-                const double c20 = JtJ[0][1] * JtJ[1][2] - JtJ[0][2] * JtJ[1][1], c21 = JtJ[0][2] * JtJ[1][0] - JtJ[0][0] * JtJ[1][2],
-                             c22 = JtJ[0][0] * JtJ[1][1] - JtJ[0][1] * JtJ[1][0];
-                const double dx = (c00 * Jtr[0] + c10 * Jtr[1] + c20 * Jtr[2]) / dt;
-                const double dy = (c01 * Jtr[0] + c11 * Jtr[1] + c21 * Jtr[2]) / dt;
-                const double dz = (c02 * Jtr[0] + c12 * Jtr[1] + c22 * Jtr[2]) / dt;
-                if (!(fabs(dx) + fabs(dy) + fabs(dz) < 1e300)) break;
-                x -= dx, y -= dy, zz -= dz;
-            }
-            double nrm = 0.0;
-#pragma unroll
-            for (int e = 0; e < 9; ++e) {
-                Ev[e] = S.lin[4 * e] * x + S.lin[4 * e + 1] * y + S.lin[4 * e + 2] * zz + S.lin[4 * e + 3];
-                nrm += Ev[e] * Ev[e];
-            }
-            nrm = sqrt(nrm);
-            if (nrm > 0.0 && nrm < 1e300) {
-                ok = true;
-#pragma unroll
-                for (int e = 0; e < 9; ++e) Ev[e] = Ev[e] / nrm;
-            }
-        }
-    }
-    // the models leave in ascending root order, the failed ones squeezed out
-    int slot = 0, n = 0;
-    for (int j = 0; j < deg; ++j) {
-        const int okj = __shfl((int)ok, j), rkj = __shfl(rank, j);
-        n += okj;
-        if (okj && rkj < rank) ++slot;
-    }
-    if (ok)
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Eout[9 * slot + e] = Ev[e];
-    return n;
-}
-
-/* least squares min |A x - b| for an R x C system (C <= R <= 6, C <= 5), Householder QR on a copy, every loop unrolled: the working array and the
- * callers' matrices stay in registers (as run-time-indexed arrays they are scratch memory). Returns 0 if a column collapses. Same
- * operations in the same order as lsq_small(R, C, ...) of the CPU restatement (solve_oracle.c). */
-template <int R, int C>
-__device__ __forceinline__ int lsq_rc(const double* A, const double* b, double* x) {
-    constexpr int r = R, c = C;
-    static_assert(C <= R && R <= 6, "an over-determined or square system of at most six rows");
-    double Q[R][C + 1];
-#pragma unroll
-    for (int i = 0; i < r; ++i) {
-#pragma unroll
-        for (int j = 0; j < c; ++j) Q[i][j] = A[i * c + j];
-        Q[i][c] = b[i];
-    }
-#pragma unroll
-    for (int j = 0; j < c; ++j) {
-        double nrm = 0.0;
-#pragma unroll
-        for (int i = j; i < r; ++i) nrm += Q[i][j] * Q[i][j];
-        nrm = sqrt(nrm);
-        if (!(nrm > 0.0)) return 0;
-        const double alpha = Q[j][j] > 0.0 ? -nrm : nrm;
-        double v[6];
-#pragma unroll
-        for (int i = j; i < r; ++i) v[i] = Q[i][j];
-        v[j] -= alpha;
-        double vv = 0.0;
-#pragma unroll
-        for (int i = j; i < r; ++i) vv += v[i] * v[i];
-        if (!(vv > 0.0)) return 0;
-#pragma unroll
-        for (int k = j; k <= c; ++k) {
-            double d = 0.0;
-#pragma unroll
-            for (int i = j; i < r; ++i) d += v[i] * Q[i][k];
-            d = 2.0 * d / vv;
-#pragma unroll
-            for (int i = j; i < r; ++i) Q[i][k] -= d * v[i];
-        }
-        Q[j][j] = alpha;
-    }
-#pragma unroll
-    for (int j = c - 1; j >= 0; --j) {
-        double s = Q[j][c];
-#pragma unroll
-        for (int k = j + 1; k < c; ++k) s -= Q[j][k] * x[k];
-        x[j] = s / Q[j][j];
-    }
-#pragma unroll
-    for (int j = 0; j < c; ++j)
-        if (!(fabs(x[j]) < 1e300)) return 0;
-    return 1;
-}
-template <int C>
-__device__ __forceinline__ int lsq6(const double* A, const double* b, double* x) { return lsq_rc<6, C>(A, b, x); }
-
-// The N x N eigenproblem (N = 9, 12) by ONE WAVE on one shared copy of A and V, in the ROUND-ROBIN ordering of
-// the CPU restatement (solve_oracle.c)'s jacobi_eig_rr: a sweep is N' - 1 rounds of N' / 2 disjoint rotations (N' = N rounded up to even; position 0
-// holds index 0, position j >= 1 holds 1 + ((j - 1 - round) mod (N' - 1)), pair i = positions i and N' - 1 - i, index N is a bye).
-// The unit of work is an ITEM (pair i, k): a lane owns item `lane` and, for N = 12, item 64 + lane (72 items). The lane forms the rotation of
-// its items' pairs ITSELF from the matrix the round starts with (the same operations on the same values in every lane that
-// needs them: the same bits, and no trip through LDS and no barrier to hand six rotations round), then the two stages —
-// columns p, q of row k; rows p, q at column k together with the eigenvector columns — run with every read of a stage issued before
-// its first write: no element is written twice inside a stage and none is read by another item after it was written, and element by
-// element the arithmetic is the restatement's, so the result is the same bits. A wave's LDS operations execute in program order:
-// the barriers only pin the compiler. (Until round 5 lanes 0..5 formed the rotations and handed them over through LDS, and a
-// stage made two dependent passes over its 72 items: ~3.7 k cycles per round, 133 us for the front half of a five-point EPnP sample.)
-struct JacRound {   // (kept for the callers' LDS layouts; the rotations no longer pass through it)
-    double c[8], s[8];
-    int p[8], q[8], on[8];
-};
-template <int N>
-__device__ __forceinline__ void jacobi_wave(double* A, double* V, double* w, JacRound& R) {
-    (void)R;
-    constexpr int n = N, np = N + (N & 1), half = np / 2;
-    constexpr int ITEMS = half * n, PASSES = (ITEMS + 63) / 64;
-    const int lane = threadIdx.x & 63;
-    for (int e = lane; e < n * n; e += 64) V[e] = (e / n == e % n) ? 1.0 : 0.0;
-    wave_sync_lds();
-#ifndef JAC_EXP_SWEEPS
-#define JAC_EXP_SWEEPS 60
-#endif
-    for (int sweep = 0; sweep < JAC_EXP_SWEEPS; ++sweep) {
-        double off = 0.0, diag = 0.0;
-        for (int p = 0; p < n; ++p) {
-            diag += A[p * n + p] * A[p * n + p];
-            for (int q = p + 1; q < n; ++q) off += A[p * n + q] * A[p * n + q];
-        }
-        if (off <= 1e-60 || off <= 1e-32 * diag) break;
-        for (int round = 0; round < np - 1; ++round) {
-            int ip[PASSES], iq[PASSES], ik[PASSES];
-            bool on[PASSES];
-            double rc[PASSES], rs[PASSES];
-#pragma unroll
-            for (int ps = 0; ps < PASSES; ++ps) {
-                const int e = lane + 64 * ps, i = e / n, j1 = i, j2 = np - 1 - i;
-                ik[ps] = e % n;
-                const int a = j1 == 0 ? 0 : 1 + ((j1 - 1 - round) % (np - 1) + (np - 1)) % (np - 1);
-                const int b = 1 + ((j2 - 1 - round) % (np - 1) + (np - 1)) % (np - 1);
-                const int p = a < b ? a : b, q = a < b ? b : a;
-                ip[ps] = p, iq[ps] = q;
-                on[ps] = false, rc[ps] = 1.0, rs[ps] = 0.0;
-                if (e < ITEMS && q < n) {
-                    const double apq = A[p * n + q];
-                    if (apq != 0.0) {
-                        const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
-                        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-                        rc[ps] = 1.0 / sqrt(t * t + 1.0), rs[ps] = t * rc[ps];
-                        on[ps] = true;
-                    }
-                }
-            }
-            {   /* columns p, q of every pair: row k of the item */
-                double akp[PASSES], akq[PASSES];
-#pragma unroll
-                for (int ps = 0; ps < PASSES; ++ps)
-                    if (on[ps]) akp[ps] = A[ik[ps] * n + ip[ps]], akq[ps] = A[ik[ps] * n + iq[ps]];
-                wave_sync_lds();   // (every lane's reads of the round's start, the pivots above included, before the first write)
-#pragma unroll
-                for (int ps = 0; ps < PASSES; ++ps)
-                    if (on[ps]) {
-                        A[ik[ps] * n + ip[ps]] = rc[ps] * akp[ps] - rs[ps] * akq[ps];
-                        A[ik[ps] * n + iq[ps]] = rs[ps] * akp[ps] + rc[ps] * akq[ps];
-                    }
-            }
-            wave_sync_lds();
-            {   /* rows p, q of every pair at column k; the eigenvector columns */
-                double apk[PASSES], aqk[PASSES], vkp[PASSES], vkq[PASSES];
-#pragma unroll
-                for (int ps = 0; ps < PASSES; ++ps)
-                    if (on[ps]) {
-                        apk[ps] = A[ip[ps] * n + ik[ps]], aqk[ps] = A[iq[ps] * n + ik[ps]];
-                        vkp[ps] = V[ik[ps] * n + ip[ps]], vkq[ps] = V[ik[ps] * n + iq[ps]];
-                    }
-                wave_sync_lds();
-#pragma unroll
-                for (int ps = 0; ps < PASSES; ++ps)
-                    if (on[ps]) {
-                        A[ip[ps] * n + ik[ps]] = rc[ps] * apk[ps] - rs[ps] * aqk[ps];
-                        A[iq[ps] * n + ik[ps]] = rs[ps] * apk[ps] + rc[ps] * aqk[ps];
-                        V[ik[ps] * n + ip[ps]] = rc[ps] * vkp[ps] - rs[ps] * vkq[ps];
-                        V[ik[ps] * n + iq[ps]] = rs[ps] * vkp[ps] + rc[ps] * vkq[ps];
-                    }
-            }
-            wave_sync_lds();
-        }
-    }
-    for (int i = 0; i < n; ++i) w[i] = A[i * n + i];
-}
-
-/* homography4 by one wave: L^T L (shared, an upper-triangle entry per lane, the four points added in order), the 9 x 9 eigenproblem by
- * jacobi_wave, the rest on identical values in every lane. a, b: this sample's 4 x 2 points. Returns 1 / 0; H (9) valid in every lane. */
-__device__ static int homography4_wave(const double* a, const double* b, double* H, double* LtL /* 81 */, double* V /* 81 */, JacRound& R) {
-    const int lane = threadIdx.x & 63;
-    const int count = 4;
-    double cM[2] = {0, 0}, cm[2] = {0, 0}, sM[2] = {0, 0}, sm[2] = {0, 0};
-#pragma unroll
-    for (int i = 0; i < count; ++i) {
-        cM[0] += a[2 * i]; cM[1] += a[2 * i + 1];
-        cm[0] += b[2 * i]; cm[1] += b[2 * i + 1];
-    }
-#pragma unroll
-    for (int k = 0; k < 2; ++k) cM[k] /= count, cm[k] /= count;
-#pragma unroll
-    for (int i = 0; i < count; ++i)
-#pragma unroll
-        for (int k = 0; k < 2; ++k) {
-            sM[k] += fabs(a[2 * i + k] - cM[k]);
-            sm[k] += fabs(b[2 * i + k] - cm[k]);
-        }
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-        if (fabs(sM[k]) < 2.220446049250313e-16 || fabs(sm[k]) < 2.220446049250313e-16) return 0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k) sM[k] = count / sM[k], sm[k] = count / sm[k];
-    for (int e = lane; e < 81; e += 64) {
-        const int j = e / 9, k = e % 9;
-        if (k < j) continue;
-        double acc = 0.0;
-#pragma unroll
-        for (int i = 0; i < count; ++i) {
-            const double x = (b[2 * i] - cm[0]) * sm[0], y = (b[2 * i + 1] - cm[1]) * sm[1];
-            const double X = (a[2 * i] - cM[0]) * sM[0], Y = (a[2 * i + 1] - cM[1]) * sM[1];
-            const double Lx[9] = {X, Y, 1, 0, 0, 0, -x * X, -x * Y, -x};
-            const double Ly[9] = {0, 0, 0, X, Y, 1, -y * X, -y * Y, -y};
-            double lxj = 0, lxk = 0, lyj = 0, lyk = 0;
-#pragma unroll
-            for (int q = 0; q < 9; ++q) {
-                if (q == j) lxj = Lx[q], lyj = Ly[q];
-                if (q == k) lxk = Lx[q], lyk = Ly[q];
-            }
-            acc += lxj * lxk + lyj * lyk;
-        }
-        LtL[j * 9 + k] = acc;
-        LtL[k * 9 + j] = acc;
-    }
-    wave_sync_lds();
-    double w[9];
-    jacobi_wave<9>(LtL, V, w, R);
-    int best = 0;
-#pragma unroll
-    for (int i = 1; i < 9; ++i) {
-        double wb = 0;
-#pragma unroll
-        for (int q = 0; q < 9; ++q)
-            if (q == best) wb = w[q];
-        if (w[i] < wb) best = i;
-    }
-    double H0[9];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H0[k] = V[k * 9 + best];
-    const double inv[9] = {1.0 / sm[0], 0, cm[0], 0, 1.0 / sm[1], cm[1], 0, 0, 1};
-    const double n2[9] = {sM[0], 0, -cM[0] * sM[0], 0, sM[1], -cM[1] * sM[1], 0, 0, 1};
-    double T[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) T[3 * r + c] = inv[3 * r] * H0[c] + inv[3 * r + 1] * H0[3 + c] + inv[3 * r + 2] * H0[6 + c];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) H[3 * r + c] = T[3 * r] * n2[c] + T[3 * r + 1] * n2[3 + c] + T[3 * r + 2] * n2[6 + c];
-    if (!(fabs(H[8]) > 0.0)) return 0;
-    const double s = 1.0 / H[8];
-#pragma unroll
-    for (int k = 0; k < 9; ++k) H[k] *= s;
-    return 1;
-}
 
 // EPnP by one wave. Lane l accumulates the points l, l + 64, ... of every pass over the points; the partial sums are added in
 // lane order — for at most 64 points that is the sequential sum over the points, bit for bit, and the CPU restatement defines the
@@ -1162,8 +418,6 @@ __device__ static double epnp_back_variant(int m, const int* idx, const double* 
     }
 }
 #undef EPNP_ALPHAS
-
-constexpr int SOLVE_WAVES = 4;   // samples (waves) per workgroup of the minimal-sample kernels
 
 // Samples of at most 64 points (the RANSAC loop's five-point samples) in two launches. Front: ONE WAVE per sample, SOLVE_WAVES samples
 // per workgroup (no workgroup barrier anywhere: waves return on their own), leaving the sample's frame — 130 doubles: c0 3, axes 9,

@@ -213,6 +213,11 @@ class HipContext:
             vp(edges_dev), edge_cap, vp(total_dev), vp(stats_dev) if stats_dev else None))
 
     # ---- profiling -------------------------------------------------------------------------
+    def lmeds_batch(self, kind: str, uv1, uv2, samples, K=None):
+        """eacham_lmeds_batch: LMedS two-view estimation of a list of pairs in one call (eacham_amd/lmeds.py)."""
+        from . import lmeds
+        return lmeds.lmeds_batch(self, kind, uv1, uv2, samples, K)
+
     def profile_enable(self, on: bool = True):
         self._check(self._L.eacham_profile_enable(self._h, int(on)))
 

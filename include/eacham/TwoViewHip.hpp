@@ -22,10 +22,12 @@
 // candidate with the most good points wins (first on ties).
 #pragma once
 
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
 #include <limits>
+#include <stdexcept>
 #include <vector>
 
 #include "CvSampling.hpp"
@@ -385,6 +387,88 @@ inline RobustModel FindHomography(Context& ctx, const std::vector<double>& uv1, 
         Mat3 H;
         if (RefitHomography(uv1, uv2, r.mask, H)) r.model = H;
     }
+    return r;
+}
+
+namespace twoview_detail {
+
+// lmeds() for a list of pairs through ONE eacham_lmeds_batch call: every pair's samples are drawn as lmeds() draws them (the
+// OpenCV stream restarts from its seed for every pair, as every OpenCV call does), the device solves, scores, picks and
+// classifies all pairs without a host turn. result[p] (and traces[p]) equal lmeds() on pair p alone, field for field.
+inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m, const std::vector<std::vector<double>>& uv1,
+                                            const std::vector<std::vector<double>>& uv2, const double* K4, int maxIters, double confidence,
+                                            uint64_t seed, Sampling sampling, std::vector<LmedsTrace>* traces) {
+    const size_t P = uv1.size();
+    std::vector<RobustModel> out(P);
+    if (traces) traces->assign(P, LmedsTrace());
+    if (uv2.size() != P) throw std::invalid_argument("lmeds_batch: uv1 and uv2 list different numbers of pairs");
+    if (P == 0) return out;
+    std::vector<int64_t> point_ptr(P + 1, 0), sample_ptr(P + 1, 0);
+    std::vector<double> a, b;
+    std::vector<int32_t> idx;
+    for (size_t p = 0; p < P; ++p) {
+        const int n = (int)(uv1[p].size() / 2);
+        if (n >= m && uv2[p].size() == uv1[p].size() && maxIters > 0) {   // (otherwise lmeds() returns at once: an empty problem here)
+            const int iterations = std::min(maxIters, std::max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3));
+            const std::vector<int32_t> s = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1[p], uv2[p], seed, sampling);
+            out[p].iterations = (int)(s.size() / m);
+            if (traces) (*traces)[p].samples = s;
+            a.insert(a.end(), uv1[p].begin(), uv1[p].begin() + 2 * (size_t)n);
+            b.insert(b.end(), uv2[p].begin(), uv2[p].begin() + 2 * (size_t)n);
+            idx.insert(idx.end(), s.begin(), s.end());
+        }
+        point_ptr[p + 1] = (int64_t)(a.size() / 2);
+        sample_ptr[p + 1] = (int64_t)(idx.size() / m);
+    }
+    std::vector<double> models(P * 9);
+    std::vector<float> med(P), thr(P);
+    std::vector<int32_t> inl(P), win(P * 3), ncand(P);
+    std::vector<uint8_t> masks(a.size() / 2 + 1);
+    ctx.check(eacham_lmeds_batch(ctx.get(), solve_kind, (int)P, point_ptr.data(), a.data(), b.data(), K4, sample_ptr.data(), idx.data(),
+                                 models.data(), med.data(), thr.data(), inl.data(), masks.data(), win.data(), ncand.data()));
+    for (size_t p = 0; p < P; ++p) {
+        if (traces) (*traces)[p].candidates = ncand[p];
+        if (win[3 * p] < 0) continue;
+        const int n = (int)(point_ptr[p + 1] - point_ptr[p]);
+        RobustModel& r = out[p];
+        for (int e = 0; e < 9; ++e) r.model[e] = models[9 * p + e];
+        r.median = med[p];
+        r.mask.assign(masks.begin() + point_ptr[p], masks.begin() + point_ptr[p + 1]);
+        r.inliers = inl[p];
+        r.ok = true;
+        if (traces) {
+            LmedsTrace& t = (*traces)[p];
+            t.candidate = win[3 * p], t.sample = win[3 * p + 1], t.root = win[3 * p + 2];
+            t.sigma = std::max(2.5 * 1.4826 * (1.0 + 5.0 / std::max(n - m, 1)) * std::sqrt((double)med[p]), 0.001);   // as lmeds() states it
+            t.threshold = thr[p];
+            t.winner = r.model;
+        }
+    }
+    return out;
+}
+
+}  // namespace twoview_detail
+
+// FindEssentialMat for every pair of a list — the geometric verification of a whole match graph — through one
+// eacham_lmeds_batch call. uv1[p], uv2[p]: the matches of pair p; K4 is shared. result[p] equals FindEssentialMat(ctx, uv1[p],
+// uv2[p], K4, maxIters, 12345, prob, sampling) field for field (Sampling::Counter draws with that default seed).
+inline std::vector<RobustModel> FindEssentialMatBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                      const std::vector<std::vector<double>>& uv2, const double* K4, int maxIters = 1000,
+                                                      double prob = 0.99, Sampling sampling = Sampling::OpenCV,
+                                                      std::vector<LmedsTrace>* traces = nullptr) {
+    return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_ESSENTIAL5, 5, uv1, uv2, K4, maxIters, prob, 12345, sampling, traces);
+}
+// FindHomography for every pair of a list: one eacham_lmeds_batch call, then the host refit of FindHomography per pair.
+inline std::vector<RobustModel> FindHomographyBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                    const std::vector<std::vector<double>>& uv2, int maxIters = 100, double confidence = 0.999,
+                                                    Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
+    std::vector<RobustModel> r = twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_HOMOGRAPHY4, 4, uv1, uv2, nullptr, maxIters, confidence, 12345,
+                                                             sampling, traces);
+    for (size_t p = 0; p < r.size(); ++p)
+        if (r[p].ok && uv1[p].size() / 2 > 4) {
+            Mat3 H;
+            if (RefitHomography(uv1[p], uv2[p], r[p].mask, H)) r[p].model = H;
+        }
     return r;
 }
 

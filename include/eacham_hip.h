@@ -412,6 +412,33 @@ int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, const double* 
 int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* object_points, const double* image_points, const double* K,
                      int sample_size, int n_samples, const int32_t* sample_idx, double* models, int32_t* n_models);
 
+/* ---- LMedS two-view estimation for a whole list of pairs ---------------------------------------------------------
+ * cv::findEssentialMat(LMEDS) / cv::findHomography(LMEDS) for every edge of a match graph in ONE call: what
+ * eacham_solve_minimal + eacham_score_hypotheses + the LMedS rule between them (include/eacham/TwoViewHip.hpp) do for
+ * one pair, for n_problems pairs with no host turn between the stages and a launch count that does not depend on
+ * n_problems. Problem p owns the points point_ptr[p] .. point_ptr[p+1] of a / b (rows of 2 doubles) and the samples
+ * sample_ptr[p] .. sample_ptr[p+1] of sample_idx (4 / 5 indices per sample, LOCAL to the problem's points; drawing them
+ * stays with the caller, as for eacham_solve_minimal). Both offset tables have n_problems + 1 entries, start at 0 and
+ * do not decrease. kind = EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5; K = fx fy cx cy shared by all problems
+ * (NULL as in eacham_solve_minimal). Per problem, with n points and m = 4 / 5:
+ *   every sample is solved and the candidates are flattened in sample order, then root order; every candidate's median
+ *   error over the problem's own points is taken; the winner is the FIRST candidate with the smallest non-NaN median
+ *   (TIES: equal medians keep the earlier candidate); sigma = max(2.5 * 1.4826 * (1 + 5 / max(n - m, 1)) *
+ *   sqrt((double)median), 0.001) in fp64, threshold = (float)(sigma * sigma); mask[i] = err_winner(i) <= threshold.
+ * Outputs (each optional, NULL = not wanted): models n_problems x 9 (the winner as solved), medians, thresholds,
+ * inliers (mask bytes set), masks (point_ptr[n_problems] bytes, in the layout of a / b), winner n_problems x 3 =
+ * {candidate index in the problem's flattened list, sample (local to the problem), root}, n_candidates.
+ * The "NONE" RECORD: a problem with fewer than m points (its samples are then not looked at), with no samples, with no
+ * candidate (every sample degenerate) or with only NaN medians gets winner -1 -1 -1, a zero model, a NaN median, a
+ * zero threshold, zero inliers and a zero mask; n_candidates is still its count. Its neighbours are not affected.
+ * Bit-identical, output by output, with the composition of eacham_solve_minimal and eacham_score_hypotheses per problem.
+ * EACHAM_ERR_INVALID: bad kind, negative size, an offset table that is null / does not start at 0 / decreases, a null
+ * required array, a sample index outside its problem (checked on the host before anything is launched; the message
+ * names the problem). */
+int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t* point_ptr, const double* a, const double* b,
+                       const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, double* models, float* medians,
+                       float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates);
+
 /* ---- view-graph query on the CSR match graph --------------------------
  * Graph::GetBestPairForValid (/root/reference/modules/sfm/data/Graph.h:59-106) evaluated directly on the
  * wire format of eacham_match_all_pairs: pair p with counts[p] > 0 is the factor f1 -> f2 with matches
