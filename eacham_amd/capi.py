@@ -25,6 +25,7 @@ KERNEL_TRIANGULATE = 6
 KERNEL_SCORE = 7
 SCORE_ESSENTIAL, SCORE_HOMOGRAPHY, SCORE_PNP = 0, 1, 2
 SOLVE_HOMOGRAPHY4, SOLVE_ESSENTIAL5 = 0, 1
+TWOVIEW_POSES, TWOVIEW_SOLUTIONS = 0, 1
 
 
 class EachamError(RuntimeError):
@@ -89,6 +90,8 @@ def lib() -> C.CDLL:
     L.eacham_solve_pnp.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     if hasattr(L, "eacham_lmeds_batch"):  # (absent from older builds selected with EACHAM_HIP_LIB; calling it on one raises AttributeError)
         L.eacham_lmeds_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "eacham_two_view_batch"):  # (likewise)
+        L.eacham_two_view_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
     L.eacham_graph_best_pair.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "eacham_graph_create"):
         L.eacham_graph_create.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, C.POINTER(vp)]

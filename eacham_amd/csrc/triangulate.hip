@@ -276,6 +276,142 @@ __global__ __launch_bounds__(TRI_BLOCK) void two_view_kernel(int n, const double
     keep[id] = ok ? 1 : 0;
 }
 
+// ---- eacham_two_view_batch: the same per-item work for a LIST of problems, and the reference's choice among each
+// problem's candidates, without a host turn ---------------------------------------------------------------------------
+// two_view_kernel's arithmetic, statement for statement, as functions for tvb_points_kernel (two_view_kernel itself keeps its
+// body: taking it apart moves its register allocation). The point of one (transform, match) ...
+__device__ __forceinline__ void two_view_point(const double2 p1, const double2 p2, const double (&K)[4], const double (&I4)[16],
+                                               const double* __restrict__ T, double (&X)[3]) {
+    const double x1 = (p1.x - K[2]) / K[0], y1 = (p1.y - K[3]) / K[1];
+    const double x2 = (p2.x - K[2]) / K[0], y2 = (p2.y - K[3]) / K[1];
+    double A[4][4], x[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        A[1][j] = x1 * I4[8 + j] - I4[j];
+        A[0][j] = y1 * I4[8 + j] - I4[4 + j];
+        A[3][j] = x2 * T[8 + j] - T[j];
+        A[2][j] = y2 * T[8 + j] - T[4 + j];
+    }
+    null_vector_4x4(A, x);
+    X[0] = x[0] / x[3], X[1] = x[1] / x[3], X[2] = x[2] / x[3];
+}
+// ... and whether the reference keeps it: z > 0, the float reprojection error in camera 1, the triangulation angle
+__device__ __forceinline__ bool two_view_keep(const double2 p1, const double (&K)[4], const double (&I4)[16], const double* __restrict__ T,
+                                              const double (&X)[3], float max_err, float min_angle, int angle_strict) {
+    bool ok = false;
+    if (!(X[2] <= 0.0)) {
+        const double u = (K[0] * X[0]) / X[2] + K[2], v = (K[1] * X[1]) / X[2] + K[3];
+        const float err = (float)sqrt((p1.x - u) * (p1.x - u) + (p1.y - v) * (p1.y - v));
+        const double ang = tri_angle(I4, T, X);
+        ok = err < max_err && (angle_strict ? ang > (double)min_angle : !(ang < (double)min_angle));
+    }
+    return ok;
+}
+
+constexpr unsigned char TVB_KEEP = 1, TVB_CHEIRAL = 2;   // the flag byte of an item
+
+// K1: flat over the items (problem, candidate, match): item_ptr[p] = items before problem p (the host's int64 prefix of
+// n_p * nt_p), a binary search finds the owning problem as tri_pairs_kernel finds its track, so problems of 1 match and of
+// 3000 cost the same per item. Writes the point and the flag byte (keep under the problem's rule; for a POSES problem also
+// recoverPose's cheirality test) to the workspace.
+__global__ __launch_bounds__(TRI_BLOCK) void tvb_points_kernel(
+    int n_problems, const long long* __restrict__ item_ptr, const long long* __restrict__ point_ptr,
+    const long long* __restrict__ transform_ptr, const int* __restrict__ rule, const double2* __restrict__ uv1,
+    const double2* __restrict__ uv2, const double* __restrict__ Kdev, const double* __restrict__ transforms,
+    const unsigned char* __restrict__ in_mask, float max_err, float min_angle, double dist, double* __restrict__ ws_points,
+    unsigned char* __restrict__ ws_flags) {
+    const long long id = (long long)blockIdx.x * TRI_BLOCK + threadIdx.x;
+    if (id >= item_ptr[n_problems]) return;
+    int lo = 0, hi = n_problems;  // largest p with item_ptr[p] <= id: the one problem that owns items there
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (item_ptr[mid] <= id) lo = mid; else hi = mid;
+    }
+    const int p = lo;
+    const long long base = point_ptr[p], local = id - item_ptr[p];
+    const int n = (int)(point_ptr[p + 1] - base);
+    const int k = (int)(local / n), i = (int)(local % n);
+    const int solutions = rule[p];   // EACHAM_TWOVIEW_SOLUTIONS = 1: the strict angle test, no cheirality vote
+    const double K[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
+    const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const double* T = transforms + 16 * (size_t)(transform_ptr[p] + k);
+    const double2 p1 = uv1[base + i], p2 = uv2[base + i];
+    double X[3];
+    two_view_point(p1, p2, K, I4, T, X);
+    double* out = ws_points + 3 * (size_t)id;
+    out[0] = X[0];
+    out[1] = X[1];
+    out[2] = X[2];
+    unsigned char f = two_view_keep(p1, K, I4, T, X, max_err, min_angle, solutions) ? TVB_KEEP : 0;
+    if (!solutions) {
+        const double z1 = X[2], z2 = ((T[8] * X[0] + T[9] * X[1]) + T[10] * X[2]) + T[11];   // (no contraction: the host loop's roundings)
+        if ((!in_mask || in_mask[base + i]) && z1 > 0 && z1 < dist && z2 > 0 && z2 < dist) f |= TVB_CHEIRAL;
+    }
+    ws_flags[id] = f;
+}
+
+// K2: one workgroup per problem: per-candidate counts of the voting bit (wave ballots, then LDS across the waves), the
+// sequential winner rule of the problem's kind, then the winner's points / keep / cheirality mask into the compact output.
+__global__ __launch_bounds__(TRI_BLOCK) void tvb_select_kernel(
+    const long long* __restrict__ item_ptr, const long long* __restrict__ point_ptr, const long long* __restrict__ transform_ptr,
+    const int* __restrict__ rule, int min_solution_matches, const double* __restrict__ ws_points,
+    const unsigned char* __restrict__ ws_flags, int* __restrict__ winner, int* __restrict__ good, int* __restrict__ kept,
+    int* __restrict__ cand_counts, double* __restrict__ points, unsigned char* __restrict__ keep, unsigned char* __restrict__ pose_mask) {
+    constexpr int WAVES = TRI_BLOCK / 64;
+    __shared__ int wcount[2][WAVES];
+    const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long base = point_ptr[p], t0 = transform_ptr[p], items = item_ptr[p];
+    const int n = (int)(point_ptr[p + 1] - base), nt = (int)(transform_ptr[p + 1] - t0);
+    const int solutions = rule[p];
+    const unsigned char vote = solutions ? TVB_KEEP : TVB_CHEIRAL;
+    int best = solutions ? -1 : (nt > 0 ? 0 : -1), best_count = 0;
+    for (int k = 0; k < nt; ++k) {   // (k, the trip counts below and the barriers are uniform over the workgroup)
+        const unsigned char* f = ws_flags + items + (long long)k * n;
+        int c = 0;
+        for (int i0 = wave * 64; i0 < n; i0 += TRI_BLOCK) {
+            const int i = i0 + lane;
+            c += __popcll(__ballot(i < n && (f[i] & vote)));
+        }
+        if (lane == 0) wcount[k & 1][wave] = c;
+        __syncthreads();   // (two buffers: the next candidate's writes cannot overtake this one's reads)
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) total += wcount[k & 1][w];
+        if (threadIdx.x == 0) cand_counts[t0 + k] = total;
+        if (total > best_count) { best_count = total; best = k; }   // strictly larger: the first one stays
+    }
+    if (solutions && !(best_count > min_solution_matches)) best = -1;
+    const unsigned char* f = ws_flags + items + (long long)(best < 0 ? 0 : best) * n;
+    const double* src = ws_points + 3 * (size_t)(items + (long long)(best < 0 ? 0 : best) * n);
+    int c = 0;
+    for (int i0 = wave * 64; i0 < n; i0 += TRI_BLOCK) {
+        const int i = i0 + lane;
+        unsigned char fl = 0;
+        if (i < n) {
+            double X0 = 0.0, X1 = 0.0, X2 = 0.0;
+            if (best >= 0) { fl = f[i]; X0 = src[3 * (size_t)i]; X1 = src[3 * (size_t)i + 1]; X2 = src[3 * (size_t)i + 2]; }
+            double* out = points + 3 * (size_t)(base + i);
+            out[0] = X0;
+            out[1] = X1;
+            out[2] = X2;
+            keep[base + i] = fl & TVB_KEEP ? 1 : 0;
+            pose_mask[base + i] = fl & TVB_CHEIRAL ? 1 : 0;
+        }
+        c += __popcll(__ballot(fl & TVB_KEEP));
+    }
+    __syncthreads();   // every wave has read the last candidate's counts
+    if (lane == 0) wcount[0][wave] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int total = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) total += wcount[0][w];
+        winner[p] = best;
+        good[p] = solutions || best < 0 ? 0 : best_count;
+        kept[p] = total;
+    }
+}
+
 inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -431,5 +567,90 @@ extern "C" int eacham_two_view_points(eacham_ctx* ctx, int n_matches, const doub
         for (int i = 0; i < n_matches; ++i) c += keep[(size_t)k * n_matches + i];
         counts[k] = c;
     }
+    return EACHAM_OK;
+}
+
+extern "C" int eacham_two_view_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* uv1, const double* uv2,
+                                     const double* K, const int32_t* rule, const int64_t* transform_ptr, const double* transforms,
+                                     const uint8_t* in_mask, float max_repr_error, float min_tri_angle, double distance_thresh,
+                                     int min_solution_matches, int32_t* winner, int32_t* good, int32_t* kept, int32_t* cand_counts,
+                                     double* points, uint8_t* keep, uint8_t* pose_mask) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: negative number of problems");
+    if (n_problems == 0) return EACHAM_OK;
+    if (!point_ptr || !transform_ptr) return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: null offset table");
+    if (!K || !rule || !winner || !good || !kept) return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: null argument");
+    const int P = n_problems;
+    if (point_ptr[0] != 0 || transform_ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: an offset table does not start at 0");
+    constexpr long long CAP = (1ll << 31) - 1;
+    std::vector<long long> item_ptr((size_t)P + 1);
+    item_ptr[0] = 0;
+    bool too_many = false;
+    for (int p = 0; p < P; ++p) {
+        const long long n = point_ptr[p + 1] - point_ptr[p], nt = transform_ptr[p + 1] - transform_ptr[p];
+        if (point_ptr[p + 1] < point_ptr[p] || transform_ptr[p + 1] < transform_ptr[p])
+            return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: problem %d: offset table not monotone", p);
+        if (rule[p] != EACHAM_TWOVIEW_POSES && rule[p] != EACHAM_TWOVIEW_SOLUTIONS)
+            return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: problem %d: unknown rule %d", p, (int)rule[p]);
+        // (both tables ascend from 0, so n, nt <= CAP once their last entries are: the product stays far inside 64 bits)
+        too_many = too_many || point_ptr[p + 1] > CAP || transform_ptr[p + 1] > CAP || (!too_many && item_ptr[p] + n * nt > CAP);
+        item_ptr[p + 1] = too_many ? 0 : item_ptr[p] + n * nt;
+    }
+    const long long NP = point_ptr[P], NT = transform_ptr[P], NI = item_ptr[P];
+    if (too_many) return ctx->fail(EACHAM_ERR_CAPACITY, "two_view_batch: more than 2^31 - 1 points, candidates or (candidate, match) items in one call");
+    if ((NP > 0 && (!uv1 || !uv2 || !points || !keep || !pose_mask)) || (NT > 0 && (!transforms || !cand_counts)))
+        return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: null array");
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
+    // the results, then the inputs (each side one contiguous span of the pinned mirror), then what never leaves the device
+    const size_t o_win = take(sizeof(int) * (size_t)P), o_good = take(sizeof(int) * (size_t)P), o_kept = take(sizeof(int) * (size_t)P);
+    const size_t o_cc = take(sizeof(int) * (size_t)NT), o_keep = take((size_t)NP), o_pm = take((size_t)NP);
+    const size_t o_pts = take(sizeof(double) * 3 * (size_t)NP);
+    const size_t o_ip = take(sizeof(long long) * ((size_t)P + 1)), o_pp = take(sizeof(int64_t) * ((size_t)P + 1));
+    const size_t o_tp = take(sizeof(int64_t) * ((size_t)P + 1)), o_rule = take(sizeof(int) * (size_t)P), o_K = take(sizeof(double) * 4);
+    const size_t o_T = take(sizeof(double) * 16 * (size_t)NT), o_im = take(in_mask ? (size_t)NP : 0);
+    const size_t o_u1 = take(sizeof(double) * 2 * (size_t)NP), o_u2 = take(sizeof(double) * 2 * (size_t)NP);
+    const size_t o_dev = off;
+    const size_t o_wp = take(sizeof(double) * 3 * (size_t)NI), o_wf = take((size_t)NI);
+    if (int rc = ensure_io(ctx, off)) return rc;
+    if (int rc = ensure_io_host(ctx, o_dev)) return rc;
+    char* base = (char*)ctx->io;
+    hipStream_t st = ctx->stream;
+    IoPack io(ctx, st);
+    if (int rc = io.in(o_ip, item_ptr.data(), sizeof(long long) * ((size_t)P + 1))) return rc;
+    if (int rc = io.in(o_pp, point_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
+    if (int rc = io.in(o_tp, transform_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
+    if (int rc = io.in(o_rule, rule, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
+    if (int rc = io.in(o_T, transforms, sizeof(double) * 16 * (size_t)NT)) return rc;
+    if (in_mask)
+        if (int rc = io.in(o_im, in_mask, (size_t)NP)) return rc;
+    if (int rc = io.in(o_u1, uv1, sizeof(double) * 2 * (size_t)NP)) return rc;
+    if (int rc = io.in(o_u2, uv2, sizeof(double) * 2 * (size_t)NP)) return rc;
+    if (int rc = io.flush_in()) return rc;
+    const long long *d_ip = (const long long*)(base + o_ip), *d_pp = (const long long*)(base + o_pp), *d_tp = (const long long*)(base + o_tp);
+    {
+        ProfileScope scope(ctx, EACHAM_KERNEL_TRIANGULATE);
+        if (NI > 0)
+            tvb_points_kernel<<<(unsigned)((NI + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
+                P, d_ip, d_pp, d_tp, (const int*)(base + o_rule), (const double2*)(base + o_u1), (const double2*)(base + o_u2),
+                (const double*)(base + o_K), (const double*)(base + o_T), in_mask ? (const unsigned char*)(base + o_im) : nullptr,
+                max_repr_error, min_tri_angle, distance_thresh, (double*)(base + o_wp), (unsigned char*)(base + o_wf));
+        tvb_select_kernel<<<P, TRI_BLOCK, 0, st>>>(d_ip, d_pp, d_tp, (const int*)(base + o_rule), min_solution_matches,
+                                                   (const double*)(base + o_wp), (const unsigned char*)(base + o_wf), (int*)(base + o_win),
+                                                   (int*)(base + o_good), (int*)(base + o_kept), (int*)(base + o_cc), (double*)(base + o_pts),
+                                                   (unsigned char*)(base + o_keep), (unsigned char*)(base + o_pm));
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    if (int rc = io.out(winner, o_win, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.out(good, o_good, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.out(kept, o_kept, sizeof(int) * (size_t)P)) return rc;
+    if (int rc = io.out(cand_counts, o_cc, sizeof(int) * (size_t)NT)) return rc;
+    if (int rc = io.out(keep, o_keep, (size_t)NP)) return rc;
+    if (int rc = io.out(pose_mask, o_pm, (size_t)NP)) return rc;
+    if (int rc = io.out(points, o_pts, sizeof(double) * 3 * (size_t)NP)) return rc;
+    if (int rc = io.finish()) return rc;
     return EACHAM_OK;
 }

@@ -218,6 +218,13 @@ class HipContext:
         from . import lmeds
         return lmeds.lmeds_batch(self, kind, uv1, uv2, samples, K)
 
+    def two_view_batch(self, uv1, uv2, K, rules, transforms, max_repr_error: float, min_tri_angle: float, in_mask=None,
+                       distance_thresh: float = 50.0, min_solution_matches: int = 20):
+        """eacham_two_view_batch: candidate poses -> the winner and its kept points, for a list of pairs in one call (eacham_amd/twoview.py)."""
+        from . import twoview
+        return twoview.two_view_batch(self, uv1, uv2, K, rules, transforms, max_repr_error, min_tri_angle, in_mask, distance_thresh,
+                                      min_solution_matches)
+
     def profile_enable(self, on: bool = True):
         self._check(self._L.eacham_profile_enable(self._h, int(on)))
 

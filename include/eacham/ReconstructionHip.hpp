@@ -119,6 +119,52 @@ public:
         return result;
     }
 
+    // RecoverPoseTwoView for a list of directed pairs (id1, id2) — the geometric verification and initialisation of a whole match
+    // graph — in THREE device calls whatever the number of pairs: FindEssentialMatBatch, FindHomographyBatch (one
+    // eacham_lmeds_batch each, every pair with the seeds RecoverPoseTwoView gives it) and TwoViewMotionBatch (one
+    // eacham_two_view_batch). result[p] equals RecoverPoseTwoView(pairs[p].first, pairs[p].second, K) field for field.
+    // With inlierThresholdPx > 0 (the non-reference option: two more scoring calls per pair between the stages) this falls back to
+    // RecoverPoseTwoView pair by pair.
+    template <class MatT>
+    std::vector<MatchTwoViewHip> RecoverPoseTwoViewBatch(const std::vector<std::pair<unsigned, unsigned>>& pairs, const MatT& K) const {
+        const size_t P = pairs.size();
+        std::vector<MatchTwoViewHip> result(P);
+        if (inlierThresholdPx_ > 0.0f) {
+            for (size_t p = 0; p < P; ++p) result[p] = RecoverPoseTwoView(pairs[p].first, pairs[p].second, K);
+            return result;
+        }
+        std::vector<std::vector<std::pair<unsigned, unsigned>>> ms(P);
+        std::vector<std::vector<double>> pts1(P), pts2(P);
+        std::vector<uint64_t> seedE(P), seedH(P);
+        for (size_t p = 0; p < P; ++p) {
+            const unsigned id1 = pairs[p].first, id2 = pairs[p].second;
+            auto* node1 = graph_->Get(id1);
+            auto* node2 = graph_->Get(id2);
+            for (const auto& m : node1->GetFactor(id2).matches) ms[p].emplace_back(m.first, m.second);
+            std::sort(ms[p].begin(), ms[p].end());
+            for (const auto& m : ms[p]) {
+                const auto& a = node1->GetKeyPoint(m.first);
+                const auto& b = node2->GetKeyPoint(m.second);
+                pts1[p].push_back(a.x), pts1[p].push_back(a.y), pts2[p].push_back(b.x), pts2[p].push_back(b.y);
+            }
+            seedE[p] = seed_ + 0x9E3779B97F4A7C15ull * ((uint64_t)id1 * 65536 + id2);
+            seedH[p] = seedE[p] + 1;
+        }
+        const double K9[9] = {K.template at<double>(0, 0), 0, K.template at<double>(0, 2), 0, K.template at<double>(1, 1),
+                              K.template at<double>(1, 2), 0, 0, 1};
+        const double K4[4] = {K9[0], K9[0], K9[2], K9[5]};
+        const std::vector<RobustModel> E = FindEssentialMatBatch(ctx_, pts1, pts2, K4, seedE, 1000, 0.99, sampling_);
+        const std::vector<RobustModel> H = FindHomographyBatch(ctx_, pts1, pts2, seedH, 100, 0.999, sampling_);
+        std::vector<int> eInliers(P), hInliers(P);
+        for (size_t p = 0; p < P; ++p) eInliers[p] = E[p].inliers, hInliers[p] = H[p].ok ? H[p].inliers : 0;
+        const std::vector<TwoViewMotion> tv = TwoViewMotionBatch(ctx_, pts1, pts2, K9, E, H, eInliers, hInliers, maxReprError_, minTriAngle_);
+        for (size_t p = 0; p < P; ++p) {
+            for (const auto& m : tv[p].matches) result[p].matches.emplace_back(ms[p][m.first].first, ms[p][m.first].second, m.second);
+            result[p].transform = tv[p].transform;
+        }
+        return result;
+    }
+
     // ReconstructionManager.cpp:185-240
     template <class MatT>
     bool RecoverPosePnP(unsigned id1, unsigned id2, const MatT& K) {

@@ -395,13 +395,15 @@ namespace twoview_detail {
 // lmeds() for a list of pairs through ONE eacham_lmeds_batch call: every pair's samples are drawn as lmeds() draws them (the
 // OpenCV stream restarts from its seed for every pair, as every OpenCV call does), the device solves, scores, picks and
 // classifies all pairs without a host turn. result[p] (and traces[p]) equal lmeds() on pair p alone, field for field.
+// seeds[p]: the seed of pair p (Sampling::Counter draws with it; the OpenCV stream does not look at it).
 inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m, const std::vector<std::vector<double>>& uv1,
                                             const std::vector<std::vector<double>>& uv2, const double* K4, int maxIters, double confidence,
-                                            uint64_t seed, Sampling sampling, std::vector<LmedsTrace>* traces) {
+                                            const std::vector<uint64_t>& seeds, Sampling sampling, std::vector<LmedsTrace>* traces) {
     const size_t P = uv1.size();
     std::vector<RobustModel> out(P);
     if (traces) traces->assign(P, LmedsTrace());
     if (uv2.size() != P) throw std::invalid_argument("lmeds_batch: uv1 and uv2 list different numbers of pairs");
+    if (seeds.size() != P) throw std::invalid_argument("lmeds_batch: one seed per pair");
     if (P == 0) return out;
     std::vector<int64_t> point_ptr(P + 1, 0), sample_ptr(P + 1, 0);
     std::vector<double> a, b;
@@ -410,7 +412,7 @@ inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m,
         const int n = (int)(uv1[p].size() / 2);
         if (n >= m && uv2[p].size() == uv1[p].size() && maxIters > 0) {   // (otherwise lmeds() returns at once: an empty problem here)
             const int iterations = std::min(maxIters, std::max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3));
-            const std::vector<int32_t> s = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1[p], uv2[p], seed, sampling);
+            const std::vector<int32_t> s = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1[p], uv2[p], seeds[p], sampling);
             out[p].iterations = (int)(s.size() / m);
             if (traces) (*traces)[p].samples = s;
             a.insert(a.end(), uv1[p].begin(), uv1[p].begin() + 2 * (size_t)n);
@@ -446,6 +448,12 @@ inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m,
     }
     return out;
 }
+// ... with one seed for every pair
+inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m, const std::vector<std::vector<double>>& uv1,
+                                            const std::vector<std::vector<double>>& uv2, const double* K4, int maxIters, double confidence,
+                                            uint64_t seed, Sampling sampling, std::vector<LmedsTrace>* traces) {
+    return lmeds_batch(ctx, solve_kind, m, uv1, uv2, K4, maxIters, confidence, std::vector<uint64_t>(uv1.size(), seed), sampling, traces);
+}
 
 }  // namespace twoview_detail
 
@@ -458,11 +466,20 @@ inline std::vector<RobustModel> FindEssentialMatBatch(Context& ctx, const std::v
                                                       std::vector<LmedsTrace>* traces = nullptr) {
     return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_ESSENTIAL5, 5, uv1, uv2, K4, maxIters, prob, 12345, sampling, traces);
 }
+// ... with a seed per pair: result[p] equals FindEssentialMat(ctx, uv1[p], uv2[p], K4, maxIters, seeds[p], prob, sampling).
+inline std::vector<RobustModel> FindEssentialMatBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                      const std::vector<std::vector<double>>& uv2, const double* K4,
+                                                      const std::vector<uint64_t>& seeds, int maxIters = 1000, double prob = 0.99,
+                                                      Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
+    return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_ESSENTIAL5, 5, uv1, uv2, K4, maxIters, prob, seeds, sampling, traces);
+}
 // FindHomography for every pair of a list: one eacham_lmeds_batch call, then the host refit of FindHomography per pair.
+// result[p] equals FindHomography(ctx, uv1[p], uv2[p], maxIters, seeds[p], confidence, sampling).
 inline std::vector<RobustModel> FindHomographyBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
-                                                    const std::vector<std::vector<double>>& uv2, int maxIters = 100, double confidence = 0.999,
-                                                    Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
-    std::vector<RobustModel> r = twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_HOMOGRAPHY4, 4, uv1, uv2, nullptr, maxIters, confidence, 12345,
+                                                    const std::vector<std::vector<double>>& uv2, const std::vector<uint64_t>& seeds,
+                                                    int maxIters = 100, double confidence = 0.999, Sampling sampling = Sampling::OpenCV,
+                                                    std::vector<LmedsTrace>* traces = nullptr) {
+    std::vector<RobustModel> r = twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_HOMOGRAPHY4, 4, uv1, uv2, nullptr, maxIters, confidence, seeds,
                                                              sampling, traces);
     for (size_t p = 0; p < r.size(); ++p)
         if (r[p].ok && uv1[p].size() / 2 > 4) {
@@ -470,6 +487,12 @@ inline std::vector<RobustModel> FindHomographyBatch(Context& ctx, const std::vec
             if (RefitHomography(uv1[p], uv2[p], r[p].mask, H)) r[p].model = H;
         }
     return r;
+}
+// ... every pair with the default seed of FindHomography
+inline std::vector<RobustModel> FindHomographyBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                    const std::vector<std::vector<double>>& uv2, int maxIters = 100, double confidence = 0.999,
+                                                    Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
+    return FindHomographyBatch(ctx, uv1, uv2, std::vector<uint64_t>(uv1.size(), 12345), maxIters, confidence, sampling, traces);
 }
 
 // cv::decomposeEssentialMat: E = U diag(1, 1, 0) V^T -> R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2] (|t| = 1)
@@ -591,6 +614,156 @@ inline std::vector<HomographyMotion> DecomposeHomographyMat(const Mat3& H, const
             m.n = {V[0] * np[0] + V[1] * np[1] + V[2] * np[2], V[3] * np[0] + V[4] * np[1] + V[5] * np[2], V[6] * np[0] + V[7] * np[1] + V[8] * np[2]};
             out.push_back(m);
         }
+    return out;
+}
+
+// ---- the second half of RecoverPoseTwoView for a list of pairs: ONE eacham_two_view_batch call ------------------------------------
+
+namespace twoview_detail {
+
+struct TwoViewBatchOut {
+    std::vector<int32_t> winner, good, kept, cand_counts;
+    std::vector<double> points;          // 3 per point, the winner's
+    std::vector<uint8_t> keep, pose_mask;
+    std::vector<int64_t> point_ptr, transform_ptr;
+};
+
+// uv1[p] / uv2[p]: the matches of problem p (null: a problem without points), T[p]: its candidates (16 doubles each), rule[p],
+// mask[p]: its in_mask or null (all ones). K9 = 3x3 row-major.
+inline TwoViewBatchOut two_view_batch(Context& ctx, const std::vector<const std::vector<double>*>& uv1, const std::vector<const std::vector<double>*>& uv2,
+                                      const double* K9, const std::vector<int32_t>& rule, const std::vector<std::vector<double>>& T,
+                                      const std::vector<const std::vector<uint8_t>*>& mask, float maxReprError, float minTriAngle,
+                                      double distanceThresh, int minSolutionMatches) {
+    const size_t P = uv1.size();
+    TwoViewBatchOut o;
+    o.point_ptr.assign(P + 1, 0), o.transform_ptr.assign(P + 1, 0);
+    std::vector<double> a, b, t;
+    std::vector<uint8_t> m;
+    bool any_mask = false;
+    for (size_t p = 0; p < P; ++p) any_mask = any_mask || mask[p];
+    for (size_t p = 0; p < P; ++p) {
+        if (uv1[p]) {
+            if (uv2[p]->size() != uv1[p]->size()) throw std::invalid_argument("two_view_batch: point lists disagree");
+            a.insert(a.end(), uv1[p]->begin(), uv1[p]->end());
+            b.insert(b.end(), uv2[p]->begin(), uv2[p]->end());
+            if (any_mask) {
+                if (mask[p] && mask[p]->size() != uv1[p]->size() / 2) throw std::invalid_argument("two_view_batch: a mask disagrees with its points");
+                if (mask[p]) m.insert(m.end(), mask[p]->begin(), mask[p]->end());
+                else m.insert(m.end(), uv1[p]->size() / 2, (uint8_t)1);
+            }
+        }
+        t.insert(t.end(), T[p].begin(), T[p].end());
+        o.point_ptr[p + 1] = (int64_t)(a.size() / 2);
+        o.transform_ptr[p + 1] = (int64_t)(t.size() / 16);
+    }
+    const size_t NP = a.size() / 2, NT = t.size() / 16;
+    o.winner.assign(P + 1, -1), o.good.assign(P + 1, 0), o.kept.assign(P + 1, 0), o.cand_counts.assign(NT + 1, 0);
+    o.points.assign(3 * NP + 3, 0.0), o.keep.assign(NP + 1, 0), o.pose_mask.assign(NP + 1, 0);
+    a.resize(a.size() + 2), b.resize(b.size() + 2), t.resize(t.size() + 16), m.resize(m.size() + 1);   // (no null data() for an empty list)
+    const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
+    ctx.check(eacham_two_view_batch(ctx.get(), (int)P, o.point_ptr.data(), a.data(), b.data(), K4, rule.data(), o.transform_ptr.data(), t.data(),
+                                    any_mask ? m.data() : nullptr, maxReprError, minTriAngle, distanceThresh, minSolutionMatches, o.winner.data(),
+                                    o.good.data(), o.kept.data(), o.cand_counts.data(), o.points.data(), o.keep.data(), o.pose_mask.data()));
+    return o;
+}
+
+// the four candidates of cv::recoverPose in its order: [R1|t], [R2|t], [R1|-t], [R2|-t] (16 doubles each) and their (R, t)
+inline std::vector<double> pose_candidates(const Mat3& E, std::array<RecoveredPose, 4>& cand) {
+    Mat3 R1, R2;
+    Vec3 t;
+    DecomposeEssentialMat(E, R1, R2, t);
+    const Mat3* Rs[4] = {&R1, &R2, &R1, &R2};
+    const double sg[4] = {1, 1, -1, -1};
+    std::vector<double> T(4 * 16);
+    for (int k = 0; k < 4; ++k) {
+        cand[k].R = *Rs[k];
+        cand[k].t = {sg[k] * t[0], sg[k] * t[1], sg[k] * t[2]};
+        const auto M = cand[k].transform();
+        std::copy(M.begin(), M.end(), T.begin() + 16 * k);
+    }
+    return T;
+}
+
+}  // namespace twoview_detail
+
+// RecoverPose for every pair of a list through one eacham_two_view_batch call (the POSES rule alone): the cheirality vote runs on
+// the device and only the winner's mask comes back. masksIn: null, or one entry per pair (null entry: all ones).
+// result[p] equals RecoverPose(ctx, E[p], uv1[p], uv2[p], K, distanceThresh, masksIn[p]) field for field.
+inline std::vector<RecoveredPose> RecoverPoseBatch(Context& ctx, const std::vector<Mat3>& E, const std::vector<std::vector<double>>& uv1,
+                                                   const std::vector<std::vector<double>>& uv2, const double* K, double distanceThresh = 50.0,
+                                                   const std::vector<const std::vector<uint8_t>*>* masksIn = nullptr) {
+    const size_t P = E.size();
+    if (uv1.size() != P || uv2.size() != P || (masksIn && masksIn->size() != P)) throw std::invalid_argument("RecoverPoseBatch: one entry per pair in every list");
+    std::vector<RecoveredPose> out(P);
+    if (P == 0) return out;
+    std::vector<std::array<RecoveredPose, 4>> cand(P);
+    std::vector<const std::vector<double>*> a(P), b(P);
+    std::vector<const std::vector<uint8_t>*> m(P, nullptr);
+    std::vector<std::vector<double>> T(P);
+    for (size_t p = 0; p < P; ++p) {
+        T[p] = twoview_detail::pose_candidates(E[p], cand[p]);
+        a[p] = &uv1[p], b[p] = &uv2[p];
+        if (masksIn) m[p] = (*masksIn)[p];
+    }
+    const auto o = twoview_detail::two_view_batch(ctx, a, b, K, std::vector<int32_t>(P, EACHAM_TWOVIEW_POSES), T, m, std::numeric_limits<float>::max(), 0.0f,
+                                                  distanceThresh, 0);
+    for (size_t p = 0; p < P; ++p) {
+        out[p] = cand[p][o.winner[p]];
+        out[p].good = o.good[p];
+        out[p].mask.assign(o.pose_mask.begin() + o.point_ptr[p], o.pose_mask.begin() + o.point_ptr[p + 1]);
+    }
+    return out;
+}
+
+// What RecoverPoseTwoView leaves for one pair once E and H are estimated: the relative transform and the kept matches.
+struct TwoViewMotion {
+    std::array<double, 16> transform{1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};   // row-major, camera 1 -> camera 2
+    std::vector<std::pair<unsigned, std::array<double, 3>>> matches;                     // (index into the pair's match list, point3d)
+    int branch = -1;   // 1: the homography branch (:89-145), 0: the essential one (:146-180), -1: no E, nothing recovered
+};
+
+// The second half of RecoverPoseTwoView (ReconstructionManager.cpp:86-180) for a list of pairs: per pair the branch the reference
+// takes (H_E_ratio = hInliers / eInliers > 0.9 -> decomposeHomographyMat and the vote among its solutions; otherwise recoverPose
+// and the structure of its pose; !E[p].ok -> an empty result), the 3x3 decompositions on the host, then ONE eacham_two_view_batch
+// call for all pairs. eInliers / hInliers: the counts the ratio is taken from (the LMedS masks' by default; the caller's own
+// when it counts at a pixel threshold).
+inline std::vector<TwoViewMotion> TwoViewMotionBatch(Context& ctx, const std::vector<std::vector<double>>& uv1, const std::vector<std::vector<double>>& uv2,
+                                                     const double* K9, const std::vector<RobustModel>& E, const std::vector<RobustModel>& H,
+                                                     const std::vector<int>& eInliers, const std::vector<int>& hInliers, float maxReprError,
+                                                     float minTriAngle) {
+    const size_t P = uv1.size();
+    if (uv2.size() != P || E.size() != P || H.size() != P || eInliers.size() != P || hInliers.size() != P)
+        throw std::invalid_argument("TwoViewMotionBatch: one entry per pair in every list");
+    std::vector<TwoViewMotion> out(P);
+    if (P == 0) return out;
+    std::vector<const std::vector<double>*> a(P, nullptr), b(P, nullptr);
+    std::vector<const std::vector<uint8_t>*> m(P, nullptr);
+    std::vector<std::vector<double>> T(P);
+    std::vector<int32_t> rule(P, EACHAM_TWOVIEW_POSES);
+    for (size_t p = 0; p < P; ++p) {
+        if (!E[p].ok) continue;   // (a problem without points and candidates: the "none" record)
+        const float ratio = hInliers[p] > 0 && eInliers[p] > 0 ? (float)hInliers[p] / (float)eInliers[p] : 0.0f;   // :87
+        out[p].branch = ratio > 0.9f ? 1 : 0;
+        a[p] = &uv1[p], b[p] = &uv2[p];
+        if (out[p].branch == 1) {
+            rule[p] = EACHAM_TWOVIEW_SOLUTIONS;
+            for (const auto& s : DecomposeHomographyMat(H[p].model, K9)) {
+                const double M[16] = {s.R[0], s.R[1], s.R[2], s.t[0], s.R[3], s.R[4], s.R[5], s.t[1], s.R[6], s.R[7], s.R[8], s.t[2], 0, 0, 0, 1};
+                T[p].insert(T[p].end(), M, M + 16);
+            }
+        } else {
+            std::array<RecoveredPose, 4> cand;
+            T[p] = twoview_detail::pose_candidates(E[p].model, cand);
+            m[p] = &E[p].mask;
+        }
+    }
+    const auto o = twoview_detail::two_view_batch(ctx, a, b, K9, rule, T, m, maxReprError, minTriAngle, 50.0, 20);
+    for (size_t p = 0; p < P; ++p) {
+        if (o.winner[p] < 0) continue;
+        std::copy(T[p].begin() + 16 * (size_t)o.winner[p], T[p].begin() + 16 * ((size_t)o.winner[p] + 1), out[p].transform.begin());
+        for (int64_t i = o.point_ptr[p]; i < o.point_ptr[p + 1]; ++i)
+            if (o.keep[i]) out[p].matches.push_back({(unsigned)(i - o.point_ptr[p]), {o.points[3 * i], o.points[3 * i + 1], o.points[3 * i + 2]}});
+    }
     return out;
 }
 

@@ -439,6 +439,44 @@ int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t*
                        const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, double* models, float* medians,
                        float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates);
 
+/* ---- two-view motion and structure for a whole list of pairs ------------------------------------------------------
+ * The second half of RecoverPoseTwoView (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:89-180)
+ * for every edge of a match graph in ONE call: what eacham_two_view_points plus the host rules behind it
+ * (cv::recoverPose's cheirality vote and the structure of its winner, :153-177; the choice among the solutions of
+ * cv::decomposeHomographyMat, :98-144) do for one pair, for n_problems pairs with two launches whatever n_problems is
+ * and only the WINNER's structure coming back. Problem p owns the points point_ptr[p] .. point_ptr[p+1] of uv1 / uv2
+ * (rows of 2 doubles, pixels) and the candidate transforms transform_ptr[p] .. transform_ptr[p+1] (16 doubles each,
+ * row-major, camera-1 -> camera-2; decomposing E / H into them stays with the caller, 3x3 host work). Both offset tables
+ * have n_problems + 1 entries, start at 0 and do not decrease. K = fx fy cx cy is shared; rule[p] is one of the two
+ * below; in_mask (point_ptr[n_problems] bytes in the layout of uv1, NULL = all ones) is read by the POSES rule only.
+ * For every (candidate k, match i) the point X, the float reprojection error in camera 1 and the triangulation angle
+ * are exactly eacham_two_view_points'. Then, per problem:
+ *   EACHAM_TWOVIEW_POSES      ch(k,i) = in_mask[i] && 0 < z1 < distance_thresh && 0 < z2 < distance_thresh with z1 = X[2],
+ *                             z2 = ((T[8] X0 + T[9] X1) + T[10] X2) + T[11], every operation rounded on its own;
+ *                             cand_counts[k] = sum of ch(k,.); the winner is candidate 0 unless a later one has a STRICTLY
+ *                             larger count; good = its count, pose_mask = its ch. For the winner only, keep(i) = z > 0 &&
+ *                             err < max_repr_error && !(angle < min_tri_angle) (independent of in_mask), kept = its sum.
+ *   EACHAM_TWOVIEW_SOLUTIONS  keep(k,i) = z > 0 && err < max_repr_error && angle > min_tri_angle; cand_counts[k] = its sum;
+ *                             the winner is the first k with the strictly largest non-zero count, accepted only if that
+ *                             count is > min_solution_matches (the reference: 20); good = 0, pose_mask = 0.
+ * Outputs (all required): winner, good, kept (n_problems each), cand_counts (transform_ptr[n_problems]), points (3 per
+ * point: the WINNER's, all of the problem's points as eacham_two_view_points returns them), keep and pose_mask (one
+ * byte per point, in the layout of uv1).
+ * The "NONE" RECORD: a problem without candidates, or a SOLUTIONS problem whose best count is not accepted, gets winner
+ * -1, good = kept = 0, zero keep / pose_mask and zero points; its cand_counts are still written. A POSES problem with
+ * candidates and no points has winner 0 and good = 0. Its neighbours are not affected.
+ * Bit-identical, output by output, with eacham_two_view_points on the problem's candidates followed by those rules.
+ * EACHAM_ERR_INVALID (checked on the host before anything is launched or written; the message names the problem): an
+ * unknown rule, a negative size, an offset table that is null / does not start at 0 / decreases, a null required array.
+ * EACHAM_ERR_CAPACITY: more than 2^31 - 1 points, candidates or (candidate, match) items in one call. */
+#define EACHAM_TWOVIEW_POSES 0
+#define EACHAM_TWOVIEW_SOLUTIONS 1
+int eacham_two_view_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* uv1, const double* uv2,
+                          const double* K, const int32_t* rule, const int64_t* transform_ptr, const double* transforms,
+                          const uint8_t* in_mask, float max_repr_error, float min_tri_angle, double distance_thresh,
+                          int min_solution_matches, int32_t* winner, int32_t* good, int32_t* kept, int32_t* cand_counts,
+                          double* points, uint8_t* keep, uint8_t* pose_mask);
+
 /* ---- view-graph query on the CSR match graph --------------------------
  * Graph::GetBestPairForValid (/root/reference/modules/sfm/data/Graph.h:59-106) evaluated directly on the
  * wire format of eacham_match_all_pairs: pair p with counts[p] > 0 is the factor f1 -> f2 with matches
