@@ -64,7 +64,7 @@ int grow(eacham_comm* c, int r, eacham_comm::Buf& b, size_t bytes) {
     return EACHAM_OK;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+using eacham::align256;
 
 }  // namespace
 

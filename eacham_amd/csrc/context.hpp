@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/eacham_hip.h"
+#include "io_layout.hpp"
 
 namespace eacham {
 
@@ -102,7 +103,7 @@ struct eacham_ctx {
     int pairs_safe_cap = 0;
     void* io = nullptr;  // staging for the host-pointer entry points
     size_t io_bytes = 0;
-    void* io_host = nullptr;  // pinned mirror of the head of `io`: the small arrays of a call travel as ONE copy each way (IoPack)
+    void* io_host = nullptr;  // pinned mirror of the head of `io`: the small arrays of a call travel as ONE copy each way (IoStage)
     size_t io_host_bytes = 0;
 
     std::vector<eacham::BaBlock> ba_pool;  // arenas of released BA problems, reused by the next eacham_ba_prepare
@@ -111,7 +112,7 @@ struct eacham_ctx {
                               // default: device for >= 65536 observations), read at create
     int stream2_attempt = -1;        // which candidate of the second-stream search was kept (0..4; 4 = the last, kept unprobed; -1 = no search)
     float stream2_lead_ms = -1.f;    // how long before the spin's end the probe on it finished (> 0.010: a hardware queue of its own)
-    bool io_busy = false;            // an IoPack call has not reached its finish(): copies out of the pinned mirror may be in flight
+    bool io_busy = false;            // an IoStage call has not reached its finish(): copies out of the pinned mirror may be in flight
     bool ba_groups_lds_set = false;  // ba_schur_groups has been granted its dynamic LDS size on this context's device
     int ba_group_rows = 0;    // EACHAM_BA_GROUP_ROWS=<n> (diagnostic): rows per landmark group instead of ba_groups.hpp's choice
     int ba_schur_mode = 0;    // EACHAM_BA_SCHUR=groups|pairs (diagnostic / tests). 0 = by problem size: the landmark groups of ba_groups.hpp for the
@@ -163,70 +164,104 @@ int ensure_io_host(eacham_ctx* ctx, size_t bytes);
 
 // The host-pointer entry points of the estimators, the triangulation and the graph query are called once or more per frame of
 // the incremental loop with a handful of small arrays each way (points, a few models, counts): as separate copies from pageable
-// memory every one of them is a submission and a wait of ~10 us (25 copies per solvePnPRansac of the loop). IoPack lays the
-// arrays that are small into a pinned mirror of the device staging buffer at the SAME offsets and moves each direction in one
-// copy (the bytes between two packed arrays travel along); arrays above PACK_MAX keep their own direct copy.
-struct IoPack {
+// memory every one of them is a submission and a wait of ~10 us (25 copies per solvePnPRansac of the loop). IoStage is how such a
+// call stages its arrays through ctx->io. Each array is declared ONCE — element type, element count, role — and yields a typed
+// handle; io_layout.hpp places them. upload() sizes the staging buffer and its pinned mirror (which covers everything before the
+// device-only group), lays the inputs that are small into the mirror at the SAME offsets and moves them in one copy (the bytes
+// between two packed arrays travel along); arrays above PACK_MAX keep their own direct copy. It hands back the IoDev that turns
+// a handle into its device pointer — not before, since growing ctx->io moves it. finish() brings the results back the same way.
+template <class T>
+struct IoArray { int k; };
+struct IoDev {
+    char* base = nullptr;
+    const size_t* off = nullptr;
+    template <class T>
+    T* operator()(IoArray<T> h) const { return (T*)(base + off[h.k]); }
+};
+struct IoStage {
     static constexpr size_t PACK_MAX = 256 * 1024;
     eacham_ctx* ctx;
-    char* dev;
     hipStream_t st;
+    IoLayout lay;
+    void* host[IoLayout::MAX_ARRAYS];   // the caller's array: source of an input, destination of a result; null = not copied
+    char* dev = nullptr;
     size_t in_lo = ~(size_t)0, in_hi = 0, out_lo = ~(size_t)0, out_hi = 0;
     size_t direct_lo = ~(size_t)0, direct_hi = 0;  // what has been copied directly so far: a packed span must not cover it
-    struct Out { void* dst; size_t off, bytes; };
-    struct In { size_t off, bytes; };
-    Out outs[8];
-    In ins[16];
-    int n_outs = 0, n_ins = 0;
-    IoPack(eacham_ctx* c, hipStream_t s) : ctx(c), dev((char*)c->io), st(s) {
+    int packed[IoLayout::MAX_ARRAYS], n_packed = 0;   // the arrays of the packed span being gathered
+    IoStage(eacham_ctx* c, hipStream_t s) : ctx(c), st(s) {}
+
+    // A null input still owns its bytes (the kernels' optional K, in_mask); a null result is not brought back.
+    template <class T>
+    IoArray<T> in(const void* src, size_t count) { return add<T>(IO_IN, const_cast<void*>(src), count); }
+    template <class T>
+    IoArray<T> out(void* dst, size_t count) { return add<T>(IO_OUT, dst, count); }
+    template <class T>
+    IoArray<T> scratch(size_t count) { return add<T>(IO_DEV, nullptr, count); }   // never leaves the device
+
+    int upload(IoDev& d) {
+        if (lay.overflow) return ctx->fail(EACHAM_ERR_CAPACITY, "more than %d staged arrays in one call", IoLayout::MAX_ARRAYS);
+        lay.place();
+        if (int rc = ensure_io(ctx, lay.total)) return rc;
+        if (int rc = ensure_io_host(ctx, lay.cut)) return rc;
+        dev = (char*)ctx->io;
         // a call that returned on an error may have left a copy out of the mirror in flight: wait before writing into it again
         if (ctx->io_busy) (void)hipStreamSynchronize(st);
         ctx->io_busy = true;
-    }
-    // host -> device: packed (memcpy now, one copy at flush_in) or direct
-    int in(size_t off, const void* src, size_t bytes) {
-        if (bytes == 0) return EACHAM_OK;
-        if (bytes <= PACK_MAX && off + bytes <= ctx->io_host_bytes && n_ins < 16) {
-            memcpy((char*)ctx->io_host + off, src, bytes);
-            in_lo = std::min(in_lo, off), in_hi = std::max(in_hi, off + bytes);
-            ins[n_ins++] = In{off, bytes};
-            return EACHAM_OK;
+        for (int k = 0; k < lay.n; ++k) {
+            const size_t off = lay.off[k], bytes = lay.bytes[k];
+            if (lay.role[k] != IO_IN || !host[k] || bytes == 0) continue;
+            if (bytes <= PACK_MAX && off + bytes <= ctx->io_host_bytes) {
+                memcpy((char*)ctx->io_host + off, host[k], bytes);
+                in_lo = std::min(in_lo, off), in_hi = std::max(in_hi, off + bytes);
+                packed[n_packed++] = k;
+                continue;
+            }
+            // (what has been packed so far goes first; the direct copy is remembered: a later packed span that would cover it — the
+            // gaps of the mirror hold stale bytes — is sent piece by piece instead)
+            if (int rc = flush_in()) return rc;
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dev + off, host[k], bytes, hipMemcpyHostToDevice, st));
+            direct_lo = std::min(direct_lo, off), direct_hi = std::max(direct_hi, off + bytes);
         }
-        // (what has been packed so far goes first; the direct copy is remembered: a later packed span that would cover it — the
-        // gaps of the mirror hold stale bytes — is sent piece by piece instead)
         if (int rc = flush_in()) return rc;
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dev + off, src, bytes, hipMemcpyHostToDevice, st));
-        direct_lo = std::min(direct_lo, off), direct_hi = std::max(direct_hi, off + bytes);
+        d.base = dev, d.off = lay.off;
         return EACHAM_OK;
+    }
+    int finish() {   // one copy back, the stream's synchronisation, the hand-over to the caller's arrays
+        n_packed = 0;
+        for (int k = 0; k < lay.n; ++k) {
+            const size_t off = lay.off[k], bytes = lay.bytes[k];
+            if (lay.role[k] != IO_OUT || !host[k] || bytes == 0) continue;
+            if (bytes <= PACK_MAX && off + bytes <= ctx->io_host_bytes) {
+                packed[n_packed++] = k;
+                out_lo = std::min(out_lo, off), out_hi = std::max(out_hi, off + bytes);
+            } else {
+                EACHAM_HIP_TRY(ctx, hipMemcpyAsync(host[k], dev + off, bytes, hipMemcpyDeviceToHost, st));
+            }
+        }
+        if (out_hi > out_lo) EACHAM_HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->io_host + out_lo, dev + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+        for (int j = 0; j < n_packed; ++j) memcpy(host[packed[j]], (char*)ctx->io_host + lay.off[packed[j]], lay.bytes[packed[j]]);
+        ctx->io_busy = false;  // (an early error return leaves it set: the next upload() waits for the stream first)
+        return EACHAM_OK;
+    }
+
+private:
+    template <class T>
+    IoArray<T> add(int role, void* p, size_t count) {
+        const int k = lay.add(role, sizeof(T) * count);
+        host[k] = p;
+        return IoArray<T>{k};
     }
     int flush_in() {
         if (in_hi > in_lo) {
             if (in_lo < direct_hi && direct_lo < in_hi) {
-                for (int k = 0; k < n_ins; ++k)
-                    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dev + ins[k].off, (char*)ctx->io_host + ins[k].off, ins[k].bytes, hipMemcpyHostToDevice, st));
+                for (int j = 0; j < n_packed; ++j)
+                    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dev + lay.off[packed[j]], (char*)ctx->io_host + lay.off[packed[j]], lay.bytes[packed[j]], hipMemcpyHostToDevice, st));
             } else {
                 EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dev + in_lo, (char*)ctx->io_host + in_lo, in_hi - in_lo, hipMemcpyHostToDevice, st));
             }
         }
-        in_lo = ~(size_t)0, in_hi = 0, n_ins = 0;
-        return EACHAM_OK;
-    }
-    // device -> host: registered now, moved by finish()
-    int out(void* dst, size_t off, size_t bytes) {
-        if (bytes == 0 || !dst) return EACHAM_OK;
-        if (bytes <= PACK_MAX && off + bytes <= ctx->io_host_bytes && n_outs < 8) {
-            outs[n_outs++] = Out{dst, off, bytes};
-            out_lo = std::min(out_lo, off), out_hi = std::max(out_hi, off + bytes);
-            return EACHAM_OK;
-        }
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(dst, dev + off, bytes, hipMemcpyDeviceToHost, st));
-        return EACHAM_OK;
-    }
-    int finish() {   // one copy back, the stream's synchronisation, the hand-over to the caller's arrays
-        if (out_hi > out_lo) EACHAM_HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->io_host + out_lo, dev + out_lo, out_hi - out_lo, hipMemcpyDeviceToHost, st));
-        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
-        for (int k = 0; k < n_outs; ++k) memcpy(outs[k].dst, (char*)ctx->io_host + outs[k].off, outs[k].bytes);
-        ctx->io_busy = false;  // (an early error return leaves it set: the next IoPack waits for the stream first)
+        in_lo = ~(size_t)0, in_hi = 0, n_packed = 0;
         return EACHAM_OK;
     }
 };

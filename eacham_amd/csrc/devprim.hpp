@@ -26,6 +26,18 @@ __host__ __device__ inline void zero(int& v) { v = 0; }
 __host__ __device__ inline void zero(long long& v) { v = 0; }
 __host__ __device__ inline void zero(I3& v) { v = I3{0, 0, 0}; }
 
+// the largest k in [0, n) with ptr[k] <= v (ptr ascending, ptr[0] <= v): the owner of item v in a flat launch over segments
+template <class T>
+__device__ __forceinline__ int segment_of(const T* __restrict__ ptr, int n, long long v) {
+    int lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)ptr[mid] <= v) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = 8;
 constexpr int SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;  // elements per workgroup

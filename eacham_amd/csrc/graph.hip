@@ -100,8 +100,6 @@ __global__ __launch_bounds__(1024) void graph_best_pair_kernel(const int2* __res
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 }  // namespace eacham
 
@@ -259,27 +257,16 @@ extern "C" int eacham_graph_set_frames(eacham_graph* g, int n, const int32_t* fr
     const long long total = has3d_offsets[n];
     if (total > 0 && !has3d) return ctx->fail(EACHAM_ERR_INVALID, "graph_set_frames: null flags");
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_fr = 0, o_off = align(sizeof(int) * (size_t)n), o_v = o_off + align(sizeof(long long) * ((size_t)n + 1));
-    const size_t o_fl = o_v + align((size_t)n), bytes = o_fl + align((size_t)std::max<long long>(total, 1));
-    if (int rc = ensure_io(ctx, bytes)) return rc;
-    if (int rc = ensure_io_host(ctx, bytes)) return rc;
-    IoPack io(ctx, ctx->stream);
-    if (int rc = io.in(o_fr, frames, sizeof(int) * (size_t)n)) return rc;
-    if (int rc = io.in(o_off, has3d_offsets, sizeof(long long) * ((size_t)n + 1))) return rc;
-    if (int rc = io.in(o_v, valid, (size_t)n)) return rc;
-    if (total > 0)
-        if (int rc = io.in(o_fl, has3d, (size_t)total)) return rc;
-    if (int rc = io.flush_in()) return rc;
-    char* base = (char*)ctx->io;
-    graph_scatter_frames_kernel<<<n, 256, 0, ctx->stream>>>(n, (const int*)(base + o_fr), (const long long*)(base + o_off), (const unsigned char*)(base + o_v),
-                                                            (const unsigned char*)(base + o_fl), g->kp_offsets, g->valid, g->has3d);
+    IoStage io(ctx, ctx->stream);
+    const auto h_fr = io.in<int>(frames, (size_t)n);
+    const auto h_off = io.in<long long>(has3d_offsets, (size_t)n + 1);
+    const auto h_v = io.in<unsigned char>(valid, (size_t)n), h_fl = io.in<unsigned char>(has3d, (size_t)total);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    graph_scatter_frames_kernel<<<n, 256, 0, ctx->stream>>>(n, d(h_fr), d(h_off), d(h_v), d(h_fl), g->kp_offsets, g->valid, g->has3d);
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    // (the staging buffer is the context's: the next call that uses it is ordered behind this kernel on the same stream, and the
-    // pinned mirror is rewritten only after a call that synchronised — every user of IoPack ends with finish() or is this one)
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    ctx->io_busy = false;  // (synchronised: nothing reads the mirror any more)
-    return EACHAM_OK;
+    // (no results: finish() is the stream's synchronisation, after which nothing reads the pinned mirror any more)
+    return io.finish();
 }
 
 // Graph::GetBestPairForValid(excluded) on the resident state

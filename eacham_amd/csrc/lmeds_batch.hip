@@ -29,18 +29,6 @@
 namespace eacham {
 namespace {
 
-// the largest k in [0, n) with ptr[k] <= v (ptr ascending, ptr[0] <= v)
-template <class T>
-__device__ __forceinline__ int segment_of(const T* __restrict__ ptr, int n, long long v) {
-    int lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if ((long long)ptr[mid] <= v) lo = mid;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_h4_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
                                                                       int n_problems, const double* __restrict__ a, const double* __restrict__ b,
                                                                       int n_samples, const int* __restrict__ idx, double* __restrict__ models,
@@ -50,7 +38,7 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_h4_kernel(const lon
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = blockIdx.x * SOLVE_WAVES + wave;
     if (s >= n_samples) return;
-    const int p = segment_of(sample_ptr, n_problems, s);
+    const int p = prim::segment_of(sample_ptr, n_problems, s);
     const long long base = point_ptr[p];
     if (lane == 0) sample_problem[s] = p;
     if (point_ptr[p + 1] - base < 4) {   // (wave-uniform) a problem without a minimal sample's worth of points has no candidates
@@ -84,7 +72,7 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_e5_kernel(const lon
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = blockIdx.x * SOLVE_WAVES + wave;
     if (s >= n_samples) return;
-    const int p = segment_of(sample_ptr, n_problems, s);
+    const int p = prim::segment_of(sample_ptr, n_problems, s);
     const long long base = point_ptr[p];
     if (lane == 0) sample_problem[s] = p;
     if (point_ptr[p + 1] - base < 5) {   // (wave-uniform)
@@ -127,7 +115,7 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_score_kernel(const long long* __r
     float* erow = rows ? rows + (size_t)blockIdx.x * row_stride : nullptr;
     const int ncand = *total;
     for (int c = blockIdx.x; c < ncand; c += gridDim.x) {   // (c, and every barrier below, is uniform over the workgroup)
-        const int s = segment_of(first, n_samples, c);
+        const int s = prim::segment_of(first, n_samples, c);
         const long long base = point_ptr[sample_problem[s]];
         const int n = (int)(point_ptr[sample_problem[s] + 1] - base);   // >= 4: the sample was solved
         const double* pm = models + 9 * ((size_t)s * max_models + (c - first[s]));
@@ -217,7 +205,7 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_select_kernel(const long long* __
 #pragma unroll
     for (int k = 0; k < 9; ++k) M[k] = 0.0;
     if (!none) {
-        s = segment_of(first, n_samples, best.at);
+        s = prim::segment_of(first, n_samples, best.at);
         const double* pm = models + 9 * ((size_t)s * max_models + (best.at - first[s]));
 #pragma unroll
         for (int k = 0; k < 9; ++k) M[k] = pm[k];
@@ -299,52 +287,39 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
     const bool need_rows = max_n > SC_MAX_LDS;
     const long long cand_cap = S * maxm;
     const int score_grid = (int)std::max<long long>(1, std::min<long long>(cand_cap, need_rows ? LB_SCORE_GRID_ROWS : LB_SCORE_GRID));
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align(off + bytes); return o; };
-    // the results, then the inputs (each side one contiguous span of the pinned mirror), then what never leaves the device
-    const size_t o_om = take(sizeof(double) * 9 * (size_t)P), o_omed = take(sizeof(float) * (size_t)P), o_othr = take(sizeof(float) * (size_t)P);
-    const size_t o_oinl = take(sizeof(int) * (size_t)P), o_owin = take(sizeof(int) * 3 * (size_t)P), o_onc = take(sizeof(int) * (size_t)P);
-    const size_t o_omask = take((size_t)NP);
-    const size_t o_pp = take(sizeof(int64_t) * ((size_t)P + 1)), o_sp = take(sizeof(int64_t) * ((size_t)P + 1)), o_K = take(sizeof(double) * 4);
-    const size_t o_a = take(sizeof(double) * 2 * (size_t)NP), o_b = take(sizeof(double) * 2 * (size_t)NP);
-    const size_t o_i = take(sizeof(int) * (size_t)S * m);
-    const size_t o_dev = off;
-    const size_t o_m = take(sizeof(double) * 9 * (size_t)cand_cap), o_n = take(sizeof(int) * (size_t)S), o_first = take(sizeof(int) * (size_t)S);
-    const size_t o_sprob = take(sizeof(int) * (size_t)S), o_tot = take(sizeof(int)), o_ws = take(sizeof(int) * prim::scan_ws_elems((size_t)S));
-    const size_t o_cmed = take(sizeof(float) * (size_t)cand_cap);
-    const size_t o_rows = take(need_rows ? sizeof(float) * (size_t)score_grid * (size_t)max_n : 0);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, o_dev)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (int rc = io.in(o_pp, point_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
-    if (int rc = io.in(o_sp, sample_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
-    if (K)
-        if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_a, a, sizeof(double) * 2 * (size_t)NP)) return rc;
-    if (int rc = io.in(o_b, b, sizeof(double) * 2 * (size_t)NP)) return rc;
-    if (int rc = io.in(o_i, sample_idx, sizeof(int) * (size_t)S * m)) return rc;
-    if (int rc = io.flush_in()) return rc;
-    const long long* d_pp = (const long long*)(base + o_pp);
-    const long long* d_sp = (const long long*)(base + o_sp);
-    const double *d_a = (const double*)(base + o_a), *d_b = (const double*)(base + o_b), *d_K = K ? (const double*)(base + o_K) : nullptr;
-    double* d_m = (double*)(base + o_m);
-    int *d_n = (int*)(base + o_n), *d_first = (int*)(base + o_first), *d_sprob = (int*)(base + o_sprob), *d_tot = (int*)(base + o_tot);
-    float* d_cmed = (float*)(base + o_cmed);
+    IoStage io(ctx, st);
+    const auto h_om = io.out<double>(models, 9 * (size_t)P);
+    const auto h_omed = io.out<float>(medians, (size_t)P), h_othr = io.out<float>(thresholds, (size_t)P);
+    const auto h_oinl = io.out<int>(inliers, (size_t)P), h_owin = io.out<int>(winner, 3 * (size_t)P), h_onc = io.out<int>(n_candidates, (size_t)P);
+    const auto h_omask = io.out<unsigned char>(masks, (size_t)NP);
+    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_a = io.in<double>(a, 2 * (size_t)NP), h_b = io.in<double>(b, 2 * (size_t)NP);
+    const auto h_i = io.in<int>(sample_idx, (size_t)S * m);
+    const auto h_m = io.scratch<double>(9 * (size_t)cand_cap);
+    const auto h_n = io.scratch<int>((size_t)S), h_first = io.scratch<int>((size_t)S), h_sprob = io.scratch<int>((size_t)S);
+    const auto h_tot = io.scratch<int>(1), h_ws = io.scratch<int>(prim::scan_ws_elems((size_t)S));
+    const auto h_cmed = io.scratch<float>((size_t)cand_cap);
+    const auto h_rows = io.scratch<float>(need_rows ? (size_t)score_grid * (size_t)max_n : 0);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    const long long *d_pp = d(h_pp), *d_sp = d(h_sp);
+    const double *d_a = d(h_a), *d_b = d(h_b), *d_K = K ? d(h_K) : nullptr;
+    double* d_m = d(h_m);
+    int *d_n = d(h_n), *d_first = d(h_first), *d_sprob = d(h_sprob), *d_tot = d(h_tot);
+    float* d_cmed = d(h_cmed);
     const int normalise = K && kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
         if (S > 0) {
             const unsigned grid = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
             if (kind == EACHAM_SOLVE_HOMOGRAPHY4)
-                lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (int)S, (const int*)(base + o_i), d_m, d_n, d_sprob);
+                lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (int)S, d(h_i), d_m, d_n, d_sprob);
             else
-                lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (const double*)(base + o_K), K ? 1 : 0, (int)S,
-                                                                      (const int*)(base + o_i), d_m, d_n, d_sprob);
+                lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, d(h_K), K ? 1 : 0, (int)S, d(h_i), d_m, d_n, d_sprob);
         }
-        prim::exclusive_scan<int>(st, d_n, d_first, (int)S, (int*)(base + o_ws), d_tot);   // (no samples: *total = 0)
+        prim::exclusive_scan<int>(st, d_n, d_first, (int)S, d(h_ws), d_tot);   // (no samples: *total = 0)
         const size_t smem = sizeof(unsigned) * (size_t)std::max<long long>(1, std::min<long long>(max_n, SC_MAX_LDS));
 #define EACHAM_LB_LAUNCH(KIND)                                                                                                                     \
     do {                                                                                                                                           \
@@ -352,25 +327,15 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
             if (smem > 48 * 1024)                                                                                                                  \
                 EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)lb_score_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
             lb_score_kernel<KIND><<<score_grid, SC_BLOCK, smem, st>>>(d_pp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_sprob, d_m, maxm, \
-                                                                      d_cmed, need_rows ? (float*)(base + o_rows) : nullptr, (size_t)max_n);       \
+                                                                      d_cmed, need_rows ? d(h_rows) : nullptr, (size_t)max_n);                \
         }                                                                                                                                          \
         lb_select_kernel<KIND><<<P, SC_BLOCK, 0, st>>>(d_pp, d_sp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_m, maxm, d_cmed,             \
-                                                       (double*)(base + o_om), (float*)(base + o_omed), (float*)(base + o_othr),                   \
-                                                       (int*)(base + o_oinl), (unsigned char*)(base + o_omask), (int*)(base + o_owin),             \
-                                                       (int*)(base + o_onc));                                                                      \
+                                                       d(h_om), d(h_omed), d(h_othr), d(h_oinl), d(h_omask), d(h_owin), d(h_onc));                 \
     } while (0)
         if (kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_LB_LAUNCH(0);
         else EACHAM_LB_LAUNCH(1);
 #undef EACHAM_LB_LAUNCH
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(models, o_om, sizeof(double) * 9 * (size_t)P)) return rc;
-    if (int rc = io.out(medians, o_omed, sizeof(float) * (size_t)P)) return rc;
-    if (int rc = io.out(thresholds, o_othr, sizeof(float) * (size_t)P)) return rc;
-    if (int rc = io.out(inliers, o_oinl, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.out(winner, o_owin, sizeof(int) * 3 * (size_t)P)) return rc;
-    if (int rc = io.out(n_candidates, o_onc, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.out(masks, o_omask, (size_t)NP)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }

@@ -103,27 +103,17 @@ extern "C" int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, 
     if (!keys_in_lds && medians && total > (1ll << 32)) return ctx->fail(EACHAM_ERR_CAPACITY, "score: error matrix too large");
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const int ma = kind == EACHAM_SCORE_PNP ? 3 : 2, mm = kind == EACHAM_SCORE_PNP ? 12 : 9;
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align(off + bytes); return o; };
     const bool need_err = errors != nullptr || (!keys_in_lds && medians != nullptr);
-    const size_t o_a = take(sizeof(double) * ma * (size_t)n_points), o_b = take(sizeof(double) * 2 * (size_t)n_points);
-    const size_t o_m = take(sizeof(double) * mm * (size_t)n_models), o_K = take(sizeof(double) * 4);
-    const size_t o_c = take(sizeof(int) * (size_t)n_models), o_med = take(sizeof(float) * (size_t)n_models);
-    const size_t o_e = take(need_err ? sizeof(float) * (size_t)total : 0);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, o_e)) return rc;   // everything but the error matrix
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (n_points > 0) {
-        if (int rc = io.in(o_a, a, sizeof(double) * ma * (size_t)n_points)) return rc;
-        if (int rc = io.in(o_b, b, sizeof(double) * 2 * (size_t)n_points)) return rc;
-    }
-    if (int rc = io.in(o_m, models, sizeof(double) * mm * (size_t)n_models)) return rc;
-    if (K)
-        if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.flush_in()) return rc;
+    IoStage io(ctx, st);
+    const auto h_a = io.in<double>(a, ma * (size_t)n_points), h_b = io.in<double>(b, 2 * (size_t)n_points);
+    const auto h_m = io.in<double>(models, mm * (size_t)n_models), h_K = io.in<double>(K, 4);
+    const auto h_c = io.out<int>(inlier_counts, (size_t)n_models);
+    const auto h_med = io.out<float>(medians, (size_t)n_models);
+    // the error matrix: a result when asked for, else the scratch of the medians' selection beyond SC_MAX_LDS points
+    const auto h_e = errors ? io.out<float>(errors, (size_t)total) : io.scratch<float>(need_err ? (size_t)total : 0);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     const size_t smem = keys_in_lds && medians ? sizeof(unsigned) * (size_t)(n_points > 0 ? n_points : 1) : 0;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
@@ -131,11 +121,10 @@ extern "C" int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, 
     do {                                                                                                                       \
         if (smem > 48 * 1024)                                                                                                  \
             EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)score_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-        score_kernel<KIND><<<n_models, SC_BLOCK, smem, st>>>(n_points, (const double*)(base + o_a), (const double*)(base + o_b),  \
-                                                             (const double*)(base + o_m), K ? (const double*)(base + o_K) : nullptr, \
+        score_kernel<KIND><<<n_models, SC_BLOCK, smem, st>>>(n_points, d(h_a), d(h_b), d(h_m), K ? d(h_K) : nullptr,                 \
                                                              K && kind == EACHAM_SCORE_ESSENTIAL ? 1 : 0, threshold,             \
-                                                             need_err ? (float*)(base + o_e) : nullptr, (int*)(base + o_c),      \
-                                                             medians ? (float*)(base + o_med) : nullptr, keys_in_lds && medians ? 1 : 0); \
+                                                             need_err ? d(h_e) : nullptr, d(h_c), medians ? d(h_med) : nullptr,  \
+                                                             keys_in_lds && medians ? 1 : 0);                                    \
     } while (0)
         if (kind == EACHAM_SCORE_ESSENTIAL) EACHAM_SCORE_LAUNCH(0);
         else if (kind == EACHAM_SCORE_HOMOGRAPHY) EACHAM_SCORE_LAUNCH(1);
@@ -143,10 +132,5 @@ extern "C" int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, 
 #undef EACHAM_SCORE_LAUNCH
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(inlier_counts, o_c, sizeof(int) * (size_t)n_models)) return rc;
-    if (int rc = io.out(medians, o_med, sizeof(float) * (size_t)n_models)) return rc;
-    if (total > 0)
-        if (int rc = io.out(errors, o_e, sizeof(float) * (size_t)total)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }

@@ -634,38 +634,25 @@ extern "C" int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, con
         if (sample_idx[k] < 0 || sample_idx[k] >= n_points)
             return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: sample index %d of %d points", (int)sample_idx[k], n_points);
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_a = take(sizeof(double) * 2 * (size_t)n_points), o_b = take(sizeof(double) * 2 * (size_t)n_points), o_K = take(sizeof(double) * 4);
-    const size_t o_i = take(sizeof(int) * (size_t)n_samples * m), o_m = take(sizeof(double) * 9 * (size_t)maxm * n_samples);
-    const size_t o_n = take(sizeof(int) * (size_t)n_samples);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, off)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (int rc = io.in(o_a, a, sizeof(double) * 2 * (size_t)n_points)) return rc;
-    if (int rc = io.in(o_b, b, sizeof(double) * 2 * (size_t)n_points)) return rc;
-    if (K)
-        if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_i, sample_idx, sizeof(int) * (size_t)n_samples * m)) return rc;
-    if (int rc = io.flush_in()) return rc;
+    IoStage io(ctx, st);
+    const auto h_a = io.in<double>(a, 2 * (size_t)n_points), h_b = io.in<double>(b, 2 * (size_t)n_points);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_i = io.in<int>(sample_idx, (size_t)n_samples * m);
+    const auto h_m = io.out<double>(models, 9 * (size_t)maxm * n_samples);
+    const auto h_n = io.out<int>(n_models, (size_t)n_samples);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
         const unsigned grid = (unsigned)((n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES);
         if (kind == EACHAM_SOLVE_HOMOGRAPHY4)
-            solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>((const double*)(base + o_a), (const double*)(base + o_b), n_samples,
-                                                               (const int*)(base + o_i), (double*)(base + o_m), (int*)(base + o_n));
+            solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d(h_a), d(h_b), n_samples, d(h_i), d(h_m), d(h_n));
         else
-            solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>((const double*)(base + o_a), (const double*)(base + o_b), (const double*)(base + o_K),
-                                                               K ? 1 : 0, n_samples, (const int*)(base + o_i), (double*)(base + o_m), (int*)(base + o_n));
+            solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d(h_a), d(h_b), d(h_K), K ? 1 : 0, n_samples, d(h_i), d(h_m), d(h_n));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(models, o_m, sizeof(double) * 9 * (size_t)maxm * n_samples)) return rc;
-    if (int rc = io.out(n_models, o_n, sizeof(int) * (size_t)n_samples)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }
 
 extern "C" int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* object_points, const double* image_points, const double* K,
@@ -681,23 +668,17 @@ extern "C" int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* obj
         if (sample_idx[k] < 0 || sample_idx[k] >= n_points)
             return ctx->fail(EACHAM_ERR_INVALID, "solve_pnp: sample index %d of %d points", (int)sample_idx[k], n_points);
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    auto align256 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_a = take(sizeof(double) * 3 * (size_t)n_points), o_b = take(sizeof(double) * 2 * (size_t)n_points), o_K = take(sizeof(double) * 4);
-    const size_t o_i = take(sizeof(int) * (size_t)total), o_m = take(sizeof(double) * 12 * (size_t)n_samples), o_n = take(sizeof(int) * (size_t)n_samples);
-    const size_t o_f = take(sample_size <= 64 ? sizeof(double) * PNP_FRAME * (size_t)n_samples : 0);   // the samples' frames between the two launches
-    const size_t o_t = take(sample_size <= 64 ? sizeof(double) * 3 * 13 * (size_t)n_samples : 0);        // error + pose of the three starts
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, o_f)) return rc;   // everything but the samples' frames, which never leave the device
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (int rc = io.in(o_a, object_points, sizeof(double) * 3 * (size_t)n_points)) return rc;
-    if (int rc = io.in(o_b, image_points, sizeof(double) * 2 * (size_t)n_points)) return rc;
-    if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_i, sample_idx, sizeof(int) * (size_t)total)) return rc;
-    if (int rc = io.flush_in()) return rc;
+    IoStage io(ctx, st);
+    const auto h_a = io.in<double>(object_points, 3 * (size_t)n_points), h_b = io.in<double>(image_points, 2 * (size_t)n_points);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_i = io.in<int>(sample_idx, (size_t)total);
+    const auto h_m = io.out<double>(models, 12 * (size_t)n_samples);
+    const auto h_n = io.out<int>(n_models, (size_t)n_samples);
+    const auto h_f = io.scratch<double>(sample_size <= 64 ? PNP_FRAME * (size_t)n_samples : 0);   // the samples' frames between the two launches
+    const auto h_t = io.scratch<double>(sample_size <= 64 ? 3 * 13 * (size_t)n_samples : 0);      // error + pose of the three starts
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
         // Bit-identical with the CPU restatement either way: samples of at most 64 points — the RANSAC loop's — a wave per sample for the
@@ -705,20 +686,14 @@ extern "C" int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* obj
         if (sample_size <= 64) {
             solve_pnp_front_kernel<<<(unsigned)((n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES), 64 * SOLVE_WAVES,
                                      sizeof(double) * SOLVE_WAVES * 24 * (size_t)std::min(sample_size, 64), st>>>(
-                (const double*)(base + o_a), (const double*)(base + o_b), (const double*)(base + o_K), sample_size, n_samples,
-                (const int*)(base + o_i), (double*)(base + o_f));
+                d(h_a), d(h_b), d(h_K), sample_size, n_samples, d(h_i), d(h_f));
             const unsigned gb = (unsigned)((n_samples + 63) / 64);
-            solve_pnp_back_kernel<<<dim3(gb, 3), 64, 0, st>>>((const double*)(base + o_a), (const double*)(base + o_b), (const double*)(base + o_K),
-                                                              sample_size, n_samples, (const int*)(base + o_i), (const double*)(base + o_f), (double*)(base + o_t));
-            solve_pnp_select_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(n_samples, (const double*)(base + o_t), (double*)(base + o_m), (int*)(base + o_n));
+            solve_pnp_back_kernel<<<dim3(gb, 3), 64, 0, st>>>(d(h_a), d(h_b), d(h_K), sample_size, n_samples, d(h_i), d(h_f), d(h_t));
+            solve_pnp_select_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(n_samples, d(h_t), d(h_m), d(h_n));
         }
         else
-            solve_pnp_big_kernel<<<(unsigned)n_samples, 192, 0, st>>>((const double*)(base + o_a), (const double*)(base + o_b), (const double*)(base + o_K),
-                                                                     sample_size, (const int*)(base + o_i), (double*)(base + o_m), (int*)(base + o_n));
+            solve_pnp_big_kernel<<<(unsigned)n_samples, 192, 0, st>>>(d(h_a), d(h_b), d(h_K), sample_size, d(h_i), d(h_m), d(h_n));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(models, o_m, sizeof(double) * 12 * (size_t)n_samples)) return rc;
-    if (int rc = io.out(n_models, o_n, sizeof(int) * (size_t)n_samples)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }

@@ -16,6 +16,7 @@
 // window (<= a few hundred 128-byte matrices) live in L2/L1. The launch is flat over pairs so short
 // tracks do not idle lanes; a binary search over the pair CSR finds the owning track.
 #include "context.hpp"
+#include "devprim.hpp"
 
 namespace eacham {
 
@@ -142,12 +143,7 @@ __global__ __launch_bounds__(TRI_BLOCK) void tri_pairs_kernel(
     const long long pid = (long long)blockIdx.x * TRI_BLOCK + threadIdx.x;
     const long long total = pair_ptr[n_tracks];
     if (pid >= total) return;
-    int lo = 0, hi = n_tracks;  // largest t with pair_ptr[t] <= pid
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (pair_ptr[mid] <= pid) lo = mid; else hi = mid;
-    }
-    const int t = lo;
+    const int t = prim::segment_of(pair_ptr, n_tracks, pid);
     const int o0 = track_ptr[t], m = track_ptr[t + 1] - o0;
     int r1, r2;
     tri_pair_rows(m, pid - pair_ptr[t], r1, r2);
@@ -236,50 +232,7 @@ __global__ __launch_bounds__(TRI_BLOCK) void reproject_kernel(const double* __re
     err[i] = (float)sqrt((p.x - u) * (p.x - u) + (p.y - v) * (p.y - v));
 }
 
-// Two-view structure for candidate relative poses (ReconstructionManager.cpp:118-143, :162-186):
-// thread = (transform, match); camera 1 is the identity.
-__global__ __launch_bounds__(TRI_BLOCK) void two_view_kernel(int n, const double2* __restrict__ uv1,
-                                                             const double2* __restrict__ uv2, const double* __restrict__ Kdev,
-                                                             int nt, const double* __restrict__ transforms, float max_err,
-                                                             float min_angle, int angle_strict, double* __restrict__ points,
-                                                             unsigned char* __restrict__ keep) {
-    const long long id = (long long)blockIdx.x * TRI_BLOCK + threadIdx.x;
-    if (id >= (long long)n * nt) return;
-    const int k = (int)(id / n), i = (int)(id % n);
-    const double K[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
-    const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    const double* T = transforms + 16 * (size_t)k;
-    const double2 p1 = uv1[i], p2 = uv2[i];
-    const double x1 = (p1.x - K[2]) / K[0], y1 = (p1.y - K[3]) / K[1];
-    const double x2 = (p2.x - K[2]) / K[0], y2 = (p2.y - K[3]) / K[1];
-    double A[4][4], x[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        A[1][j] = x1 * I4[8 + j] - I4[j];
-        A[0][j] = y1 * I4[8 + j] - I4[4 + j];
-        A[3][j] = x2 * T[8 + j] - T[j];
-        A[2][j] = y2 * T[8 + j] - T[4 + j];
-    }
-    null_vector_4x4(A, x);
-    const double X[3] = {x[0] / x[3], x[1] / x[3], x[2] / x[3]};
-    double* out = points + 3 * (size_t)id;
-    out[0] = X[0];
-    out[1] = X[1];
-    out[2] = X[2];
-    bool ok = false;
-    if (!(X[2] <= 0.0)) {
-        const double u = (K[0] * X[0]) / X[2] + K[2], v = (K[1] * X[1]) / X[2] + K[3];
-        const float err = (float)sqrt((p1.x - u) * (p1.x - u) + (p1.y - v) * (p1.y - v));
-        const double ang = tri_angle(I4, T, X);
-        ok = err < max_err && (angle_strict ? ang > (double)min_angle : !(ang < (double)min_angle));
-    }
-    keep[id] = ok ? 1 : 0;
-}
-
-// ---- eacham_two_view_batch: the same per-item work for a LIST of problems, and the reference's choice among each
-// problem's candidates, without a host turn ---------------------------------------------------------------------------
-// two_view_kernel's arithmetic, statement for statement, as functions for tvb_points_kernel (two_view_kernel itself keeps its
-// body: taking it apart moves its register allocation). The point of one (transform, match) ...
+// The point of one (transform, match) item, camera 1 the identity ...
 __device__ __forceinline__ void two_view_point(const double2 p1, const double2 p2, const double (&K)[4], const double (&I4)[16],
                                                const double* __restrict__ T, double (&X)[3]) {
     const double x1 = (p1.x - K[2]) / K[0], y1 = (p1.y - K[3]) / K[1];
@@ -308,6 +261,31 @@ __device__ __forceinline__ bool two_view_keep(const double2 p1, const double (&K
     return ok;
 }
 
+// Two-view structure for candidate relative poses (ReconstructionManager.cpp:118-143, :162-186):
+// thread = (transform, match); camera 1 is the identity.
+__global__ __launch_bounds__(TRI_BLOCK) void two_view_kernel(int n, const double2* __restrict__ uv1,
+                                                             const double2* __restrict__ uv2, const double* __restrict__ Kdev,
+                                                             int nt, const double* __restrict__ transforms, float max_err,
+                                                             float min_angle, int angle_strict, double* __restrict__ points,
+                                                             unsigned char* __restrict__ keep) {
+    const long long id = (long long)blockIdx.x * TRI_BLOCK + threadIdx.x;
+    if (id >= (long long)n * nt) return;
+    const int k = (int)(id / n), i = (int)(id % n);
+    const double K[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
+    const double I4[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    const double* T = transforms + 16 * (size_t)k;
+    const double2 p1 = uv1[i], p2 = uv2[i];
+    double X[3];
+    two_view_point(p1, p2, K, I4, T, X);
+    double* out = points + 3 * (size_t)id;
+    out[0] = X[0];
+    out[1] = X[1];
+    out[2] = X[2];
+    keep[id] = two_view_keep(p1, K, I4, T, X, max_err, min_angle, angle_strict) ? 1 : 0;
+}
+
+// ---- eacham_two_view_batch: the same per-item work for a LIST of problems, and the reference's choice among each
+// problem's candidates, without a host turn ---------------------------------------------------------------------------
 constexpr unsigned char TVB_KEEP = 1, TVB_CHEIRAL = 2;   // the flag byte of an item
 
 // K1: flat over the items (problem, candidate, match): item_ptr[p] = items before problem p (the host's int64 prefix of
@@ -322,12 +300,7 @@ __global__ __launch_bounds__(TRI_BLOCK) void tvb_points_kernel(
     unsigned char* __restrict__ ws_flags) {
     const long long id = (long long)blockIdx.x * TRI_BLOCK + threadIdx.x;
     if (id >= item_ptr[n_problems]) return;
-    int lo = 0, hi = n_problems;  // largest p with item_ptr[p] <= id: the one problem that owns items there
-    while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (item_ptr[mid] <= id) lo = mid; else hi = mid;
-    }
-    const int p = lo;
+    const int p = prim::segment_of(item_ptr, n_problems, id);   // the one problem that owns items there
     const long long base = point_ptr[p], local = id - item_ptr[p];
     const int n = (int)(point_ptr[p + 1] - base);
     const int k = (int)(local / n), i = (int)(local % n);
@@ -412,8 +385,6 @@ __global__ __launch_bounds__(TRI_BLOCK) void tvb_select_kernel(
     }
 }
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 }  // namespace
 
 }  // namespace eacham
@@ -446,47 +417,30 @@ extern "C" int eacham_triangulate_tracks(eacham_ctx* ctx, const double* transfor
     if (n_pairs > (1ll << 31) * TRI_BLOCK) return ctx->fail(EACHAM_ERR_CAPACITY, "triangulate: too many pairs");
 
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_T = take(sizeof(double) * 16 * (size_t)n_frames), o_K = take(sizeof(double) * 4);
-    const size_t o_tp = take(sizeof(int) * ((size_t)n_tracks + 1)), o_pp = take(sizeof(long long) * ((size_t)n_tracks + 1));
-    const size_t o_of = take(sizeof(unsigned) * (size_t)n_obs), o_uv = take(sizeof(double) * 2 * (size_t)n_obs);
-    const size_t o_pt = take(sizeof(double) * 3 * (size_t)n_tracks), o_ac = take(sizeof(int) * (size_t)n_tracks);
-    const size_t o_mk = take((size_t)n_obs), o_pi = take(sizeof(int) * (size_t)n_pairs);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, o_pi)) return rc;   // everything but the per-pair scratch
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (n_obs > 0)
-        if (int rc = io.in(o_T, transforms, sizeof(double) * 16 * (size_t)n_frames)) return rc;
-    if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_tp, track_ptr, sizeof(int) * ((size_t)n_tracks + 1))) return rc;
-    if (int rc = io.in(o_pp, pair_ptr.data(), sizeof(long long) * ((size_t)n_tracks + 1))) return rc;
-    if (n_obs > 0) {
-        if (int rc = io.in(o_of, obs_frame, sizeof(unsigned) * (size_t)n_obs)) return rc;
-        if (int rc = io.in(o_uv, obs_uv, sizeof(double) * 2 * (size_t)n_obs)) return rc;
-    }
-    if (int rc = io.flush_in()) return rc;
+    IoStage io(ctx, st);
+    const auto h_T = io.in<double>(n_obs > 0 ? transforms : nullptr, 16 * (size_t)n_frames), h_K = io.in<double>(K, 4);
+    const auto h_tp = io.in<int>(track_ptr, (size_t)n_tracks + 1);
+    const auto h_pp = io.in<long long>(pair_ptr.data(), (size_t)n_tracks + 1);
+    const auto h_of = io.in<unsigned>(obs_frame, (size_t)n_obs);
+    const auto h_uv = io.in<double2>(obs_uv, (size_t)n_obs);
+    const auto h_pt = io.out<double>(points, 3 * (size_t)n_tracks);
+    const auto h_ac = io.out<int>(status, (size_t)n_tracks);
+    const auto h_mk = io.out<unsigned char>(masks, (size_t)n_obs);
+    const auto h_pi = io.scratch<int>((size_t)n_pairs);   // the per-pair inlier counts
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_TRIANGULATE);
         if (n_pairs > 0)
             tri_pairs_kernel<<<(unsigned)((n_pairs + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
-                (const double*)(base + o_T), n_tracks, (const int*)(base + o_tp), (const long long*)(base + o_pp),
-                (const unsigned*)(base + o_of), (const double2*)(base + o_uv), (const double*)(base + o_K), max_repr_error,
-                min_tri_angle, (double*)(base + o_pt), (int*)(base + o_pi));
+                d(h_T), n_tracks, d(h_tp), d(h_pp), d(h_of), d(h_uv), d(h_K), max_repr_error, min_tri_angle, d(h_pt), d(h_pi));
         tri_select_kernel<<<(unsigned)((n_tracks + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
-            (const double*)(base + o_T), n_tracks, (const int*)(base + o_tp), (const long long*)(base + o_pp),
-            (const unsigned*)(base + o_of), (const double2*)(base + o_uv), (const double*)(base + o_K), max_repr_error,
-            min_tri_angle, (const int*)(base + o_pi), (double*)(base + o_pt), (int*)(base + o_ac), (unsigned char*)(base + o_mk));
+            d(h_T), n_tracks, d(h_tp), d(h_pp), d(h_of), d(h_uv), d(h_K), max_repr_error, min_tri_angle, d(h_pi), d(h_pt), d(h_ac),
+            d(h_mk));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(points, o_pt, sizeof(double) * 3 * (size_t)n_tracks)) return rc;
-    if (int rc = io.out(status, o_ac, sizeof(int) * (size_t)n_tracks)) return rc;
-    if (n_obs > 0)
-        if (int rc = io.out(masks, o_mk, (size_t)n_obs)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }
 
 extern "C" int eacham_reprojection_errors(eacham_ctx* ctx, const double* transforms, int n_frames, int n,
@@ -501,29 +455,18 @@ extern "C" int eacham_reprojection_errors(eacham_ctx* ctx, const double* transfo
         if (frame[i] >= (uint32_t)n_frames)
             return ctx->fail(EACHAM_ERR_INVALID, "reprojection: item %d names frame %u of %d", i, frame[i], n_frames);
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_T = take(sizeof(double) * 16 * (size_t)n_frames), o_K = take(sizeof(double) * 4);
-    const size_t o_f = take(sizeof(unsigned) * (size_t)n), o_p = take(sizeof(double) * 3 * (size_t)n);
-    const size_t o_uv = take(sizeof(double) * 2 * (size_t)n), o_e = take(sizeof(float) * (size_t)n);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, off)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (int rc = io.in(o_T, transforms, sizeof(double) * 16 * (size_t)n_frames)) return rc;
-    if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_f, frame, sizeof(unsigned) * (size_t)n)) return rc;
-    if (int rc = io.in(o_p, points, sizeof(double) * 3 * (size_t)n)) return rc;
-    if (int rc = io.in(o_uv, uv, sizeof(double) * 2 * (size_t)n)) return rc;
-    if (int rc = io.flush_in()) return rc;
-    reproject_kernel<<<(unsigned)((n + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
-        (const double*)(base + o_T), n, (const unsigned*)(base + o_f), (const double*)(base + o_p),
-        (const double2*)(base + o_uv), (const double*)(base + o_K), (float*)(base + o_e));
+    IoStage io(ctx, st);
+    const auto h_T = io.in<double>(transforms, 16 * (size_t)n_frames), h_K = io.in<double>(K, 4);
+    const auto h_f = io.in<unsigned>(frame, (size_t)n);
+    const auto h_p = io.in<double>(points, 3 * (size_t)n);
+    const auto h_uv = io.in<double2>(uv, (size_t)n);
+    const auto h_e = io.out<float>(err, (size_t)n);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    reproject_kernel<<<(unsigned)((n + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(d(h_T), n, d(h_f), d(h_p), d(h_uv), d(h_K), d(h_e));
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(err, o_e, sizeof(float) * (size_t)n)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }
 
 extern "C" int eacham_two_view_points(eacham_ctx* ctx, int n_matches, const double* uv1, const double* uv2, const double* K,
@@ -539,29 +482,21 @@ extern "C" int eacham_two_view_points(eacham_ctx* ctx, int n_matches, const doub
     if (!uv1 || !uv2 || !transforms || !points || !keep || !counts) return ctx->fail(EACHAM_ERR_INVALID, "two_view: null array");
     if (total > (1ll << 31) - 1) return ctx->fail(EACHAM_ERR_CAPACITY, "two_view: too many (transform, match) items");
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_u1 = take(sizeof(double) * 2 * (size_t)n_matches), o_u2 = take(sizeof(double) * 2 * (size_t)n_matches);
-    const size_t o_K = take(sizeof(double) * 4), o_T = take(sizeof(double) * 16 * (size_t)n_transforms);
-    const size_t o_p = take(sizeof(double) * 3 * (size_t)total), o_k = take((size_t)total);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(base + o_u1, uv1, sizeof(double) * 2 * (size_t)n_matches, hipMemcpyHostToDevice, st));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(base + o_u2, uv2, sizeof(double) * 2 * (size_t)n_matches, hipMemcpyHostToDevice, st));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(base + o_K, K, sizeof(double) * 4, hipMemcpyHostToDevice, st));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(base + o_T, transforms, sizeof(double) * 16 * (size_t)n_transforms, hipMemcpyHostToDevice, st));
+    IoStage io(ctx, st);
+    const auto h_u1 = io.in<double2>(uv1, (size_t)n_matches), h_u2 = io.in<double2>(uv2, (size_t)n_matches);
+    const auto h_K = io.in<double>(K, 4), h_T = io.in<double>(transforms, 16 * (size_t)n_transforms);
+    const auto h_p = io.out<double>(points, 3 * (size_t)total);
+    const auto h_k = io.out<unsigned char>(keep, (size_t)total);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_TRIANGULATE);
         two_view_kernel<<<(unsigned)((total + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
-            n_matches, (const double2*)(base + o_u1), (const double2*)(base + o_u2), (const double*)(base + o_K), n_transforms,
-            (const double*)(base + o_T), max_repr_error, min_tri_angle, angle_strict, (double*)(base + o_p),
-            (unsigned char*)(base + o_k));
+            n_matches, d(h_u1), d(h_u2), d(h_K), n_transforms, d(h_T), max_repr_error, min_tri_angle, angle_strict, d(h_p), d(h_k));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(points, base + o_p, sizeof(double) * 3 * (size_t)total, hipMemcpyDeviceToHost, st));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(keep, base + o_k, (size_t)total, hipMemcpyDeviceToHost, st));
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (int rc = io.finish()) return rc;
     for (int k = 0; k < n_transforms; ++k) {  // counts on the host: the masks are here anyway
         int32_t c = 0;
         for (int i = 0; i < n_matches; ++i) c += keep[(size_t)k * n_matches + i];
@@ -602,55 +537,31 @@ extern "C" int eacham_two_view_batch(eacham_ctx* ctx, int n_problems, const int6
     if ((NP > 0 && (!uv1 || !uv2 || !points || !keep || !pose_mask)) || (NT > 0 && (!transforms || !cand_counts)))
         return ctx->fail(EACHAM_ERR_INVALID, "two_view_batch: null array");
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    // the results, then the inputs (each side one contiguous span of the pinned mirror), then what never leaves the device
-    const size_t o_win = take(sizeof(int) * (size_t)P), o_good = take(sizeof(int) * (size_t)P), o_kept = take(sizeof(int) * (size_t)P);
-    const size_t o_cc = take(sizeof(int) * (size_t)NT), o_keep = take((size_t)NP), o_pm = take((size_t)NP);
-    const size_t o_pts = take(sizeof(double) * 3 * (size_t)NP);
-    const size_t o_ip = take(sizeof(long long) * ((size_t)P + 1)), o_pp = take(sizeof(int64_t) * ((size_t)P + 1));
-    const size_t o_tp = take(sizeof(int64_t) * ((size_t)P + 1)), o_rule = take(sizeof(int) * (size_t)P), o_K = take(sizeof(double) * 4);
-    const size_t o_T = take(sizeof(double) * 16 * (size_t)NT), o_im = take(in_mask ? (size_t)NP : 0);
-    const size_t o_u1 = take(sizeof(double) * 2 * (size_t)NP), o_u2 = take(sizeof(double) * 2 * (size_t)NP);
-    const size_t o_dev = off;
-    const size_t o_wp = take(sizeof(double) * 3 * (size_t)NI), o_wf = take((size_t)NI);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    if (int rc = ensure_io_host(ctx, o_dev)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    IoPack io(ctx, st);
-    if (int rc = io.in(o_ip, item_ptr.data(), sizeof(long long) * ((size_t)P + 1))) return rc;
-    if (int rc = io.in(o_pp, point_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
-    if (int rc = io.in(o_tp, transform_ptr, sizeof(int64_t) * ((size_t)P + 1))) return rc;
-    if (int rc = io.in(o_rule, rule, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.in(o_K, K, sizeof(double) * 4)) return rc;
-    if (int rc = io.in(o_T, transforms, sizeof(double) * 16 * (size_t)NT)) return rc;
-    if (in_mask)
-        if (int rc = io.in(o_im, in_mask, (size_t)NP)) return rc;
-    if (int rc = io.in(o_u1, uv1, sizeof(double) * 2 * (size_t)NP)) return rc;
-    if (int rc = io.in(o_u2, uv2, sizeof(double) * 2 * (size_t)NP)) return rc;
-    if (int rc = io.flush_in()) return rc;
-    const long long *d_ip = (const long long*)(base + o_ip), *d_pp = (const long long*)(base + o_pp), *d_tp = (const long long*)(base + o_tp);
+    IoStage io(ctx, st);
+    const auto h_win = io.out<int>(winner, (size_t)P), h_good = io.out<int>(good, (size_t)P), h_kept = io.out<int>(kept, (size_t)P);
+    const auto h_cc = io.out<int>(cand_counts, (size_t)NT);
+    const auto h_keep = io.out<unsigned char>(keep, (size_t)NP), h_pm = io.out<unsigned char>(pose_mask, (size_t)NP);
+    const auto h_pts = io.out<double>(points, 3 * (size_t)NP);
+    const auto h_ip = io.in<long long>(item_ptr.data(), (size_t)P + 1);
+    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_tp = io.in<long long>(transform_ptr, (size_t)P + 1);
+    const auto h_rule = io.in<int>(rule, (size_t)P);
+    const auto h_K = io.in<double>(K, 4), h_T = io.in<double>(transforms, 16 * (size_t)NT);
+    const auto h_im = io.in<unsigned char>(in_mask, in_mask ? (size_t)NP : 0);
+    const auto h_u1 = io.in<double2>(uv1, (size_t)NP), h_u2 = io.in<double2>(uv2, (size_t)NP);
+    const auto h_wp = io.scratch<double>(3 * (size_t)NI);          // every item's point and flag byte
+    const auto h_wf = io.scratch<unsigned char>((size_t)NI);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_TRIANGULATE);
         if (NI > 0)
             tvb_points_kernel<<<(unsigned)((NI + TRI_BLOCK - 1) / TRI_BLOCK), TRI_BLOCK, 0, st>>>(
-                P, d_ip, d_pp, d_tp, (const int*)(base + o_rule), (const double2*)(base + o_u1), (const double2*)(base + o_u2),
-                (const double*)(base + o_K), (const double*)(base + o_T), in_mask ? (const unsigned char*)(base + o_im) : nullptr,
-                max_repr_error, min_tri_angle, distance_thresh, (double*)(base + o_wp), (unsigned char*)(base + o_wf));
-        tvb_select_kernel<<<P, TRI_BLOCK, 0, st>>>(d_ip, d_pp, d_tp, (const int*)(base + o_rule), min_solution_matches,
-                                                   (const double*)(base + o_wp), (const unsigned char*)(base + o_wf), (int*)(base + o_win),
-                                                   (int*)(base + o_good), (int*)(base + o_kept), (int*)(base + o_cc), (double*)(base + o_pts),
-                                                   (unsigned char*)(base + o_keep), (unsigned char*)(base + o_pm));
+                P, d(h_ip), d(h_pp), d(h_tp), d(h_rule), d(h_u1), d(h_u2), d(h_K), d(h_T), in_mask ? d(h_im) : nullptr, max_repr_error,
+                min_tri_angle, distance_thresh, d(h_wp), d(h_wf));
+        tvb_select_kernel<<<P, TRI_BLOCK, 0, st>>>(d(h_ip), d(h_pp), d(h_tp), d(h_rule), min_solution_matches, d(h_wp), d(h_wf), d(h_win),
+                                                   d(h_good), d(h_kept), d(h_cc), d(h_pts), d(h_keep), d(h_pm));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    if (int rc = io.out(winner, o_win, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.out(good, o_good, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.out(kept, o_kept, sizeof(int) * (size_t)P)) return rc;
-    if (int rc = io.out(cand_counts, o_cc, sizeof(int) * (size_t)NT)) return rc;
-    if (int rc = io.out(keep, o_keep, (size_t)NP)) return rc;
-    if (int rc = io.out(pose_mask, o_pm, (size_t)NP)) return rc;
-    if (int rc = io.out(points, o_pts, sizeof(double) * 3 * (size_t)NP)) return rc;
-    if (int rc = io.finish()) return rc;
-    return EACHAM_OK;
+    return io.finish();
 }

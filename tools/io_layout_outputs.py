@@ -1,0 +1,132 @@
+"""Every output of the nine host-pointer entry points that stage through IoStage, as raw bytes, for a before/after run of two
+builds of the library (EACHAM_HIP_LIB selects the build; each build needs a process of its own):
+
+    EACHAM_HIP_LIB=<parent build> python tools/io_layout_outputs.py --dump /tmp/parent.npz
+    python tools/io_layout_outputs.py --dump /tmp/new.npz
+    python tools/io_layout_outputs.py --compare /tmp/parent.npz /tmp/new.npz [--out profiles/io_layout_parent_vs_new.txt]
+
+Inputs: the cases of tests/two_view_batch_cases.py (eacham_two_view_batch, and eacham_two_view_points problem by problem), the
+cases of tests/lmeds_batch_cases.py in their three variants (eacham_lmeds_batch, and eacham_solve_minimal +
+eacham_score_hypotheses problem by problem), tests/test_tri_oracle.py's two-view case (seed 5, 2000 matches, both angle rules), one
+synth.make_tracks scene (eacham_triangulate_tracks, eacham_reprojection_errors), one PnP batch (eacham_solve_pnp,
+eacham_score_hypotheses) and the resident graph after eacham_graph_set_frames (its query's answer)."""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def dump(path):
+    from eacham_amd import HipContext, score, synth, triangulate as tri
+    from eacham_amd import graph as G
+    import lmeds_batch_cases as LC
+    import score_cases as SC
+    import two_view_batch_cases as TC
+    from test_graph_oracle import scenario
+    from test_tri_oracle import _two_view_case
+
+    out = {}
+
+    def put(name, *arrays):
+        for k, a in enumerate(arrays):
+            a = np.ascontiguousarray(a)
+            out[f"{name}/{k}"] = np.frombuffer(a.tobytes(), np.uint8)
+
+    with HipContext(0) as ctx:
+        for name, make in TC.CASES.items():
+            c = make()
+            g = ctx.two_view_batch(c["uv1"], c["uv2"], c["K"], c["rules"], c["transforms"], c["max_err"], c["min_angle"], c["in_mask"], c["dist"],
+                                   c["min_solution_matches"])
+            put(f"two_view_batch/{name}", g.winner, g.good, g.kept, *g.cand_counts, *g.points, *g.keep, *g.pose_mask)
+            for p in range(len(c["uv1"])):
+                if len(c["transforms"][p]):
+                    for strict in (False, True):
+                        put(f"two_view_points/{name}/{p}/{int(strict)}",
+                            *tri.two_view_points(ctx, c["uv1"][p], c["uv2"][p], c["K"], c["transforms"][p], c["max_err"], c["min_angle"], strict))
+        for name, make in LC.CASES.items():
+            for variant in ("homography", "essential", "essential_noK"):
+                c = make(variant.split("_")[0])
+                if variant.endswith("noK"):
+                    c = LC.normalised(c)
+                g = ctx.lmeds_batch(c["kind"], c["uv1"], c["uv2"], c["samples"], c["K"])
+                put(f"lmeds_batch/{name}/{variant}", g.models, g.medians, g.thresholds, g.inliers, *g.masks, g.winner, g.n_candidates)
+                solver = "homography4" if c["kind"] == "homography" else "essential5"
+                for p in range(len(c["uv1"])):
+                    if len(c["samples"][p]) == 0:
+                        continue
+                    models, nm = score.solve_minimal(ctx, solver, c["uv1"][p], c["uv2"][p], c["samples"][p], c["K"])
+                    put(f"solve_minimal/{name}/{variant}/{p}", models, nm)
+                    cand = np.concatenate([models[s, :nm[s]] for s in range(len(nm))]).reshape(-1, 9)
+                    if len(cand):
+                        put(f"score/{name}/{variant}/{p}", *score.score_hypotheses(ctx, c["kind"], c["uv1"][p], c["uv2"][p], cand, c["K"], 1e-4))
+                        put(f"score_medians_only/{name}/{variant}/{p}",
+                            *score.score_hypotheses(ctx, c["kind"], c["uv1"][p], c["uv2"][p], cand, c["K"], 0.0, want_errors=False)[1:])
+        uv1, uv2, K, Ts = _two_view_case(seed=5, n=2000)
+        for strict in (True, False):
+            put(f"two_view_points/seed5/{int(strict)}", *tri.two_view_points(ctx, uv1, uv2, K, Ts, 4.0, float(np.deg2rad(1.0)), strict))
+        sc = synth.make_scene(12, 600, 6, seed=7)
+        tr = synth.make_tracks(sc, seed=7, min_obs=2, outlier_frac=0.3)
+        pts, status, masks = tri.triangulate_tracks(ctx, tr["transforms"], tr["track_ptr"], tr["obs_frame"], tr["obs_uv"], tr["K"], 4.0,
+                                                    float(np.deg2rad(1.0)))
+        put("triangulate_tracks", pts, status, masks)
+        first = np.asarray(tr["track_ptr"][:-1])
+        keep = np.diff(tr["track_ptr"]) > 0
+        put("reprojection_errors", tri.reprojection_errors(ctx, tr["transforms"], np.asarray(tr["obs_frame"])[first[keep]], pts[keep],
+                                                           np.asarray(tr["obs_uv"]).reshape(-1, 2)[first[keep]], tr["K"]))
+        c = SC.pnp_case(n=800, n_models=64, seed=17)
+        rng = np.random.default_rng(17)
+        for size in (5, 6, 100):                                          # the loop's sample sizes, and the all-inlier refit's form
+            samples = np.array([rng.choice(800, size=size, replace=False) for _ in range(300)], np.int32)
+            models, ok = score.solve_pnp(ctx, c["X"], c["uv"], c["K"], samples)
+            put(f"solve_pnp/{size}", models, ok)
+            put(f"score_pnp/{size}", *score.score_hypotheses(ctx, "pnp", c["X"], c["uv"], models, c["K"], 16.0))
+        pairs, counts, offsets, q, t, valid, has3d, excluded = scenario(40, 3)
+        rg = G.ResidentGraph(ctx, 40, pairs, counts, offsets, q, t, [len(a) for a in has3d])
+        try:
+            for lo in range(0, 40, 7):
+                fr = list(range(lo, min(lo + 7, 40)))
+                rg.set_frames(fr, [valid[f] for f in fr], [has3d[f] for f in fr])
+                put(f"graph_set_frames/{lo}", np.array(rg.query(), np.int64), np.array(rg.query(np.nonzero(excluded)[0]), np.int64))
+        finally:
+            rg.close()
+    np.savez(path, **out)
+    print(f"{len(out)} arrays, {sum(a.size for a in out.values())} bytes -> {path}")
+
+
+def compare(a_path, b_path, out_path):
+    a, b = np.load(a_path), np.load(b_path)
+    lines = [f"Outputs of the nine staged entry points, parent build against this one, as raw bytes ({os.path.basename(a_path)} vs {os.path.basename(b_path)})"]
+    groups = {}
+    bad = sorted(set(a.files) ^ set(b.files))
+    for k in sorted(set(a.files) & set(b.files)):
+        g = groups.setdefault(k.split("/")[0], [0, 0, 0])
+        x, y = a[k], b[k]
+        g[0] += 1
+        g[1] += x.size
+        g[2] += int((x != y).sum()) if x.size == y.size else max(x.size, y.size)
+    for name, (n, size, diff) in groups.items():
+        lines.append(f"  {name:22s} {n:5d} arrays {size:10d} bytes   differing bytes: {diff}")
+    total = sum(g[2] for g in groups.values())
+    lines.append(f"  arrays in one file only: {len(bad)}   differing bytes in all: {total}")
+    print("\n".join(lines))
+    if out_path:
+        with open(out_path, "w") as f:
+            f.write("\n".join(lines) + "\n")
+    return 0 if total == 0 and not bad else 1
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--dump")
+    ap.add_argument("--compare", nargs=2)
+    ap.add_argument("--out")
+    args = ap.parse_args()
+    if args.dump:
+        dump(args.dump)
+        sys.exit(0)
+    sys.exit(compare(args.compare[0], args.compare[1], args.out))
