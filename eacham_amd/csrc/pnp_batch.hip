@@ -1,0 +1,338 @@
+// pnp_batch.hip — cv::solvePnPRansac's two device stages for a whole LIST of problems per call, gfx950.
+//
+// What SolvePnPRansac (include/eacham/PnPHip.hpp) does for one frame with two blocking calls per chunk of samples (eacham_solve_pnp,
+// eacham_score_hypotheses) and two more for the refit runs here for n_problems (map points, pixels) problems: the inputs go up
+// once, the results come back once, and the number of launches does not depend on n_problems.
+//
+// eacham_pnp_hypotheses_batch — one RANSAC round:
+//   pb_front        a wave per sample, SOLVE_WAVES samples per workgroup: the body of solve_pnp_front_kernel (epnp_front<false>,
+//                   solve_dev.hpp) on the sample's own problem, found by a binary search in sample_ptr (left in sample_problem[])
+//   pb_back         a lane per (sample, linearised start), blockIdx.y the start: the body of solve_pnp_back_kernel
+//   pb_count        a wave per sample: the first strictly smallest error of the three starts (solve_pnp_select_kernel's rule)
+//                   gives the model; score_one<PNP> over the problem's own points, a ballot and a popcount per 64 points,
+//                   gives its inlier count. The model passes from the choice to the count in registers.
+// eacham_pnp_refit_batch — the tail of solvePnPRansac:
+//   pb_refit        a workgroup per problem: scores the model, writes the mask, compacts the inlier indices IN ASCENDING ORDER
+//                   into the problem's own row of a workspace (ballot prefix: EPnP's sums run in row order), then the
+//                   three-wave body of solve_pnp_big_kernel runs on that row — for every size of the inlier set: with at most
+//                   64 rows a lane holds one term and the partials are added in lane order, which is the sequential sum of the
+//                   at-most-64-point form term by term.
+#include "context.hpp"
+#include "devprim.hpp"
+#include "score_dev.hpp"
+#include "solve_dev.hpp"
+
+#include <algorithm>
+#include <climits>
+
+namespace eacham {
+namespace {
+
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_front_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
+                                                                   int n_problems, const double* __restrict__ obj, const double* __restrict__ img,
+                                                                   const double* __restrict__ K, int sample_size, int n_samples,
+                                                                   const int* __restrict__ idx, double* __restrict__ frame,
+                                                                   int* __restrict__ sample_problem) {
+    __shared__ PnpLds lds[SOLVE_WAVES];
+    extern __shared__ double rows_dyn[];   // SOLVE_WAVES x sample_size x 24: the two rows of every point of a wave's sample
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * SOLVE_WAVES + wave;
+    if (s >= n_samples) return;
+    const int p = prim::segment_of(sample_ptr, n_problems, s);
+    const long long base = point_ptr[p];
+    if (lane == 0) sample_problem[s] = p;
+    double* rows = rows_dyn + (size_t)wave * 24 * sample_size;
+    const double K4[4] = {K[0], K[1], K[2], K[3]};
+    PnpFrame F;
+    PnpLds& S = lds[wave];
+    int ok = 0;
+    if (point_ptr[p + 1] - base >= sample_size)   // (wave-uniform) a problem without a sample's worth of points has no models
+        ok = epnp_front<false>(sample_size, idx + (size_t)s * sample_size, obj + 3 * base, img + 2 * base, K4, F, S, rows, nullptr);
+    const size_t ns = (size_t)n_samples;
+    double* dst = frame + s;
+    if (lane == 0) {
+        dst[PNP_F_VALID * ns] = ok ? 1.0 : 0.0;
+        if (ok) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) dst[e * ns] = F.c0[e], dst[(12 + e) * ns] = F.sc[e];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) dst[(3 + 3 * k + e) * ns] = F.ax[k][e];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) dst[(15 + q) * ns] = F.rho[q];
+        }
+    }
+    if (ok) {
+        if (lane < 48) dst[(PNP_F_EV + lane) * ns] = S.ev[lane];
+        if (lane < 60) dst[(PNP_F_L + lane) * ns] = S.L[lane];
+    }
+}
+
+template <int variant>
+__device__ __forceinline__ void pb_back_body(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
+                                             const double* __restrict__ img, const double* __restrict__ K, int sample_size, int n_samples,
+                                             const int* __restrict__ idx, const int* __restrict__ sample_problem,
+                                             const double* __restrict__ frame, double* __restrict__ tmp) {
+    const int s = blockIdx.x * 64 + threadIdx.x;
+    if (s >= n_samples) return;
+    const size_t ns = (size_t)n_samples;
+    const double* src = frame + s;
+    const double K4[4] = {K[0], K[1], K[2], K[3]};
+    double cand[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) cand[k] = 0.0;
+    double err = -1.0;
+    if (src[PNP_F_VALID * ns] != 0.0) {
+        PnpFrame F;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) F.c0[e] = src[e * ns], F.sc[e] = src[(12 + e) * ns];
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int e = 0; e < 3; ++e) F.ax[k][e] = src[(3 + 3 * k + e) * ns];
+#pragma unroll
+        for (int q = 0; q < 6; ++q) F.rho[q] = src[(15 + q) * ns];
+        F.planar = F.sc[2] == 0.0;
+        const long long base = point_ptr[sample_problem[s]];
+        err = epnp_back_variant<true, variant>(sample_size, idx + (size_t)s * sample_size, obj + 3 * base, img + 2 * base, K4, F,
+                                               src + PNP_F_EV * ns, src + PNP_F_L * ns, ns, nullptr, cand);
+    }
+    double* dst = tmp + ((size_t)variant * ns + s) * 13;
+    dst[0] = err;
+#pragma unroll
+    for (int k = 0; k < 12; ++k) dst[1 + k] = cand[k];
+}
+__global__ __launch_bounds__(64) void pb_back_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
+                                                     const double* __restrict__ img, const double* __restrict__ K, int sample_size,
+                                                     int n_samples, const int* __restrict__ idx, const int* __restrict__ sample_problem,
+                                                     const double* __restrict__ frame, double* __restrict__ tmp) {
+    if (blockIdx.y == 0) pb_back_body<0>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);   // (workgroup-uniform)
+    else if (blockIdx.y == 1) pb_back_body<1>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);
+    else pb_back_body<2>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);
+}
+
+// A wave per sample: the choice among the three starts, then the count. models may be null (not wanted).
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_count_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
+                                                                   const double* __restrict__ img, const double* __restrict__ Kdev,
+                                                                   int n_samples, const int* __restrict__ sample_problem,
+                                                                   const double* __restrict__ tmp, float threshold,
+                                                                   double* __restrict__ models, int* __restrict__ n_models,
+                                                                   int* __restrict__ counts) {
+    const int lane = threadIdx.x & 63;
+    const int s = blockIdx.x * SOLVE_WAVES + (threadIdx.x >> 6);
+    if (s >= n_samples) return;
+    double best = -1.0;
+    int which = -1;
+    for (int v = 0; v < 3; ++v) {
+        const double err = tmp[((size_t)v * n_samples + s) * 13];
+        if (err >= 0.0 && (best < 0.0 || err < best)) best = err, which = v;
+    }
+    double M[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M[k] = which >= 0 ? tmp[((size_t)which * n_samples + s) * 13 + 1 + k] : 0.0;
+    if (models && lane < 12) models[12 * (size_t)s + lane] = which >= 0 ? tmp[((size_t)which * n_samples + s) * 13 + 1 + lane] : 0.0;
+    int c = 0;
+    if (which >= 0) {   // (wave-uniform)
+        const double K[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
+        const long long base = point_ptr[sample_problem[s]];
+        const int n = (int)(point_ptr[sample_problem[s] + 1] - base);
+        const double* pa = obj + 3 * base;
+        const double* pb = img + 2 * base;
+        for (int i0 = 0; i0 < n; i0 += 64) {   // (every lane takes every trip: the ballot sees the whole wave)
+            const int i = i0 + lane;
+            bool in = false;
+            if (i < n) {
+                const double X[3] = {pa[3 * (size_t)i], pa[3 * (size_t)i + 1], pa[3 * (size_t)i + 2]}, x[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
+                in = score_one<2>(X, x, M, K, false) <= threshold;
+            }
+            c += __popcll(__ballot(in));
+        }
+    }
+    if (lane == 0) n_models[s] = which >= 0 ? 1 : 0, counts[s] = c;
+}
+
+constexpr int PB_REFIT_BLOCK = 256;   // four waves score and compact; three of them then take EPnP's three starts
+
+__global__ __launch_bounds__(PB_REFIT_BLOCK) void pb_refit_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
+                                                                 const double* __restrict__ img, const double* __restrict__ Kdev,
+                                                                 const double* __restrict__ models, const unsigned char* __restrict__ has_model,
+                                                                 float threshold, unsigned char* __restrict__ mask, int* __restrict__ n_inliers,
+                                                                 int* rows_all, double* __restrict__ refit, int* __restrict__ refit_ok) {
+    __shared__ PnpLds lds;
+    __shared__ double part[78 * 64];
+    __shared__ PnpFrame frame;
+    __shared__ int front_ok;
+    __shared__ double red[3][64], result[3][13];
+    __shared__ int wcnt[PB_REFIT_BLOCK / 64];
+    const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long long base = point_ptr[p];
+    const int n = (int)(point_ptr[p + 1] - base);
+    const bool has = has_model[p] != 0;
+    const double K4[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
+    obj += 3 * base, img += 2 * base;
+    int* rows = rows_all + base;   // (not __restrict__: written here, read by EPnP below after a workgroup barrier)
+    double M[12];
+#pragma unroll
+    for (int k = 0; k < 12; ++k) M[k] = has ? models[12 * (size_t)p + k] : 0.0;
+    int m = 0;   // inliers so far = where the next trip's first inlier goes
+    for (int i0 = 0; i0 < n; i0 += PB_REFIT_BLOCK) {   // (every thread takes every trip)
+        const int i = i0 + (int)threadIdx.x;
+        bool in = false;
+        if (has && i < n) {
+            const double X[3] = {obj[3 * (size_t)i], obj[3 * (size_t)i + 1], obj[3 * (size_t)i + 2]}, x[2] = {img[2 * (size_t)i], img[2 * (size_t)i + 1]};
+            in = score_one<2>(X, x, M, K4, false) <= threshold;
+        }
+        if (i < n) mask[base + i] = in;
+        const unsigned long long b = __ballot(in);
+        if (lane == 0) wcnt[wave] = __popcll(b);
+        __syncthreads();
+        int before = __popcll(b & ((1ull << lane) - 1ull)), all = 0;
+#pragma unroll
+        for (int w = 0; w < PB_REFIT_BLOCK / 64; ++w) {
+            if (w < wave) before += wcnt[w];
+            all += wcnt[w];
+        }
+        if (in) rows[m + before] = i;   // m + before < n: one slot per inlier of the problem
+        m += all;
+        __syncthreads();   // wcnt is read before the next trip writes it; after the last trip: rows[] is complete and visible
+    }
+    if (threadIdx.x == 0) n_inliers[p] = m;
+    if (threadIdx.x == 0) front_ok = 0;
+    __syncthreads();
+    if (m >= 5) {   // (workgroup-uniform) the body of solve_pnp_big_kernel on the row of inliers
+        if (wave == 0) {
+            PnpFrame F;
+            const int ok = epnp_front<true>(m, rows, obj, img, K4, F, lds, nullptr, part);
+            if (lane == 0) frame = F, front_ok = ok;
+        }
+        __syncthreads();
+        if (front_ok && wave < 3) {
+            const PnpFrame F = frame;
+            double cand[12];
+#pragma unroll
+            for (int k = 0; k < 12; ++k) cand[k] = 0.0;
+            double err;
+            if (wave == 0) err = epnp_back_variant<false, 0>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[0], cand);
+            else if (wave == 1) err = epnp_back_variant<false, 1>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[1], cand);
+            else err = epnp_back_variant<false, 2>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[2], cand);
+            if (lane == 0) {
+                result[wave][0] = err;
+#pragma unroll
+                for (int k = 0; k < 12; ++k) result[wave][1 + k] = cand[k];
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        double best = -1.0;
+        int which = -1;
+        if (front_ok)
+            for (int v = 0; v < 3; ++v)
+                if (result[v][0] >= 0.0 && (best < 0.0 || result[v][0] < best)) best = result[v][0], which = v;
+        for (int k = 0; k < 12; ++k) refit[12 * (size_t)p + k] = which >= 0 ? result[which][1 + k] : 0.0;
+        refit_ok[p] = which >= 0 ? 1 : 0;
+    }
+}
+
+// The checks both entry points share, before anything is launched. Returns EACHAM_OK with *total = ptr[n_problems].
+int check_table(eacham_ctx* ctx, const char* call, const char* what, int n_problems, const int64_t* ptr) {
+    if (!ptr) return ctx->fail(EACHAM_ERR_INVALID, "%s: null %s", call, what);
+    if (ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: %s does not start at 0", call, what);
+    for (int p = 0; p < n_problems; ++p)
+        if (ptr[p + 1] < ptr[p]) return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: %s decreases", call, p, what);
+    if (ptr[n_problems] > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %s ends at %lld: more than 2^31 - 1 in one call", call, what, (long long)ptr[n_problems]);
+    return EACHAM_OK;
+}
+
+}  // namespace
+}  // namespace eacham
+
+using namespace eacham;
+
+extern "C" int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                                           const double* image_points, const double* K, const int64_t* sample_ptr, int sample_size,
+                                           const int32_t* sample_idx, float threshold, double* models, int32_t* n_models,
+                                           int32_t* inlier_counts) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const char* call = "pnp_hypotheses_batch";
+    if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative number of problems", call);
+    if (sample_size < 5 || sample_size > 64) return ctx->fail(EACHAM_ERR_INVALID, "%s: sample_size %d outside 5..64", call, sample_size);
+    if (n_problems == 0) return EACHAM_OK;
+    const int P = n_problems, m = sample_size;
+    if (int rc = check_table(ctx, call, "point_ptr", P, point_ptr)) return rc;
+    if (int rc = check_table(ctx, call, "sample_ptr", P, sample_ptr)) return rc;
+    const long long NP = point_ptr[P], S = sample_ptr[P];
+    if (!K || (NP > 0 && (!object_points || !image_points)) || (S > 0 && (!sample_idx || !n_models || !inlier_counts)))
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: null array", call);
+    for (int p = 0; p < P; ++p) {
+        const long long n = point_ptr[p + 1] - point_ptr[p];
+        if (n < m) continue;   // its samples are not looked at: each gets n_models = 0
+        for (long long k = sample_ptr[p] * m; k < sample_ptr[p + 1] * m; ++k)
+            if (sample_idx[k] < 0 || sample_idx[k] >= n)
+                return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: sample index %d of %lld points", call, p, (int)sample_idx[k], n);
+    }
+    if (S == 0) return EACHAM_OK;
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    IoStage io(ctx, st);
+    const auto h_m = io.out<double>(models, models ? 12 * (size_t)S : 0);
+    const auto h_n = io.out<int>(n_models, (size_t)S), h_c = io.out<int>(inlier_counts, (size_t)S);
+    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_a = io.in<double>(object_points, 3 * (size_t)NP), h_b = io.in<double>(image_points, 2 * (size_t)NP);
+    const auto h_i = io.in<int>(sample_idx, (size_t)S * m);
+    const auto h_f = io.scratch<double>(PNP_FRAME * (size_t)S);   // the samples' frames between the front and the back half
+    const auto h_t = io.scratch<double>(3 * 13 * (size_t)S);      // error + pose of the three starts
+    const auto h_sprob = io.scratch<int>((size_t)S);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    {
+        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+        const unsigned gw = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
+        pb_front_kernel<<<gw, 64 * SOLVE_WAVES, sizeof(double) * SOLVE_WAVES * 24 * (size_t)m, st>>>(
+            d(h_pp), d(h_sp), P, d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_f), d(h_sprob));
+        pb_back_kernel<<<dim3((unsigned)((S + 63) / 64), 3), 64, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_sprob), d(h_f), d(h_t));
+        pb_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), (int)S, d(h_sprob), d(h_t), threshold,
+                                                         models ? d(h_m) : nullptr, d(h_n), d(h_c));
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    return io.finish();
+}
+
+extern "C" int eacham_pnp_refit_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                                      const double* image_points, const double* K, const double* models, const uint8_t* has_model,
+                                      float threshold, uint8_t* inlier_mask, int32_t* n_inliers, double* refit, int32_t* refit_ok) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    const char* call = "pnp_refit_batch";
+    if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative number of problems", call);
+    if (n_problems == 0) return EACHAM_OK;
+    const int P = n_problems;
+    if (int rc = check_table(ctx, call, "point_ptr", P, point_ptr)) return rc;
+    const long long NP = point_ptr[P];
+    if (!K || !models || !has_model || !n_inliers || !refit || !refit_ok || (NP > 0 && (!object_points || !image_points || !inlier_mask)))
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: null array", call);
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    IoStage io(ctx, st);
+    const auto h_mask = io.out<unsigned char>(inlier_mask, (size_t)NP);
+    const auto h_ni = io.out<int>(n_inliers, (size_t)P), h_ok = io.out<int>(refit_ok, (size_t)P);
+    const auto h_r = io.out<double>(refit, 12 * (size_t)P);
+    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_a = io.in<double>(object_points, 3 * (size_t)NP), h_b = io.in<double>(image_points, 2 * (size_t)NP);
+    const auto h_m = io.in<double>(models, 12 * (size_t)P);
+    const auto h_has = io.in<unsigned char>(has_model, (size_t)P);
+    const auto h_rows = io.scratch<int>((size_t)NP);   // problem p's inlier indices, ascending, from point_ptr[p]
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    {
+        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+        pb_refit_kernel<<<(unsigned)P, PB_REFIT_BLOCK, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), d(h_m), d(h_has), threshold, d(h_mask), d(h_ni),
+                                                               d(h_rows), d(h_r), d(h_ok));
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    return io.finish();
+}

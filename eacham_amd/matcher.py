@@ -225,6 +225,16 @@ class HipContext:
         return twoview.two_view_batch(self, uv1, uv2, K, rules, transforms, max_repr_error, min_tri_angle, in_mask, distance_thresh,
                                       min_solution_matches)
 
+    def pnp_hypotheses_batch(self, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True):
+        """eacham_pnp_hypotheses_batch: one PnP RANSAC round (EPnP per sample, its inlier count) for a list of problems (eacham_amd/pnp.py)."""
+        from . import pnp
+        return pnp.pnp_hypotheses_batch(self, X, uv, K, samples, threshold, want_models)
+
+    def pnp_refit_batch(self, X, uv, K, models, has_model, threshold: float = 16.0):
+        """eacham_pnp_refit_batch: the inlier mask of one model per problem and EPnP on its inliers, for a list of problems (eacham_amd/pnp.py)."""
+        from . import pnp
+        return pnp.pnp_refit_batch(self, X, uv, K, models, has_model, threshold)
+
     def profile_enable(self, on: bool = True):
         self._check(self._L.eacham_profile_enable(self._h, int(on)))
 

@@ -1,0 +1,180 @@
+"""Host-side mirror of eacham_pnp_hypotheses_batch / eacham_pnp_refit_batch (include/eacham_hip.h): cv::solvePnPRansac with EPnP —
+RecoverPosePnP's estimator (modules/sfm/reconstruction/ReconstructionManager.cpp:227-228) — for a whole list of (map points,
+pixels) problems: one call per RANSAC round of CHUNK samples for every problem still running, one call for all the refits, and
+the sequential rule replayed per problem on the host in between (pnp_ransac_batch, what SolvePnPRansacBatch of
+include/eacham/PnPHip.hpp does). Drawing the samples stays with the caller. Test / bench driver."""
+from __future__ import annotations
+
+import ctypes as C
+import math
+from typing import NamedTuple
+
+import numpy as np
+
+from . import capi
+
+CHUNK = 256   # pnp_detail::kChunk: samples per problem and round
+
+
+class PnpHypotheses(NamedTuple):
+    models: list | None       # P arrays [s_p, 12] float64 = R | t (zeros: degenerate sample); None: not asked for
+    n_models: list            # P arrays [s_p] int32
+    inlier_counts: list       # P arrays [s_p] int32
+    point_ptr: np.ndarray     # [P + 1] int64
+    sample_ptr: np.ndarray    # [P + 1] int64
+
+
+class PnpRefit(NamedTuple):
+    masks: list               # P arrays of uint8, one byte per point of the problem
+    n_inliers: np.ndarray     # [P] int32
+    refit: np.ndarray         # [P, 12] float64 (zeros where refit_ok is 0)
+    refit_ok: np.ndarray      # [P] int32
+    point_ptr: np.ndarray
+
+
+def _K4(K):
+    K = np.asarray(K, dtype=np.float64)
+    return np.array([K[0, 0], K[1, 1], K[0, 2], K[1, 2]]) if K.shape == (3, 3) else np.ascontiguousarray(K).reshape(4)
+
+
+def _cat(xs, shape, dt):
+    return np.ascontiguousarray(np.concatenate(xs)) if len(xs) else np.zeros(shape, dt)
+
+
+def _ptr(lengths):
+    t = np.zeros(len(lengths) + 1, dtype=np.int64)
+    np.cumsum(lengths, out=t[1:])
+    return t
+
+
+def pack_points(X, uv):
+    """(point_ptr, object rows, image rows) of a list of problems. X[p]: n_p x 3, uv[p]: n_p x 2."""
+    A = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in X]
+    B = [np.asarray(x, dtype=np.float64).reshape(-1, 2) for x in uv]
+    if len(A) != len(B) or any(len(a) != len(b) for a, b in zip(A, B)):
+        raise ValueError("point lists disagree")
+    return _ptr([len(a) for a in A]), _cat(A, (0, 3), np.float64), _cat(B, (0, 2), np.float64)
+
+
+def _seg(x, t):
+    return [x[int(t[p]):int(t[p + 1])] for p in range(len(t) - 1)]
+
+
+def pnp_hypotheses_batch_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_size, sample_idx, threshold, want_models=True, n_problems=None):
+    """eacham_pnp_hypotheses_batch on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
+    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
+    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
+    point_ptr, sample_ptr = as_(point_ptr, np.int64), as_(sample_ptr, np.int64)
+    X, uv, sample_idx = as_(X, np.float64), as_(uv, np.float64), as_(sample_idx, np.int32)
+    K4 = None if K is None else _K4(K)
+    P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
+    S = max(int(sample_ptr[-1]), 0) if sample_ptr is not None and len(sample_ptr) and P > 0 else 0
+    if S > 1 << 28:   # (a table the library is about to refuse: nothing that size is allocated for it)
+        S = 0
+    models = np.zeros((S, 12), np.float64) if want_models else None
+    nm, cnt = np.zeros(S, np.int32), np.zeros(S, np.int32)
+    ctx._check(capi.lib().eacham_pnp_hypotheses_batch(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(sample_ptr), int(sample_size),
+                                                      ptr(sample_idx), float(threshold), ptr(models), ptr(nm), ptr(cnt)))
+    return PnpHypotheses(_seg(models, sample_ptr) if want_models else None, _seg(nm, sample_ptr), _seg(cnt, sample_ptr), point_ptr, sample_ptr)
+
+
+def pnp_hypotheses_batch(ctx, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True) -> PnpHypotheses:
+    """One RANSAC round: X[p] / uv[p] the n_p object points / pixels of problem p, samples[p] its s_p x m rows of indices into
+    them (5 <= m <= 64, the same m for every problem; s_p may be 0), threshold in squared pixels."""
+    point_ptr, A, B = pack_points(X, uv)
+    I = [np.asarray(s, dtype=np.int32) for s in samples]
+    ms = {i.shape[1] for i in I if i.ndim == 2 and len(i)}
+    if len(I) != len(point_ptr) - 1 or len(ms) > 1:
+        raise ValueError("one [s_p, m] index array per problem, one m for all")
+    m = ms.pop() if ms else 5
+    I = [i.reshape(-1, m) for i in I]
+    return pnp_hypotheses_batch_raw(ctx, point_ptr, A, B, K, _ptr([len(i) for i in I]), m, _cat(I, (0, m), np.int32), threshold, want_models)
+
+
+def pnp_refit_batch_raw(ctx, point_ptr, X, uv, K, models, has_model, threshold, n_problems=None):
+    """eacham_pnp_refit_batch on arrays already in its wire form."""
+    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
+    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
+    point_ptr, X, uv, models = as_(point_ptr, np.int64), as_(X, np.float64), as_(uv, np.float64), as_(models, np.float64)
+    has_model = as_(has_model, np.uint8)
+    K4 = None if K is None else _K4(K)
+    P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
+    npts = max(int(point_ptr[-1]), 0) if point_ptr is not None and len(point_ptr) and P > 0 else 0
+    if npts > 1 << 28:
+        npts = 0
+    mask, ni = np.zeros(npts, np.uint8), np.zeros(max(P, 0), np.int32)
+    refit, ok = np.zeros((max(P, 0), 12), np.float64), np.zeros(max(P, 0), np.int32)
+    ctx._check(capi.lib().eacham_pnp_refit_batch(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(models), ptr(has_model),
+                                                 float(threshold), ptr(mask), ptr(ni), ptr(refit), ptr(ok)))
+    return PnpRefit(_seg(mask, point_ptr), ni, refit, ok, point_ptr)
+
+
+def pnp_refit_batch(ctx, X, uv, K, models, has_model, threshold: float = 16.0) -> PnpRefit:
+    """The tail of solvePnPRansac per problem: the mask of models[p] (12 doubles; has_model[p] = 0: none), and EPnP on its inliers."""
+    point_ptr, A, B = pack_points(X, uv)
+    models = np.ascontiguousarray(models, dtype=np.float64).reshape(-1, 12)
+    has_model = np.ascontiguousarray(has_model, dtype=np.uint8).reshape(-1)
+    if not (len(models) == len(has_model) == len(point_ptr) - 1):
+        raise ValueError("one model and one has_model byte per problem")
+    return pnp_refit_batch_raw(ctx, point_ptr, A, B, K, models, has_model, threshold)
+
+
+def ransac_update_num_iters(p: float, ep: float, m: int, max_iters: int) -> int:
+    """RANSACUpdateNumIters as twoview_detail::ransac_update_num_iters states it (host log and pow, lround)."""
+    tiny = np.finfo(np.float64).tiny
+    p, ep = min(max(p, 0.0), 1.0), min(max(ep, 0.0), 1.0)
+    num, denom = max(1.0 - p, tiny), 1.0 - (1.0 - ep) ** m
+    if denom < tiny:
+        return 0
+    num, denom = math.log(num), math.log(denom)
+    if denom >= 0 or -num >= max_iters * (-denom):
+        return max_iters
+    x = num / denom
+    f = math.floor(abs(x))
+    return int(math.copysign(f + (1 if abs(x) - f >= 0.5 else 0), x))
+
+
+def pnp_ransac_batch(ctx, X, uv, K, samples, max_iters: int, reprojection_error: float = 4.0, confidence: float = 0.999,
+                     hypotheses=None, refit=None):
+    """cv::solvePnPRansac per problem over rounds of CHUNK samples. samples[p]: the stream problem p would draw, in order, s x 5
+    (rows past its end are not drawn: give at least as many as the loop consumes). Returns (results, turns): per problem a dict
+    ok, iterations, winner (sample index, -1: none) and when ok: model, inliers, pose; turns = device calls made (rounds + 1).
+    hypotheses / refit: the two calls (default: this context's batched entry points), same signatures as pnp_hypotheses_batch /
+    pnp_refit_batch without the context."""
+    hypotheses = hypotheses or (lambda *a: pnp_hypotheses_batch(ctx, *a))
+    refit = refit or (lambda *a: pnp_refit_batch(ctx, *a))
+    m = 5
+    X = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in X]
+    uv = [np.asarray(x, dtype=np.float64).reshape(-1, 2) for x in uv]
+    S = [np.asarray(s, dtype=np.int32).reshape(-1, m) for s in samples]
+    P = len(X)
+    thr = float(np.float32(reprojection_error) * np.float32(reprojection_error))
+    out = [{"ok": False, "iterations": 0, "winner": -1} for _ in range(P)]
+    budget = [max_iters if len(uv[p]) >= m and max_iters > 0 and len(S[p]) else 0 for p in range(P)]
+    best = [-1] * P
+    model = np.zeros((P, 12))
+    turns, first = 0, 0
+    while any(first < min(budget[p], len(S[p])) for p in range(P)):
+        rows = [S[p][first:min(first + CHUNK, max_iters)] if first < budget[p] else np.zeros((0, m), np.int32) for p in range(P)]
+        h = hypotheses(X, uv, K, rows, thr, True)
+        turns += 1
+        for p in range(P):
+            n = len(uv[p])
+            for k in range(len(rows[p])):
+                if first + k >= budget[p]:
+                    break
+                out[p]["iterations"] = first + k + 1
+                if h.n_models[p][k] and h.inlier_counts[p][k] > max(best[p], m - 1):
+                    best[p] = int(h.inlier_counts[p][k])
+                    out[p]["winner"] = first + k
+                    model[p] = h.models[p][k]
+                    budget[p] = ransac_update_num_iters(confidence, (n - best[p]) / n, m, budget[p])
+        first += CHUNK
+    has = np.array([b >= m for b in best], dtype=np.uint8)
+    if has.any():
+        r = refit(X, uv, K, model, has, thr)
+        turns += 1
+        for p in np.nonzero(has)[0]:
+            out[p].update(ok=True, model=model[p].copy(), inliers=np.nonzero(r.masks[p])[0].astype(np.int32),
+                          pose=r.refit[p].copy() if r.refit_ok[p] else model[p].copy())
+    return out, turns

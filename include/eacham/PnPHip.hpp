@@ -141,5 +141,95 @@ inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object,
     return out;
 }
 
+// One (map points, pixels) problem of SolvePnPRansacBatch: object n x 3, image n x 2 (pixels).
+struct PnPProblem {
+    std::vector<double> object, image;
+};
+
+// SolvePnPRansac for a LIST of problems in rounds + 1 device calls, whatever the length of the list. In round r every problem
+// still running draws its rows [256 r, min(256 (r + 1), iterations)) from its OWN stream (Sampling::OpenCV: a CvRNG seeded
+// (uint64)-1 per problem, kept across the rounds; Sampling::Counter: seeds[p]) and ONE eacham_pnp_hypotheses_batch call solves and
+// counts them all; the sequential rule of SolvePnPRansac is then replayed per problem on the host over that problem's counts in
+// sample order (ransac_update_num_iters uses the host's log and pow: a device libm may round differently at a knife edge). A
+// problem leaves the list when its budget is within the samples already seen. After the last round ONE eacham_pnp_refit_batch
+// call serves every problem whose best count is >= 5; a failed refit keeps the winner. result[p] — and traces[p], when asked
+// for — equal what SolvePnPRansac returns for problem p alone with seeds[p] and the same arguments, field for field.
+inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9, int iterations = 10000,
+                                                  float reprojectionError = 4.0f, double confidence = 0.999,
+                                                  const std::vector<uint64_t>& seeds = {}, Sampling sampling = Sampling::OpenCV,
+                                                  std::vector<PnPTrace>* traces = nullptr) {
+    const size_t P = problems.size();
+    const int m = 5, chunk = pnp_detail::kChunk;
+    std::vector<PnPResult> out(P);
+    if (traces) traces->assign(P, PnPTrace{});
+    const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
+    const float thr = reprojectionError * reprojectionError;
+    std::vector<int64_t> point_ptr(P + 1, 0), sample_ptr(P + 1, 0);
+    std::vector<double> object, image;
+    std::vector<int> npts(P), budget(P), best_inl(P, -1);
+    std::vector<CvRNG> rng(P, CvRNG(0xffffffffffffffffull));
+    for (size_t p = 0; p < P; ++p) {
+        npts[p] = (int)(problems[p].image.size() / 2);
+        // (what SolvePnPRansac turns away takes part with its points and never with a sample)
+        budget[p] = npts[p] >= m && problems[p].object.size() == (size_t)3 * npts[p] && iterations > 0 ? iterations : 0;
+        point_ptr[p + 1] = point_ptr[p] + npts[p];
+        object.insert(object.end(), problems[p].object.begin(), problems[p].object.end());
+        object.resize((size_t)3 * point_ptr[p + 1], 0.0);
+        image.insert(image.end(), problems[p].image.begin(), problems[p].image.begin() + 2 * (size_t)npts[p]);
+    }
+    std::vector<double> best_model(12 * P, 0.0), models;
+    std::vector<int32_t> idx, okv, inl;
+    for (int first = 0;; first += chunk) {
+        idx.clear();
+        for (size_t p = 0; p < P; ++p) {
+            const int cnt = first < budget[p] ? std::min(chunk, iterations - first) : 0;
+            if (cnt > 0) {
+                const std::vector<int32_t> rows = pnp_detail::pnp_samples(npts[p], m, first, cnt, rng[p], p < seeds.size() ? seeds[p] : 1, sampling);
+                if (traces) (*traces)[p].samples.insert((*traces)[p].samples.end(), rows.begin(), rows.end());
+                idx.insert(idx.end(), rows.begin(), rows.end());
+            }
+            sample_ptr[p + 1] = sample_ptr[p] + cnt;
+        }
+        const size_t S = (size_t)sample_ptr[P];
+        if (S == 0) break;
+        models.resize(12 * S), okv.resize(S), inl.resize(S);
+        ctx.check(eacham_pnp_hypotheses_batch(ctx.get(), (int)P, point_ptr.data(), object.data(), image.data(), K4, sample_ptr.data(), m, idx.data(),
+                                              thr, models.data(), okv.data(), inl.data()));
+        for (size_t p = 0; p < P; ++p) {
+            const size_t s0 = (size_t)sample_ptr[p];
+            const int cnt = (int)(sample_ptr[p + 1] - sample_ptr[p]), n = npts[p];
+            for (int k = 0; k < cnt && first + k < budget[p]; ++k) {
+                out[p].iterations = first + k + 1;
+                if (!okv[s0 + k]) continue;
+                if (inl[s0 + k] > std::max(best_inl[p], m - 1)) {
+                    best_inl[p] = inl[s0 + k];
+                    if (traces) (*traces)[p].winner = first + k;
+                    std::copy_n(&models[12 * (s0 + k)], 12, &best_model[12 * p]);
+                    budget[p] = twoview_detail::ransac_update_num_iters(confidence, (double)(n - inl[s0 + k]) / n, m, budget[p]);
+                }
+            }
+        }
+    }
+    std::vector<uint8_t> has(P, 0), mask((size_t)point_ptr[P], 0);
+    bool any = false;
+    for (size_t p = 0; p < P; ++p) any |= (has[p] = best_inl[p] >= m) != 0;
+    if (!any) return out;
+    std::vector<int32_t> n_inl(P), rok(P);
+    std::vector<double> refit(12 * P);
+    ctx.check(eacham_pnp_refit_batch(ctx.get(), (int)P, point_ptr.data(), object.data(), image.data(), K4, best_model.data(), has.data(), thr,
+                                     mask.data(), n_inl.data(), refit.data(), rok.data()));
+    for (size_t p = 0; p < P; ++p) {
+        if (!has[p]) continue;
+        for (int i = 0; i < npts[p]; ++i)
+            if (mask[(size_t)point_ptr[p] + i]) out[p].inliers.push_back(i);
+        const double* pose = rok[p] ? &refit[12 * p] : &best_model[12 * p];
+        for (int e = 0; e < 9; ++e) out[p].R[e] = pose[e];
+        for (int e = 0; e < 3; ++e) out[p].t[e] = pose[9 + e];
+        out[p].rvec = RodriguesFromMatrix(out[p].R);
+        out[p].ok = true;
+    }
+    return out;
+}
+
 }  // namespace hip
 }  // namespace eacham

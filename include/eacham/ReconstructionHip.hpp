@@ -201,6 +201,64 @@ public:
         return true;
     }
 
+    // cv::solvePnPRansac of RecoverPosePnP for a list of directed pairs (id1, id2) — every candidate next frame against the current
+    // map, the frames the loop left out — through SolvePnPRansacBatch: rounds + 1 device calls whatever the number of pairs. The 3-D–2-D
+    // correspondences of every pair are gathered exactly as RecoverPosePnP gathers them and the per-pair seed is RecoverPosePnP's;
+    // nothing is written. A pair below minPnpInliers correspondences takes no part (its result is the empty, not-ok one).
+    template <class MatT>
+    std::vector<PnPResult> PnPBatch(const std::vector<std::pair<unsigned, unsigned>>& pairs, const MatT& K) const {
+        const size_t P = pairs.size();
+        std::vector<PnPProblem> problems(P);
+        std::vector<uint64_t> seeds(P);
+        for (size_t p = 0; p < P; ++p) {
+            const unsigned id1 = pairs[p].first, id2 = pairs[p].second;
+            auto* node1 = graph_->Get(id1);
+            auto* node2 = graph_->Get(id2);
+            std::vector<std::pair<unsigned, unsigned>> ms;
+            for (const auto& m : node1->GetFactor(id2).matches) ms.emplace_back(m.first, m.second);
+            std::sort(ms.begin(), ms.end());
+            for (const auto& m : ms)
+                if (node1->HasPoint3d(m.first)) {
+                    const auto X = map_->Get(node1->GetPoint3d(m.first));
+                    problems[p].object.push_back(X(0)), problems[p].object.push_back(X(1)), problems[p].object.push_back(X(2));
+                    const auto& b = node2->GetKeyPoint(m.second);
+                    problems[p].image.push_back(b.x), problems[p].image.push_back(b.y);
+                }
+            if ((int)(problems[p].image.size() / 2) < minPnpInliers_) problems[p] = PnPProblem{};       // :214-217
+            seeds[p] = seed_ + 0xD1B54A32D192ED03ull * ((uint64_t)id1 * 65536 + id2);
+        }
+        const double K9[9] = {K.template at<double>(0, 0), 0, K.template at<double>(0, 2), 0, K.template at<double>(1, 1),
+                              K.template at<double>(1, 2), 0, 0, 1};
+        return SolvePnPRansacBatch(ctx_, problems, K9, 10000, 4.0f, 0.999, seeds, sampling_);
+    }
+
+    // RecoverPosePnP for a list of pairs: PnPBatch, then RecoverPosePnP's gates and its three writes, pair by pair in list order.
+    // The gather reads nothing those writes touch (matches, key points, 3-D ids, map points), so the flags and the graph equal
+    // calling RecoverPosePnP on the pairs one after another.
+    template <class MatT>
+    std::vector<bool> RecoverPosePnPBatch(const std::vector<std::pair<unsigned, unsigned>>& pairs, const MatT& K) {
+        const std::vector<PnPResult> rs = PnPBatch(pairs, K);
+        std::vector<bool> done(pairs.size(), false);
+        for (size_t p = 0; p < pairs.size(); ++p) {
+            const PnPResult& r = rs[p];
+            if (!r.ok || (int)r.inliers.size() < minPnpInliers_) continue;                         // :229-234
+            auto* node2 = graph_->Get(pairs[p].second);
+            using Mat4 = std::decay_t<decltype(node2->GetTransform())>;
+            Mat4 M;
+            for (int i = 0; i < 3; ++i) {
+                for (int j = 0; j < 3; ++j) M(i, j) = r.R[3 * i + j];
+                M(i, 3) = r.t[i];
+                M(3, i) = 0.0;
+            }
+            M(3, 3) = 1.0;
+            graph_->Get(pairs[p].first)->GetFactor(pairs[p].second).transform = M;                 // :236-240
+            node2->SetTransform(M);
+            node2->SetValid(true);
+            done[p] = true;
+        }
+        return done;
+    }
+
     Context& context() const { return ctx_; }
 
 private:

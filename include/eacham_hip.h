@@ -439,6 +439,45 @@ int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t*
                        const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, double* models, float* medians,
                        float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates);
 
+/* ---- PnP RANSAC for a whole list of problems ------------------------------------------------------------------------
+ * cv::solvePnPRansac(..., SOLVEPNP_EPNP) (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:227-228) for
+ * a list of (map points, pixels) problems: what eacham_solve_pnp + eacham_score_hypotheses(kind PNP) do for one frame per
+ * chunk of samples, and once more for the refit, for n_problems frames per call with no host turn between the stages and a
+ * launch count that does not depend on n_problems. The round loop and the sequential RANSAC rule between the two calls stay
+ * on the host (include/eacham/PnPHip.hpp: SolvePnPRansacBatch). Problem p owns the rows point_ptr[p] .. point_ptr[p+1] of
+ * object_points (3 doubles) and image_points (2 doubles, pixels); point_ptr has n_problems + 1 entries, starts at 0 and does
+ * not decrease. K = fx fy cx cy, shared by all problems, required.
+ *
+ * eacham_pnp_hypotheses_batch: ONE RANSAC ROUND for every problem. Problem p owns the samples sample_ptr[p] ..
+ * sample_ptr[p+1] (a table like point_ptr) of sample_idx: sample_size indices per sample (5 <= sample_size <= 64), LOCAL to
+ * the problem's points. threshold: squared pixels, as eacham_score_hypotheses takes it. Per sample: models (12 doubles,
+ * R | t; optional, NULL = not wanted), n_models (1, or 0 with a zero model for a degenerate sample) and inlier_counts (the
+ * problem's own points with err <= threshold under the sample's model; 0 where n_models is 0). A problem with no samples
+ * in this call costs nothing (later rounds address only the problems still running); one with fewer than sample_size
+ * points gets n_models = 0 for all its samples, which are then not looked at.
+ * Bit-identical, output by output, with eacham_solve_pnp on the problem's rows followed by
+ * eacham_score_hypotheses(kind PNP) per problem.
+ *
+ * eacham_pnp_refit_batch: THE TAIL of solvePnPRansac for every problem. models: 12 doubles per problem, has_model: one byte
+ * per problem. Per problem with a model: inlier_mask[i] = err(i) <= threshold (bytes, in the layout of image_points),
+ * n_inliers, and EPnP on the inliers IN ASCENDING POINT INDEX: refit (12 doubles) and refit_ok. A problem without a model,
+ * with fewer than 5 inliers or with an inlier set EPnP calls degenerate (collinear or coincident) is not an error:
+ * refit_ok = 0 and a zero refit; the mask and the count are still written (the real ones; zero without a model). Its
+ * neighbours are not affected. Every output is required.
+ * Bit-identical with eacham_score_hypotheses (one model, errors requested), the host compaction err <= threshold and
+ * eacham_solve_pnp on one row of all inliers, per problem, whatever the size of the inlier set.
+ *
+ * EACHAM_ERR_INVALID: a negative size, an offset table that is null / does not start at 0 / decreases, a null required
+ * array, sample_size outside 5..64, a sample index outside its problem (checked on the host before anything is launched;
+ * the message names the problem). EACHAM_ERR_CAPACITY: more than 2^31 - 1 points or samples in one call. */
+int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                                const double* image_points, const double* K, const int64_t* sample_ptr, int sample_size,
+                                const int32_t* sample_idx, float threshold, double* models, int32_t* n_models,
+                                int32_t* inlier_counts);
+int eacham_pnp_refit_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                           const double* image_points, const double* K, const double* models, const uint8_t* has_model,
+                           float threshold, uint8_t* inlier_mask, int32_t* n_inliers, double* refit, int32_t* refit_ok);
+
 /* ---- two-view motion and structure for a whole list of pairs ------------------------------------------------------
  * The second half of RecoverPoseTwoView (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:89-180)
  * for every edge of a match graph in ONE call: what eacham_two_view_points plus the host rules behind it
