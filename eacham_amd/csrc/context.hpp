@@ -91,7 +91,8 @@ struct eacham_ctx {
     int frame_table_cap = 0;
     bool frame_table_dirty = true;
     int* flag_dev = nullptr;  // [0] = non-integer descriptor seen, [1] = a device-side pair list named a frame that is not
-                              // resident, [8..9] = meta of the empty stand-in frame (zeros), [16..] scratch
+                              // resident, [8..9] = meta of the empty stand-in frame (zeros), [16..] scratch, [32..35] = the two 64-bit
+                              // totals {settled, verified} of the last matching call's candidate columns (eacham_match_debug_colprune)
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
     int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip)
     void* last_matches = nullptr;  // per-pair match lists of the last run (directed API reads them back)
@@ -128,6 +129,7 @@ struct eacham_ctx {
     int exp_stream2_cus = 0;          // EACHAM_EXP_STREAM2_CUS=<n> (diagnostic A/B): the second stream may use n of the 256 CUs only (hipExtStreamCreateWithCUMask)
     int match_sweep_form = 0;         // EACHAM_MATCH_SWEEP_FORM=exact|bound (diagnostic A/B, tests): the lean form's row sweep keeps every row's exact top-2 (1), or
                                       // runs its bound form + the exact pass over the rows left open (2); 0 = by descriptor dimension (bound up to 128-D)
+    bool match_colprune = true;       // EACHAM_MATCH_COLPRUNE=0 (A/B, tests): no candidate column is settled from the sweep's row minima, all go to match_colverify_kernel
     bool match_tile_sweep = false;    // EACHAM_MATCH_TILE_SWEEP (diagnostic A/B: the lean form's sweep by match_tile_kernel, the first round-4 form)
     bool match_full_columns = false;  // EACHAM_MATCH_FULL_COLUMNS (diagnostic A/B: every column's top-2 from the sweep, the round-1..3 form)
     int match_budget_mb = 1024;     // EACHAM_MATCH_BUDGET_MB (diagnostic: workspace budget of one batch of pairs), read at create

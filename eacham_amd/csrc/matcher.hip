@@ -1110,16 +1110,20 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
 // The rows kernel of the operand-swapped sweep (match_sweep_kernel): rowres carries the TILE of a row's minimum, not its column.
 // Besides what match_rows_kernel does, the passing rows of a pair that goes on are grouped by that tile (bytile[p][..], a counting
 // sort in LDS) and one argmin item is appended per (tile, <= 32 rows) — match_argmin_kernel turns the tile into the column.
+// state[p].z = L(p), a lower bound of d2(q', t) for every real row q' and every column t that is not q''s own best column: the
+// smallest of d2_1 over the rows that are no candidates (their minimum bounds ALL their distances; under the bound form of the sweep
+// their third word is no runner-up, so only the first is used) and of d2_2 over the candidates (exact {v1, tile, v2} in both forms:
+// every column but the best one is at least the runner-up). match_argmin_kernel settles candidate columns with it.
 constexpr int MAX_TILES = MAX_ROWS / 32;
+constexpr int AITEM_SHARED = 1 << 16;   // aitems[..].y: the tile, plus this flag when the pair has more than one item of that tile
 __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand, int* __restrict__ candlist, int* __restrict__ bytile,
-    int4* __restrict__ state, int2* __restrict__ vitems, int* __restrict__ n_vitems, int4* __restrict__ aitems, int* __restrict__ n_aitems,
-    int exp_all) {
+    int4* __restrict__ state, int4* __restrict__ aitems, int* __restrict__ n_aitems, int exp_all) {
     __shared__ int s_wave[FIN_THREADS / 64];
     __shared__ int s_cnt[MAX_TILES], s_pos[MAX_TILES], s_grp[MAX_TILES];
     __shared__ int s_scan[FIN_THREADS], s_scan2[FIN_THREADS];
-    __shared__ int s_item0, s_aitem0;
+    __shared__ int s_aitem0, s_low;
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
     const int2 pr = pairs[p];
@@ -1129,8 +1133,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     uint2* rc = rowcand + (size_t)p * row_stride;
     int* cl = candlist + (size_t)p * row_stride;
     for (int t = tid; t < MAX_TILES; t += FIN_THREADS) s_cnt[t] = 0;
+    if (tid == 0) s_low = 0x7fffffff;
     __syncthreads();
-    int base = 0;
+    int base = 0, low = 0x7fffffff;
     for (int j0 = 0; j0 < 32 * A_tiles; j0 += FIN_THREADS) {
         const int j = j0 + tid;
         bool ok = false;
@@ -1142,6 +1147,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
             tile = e.y;
             d2 = (int)(e.x + pa) - 2;
             ok = e.z < PAD_V && ratio_pass(d2, (int)(e.z + pa) - 2, ratio);  // pad second => < 2 train rows
+            low = imin(low, ok ? (int)(e.z + pa) - 2 : d2);   // (a row without a real minimum gives a negative value: nothing is settled then)
             if (exp_all) ok = e.x < PAD_V;
         }
         if (j < 32 * A_tiles) rc[j] = ok ? make_uint2(tile, (unsigned)d2) : make_uint2(0xffffffffu, 0u);
@@ -1154,7 +1160,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     // main.cpp:111,142: an edge needs |m12| >= min_dir and |mutual| > min_mutual, and mutual is a subset of m12
     const bool live = (mode == 0 && base >= min_dir && base > min_mutual) || (exp_all && base > 0);
     const bool want_col = live || (mode == 1 && base > 0);   // directed lists need the column of every passing row
-    const int groups = (base + VER_CANDS - 1) / VER_CANDS;
+    atomicMin(&s_low, low);
     __syncthreads();
     if (want_col) {  // workgroup-uniform
         // exclusive prefix of the per-tile counts (positions in bytile) and of the per-tile item counts, two tiles per thread
@@ -1180,7 +1186,8 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
         __syncthreads();
         for (int t = tid; t < B_tiles; t += FIN_THREADS) {  // the items of tile t: rows [pos, pos + cnt) of bytile in groups of 32
             const int cnt = s_cnt[t], pos = s_pos[t];
-            for (int g = 0; g < (cnt + 31) / 32; ++g) aitems[s_aitem0 + s_grp[t] + g] = make_int4(p, t, pos + 32 * g, min(32, cnt - 32 * g));
+            for (int g = 0; g < (cnt + 31) / 32; ++g)
+                aitems[s_aitem0 + s_grp[t] + g] = make_int4(p, t | (cnt > 32 ? AITEM_SHARED : 0), pos + 32 * g, min(32, cnt - 32 * g));
         }
         __syncthreads();
         int* bt = bytile + (size_t)p * row_stride;
@@ -1189,29 +1196,40 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
             bt[atomicAdd(&s_pos[rc[j].x], 1)] = j;   // (any order inside a tile: every row is resolved on its own)
         }
     }
-    if (tid == 0) {
-        state[p] = make_int4(base, live ? 1 : 0, 0, 0);
-        if (live) s_item0 = atomicAdd(n_vitems, groups);
-    }
-    if (live) {  // workgroup-uniform
-        __syncthreads();
-        for (int g = tid; g < groups; g += FIN_THREADS) vitems[s_item0 + g] = make_int2(p, g);
-    }
+    if (tid == 0) state[p] = make_int4(base, live ? 1 : 0, s_low, 0);   // .w: match_colpick_kernel's count
 }
 
 // rowcand[p][j].x: the tile of row j's minimum -> its column. One wave per item (train tile T of the pair, <= 32 passing rows whose
 // minimum lies in T): the 32 x 32 distance block on the MFMA with the operands of match_sweep_kernel (the tile as A, the gathered
 // query rows as B, hb as C-init), then every lane scans its 16 train rows in ascending order with a strict '<', the two halves
 // of a query row are joined lower-index-first: the lowest train row of the minimum, the reference's tie rule.
+//
+// colres != nullptr (mode 0): the wave also SETTLES candidate columns from what the row sweep left behind, so that
+// match_colverify_kernel streams the query frame for the others only. Candidate (q, t) with v = d2(q, t) survives the mutual check
+// of match_finalize2_kernel iff ratio_pass(v, m), m = the smallest d2(q', t) over the OTHER rows q' (ratio_pass is monotone in its
+// second argument and false for m <= v at any ratio <= 1: the unique minimum and the column's ratio test in one condition). Every
+// other row is bounded from below:
+//   * a row that is no candidate, or a candidate whose best column is not t:  d2(q', t) >= L(p)   (state[p].z, match_rows2_kernel);
+//   * a candidate whose best column IS t has its minimum in t's tile: it is a row of this item when the tile has one item only,
+//     and then d2(q', t) is in this wave's accumulators, exactly (put in LDS: a candidate walks its column over the item's rows).
+// So with lo = min(L(p), the exact values of the item's other rows): m >= lo, and ratio_pass(v, lo) implies ratio_pass(v, m) — the
+// candidate is kept, and colres[p][j] = {v, lo} (encoded as match_colverify_kernel encodes them) makes match_finalize2_kernel keep it.
+// A tile with more than 32 candidates (a second item, whose rows this wave does not hold), a query frame with fewer than two rows
+// (the reference needs two neighbours) and every candidate with !ratio_pass(v, lo) stay unresolved: colres[p][j].x = COL_OPEN,
+// match_colpick_kernel lists them for match_colverify_kernel, which decides them as before. settle = 0: every candidate unresolved.
+constexpr unsigned COL_OPEN = 0xffffffffu;
 template <int KS>
 __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
                                                           uint2* __restrict__ rowcand, const int* __restrict__ bytile,
-                                                          const int4* __restrict__ aitems, const int* __restrict__ n_aitems, int row_stride) {
+                                                          const int4* __restrict__ aitems, const int* __restrict__ n_aitems, int row_stride,
+                                                          uint2* __restrict__ colres, const int4* __restrict__ state, double ratio, int settle) {
+    __shared__ int sD[32 * 33];   // d2 of the item's block: [query row of the item][train row of the tile], rows padded to 33 words
+    constexpr unsigned PAD_V = 2u * PADH;
     const int lane = threadIdx.x & 63, cl = lane & 31, h = lane >> 5;
     const int n = *n_aitems;
     for (int w = blockIdx.x; w < n; w += gridDim.x) {
         const int4 it = aitems[w];
-        const int p = it.x, tile = it.y;
+        const int p = it.x, tile = it.y & (AITEM_SHARED - 1);
         const int2 pr = pairs[p];
         const FrameDev A = frames[pr.x], B = frames[pr.y];
         const gfrag_t Afrag = (gfrag_t)A.frag, Bfrag = (gfrag_t)B.frag;
@@ -1237,9 +1255,71 @@ __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __rest
             if (acc[r] < best) best = acc[r], bi = row;
         }
         const int o = __shfl_xor(best, 32), oi = __shfl_xor(bi, 32);
-        if (o < best || (o == best && oi < bi)) bi = oi;
+        if (o < best || (o == best && oi < bi)) bi = oi;   // (both lanes of a query row end with the same train row)
         if (h == 0 && cl < it.w) rowcand[(size_t)p * row_stride + j].x = (unsigned)(32 * tile + bi);
+        if (colres == nullptr) continue;   // directed lists: no column direction
+        const int low = state[p].z;
+        const int v = (int)rowcand[(size_t)p * row_stride + j].y;
+        // (a pair whose L(p) cannot settle even this item's smallest candidate skips the walk)
+        const bool open = settle && !(it.y & AITEM_SHARED) && A.n >= 2 && cl < it.w && ratio_pass(v, low, ratio);
+        uint2 res = make_uint2(COL_OPEN, 0u);
+        if (__ballot(open)) {   // wave-uniform
+            const int pb = tile >= B.meta[0] ? 1 : 0;
+            const int add = 2 * ((gint_t)A.norm)[j] + ((j >> 5) >= A.meta[0] ? 1 : 0) + pb - 2;   // d2 = 2 (acc + ca) + pa + pb - 2, as the sweep's epilogue forms it
+#pragma unroll
+            for (int r = 0; r < 16; ++r) sD[33 * cl + (r & 3) + 8 * (r >> 2) + 4 * h] = 2 * acc[r] + add;
+            __syncthreads();
+            int lo = low;
+            for (int k = 0; k < 16; ++k) {   // each lane of a candidate walks half of the item's rows
+                const int q = 16 * h + k;
+                if (q < it.w && q != cl) lo = imin(lo, sD[33 * q + bi]);
+            }
+            lo = imin(lo, __shfl_xor(lo, 32));
+            __syncthreads();
+            const unsigned second = (unsigned)(lo - pb + 2);
+            if (open && ratio_pass(v, lo, ratio) && second < PAD_V) res = make_uint2((unsigned)(v - pb + 2), second);
+        }
+        if (h == 0 && cl < it.w) colres[(size_t)p * row_stride + j] = res;
     }
+}
+
+// Behind match_argmin_kernel: openlist[p][i] = stored row of the i-th candidate of live pair p that is still unresolved (ascending,
+// as candlist), state[p].w = their number, one match_colverify_kernel item per 64 of them. totals (optional): {settled, verified}
+// candidates of the call, one atomic add per pair each.
+__global__ __launch_bounds__(FIN_THREADS) void match_colpick_kernel(const int* __restrict__ candlist, const uint2* __restrict__ colres,
+                                                                    int4* __restrict__ state, int row_stride, int* __restrict__ openlist,
+                                                                    int2* __restrict__ vitems, int* __restrict__ n_vitems,
+                                                                    unsigned long long* __restrict__ totals) {
+    __shared__ int s_wave[FIN_THREADS / 64];
+    __shared__ int s_item0;
+    const int tid = threadIdx.x;
+    const int p = blockIdx.x;
+    const int4 st = state[p];
+    if (!st.y) return;   // workgroup-uniform: the pair cannot reach the thresholds
+    const int* cl = candlist + (size_t)p * row_stride;
+    const uint2* cr = colres + (size_t)p * row_stride;
+    int* ol = openlist + (size_t)p * row_stride;
+    int base = 0;
+    for (int i0 = 0; i0 < st.x; i0 += FIN_THREADS) {
+        const int i = i0 + tid;
+        const int j = i < st.x ? cl[i] : 0;
+        const bool open = i < st.x && cr[j].x == COL_OPEN;
+        int total;
+        const int rank = block_rank(open, tid, s_wave, total);
+        if (open) ol[base + rank] = j;
+        base += total;
+    }
+    const int groups = (base + VER_CANDS - 1) / VER_CANDS;
+    if (tid == 0) {
+        state[p].w = base;
+        s_item0 = groups ? atomicAdd(n_vitems, groups) : 0;
+        if (totals) {
+            atomicAdd(&totals[0], (unsigned long long)(st.x - base));
+            atomicAdd(&totals[1], (unsigned long long)base);
+        }
+    }
+    __syncthreads();
+    for (int g = tid; g < groups; g += FIN_THREADS) vitems[s_item0 + g] = make_int2(p, g);
 }
 
 // colres[p][j] = {v1, v2}: the two smallest 2H + pa over ALL stored rows of frame A against column rowcand[p][j].x of
@@ -1251,7 +1331,8 @@ __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __rest
 // column, the column's constant hb is added once at the very end and the top-2 runs on the raw accumulators, three at a
 // time: 27 VALU operations per 16 distances (the sweep needs 48) under 8 MFMAs — the kernel is bound by the matrix pipe,
 // which the sweep (bound by the VALU port) leaves idle more than half of the time. Rows of the two parity classes are kept
-// apart (a tile has one parity) and joined when 2H + pa is formed.
+// apart (a tile has one parity) and joined when 2H + pa is formed. candlist is the pair's list of stored rows, state[p] word
+// count_word its length: every passing row (match_rows_kernel), or the ones match_argmin_kernel left unresolved (match_colpick_kernel).
 // ROWS = true: the same pass with the frames' roles swapped — the candidates are stored ROWS of the query frame (candlist holds them
 // directly), the train frame's tiles stream — for the rows the bound form of the sweep (match_sweep_kernel<KS, true>) could not
 // finish: their exact {v1 = 2H + pb minimum, first tile holding it, v2} go to rowres[p][j], what match_rows2_kernel reads. A wave
@@ -1261,7 +1342,7 @@ template <int KS, bool ROWS = false>
 __global__ __launch_bounds__(WG_THREADS) void match_colverify_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint2* __restrict__ rowcand,
     const int* __restrict__ candlist, const int4* __restrict__ state, const int2* __restrict__ items,
-    const int* __restrict__ n_items, int row_stride, uint2* __restrict__ colres, uint4* __restrict__ rowres_out = nullptr) {
+    const int* __restrict__ n_items, int row_stride, int count_word, uint2* __restrict__ colres, uint4* __restrict__ rowres_out = nullptr) {
     __shared__ int4 sM[WAVES][VER_GROUPS][32];  // per wave, group, column: {m1 even, m2 even, m1 odd, m2 odd}
     __shared__ int2 sT[WAVES][VER_GROUPS][32];  // ROWS: {tile of m1 even, tile of m1 odd}
     const int tid = threadIdx.x;
@@ -1276,7 +1357,7 @@ __global__ __launch_bounds__(WG_THREADS) void match_colverify_kernel(
         const int2 pr = pairs[p];
         const FrameDev A = frames[ROWS ? pr.y : pr.x], B = frames[ROWS ? pr.x : pr.y];   // A: the frame whose tiles stream, B: the candidates'
         const int A_even = ((gint_t)A.meta)[0], A_tiles = ((gint_t)A.meta)[1];
-        const int ncand = state[p].x;
+        const int ncand = ((const int*)&state[p])[count_word];   // length of the pair's list: .x of candlist, .w of match_colpick_kernel's
         const gfrag_t Afrag = (gfrag_t)A.frag, Bfrag = (gfrag_t)B.frag;
         const gint_t Aca = (gint_t)A.norm;
         const int* cand = candlist + (size_t)p * row_stride;
@@ -1562,6 +1643,9 @@ static int check_integer_flag(eacham_ctx* ctx) {
     return EACHAM_OK;
 }
 
+// {settled, verified}: the candidate columns of the last matching call that match_argmin_kernel settled / that went to match_colverify_kernel
+static unsigned long long* colprune_totals(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 32); }
+
 struct MatchPlan {
     int batch;       // pairs per launch
     int round_pairs; // pairs of one round of 512 workgroups (launches are sized in whole rounds)
@@ -1572,7 +1656,7 @@ struct MatchPlan {
     int slots;       // workspace copies: batch i+1's tile kernel overlaps batch i's finalize
     size_t off_rowres, off_colpart, off_matches, slot_bytes, total;
     // the candidate-only column pass: rowcand | candlist | colres | state | items | n_items
-    size_t off_rowcand, off_candlist, off_colres, off_state, off_items, off_nitems, off_bytile, off_aitems;
+    size_t off_rowcand, off_candlist, off_colres, off_state, off_items, off_nitems, off_bytile, off_aitems, off_openlist;
 };
 
 static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
@@ -1586,7 +1670,7 @@ static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     pl.col_chunks = (max_tiles + CHUNK_TILES - 1) / CHUNK_TILES;
     // per pair: row results + match list, and EITHER the column partials of the full sweep OR the arrays of the candidate pass
     const size_t colpart_pp = full_cols ? (size_t)pl.wb_stride * pl.row_stride * sizeof(int2) : 0;
-    const size_t cand_pp = full_cols ? 0 : (size_t)pl.row_stride * (sizeof(uint2) + 2 * sizeof(int) + sizeof(uint2)) + sizeof(int4) +
+    const size_t cand_pp = full_cols ? 0 : (size_t)pl.row_stride * (sizeof(uint2) + 3 * sizeof(int) + sizeof(uint2)) + sizeof(int4) +
                                                (size_t)max_tiles * (sizeof(int2) + 2 * sizeof(int4));
     size_t per_pair = (size_t)pl.col_chunks * pl.row_stride * sizeof(int4) + (size_t)pl.row_stride * sizeof(uint2) + colpart_pp + cand_pp;
     // bound a slot near 1 GiB so the column partials of one batch stay cache-friendly
@@ -1617,7 +1701,8 @@ static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     pl.off_nitems = align(pl.off_items + cb * max_tiles * sizeof(int2));
     pl.off_bytile = align(pl.off_nitems + 256);
     pl.off_aitems = align(pl.off_bytile + cb * pl.row_stride * sizeof(int));
-    pl.slot_bytes = align(pl.off_aitems + cb * 2 * max_tiles * sizeof(int4));
+    pl.off_openlist = align(pl.off_aitems + cb * 2 * max_tiles * sizeof(int4));
+    pl.slot_bytes = align(pl.off_openlist + cb * pl.row_stride * sizeof(int));
     pl.total = pl.slot_bytes * pl.slots;
     return pl;
 }
@@ -1678,6 +1763,7 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     hipStream_t st1 = ctx->stream, st2 = pl.slots == 2 || npairs <= pl.batch ? ctx->stream2 : ctx->stream;
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st1));        // inputs queued on the context stream
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_join, 0));
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(colprune_totals(ctx), 0, 2 * sizeof(unsigned long long), st2));
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job's last batch is cut short (an eighth of a full one),
     // so the exposed tail is that of ~1 500 pairs instead of ~10 000 (0.8 ms of a 21 ms S200 step).
@@ -1733,6 +1819,8 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                 int2* items = (int2*)(ws + pl.off_items);
                 int* n_items = (int*)(ws + pl.off_nitems);
                 int* n_aitems = n_items + 16;
+                const int* vlist = candlist;   // what match_colverify_kernel<KS> runs over: every passing row (state[p].x of them) ...
+                int vword = 0;
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
                 if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
                     int* n_pre = n_items + 8;
@@ -1740,22 +1828,28 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                                                                       candlist, state, items, n_pre);
                     const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
                     switch (ctx->ks_common) {
-                        case 2: match_colverify_kernel<2, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, nullptr, (uint4*)(ws + pl.off_rowres)); break;
-                        case 4: match_colverify_kernel<4, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, nullptr, (uint4*)(ws + pl.off_rowres)); break;
-                        default: match_colverify_kernel<8, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, nullptr, (uint4*)(ws + pl.off_rowres)); break;
+                        case 2: match_colverify_kernel<2, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
+                        case 4: match_colverify_kernel<4, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
+                        default: match_colverify_kernel<8, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
                     }
                 }
                 if (row_sweep) {
                     int* bytile = (int*)(ws + pl.off_bytile);
                     int4* aitems = (int4*)(ws + pl.off_aitems);
                     match_rows2_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres), pl.row_stride, ratio,
-                                                                    min_dir, min_mutual, mode, rowcand, candlist, bytile, state, items, n_items, aitems,
-                                                                    n_aitems, ctx->exp_all_candidates ? 1 : 0);
+                                                                    min_dir, min_mutual, mode, rowcand, candlist, bytile, state, aitems, n_aitems,
+                                                                    ctx->exp_all_candidates ? 1 : 0);
+                    const int settle = ctx->match_colprune && !ctx->exp_all_candidates ? 1 : 0;
                     const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
                     switch (ctx->ks_common) {
-                        case 2: match_argmin_kernel<2><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride); break;
-                        case 4: match_argmin_kernel<4><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride); break;
-                        default: match_argmin_kernel<8><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride); break;
+                        case 2: match_argmin_kernel<2><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
+                        case 4: match_argmin_kernel<4><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
+                        default: match_argmin_kernel<8><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
+                    }
+                    if (mode == 0) {   // the candidates the arg-min pass could not settle: the list and the items of the column pass
+                        int* openlist = (int*)(ws + pl.off_openlist);
+                        match_colpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(candlist, colres, state, pl.row_stride, openlist, items, n_items, colprune_totals(ctx));
+                        vlist = openlist, vword = 3;   // ... or the unresolved ones (state[p].w)
                     }
                 } else {
                     match_rows_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres), pl.col_chunks,
@@ -1766,9 +1860,9 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                     // persistent workgroups over the item list (its length is only known on the device): one round of the chip
                     const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
                     switch (ctx->ks_common) {
-                        case 2: match_colverify_kernel<2><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, candlist, state, items, n_items, pl.row_stride, colres); break;
-                        case 4: match_colverify_kernel<4><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, candlist, state, items, n_items, pl.row_stride, colres); break;
-                        default: match_colverify_kernel<8><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, candlist, state, items, n_items, pl.row_stride, colres); break;
+                        case 2: match_colverify_kernel<2><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
+                        case 4: match_colverify_kernel<4><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
+                        default: match_colverify_kernel<8><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
                     }
                 }
                 match_finalize2_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
@@ -1972,6 +2066,19 @@ int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int3
     }
     *n_batches = b;
     if (n_slots) *n_slots = pl.slots;
+    return EACHAM_OK;
+}
+
+int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* verified) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    if (!settled || !verified) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+    unsigned long long tot[2] = {0, 0};
+    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpy(tot, colprune_totals(ctx), sizeof(tot), hipMemcpyDeviceToHost));
+    *settled = (int64_t)tot[0];
+    *verified = (int64_t)tot[1];
     return EACHAM_OK;
 }
 

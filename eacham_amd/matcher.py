@@ -145,6 +145,13 @@ class HipContext:
         self._check(self._L.eacham_match_debug_batches(self._h, npairs, int(stats), starts.ctypes.data, len(starts), C.byref(nb), C.byref(ns)))
         return starts[:min(nb.value, len(starts))].copy(), ns.value
 
+    def match_colprune(self):
+        """(settled, verified): candidate columns of the last match_all_pairs call that the arg-min pass settled from the row sweep's
+        minima / that went through the column pass (eacham_match_debug_colprune)."""
+        s, v = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.eacham_match_debug_colprune(self._h, C.byref(s), C.byref(v)))
+        return s.value, v.value
+
     def match_pairs_directed(self, frames, ordered_pairs, ratio: float = RATIO, f32: bool = False) -> list:
         """Uploads `frames` (list of N x D matrices) as frames 0.. and runs every ordered pair (i, j) as one directed
         Match(frames[i], frames[j]) in ONE launch sequence; returns a list of {queryIdx: trainIdx} dicts."""

@@ -140,6 +140,12 @@ int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int np
  * oracle samples on both sides of every launch boundary of the job of apps/sfm/main.cpp:84-147. */
 int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int32_t* starts, int cap, int* n_batches, int* n_slots);
 
+/* Debug getter (tests, A/B runs): the candidate columns of the LAST eacham_match_all_pairs[_dev] call on this context (lean form,
+ * int8 frames) that were settled from the row sweep's minima without computing a distance (*settled) and that went through the
+ * column pass (*verified); live pairs only. EACHAM_MATCH_COLPRUNE=0 at eacham_ctx_create sends every candidate down the column
+ * pass (*settled = 0). Waits for the context's stream. */
+int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* verified);
+
 /* ---- dot-product similarity for float descriptors, scores returned ----------------------------
  * The brute-force rule for SuperPoint-class descriptors (modules/onnx/lightglue/feature/Types.h:11-14): nearest neighbour
  * by similarity with a score threshold, where the reference's LightGlue plug-in keeps a match by `mscores0 > 0.5`
