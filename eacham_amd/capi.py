@@ -105,6 +105,10 @@ def lib() -> C.CDLL:
         L.eacham_graph_set_frame.argtypes = [vp, i32, i32, vp, i32]
         L.eacham_graph_set_frames.argtypes = [vp, i32, vp, vp, vp, vp]
         L.eacham_graph_query.argtypes = [vp, vp, i32, vp]
+    if hasattr(L, "eacham_tracks_build"):  # (absent from older builds selected with EACHAM_HIP_LIB; calling it on one raises AttributeError)
+        L.eacham_tracks_build.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
+        L.eacham_graph_tracks.argtypes = [vp, vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
+        L.eacham_tracks_debug_last.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]
     L.eacham_reprojection_errors.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.eacham_profile_enable.argtypes = [vp, i32]
     L.eacham_profile_reset.argtypes = [vp]

@@ -135,6 +135,11 @@ struct eacham_ctx {
     int match_budget_mb = 1024;     // EACHAM_MATCH_BUDGET_MB (diagnostic: workspace budget of one batch of pairs), read at create
     bool match_no_overlap = false;  // EACHAM_NO_OVERLAP (diagnostic: finalize on the tile kernel's stream), read at create
 
+    // the last track-building call (tracks.hip; eacham_tracks_debug_last): hook-and-compress rounds it ran until one changed nothing,
+    // its cap, the read-backs of device words it made, and (profiling on) the device time between its upload and its copies back
+    int tracks_rounds = 0, tracks_round_cap = 0, tracks_readbacks = 0;
+    float tracks_ms = -1.f;
+
     // profiling
     bool profile = false;
     eacham::ProfileSlot prof[EACHAM_KERNEL_COUNT];
@@ -148,6 +153,24 @@ struct eacham_ctx {
         err = buf;
         return code;
     }
+};
+
+// The resident CSR match graph (graph.hip builds and queries it, tracks.hip forms tracks on it): the edges are the pairs with
+// matches, compacted, their match lists packed in pair order.
+struct eacham_graph {
+    eacham_ctx* ctx = nullptr;
+    int n_frames = 0, n_edges = 0;       // edges = pairs with matches
+    long long n_matches = 0, n_kp = 0;
+    long long n_src = 0;                 // matches the caller's arrays spanned (max offsets + counts): the length of a `keep` mask
+    char* dev = nullptr;
+    int2* pairs = nullptr;
+    int* counts = nullptr;
+    long long* offsets = nullptr;
+    unsigned *q = nullptr, *t = nullptr, *edge_counts = nullptr, *best = nullptr;
+    unsigned char *valid = nullptr, *excluded = nullptr, *has3d = nullptr;
+    long long* kp_offsets = nullptr;
+    long long* src_offsets = nullptr;    // per edge: where its match list began in the caller's arrays
+    std::vector<long long> kp_offsets_h;
 };
 
 #define EACHAM_HIP_TRY(ctx, expr)                                                              \

@@ -109,19 +109,7 @@ using namespace eacham;
 // carry a not-two-view 3-D point) is updated frame by frame as the incremental loop changes it, a query is two small kernels.
 // (The one-shot entry point below re-validates and re-uploads the whole graph per call: 3.9 ms per query on a 500-frame sequence,
 // more than PnP + triangulation + bundle adjustment of the frame the query is for.)
-struct eacham_graph {
-    eacham_ctx* ctx = nullptr;
-    int n_frames = 0, n_edges = 0;       // edges = pairs with matches
-    long long n_matches = 0, n_kp = 0;
-    char* dev = nullptr;
-    int2* pairs = nullptr;
-    int* counts = nullptr;
-    long long* offsets = nullptr;
-    unsigned *q = nullptr, *t = nullptr, *edge_counts = nullptr, *best = nullptr;
-    unsigned char *valid = nullptr, *excluded = nullptr, *has3d = nullptr;
-    long long* kp_offsets = nullptr;
-    std::vector<long long> kp_offsets_h;
-};
+// (struct eacham_graph: context.hpp — tracks.hip runs on the same resident arrays)
 
 extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t* pairs, int npairs, const int32_t* counts,
                                    const int64_t* offsets, const uint32_t* q, const uint32_t* t, const int64_t* kp_offsets,
@@ -136,8 +124,9 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
         if (kp_offsets[f + 1] < kp_offsets[f] || kp_offsets[f] < 0) return ctx->fail(EACHAM_ERR_INVALID, "graph_create: kp_offsets not monotone");
     // the edges (pairs with matches), compacted, their match lists packed in pair order
     std::vector<int> e_pairs, e_counts;
-    std::vector<long long> e_off;
+    std::vector<long long> e_off, e_src;   // e_src: where the edge's match list began in the caller's arrays (the index space of a `keep` mask)
     std::vector<unsigned> e_q, e_t;
+    long long n_src = 0;
     for (int p = 0; p < npairs; ++p) {
         const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
         if (f1 < 0 || f2 < 0 || f1 >= n_frames || f2 >= n_frames)
@@ -151,6 +140,8 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
         e_pairs.push_back(f2);
         e_counts.push_back(counts[p]);
         e_off.push_back((long long)e_q.size());
+        e_src.push_back(offsets[p]);
+        n_src = std::max<long long>(n_src, offsets[p] + counts[p]);
         for (long long k = offsets[p]; k < offsets[p] + counts[p]; ++k) {
             if (q[k] >= n1 || t[k] >= n2) return ctx->fail(EACHAM_ERR_INVALID, "graph_create: match %lld of pair %d is out of range", k, p);
             e_q.push_back(q[k]);
@@ -163,6 +154,7 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     g->n_edges = (int)e_counts.size();
     g->n_matches = (long long)e_q.size();
     g->n_kp = kp_offsets[n_frames];
+    g->n_src = n_src;
     g->kp_offsets_h.assign(kp_offsets, kp_offsets + n_frames + 1);
     (void)hipSetDevice(ctx->device);
     size_t off = 0;
@@ -172,6 +164,7 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     const size_t o_t = take(sizeof(unsigned) * (size_t)g->n_matches), o_valid = take((size_t)n_frames), o_excl = take((size_t)n_frames);
     const size_t o_kpo = take(sizeof(long long) * ((size_t)n_frames + 1)), o_h3 = take((size_t)g->n_kp);
     const size_t o_ec = take(sizeof(unsigned) * 2 * (size_t)g->n_edges), o_best = take(sizeof(unsigned) * 4);
+    const size_t o_src = take(sizeof(long long) * (size_t)g->n_edges);
     if (hipMalloc((void**)&g->dev, off) != hipSuccess) {
         delete g;
         return ctx->fail(EACHAM_ERR_HIP, "graph_create: allocating %zu bytes failed", off);
@@ -181,12 +174,14 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     g->q = (unsigned*)(base + o_q); g->t = (unsigned*)(base + o_t); g->valid = (unsigned char*)(base + o_valid);
     g->excluded = (unsigned char*)(base + o_excl); g->kp_offsets = (long long*)(base + o_kpo); g->has3d = (unsigned char*)(base + o_h3);
     g->edge_counts = (unsigned*)(base + o_ec); g->best = (unsigned*)(base + o_best);
+    g->src_offsets = (long long*)(base + o_src);
     hipStream_t st = ctx->stream;
     bool ok = hipMemsetAsync(base, 0, off, st) == hipSuccess;
     auto up = [&](void* dst, const void* src, size_t bytes) { return !bytes || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
     ok = ok && up(g->pairs, e_pairs.data(), sizeof(int) * e_pairs.size()) && up(g->counts, e_counts.data(), sizeof(int) * e_counts.size()) &&
          up(g->offsets, e_off.data(), sizeof(long long) * e_off.size()) && up(g->q, e_q.data(), sizeof(unsigned) * e_q.size()) &&
-         up(g->t, e_t.data(), sizeof(unsigned) * e_t.size()) && up(g->kp_offsets, kp_offsets, sizeof(long long) * ((size_t)n_frames + 1));
+         up(g->t, e_t.data(), sizeof(unsigned) * e_t.size()) && up(g->kp_offsets, kp_offsets, sizeof(long long) * ((size_t)n_frames + 1)) &&
+         up(g->src_offsets, e_src.data(), sizeof(long long) * e_src.size());
     ok = ok && hipStreamSynchronize(st) == hipSuccess;   // (the host vectors die here)
     if (!ok) {
         (void)hipFree(g->dev);

@@ -65,6 +65,13 @@ class ResidentGraph:
         ctx._check(ctx._L.eacham_graph_create(ctx.handle, n_frames, pairs.ctypes.data, pairs.shape[0], counts.ctypes.data, offsets.ctypes.data,
                                               q.ctypes.data, t.ctypes.data, kpo.ctypes.data, C.byref(h)))
         self._h = h
+        self._n_nodes, self._n_matches = int(kpo[-1]), int(counts[counts > 0].sum())
+
+    def tracks(self, keep=None, min_len: int = 2, conflict_policy: int = 0, cap_obs=None, cap_tracks=None):
+        """eacham_graph_tracks: the multi-view tracks of the resident graph (eacham_amd/tracks.py); only `keep` — a byte per match,
+        indexed like the q and t the graph was made from — is uploaded."""
+        from .tracks import graph_tracks
+        return graph_tracks(self.ctx, self._h, self._n_nodes, self._n_matches, keep, min_len, conflict_policy, cap_obs, cap_tracks)
 
     def set_frame(self, frame: int, valid: bool, has3d=None):
         f = None if has3d is None else np.ascontiguousarray(has3d, dtype=np.uint8)

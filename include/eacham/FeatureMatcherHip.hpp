@@ -552,6 +552,8 @@ inline BestPair GetBestPairForValid(Context& ctx, const std::vector<std::pair<un
     return r;
 }
 
+struct Tracks;   // TracksHip.hpp
+
 // The resident form for the incremental loop (apps/sfm/main.cpp:188-214 asks after every frame it adds): the graph is uploaded once,
 // SetFrame refreshes the frames the loop has just changed — the one it posed and triangulated and that frame's factor neighbours —
 // and Query costs two small kernels (eacham_graph_create / _set_frame / _query).
@@ -566,6 +568,8 @@ public:
         for (size_t f = 0; f < keypointsPerFrame.size(); ++f) kpo[f + 1] = kpo[f] + (int64_t)keypointsPerFrame[f];
         ctx.check(eacham_graph_create(ctx.get(), (int)keypointsPerFrame.size(), flat.data(), (int)pairs.size(), g.counts.data(), g.offsets.data(),
                                       g.q.data(), g.t.data(), kpo.data(), &h_));
+        nodes_ = kpo.back();
+        for (int32_t c : g.counts) matches_ += c > 0 ? c : 0;
     }
     ~ResidentMatchGraph() { eacham_graph_destroy(h_); }
     ResidentMatchGraph(const ResidentMatchGraph&) = delete;
@@ -596,9 +600,13 @@ public:
         r.id = best[0], r.id2 = best[1], r.points3dCount = best[2];
         return r;
     }
+    // The multi-view tracks of the graph (eacham_graph_tracks; defined in TracksHip.hpp): keep = optional byte per match, indexed like
+    // the q and t the graph was made from.
+    struct Tracks Tracks(const uint8_t* keep = nullptr, int min_len = 2, int conflict_policy = 0);
 private:
     Context& ctx_;
     eacham_graph* h_ = nullptr;
+    int64_t nodes_ = 0, matches_ = 0;
 };
 
 }  // namespace hip

@@ -559,6 +559,46 @@ int eacham_graph_set_frames(eacham_graph* graph, int n, const int32_t* frames, c
                             const int64_t* has3d_offsets);
 int eacham_graph_query(eacham_graph* graph, const int32_t* excluded_frames, int n_excluded, uint32_t* best);
 
+/* ---- multi-view tracks from the match graph ---------------------------------------------------
+ * The stage between pairwise matches and eacham_triangulate_tracks / eacham_ba_solve: a NODE is a keypoint (global id
+ * kp_offsets[f] + k), an EDGE a match (q of f1, t of f2) of a pair whose `keep` byte is non-zero (keep == NULL: every match),
+ * a TRACK a connected component with at least min_len (>= 2) nodes. The reference forms a star around one frame's keypoints
+ * with hash maps, frame by frame (Triangulator.cpp:202-241); this is the whole graph at once, as an exact integer answer that
+ * does not depend on the order anything runs in: a component is labelled by its smallest node id, tracks come out ordered by
+ * that label, the observations of a track by ascending node id (frame-major, then keypoint).
+ *   pairs .. kp_offsets   the arguments of eacham_graph_create: pairs in either orientation, duplicate edges and pairs with
+ *                         counts[p] == 0 are legal, so are frames without keypoints; offsets has npairs entries, starts at 0
+ *                         and does not decrease
+ *   keep                  optional, one byte per match, indexed like q and t (e.g. the inlier masks of eacham_lmeds_batch)
+ *   conflict_policy       a track that holds two keypoints of ONE frame is a conflict: 0 = keep it, bit 0 of its track_flags
+ *                         set; 1 = drop such tracks whole
+ * Outputs: *n_tracks, *n_obs; track_ptr (n_tracks + 1 CSR offsets, cap_tracks + 1 entries of room), obs_frame / obs_kp
+ * (cap_obs entries of room; obs_frame is what eacham_triangulate_tracks takes), track_flags (cap_tracks), node_track (optional,
+ * kp_offsets[n_frames] entries: the track of every keypoint, -1 = none).
+ * EACHAM_ERR_INVALID (checked on the host before anything is launched or written; the message names the problem): a null
+ * required pointer, a negative size, offsets / kp_offsets that do not start at 0 or that decrease, a negative count, a frame id
+ * out of range, q or t beyond the frame's keypoint count, min_len < 2, an unknown policy.
+ * EACHAM_ERR_CAPACITY: more than 2^31 - 1 nodes or matches in one call (the totals are then left as they were), more than 2^30
+ * nodes that a match can touch (min(nodes, 2 x matches): the sort's limit), or n_obs > cap_obs or n_tracks > cap_tracks — then
+ * *n_tracks and *n_obs hold what is needed and nothing else has been written. n_obs <= min(nodes, 2 x matches) and
+ * n_tracks <= n_obs / 2 always suffice.
+ * EACHAM_ERR_HIP with a message if the components have not settled within the round cap (see eacham_tracks_debug_last). */
+int eacham_tracks_build(eacham_ctx* ctx, int n_frames, const int32_t* pairs, int npairs, const int32_t* counts,
+                        const int64_t* offsets, const uint32_t* q, const uint32_t* t, const int64_t* kp_offsets,
+                        const uint8_t* keep, int min_len, int conflict_policy, int64_t cap_obs, int32_t cap_tracks,
+                        int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame, uint32_t* obs_kp,
+                        uint8_t* track_flags, int32_t* node_track);
+/* The same kernels on the arrays a resident graph already holds: only `keep` (optional; indexed like the q and t that
+ * eacham_graph_create was given) is uploaded. Same result as eacham_tracks_build, byte for byte; leaves no state in the graph. */
+int eacham_graph_tracks(eacham_graph* graph, const uint8_t* keep, int min_len, int conflict_policy, int64_t cap_obs,
+                        int32_t cap_tracks, int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame,
+                        uint32_t* obs_kp, uint8_t* track_flags, int32_t* node_track);
+/* Diagnostic: how the context's last track-building call ran (any pointer may be NULL). rounds = hook-and-compress rounds until
+ * one changed nothing (that one included; 0 if the call had no kept edge), round_cap = the bound it is held to,
+ * 2 * ceil(log2(touched-node bound)) + 1 with the bound min(nodes, 2 x matches), readbacks = device-to-host read-backs of status words (one per batch of rounds, one
+ * for the totals), kernel_ms = device time from the first kernel to the last by HIP events if eacham_profile_enable is on, else -1. */
+int eacham_tracks_debug_last(eacham_ctx* ctx, int32_t* rounds, int32_t* round_cap, int32_t* readbacks, float* kernel_ms);
+
 /* ---- kernel timing (HIP events on the context stream; used for roofline reporting) ---------- */
 
 #define EACHAM_KERNEL_MATCH_TILE 0     /* all-pairs int8 MFMA distance + fused row/col top-2      */
