@@ -76,6 +76,10 @@ def lib() -> C.CDLL:
         L.eacham_match_pair_dot.argtypes = [vp, i32, i32, f32, vp, vp, vp, i32, C.POINTER(i32)]
         L.eacham_match_pairs_directed_dot.argtypes = [vp, vp, i32, f32, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
         L.eacham_match_all_pairs_dot.argtypes = [vp, vp, i32, f32, i32, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]
+    if hasattr(L, "eacham_match_all_pairs_dot_screened"):
+        L.eacham_match_all_pairs_dot_screened.argtypes = L.eacham_match_all_pairs_dot.argtypes
+        L.eacham_match_debug_dot_screen.argtypes = [vp, C.POINTER(i64)]
+        L.eacham_match_debug_dot_coarse.argtypes = [vp, i32, i32, vp, vp, vp]
     L.eacham_ba_solve.argtypes = [vp, vp, vp, vp]
     L.eacham_ba_prepare.argtypes = [vp, vp, C.POINTER(vp)]
     L.eacham_ba_run.argtypes = [vp, vp, vp, vp]

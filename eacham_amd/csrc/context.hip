@@ -357,6 +357,7 @@ int eacham_clear_descriptors(eacham_ctx* ctx) {
     for (auto& f : ctx->frames) {
         if (f.frag) (void)hipFree(f.frag);
         if (f.norm) (void)hipFree(f.norm);
+        free_frame_image16(f);
         f = FrameHost();
     }
     ctx->frames.clear();
@@ -373,7 +374,9 @@ void eacham_ctx_destroy(eacham_ctx* ctx) {
     for (auto& f : ctx->frames) {
         if (f.frag) (void)hipFree(f.frag);
         if (f.norm) (void)hipFree(f.norm);
+        free_frame_image16(f);
     }
+    if (ctx->table16_dev) (void)hipFree(ctx->table16_dev);
     if (ctx->frame_table_dev) (void)hipFree(ctx->frame_table_dev);
     if (ctx->flag_dev) (void)hipFree(ctx->flag_dev);
     if (ctx->pairs_safe) (void)hipFree(ctx->pairs_safe);

@@ -49,6 +49,12 @@ struct FrameHost {
     int ks = 0;
     int ntiles = 0;      // allocated tiles
     int tiles_used = 0;  // tiles in use (<= ntiles), known after sync_frame_table
+    // fp16 image of an fp32 frame (matcher_dot16.hip): one allocation, fragments | norm bounds | {max bound, flag}; built on the
+    // frame's first screened call, freed wherever frag is (free_frame_image16)
+    void* img16 = nullptr;
+    bool img16_ready = false;   // built (or nothing to build: an empty frame)
+    bool img16_bad = false;     // holds a value that is not finite or beyond the fp16 range: its pairs run the fp32 tile kernel
+    float img16_maxn = 0.0f;    // max of the per-row norm bounds
 };
 
 // One arena of the bundle adjuster: every device array of a prepared problem is carved out of ONE allocation, and the
@@ -96,6 +102,9 @@ struct eacham_ctx {
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
     int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip)
     void* last_matches = nullptr;  // per-pair match lists of the last run (directed API reads them back)
+    void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
+    int table16_cap = 0;
+    long long dot16_fallback_pairs = 0;  // pairs of the last screened call that ran the fp32 tile kernel (eacham_match_debug_dot_screen)
 
     // matcher workspace (grown on demand, never inside a timed launch sequence after warm-up)
     void* ws = nullptr;
@@ -311,6 +320,17 @@ MatchPlanF32 plan_match_f32(const eacham_ctx* ctx, int npairs);
 int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_score, int min_dir, int min_mutual, int mode,
                   int* counts_dev, long long* offsets_dev, uint2* edges_dev, float* scores_dev, long long edge_cap,
                   long long* total_dev, int4* stats_dev);
+// the launches of run_match_dot, shared with the screened form: the fp32 tile kernel over nb pairs, and finalize + scan + compaction
+void launch_match_tile_dot(eacham_ctx* ctx, const int2* pb, int nb, const MatchPlanF32& pl, int2* rr, int2* cp);
+int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const int2* pb, int nb, int first, bool is_last, int2* rr, int2* cp,
+                          float min_score, int min_dir, int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
+                          uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev);
+// matcher_dot16.hip
+void free_frame_image16(FrameHost& f);
+int prepare_match_dot_screened(eacham_ctx* ctx, const int32_t* pairs, int npairs, int32_t* pairs_fb, int* n_fallback);
+int run_match_dot_screened(eacham_ctx* ctx, const int2* pairs_dev, const int2* pairs_fb_dev, const int32_t* pairs_fb_host, int npairs,
+                           int n_fallback, float min_score, int min_dir, int min_mutual, int* counts_dev, long long* offsets_dev,
+                           uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev);
 // matcher.hip
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);
 void launch_compact_edges(eacham_ctx* ctx, int nb, const uint2* matches, const int* counts, const long long* offsets,

@@ -1596,8 +1596,10 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
         EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (f.frag) (void)hipFree(f.frag);
         if (f.norm) (void)hipFree(f.norm);  // the other per-row arrays share the allocation
+        free_frame_image16(f);
         f = FrameHost();
     }
+    f.img16_ready = false;  // (an empty frame has no allocation, yet counts as imaged: the new rows need an image of their own)
     const int npad = ntiles * 32;
     {
         // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[2]
@@ -2093,7 +2095,7 @@ int eacham_match_pairs_directed(eacham_ctx* ctx, const int32_t* pairs, int npair
 // ---- dot-product form (matcher_dot.hip): host pointers in, CSR over the pairs + scores out ----
 static int match_pairs_dot_host(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
                                 int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score,
-                                int64_t cap, int64_t* out_total, int32_t* stats) {
+                                int64_t cap, int64_t* out_total, int32_t* stats, bool screened = false) {
     if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
         return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to the dot-product matcher");
     int rc = check_pairs_host(ctx, pairs, npairs);
@@ -2115,13 +2117,27 @@ static int match_pairs_dot_host(eacham_ctx* ctx, const int32_t* pairs, int npair
     const size_t o_stats = align(o_total + sizeof(int64_t));
     const size_t o_edges = align(o_stats + (size_t)npairs * 4 * sizeof(int32_t));
     const size_t o_scores = align(o_edges + (size_t)cap * sizeof(uint2));
-    rc = ensure_io(ctx, o_scores + (size_t)cap * sizeof(float));
+    const size_t o_pairs_fb = align(o_scores + (size_t)cap * sizeof(float));  // the screened form's second pair list
+    rc = ensure_io(ctx, screened ? o_pairs_fb + (size_t)npairs * 2 * sizeof(int32_t) : o_pairs_fb);
     if (rc) return rc;
     char* io = (char*)ctx->io;
     EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs, pairs, (size_t)npairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    rc = run_match_dot(ctx, (const int2*)(io + o_pairs), npairs, min_score, min_dir, min_mutual, mode, (int*)(io + o_counts),
-                       (long long*)(io + o_offsets), (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
-                       stats ? (int4*)(io + o_stats) : nullptr);
+    if (screened) {
+        std::vector<int32_t> pairs_fb((size_t)npairs * 2);
+        int n_fallback = 0;
+        rc = prepare_match_dot_screened(ctx, pairs, npairs, pairs_fb.data(), &n_fallback);
+        if (rc) return rc;
+        // (pageable source: the copy is staged before hipMemcpyAsync returns)
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs_fb, pairs_fb.data(), pairs_fb.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        rc = run_match_dot_screened(ctx, (const int2*)(io + o_pairs), (const int2*)(io + o_pairs_fb), pairs_fb.data(), npairs, n_fallback,
+                                    min_score, min_dir, min_mutual, (int*)(io + o_counts), (long long*)(io + o_offsets),
+                                    (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
+                                    stats ? (int4*)(io + o_stats) : nullptr);
+    } else {
+        rc = run_match_dot(ctx, (const int2*)(io + o_pairs), npairs, min_score, min_dir, min_mutual, mode, (int*)(io + o_counts),
+                           (long long*)(io + o_offsets), (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
+                           stats ? (int4*)(io + o_stats) : nullptr);
+    }
     if (rc) return rc;
     long long total = 0;
     EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&total, io + o_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
@@ -2186,6 +2202,15 @@ int eacham_match_all_pairs_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs
     return dot_entry(ctx, [&]() -> int {
         return match_pairs_dot_host(ctx, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
                                     out_total, stats);
+    });
+}
+
+int eacham_match_all_pairs_dot_screened(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
+                                        int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score,
+                                        int64_t cap, int64_t* out_total, int32_t* stats) {
+    return dot_entry(ctx, [&]() -> int {
+        return match_pairs_dot_host(ctx, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
+                                    out_total, stats, true);
     });
 }
 

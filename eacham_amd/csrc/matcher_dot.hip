@@ -236,6 +236,35 @@ __global__ void compact_dot_kernel(const uint2* __restrict__ matches, const int2
         }
 }
 
+void launch_match_tile_dot(eacham_ctx* ctx, const int2* pb, int nb, const MatchPlanF32& pl, int2* rr, int2* cp) {
+    const int grid = nb * pl.wgs_per_pair;
+    switch (ctx->ks_common) {
+        case 32: match_tile_dot_kernel<32><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
+        case 64: match_tile_dot_kernel<64><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
+        default: match_tile_dot_kernel<128><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
+    }
+}
+
+// finalize, scan of the counts and compaction of one launch's pairs [first, first + nb)
+int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const int2* pb, int nb, int first, bool is_last, int2* rr, int2* cp,
+                          float min_score, int min_dir, int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
+                          uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev) {
+    const size_t fin_smem = (size_t)2 * pl.row_stride * sizeof(int);
+    if (fin_smem > 48 * 1024)
+        EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_dot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
+    uint2* mt = (uint2*)((char*)ctx->ws + pl.off_matches);
+    {
+        ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
+        int* cnt = counts_dev + first;
+        match_finalize_dot_kernel<<<nb, FIN_T, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, cp, pl.wb_stride, pl.row_stride, min_score,
+                                                                       min_dir, min_mutual, mode, mt, cnt, stats_dev ? stats_dev + first : nullptr);
+        launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, is_last);
+        compact_dot_kernel<<<nb, 256, 0, ctx->stream>>>(mt, rr, cnt, offsets_dev + first, pl.row_stride, edges_dev, scores_dev, edge_cap);
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    return EACHAM_OK;
+}
+
 // mode 0 = mutual + thresholds, mode 1 = directed lists; CSR over the pairs either way
 int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_score, int min_dir, int min_mutual, int mode,
                   int* counts_dev, long long* offsets_dev, uint2* edges_dev, float* scores_dev, long long edge_cap,
@@ -244,33 +273,18 @@ int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_
     int rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
     char* ws = (char*)ctx->ws;
-    const size_t fin_smem = (size_t)2 * pl.row_stride * sizeof(int);
-    if (fin_smem > 48 * 1024)
-        EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_dot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
     int2* rr = (int2*)(ws + pl.off_rowres);   // the plan's int4 slots, half used: one plan for both forms
     int2* cp = (int2*)(ws + pl.off_colpart);
-    uint2* mt = (uint2*)(ws + pl.off_matches);
     for (int first = 0; first < npairs; first += pl.batch) {
         const int nb = std::min(pl.batch, npairs - first);
         const int2* pb = pairs_dev + first;
-        const int grid = nb * pl.wgs_per_pair;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE);
-            switch (ctx->ks_common) {
-                case 32: match_tile_dot_kernel<32><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
-                case 64: match_tile_dot_kernel<64><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
-                default: match_tile_dot_kernel<128><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rr, cp, pl.wb_stride, pl.row_stride); break;
-            }
+            launch_match_tile_dot(ctx, pb, nb, pl, rr, cp);
         }
-        {
-            ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
-            int* cnt = counts_dev + first;
-            match_finalize_dot_kernel<<<nb, FIN_T, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, cp, pl.wb_stride, pl.row_stride, min_score,
-                                                                           min_dir, min_mutual, mode, mt, cnt, stats_dev ? stats_dev + first : nullptr);
-            launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-            compact_dot_kernel<<<nb, 256, 0, ctx->stream>>>(mt, rr, cnt, offsets_dev + first, pl.row_stride, edges_dev, scores_dev, edge_cap);
-        }
-        EACHAM_HIP_TRY(ctx, hipGetLastError());
+        rc = launch_match_dot_tail(ctx, pl, pb, nb, first, first + nb == npairs, rr, cp, min_score, min_dir, min_mutual, mode, counts_dev,
+                                   offsets_dev, edges_dev, scores_dev, edge_cap, total_dev, stats_dev);
+        if (rc) return rc;
     }
     return EACHAM_OK;
 }

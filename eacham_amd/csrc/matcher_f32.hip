@@ -287,8 +287,10 @@ int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n,
         EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (f.frag) (void)hipFree(f.frag);
         if (f.norm) (void)hipFree(f.norm);
+        free_frame_image16(f);
         f = FrameHost();
     }
+    f.img16_ready = false;  // (an empty frame has no allocation, yet counts as imaged: the new rows need an image of their own)
     const int npad = ntiles * 32;
     if (npad > 0) {
         EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, (size_t)npad * D2 * 2 * sizeof(float)));

@@ -200,16 +200,35 @@ class HipContext:
         return counts, offsets, q[:n].copy(), t[:n].copy(), s[:n].copy()
 
     def match_all_pairs_dot(self, pairs, min_score: float = MIN_SCORE, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL,
-                            cap: int | None = None, stats: bool = True):
-        """The mutual form (eacham_match_all_pairs_dot). Returns (counts, offsets, q, t, scores, stats)."""
+                            cap: int | None = None, stats: bool = True, screened: bool = False):
+        """The mutual form (eacham_match_all_pairs_dot). Returns (counts, offsets, q, t, scores, stats). screened=True runs
+        eacham_match_all_pairs_dot_screened: an fp16 sweep + exact fp32 work where it decides nothing — the same bytes."""
         pairs, npairs, cap, counts, offsets, q, t, s = self._dot_buffers(pairs, cap)
         st = np.zeros((npairs, 4), dtype=np.int32) if stats else None
         total = C.c_int64(0)
-        self._check(self._L.eacham_match_all_pairs_dot(
+        call = self._L.eacham_match_all_pairs_dot_screened if screened else self._L.eacham_match_all_pairs_dot
+        self._check(call(
             self._h, pairs.ctypes.data, npairs, min_score, min_dir, min_mutual, counts.ctypes.data, offsets.ctypes.data,
             q.ctypes.data, t.ctypes.data, s.ctypes.data, cap, C.byref(total), st.ctypes.data if stats else None))
         n = total.value
         return counts, offsets, q[:n].copy(), t[:n].copy(), s[:n].copy(), st
+
+    def match_dot_screen(self):
+        """{rows: (dead, settled, open), cols: (dead, settled, open), fallback_pairs} of the last screened call
+        (eacham_match_debug_dot_screen)."""
+        out = (C.c_int64 * 7)()
+        self._check(self._L.eacham_match_debug_dot_screen(self._h, out))
+        v = [int(x) for x in out]
+        return {"rows": tuple(v[0:3]), "cols": tuple(v[3:6]), "fallback_pairs": v[6]}
+
+    def match_dot_coarse(self, f1: int, f2: int):
+        """(s_coarse, row_E, col_E): the fp16 sweep's raw n1 x n2 similarities of the pair and the error bounds it classifies rows
+        and columns with (eacham_match_debug_dot_coarse; test hook, frames of <= 4096 rows)."""
+        n1, n2 = self.frame_rows(f1), self.frame_rows(f2)
+        s = np.zeros((n1, n2), dtype=np.float32)
+        re, ce = np.zeros(max(n1, 1), dtype=np.float32), np.zeros(max(n2, 1), dtype=np.float32)
+        self._check(self._L.eacham_match_debug_dot_coarse(self._h, f1, f2, s.ctypes.data if s.size else None, re.ctypes.data, ce.ctypes.data))
+        return s, re[:n1], ce[:n2]
 
     def match_all_pairs_dev(self, pairs_dev: int, npairs: int, counts_dev: int, offsets_dev: int,
                             edges_dev: int, edge_cap: int, total_dev: int, stats_dev: int = 0,

@@ -486,10 +486,11 @@ struct MatchGraphDot : MatchGraph {
 };
 
 // MatchAllPairs for float descriptors under dot-product similarity: rewrites the context's descriptor store (frame f -> id f),
-// matches every pair in both directions with the mutual check and the thresholds given.
+// matches every pair in both directions with the mutual check and the thresholds given. screened = true runs
+// eacham_match_all_pairs_dot_screened (an fp16 sweep + exact fp32 work for the winners and near-ties): the same bytes, opt-in.
 inline MatchGraphDot MatchAllPairsDot(Context& ctx, const std::vector<DescriptorView>& frames,
                                       const std::vector<std::pair<unsigned, unsigned>>& pairs, float minScore = 0.5f,
-                                      int minDir = 30, int minMutual = 30) {
+                                      int minDir = 30, int minMutual = 30, bool screened = false) {
     ctx.store_rewritten();
     ctx.check(eacham_clear_descriptors(ctx.get()));
     for (size_t f = 0; f < frames.size(); ++f)
@@ -508,8 +509,9 @@ inline MatchGraphDot MatchAllPairsDot(Context& ctx, const std::vector<Descriptor
     g.t.resize(g.q.size());
     g.scores.resize(g.q.size());
     int64_t total = 0;
-    ctx.check(eacham_match_all_pairs_dot(ctx.get(), flat.data(), (int)pairs.size(), minScore, minDir, minMutual, g.counts.data(),
-                                         g.offsets.data(), g.q.data(), g.t.data(), g.scores.data(), cap, &total, nullptr));
+    ctx.check((screened ? eacham_match_all_pairs_dot_screened : eacham_match_all_pairs_dot)(
+        ctx.get(), flat.data(), (int)pairs.size(), minScore, minDir, minMutual, g.counts.data(), g.offsets.data(), g.q.data(), g.t.data(),
+        g.scores.data(), cap, &total, nullptr));
     g.q.resize(total);
     g.t.resize(total);
     g.scores.resize(total);

@@ -179,6 +179,34 @@ int eacham_match_all_pairs_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs
                                uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap, int64_t* out_total,
                                int32_t* stats);
 
+/* The screened form of eacham_match_all_pairs_dot: the same arguments, and outputs that are identical to that
+ * call's byte for byte — counts, offsets, q, t, the bits of every score, stats — with the same error codes for the same bad
+ * inputs. An fp16 sweep on the matrix cores decides every row and column that a proven bound on |fp16 value - fp32 value| lets
+ * it decide (dead: cannot pass min_score; settled: the arg-max is certain); the exact fp32 chain is then evaluated for the
+ * winners, and against the whole other frame for the rows and columns left open. A pair with a frame that holds a value that
+ * is not finite or beyond the fp16 range (|x| > 65504) runs the fp32 kernel of the unscreened call. A frame's fp16 image is
+ * built on its first screened call and dropped on re-upload and eacham_clear_descriptors; callers of the unscreened entry
+ * points pay nothing for it. Opt-in: whether it is faster depends on how many rows the bound leaves open.
+ * Out of scope: the directed calls and eacham_match_pair_dot have no screened form. */
+int eacham_match_all_pairs_dot_screened(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score,
+                                        int min_dir, int min_mutual,
+                                        int32_t* counts, int64_t* offsets,
+                                        uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap, int64_t* out_total,
+                                        int32_t* stats);
+
+/* Debug getter (tests, rate tools): the LAST eacham_match_all_pairs_dot_screened call on this context. out[0..2] = rows dead /
+ * settled / open, out[3..5] = columns dead / settled / open (screened pairs only, real rows and columns), out[6] = pairs that
+ * fell back to the fp32 kernels. Waits for the context's stream. */
+int eacham_match_debug_dot_screen(eacham_ctx* ctx, int64_t out[7]);
+
+/* Test hook: the fp16 sweep's raw similarities of the pair (f1, f2), s_coarse[q * n2 + t] (n1 x n2 floats), and the bounds the
+ * screen classifies with: row_E[q] (n1) and col_E[t] (n2), |s_coarse - s| <= min(row_E[q], col_E[t]). Small frames only:
+ * EACHAM_ERR_CAPACITY above 4096 x 4096; EACHAM_ERR_UNSUPPORTED for int8 frames and for a pair that is not screened.
+ * These are restatements, not the matcher's own memory: s_coarse comes from an instantiation of the tile kernel that also stores
+ * every accumulator (the same MFMA sequence per tile, another code object), row_E and col_E are recomputed on the host from the
+ * stored norm bounds with the formula and rounding steps of the classify kernel. */
+int eacham_match_debug_dot_coarse(eacham_ctx* ctx, int f1, int f2, float* s_coarse, float* row_E, float* col_E);
+
 /* ---- bundle adjustment: RefineBA (modules/sfm/reconstruction/BundleAdjuster.cpp:40-250) --------
  *
  * The caller (the C++ adapter in include/eacham/BundleAdjusterHip.hpp) performs the reference's
