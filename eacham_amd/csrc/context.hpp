@@ -132,15 +132,9 @@ struct eacham_ctx {
                               // Any other value means 0: the retired =dense (docs/HISTORY.md) now gives a local window its default, the pair lists
     int ba_ordering = 0;  // EACHAM_BA_ORDERING=natural|rcm|nd read ONCE at eacham_ctx_create (diagnostic override of
                           // eacham_ba_problem.ordering == AUTO); nothing on the solve path reads the environment
-    bool exp_no_coltop2 = false;    // EACHAM_EXP_NO_COLTOP2 (diagnostic, WRONG RESULTS: the tile sweep without its column direction — timing only)
-    bool exp_all_candidates = false;  // EACHAM_EXP_ALL_CANDIDATES (diagnostic, timing only: every row is a candidate of the column pass)
-    int exp_sweep_prio = 0;           // EACHAM_EXP_SWEEP_PRIO=1..3 (diagnostic A/B): s_setprio of the sweep's waves (the candidate pass beside it stays at 0)
-    int exp_stream2_cus = 0;          // EACHAM_EXP_STREAM2_CUS=<n> (diagnostic A/B): the second stream may use n of the 256 CUs only (hipExtStreamCreateWithCUMask)
     int match_sweep_form = 0;         // EACHAM_MATCH_SWEEP_FORM=exact|bound (diagnostic A/B, tests): the lean form's row sweep keeps every row's exact top-2 (1), or
                                       // runs its bound form + the exact pass over the rows left open (2); 0 = by descriptor dimension (bound up to 128-D)
     bool match_colprune = true;       // EACHAM_MATCH_COLPRUNE=0 (A/B, tests): no candidate column is settled from the sweep's row minima, all go to match_colverify_kernel
-    bool match_tile_sweep = false;    // EACHAM_MATCH_TILE_SWEEP (diagnostic A/B: the lean form's sweep by match_tile_kernel, the first round-4 form)
-    bool match_full_columns = false;  // EACHAM_MATCH_FULL_COLUMNS (diagnostic A/B: every column's top-2 from the sweep, the round-1..3 form)
     int match_budget_mb = 1024;     // EACHAM_MATCH_BUDGET_MB (diagnostic: workspace budget of one batch of pairs), read at create
     bool match_no_overlap = false;  // EACHAM_NO_OVERLAP (diagnostic: finalize on the tile kernel's stream), read at create
 

@@ -50,10 +50,7 @@ constexpr int CHUNK_TILES = 1 << KEY_SHIFT;  // column tiles one sweep can tag i
 constexpr int MAX_ROWS = 16384;              // rows per frame (K2 keeps two int per stored row in LDS)
 constexpr int WG_THREADS = 256;            // 4 waves (1 per SIMD); 2 workgroups per CU drift out of phase so MFMA and VALU overlap
 constexpr int WAVES = WG_THREADS / 64;
-#ifndef EACHAM_MATCH_NSUB
-#define EACHAM_MATCH_NSUB 2
-#endif
-constexpr int MATCH_NSUB = EACHAM_MATCH_NSUB;        // 32-row MFMA sub-tiles per wave (A fragments live in VGPRs)
+constexpr int MATCH_NSUB = 2;                        // 32-row MFMA sub-tiles per wave (A fragments live in VGPRs)
 constexpr int ROWS_PER_WAVE = 32 * MATCH_NSUB;
 constexpr int ROWS_PER_WG = WAVES * ROWS_PER_WAVE;
 constexpr int GROUP_TILES = MATCH_NSUB;              // tiles in use are padded to whole wave-blocks
@@ -204,10 +201,11 @@ __device__ __forceinline__ void lds_read_frag(V& dst, unsigned addr, int offset_
     asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(offset_bytes));
 }
 
-template <int KS, int NSUB, bool COL>
-__global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_kernel(
+template <int KS>
+__global__ __launch_bounds__(WG_THREADS, 2) void match_tile_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int wgs_per_pair, int col_chunks,
     uint4* __restrict__ rowres, uint2* __restrict__ colpart, int wb_stride, int row_stride) {
+    constexpr int NSUB = MATCH_NSUB;
     constexpr int TILE_V4 = KS * 64;          // int4 per B tile
     constexpr int ROWS_WAVE = 32 * NSUB;      // query rows a wave keeps in registers
     constexpr int ROWS_WG = WAVES * ROWS_WAVE;
@@ -357,7 +355,7 @@ __global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_ke
         const unsigned lowc = ((unsigned)hb_cur << (KEY_SHIFT + 1)) | (unsigned)((tbeg + t >= B_even ? (1 << KEY_SHIFT) : 0) | t);
         const int t1 = min(t + 1, T - 1), t2 = min(t + 2, T - 1);
         hb_cur = Bhb[32 * t1 + cl];
-        if (COL && t > 0 && t % BURST == 0) merge_burst(t - BURST);  // tiles t-8 .. t-1 are published; their buffer is rewritten from tile t+8 on
+        if (t > 0 && t % BURST == 0) merge_burst(t - BURST);  // tiles t-8 .. t-1 are published; their buffer is rewritten from tile t+8 on
         stage_tile(t2, slot_new);  // lands during this iteration; the barrier below publishes it
         unsigned cm1[NSUB], cm2[NSUB], pend[3] = {0, 0, 0};  // column top-2 per sub-tile (a sub-tile has one parity)
         if (active) {
@@ -392,22 +390,20 @@ __global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_ke
                     // are taken three at a time — {min3, med3} of a triple (2 ops) then one sorted-pair
                     // insert (3 ops) = 5 ops per 3 keys instead of 6 (and the first triple needs no insert).
                     const int eg = ks * EPK + e;  // 0..15 within the sub-tile, compile-time after unrolling
-                    if constexpr (COL) {
-                        pend[eg % 3] = key;
-                        if (eg % 3 == 2) {
-                            const unsigned s1 = umin(umin(pend[0], pend[1]), pend[2]);
-                            const unsigned s2 = vmed3(pend[0], pend[1], pend[2]);
-                            if (eg == 2) {
-                                cm1[ph] = s1;
-                                cm2[ph] = s2;
-                            } else {
-                                cm2[ph] = umin(umin(umax(cm1[ph], s1), cm2[ph]), s2);
-                                cm1[ph] = umin(cm1[ph], s1);
-                            }
-                        } else if (eg == 15) {  // 16 = 5 triples + 1
-                            cm2[ph] = vmed3(cm1[ph], cm2[ph], key);
-                            cm1[ph] = umin(cm1[ph], key);
+                    pend[eg % 3] = key;
+                    if (eg % 3 == 2) {
+                        const unsigned s1 = umin(umin(pend[0], pend[1]), pend[2]);
+                        const unsigned s2 = vmed3(pend[0], pend[1], pend[2]);
+                        if (eg == 2) {
+                            cm1[ph] = s1;
+                            cm2[ph] = s2;
+                        } else {
+                            cm2[ph] = umin(umin(umax(cm1[ph], s1), cm2[ph]), s2);
+                            cm1[ph] = umin(cm1[ph], s1);
                         }
+                    } else if (eg == 15) {  // 16 = 5 triples + 1
+                        cm2[ph] = vmed3(cm1[ph], cm2[ph], key);
+                        cm1[ph] = umin(cm1[ph], key);
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -419,7 +415,7 @@ __global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_ke
             // straddles the even/odd boundary of frame A, which keeps the two parities apart.
             unsigned g1[2] = {0xffffffffu, 0xffffffffu}, g2[2] = {0xffffffffu, 0xffffffffu};
 #pragma unroll
-            for (int s = 0; COL && s < NSUB; ++s) {
+            for (int s = 0; s < NSUB; ++s) {
                 const int g = (split && NSUB * wb + s >= A_even) ? 1 : 0;  // wave-uniform
                 if (g == 0) {
                     g2[0] = umin(umin(umax(g1[0], cm1[s]), g2[0]), cm2[s]);
@@ -431,21 +427,21 @@ __global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_ke
             }
             // lanes l and l+32 hold the same column, rows 4h.. of each 8-row group: merge halves
             // (v_permlane32_swap: lanes 0-31 of the 2nd operand <-> lanes 32-63 of the 1st, pure VALU)
-            if constexpr (COL) {
+            {
                 auto w1 = __builtin_amdgcn_permlane32_swap(g1[0], g1[0], false, false);
                 auto w2 = __builtin_amdgcn_permlane32_swap(g2[0], g2[0], false, false);
                 const unsigned n1 = umin(w1[0], w1[1]);
                 const unsigned n2 = umin(umax(w1[0], w1[1]), umin(w2[0], w2[1]));
                 if (h == 0) sU.c.e[(t / BURST) & 1][t % BURST][0][wave][cl] = make_uint2(n1, n2);
             }
-            if (COL && split) {
+            if (split) {
                 auto w1 = __builtin_amdgcn_permlane32_swap(g1[1], g1[1], false, false);
                 auto w2 = __builtin_amdgcn_permlane32_swap(g2[1], g2[1], false, false);
                 const unsigned n1 = umin(w1[0], w1[1]);
                 const unsigned n2 = umin(umax(w1[0], w1[1]), umin(w2[0], w2[1]));
                 if (h == 0) sU.c.e[(t / BURST) & 1][t % BURST][1][wave][cl] = make_uint2(n1, n2);
             }
-        } else if constexpr (COL) {  // a wave beyond the frame's rows contributes nothing
+        } else {  // a wave beyond the frame's rows contributes nothing
             if (h == 0) sU.c.e[(t / BURST) & 1][t % BURST][0][wave][cl] = make_uint2(0xffffffffu, 0xffffffffu);
             if (split && h == 0) sU.c.e[(t / BURST) & 1][t % BURST][1][wave][cl] = make_uint2(0xffffffffu, 0xffffffffu);
         }
@@ -469,7 +465,7 @@ __global__ __launch_bounds__(WG_THREADS, (NSUB <= 2 ? 2 : 1)) void match_tile_ke
             if (t + 1 < T) tile(P1{}, S1{}, t + 1);
         }
     }
-    if (COL && T > 0) merge_burst((T - 1) / BURST * BURST);  // the last 1..8 tiles, published by the loop's last barrier
+    if (T > 0) merge_burst((T - 1) / BURST * BURST);  // the last 1..8 tiles, published by the loop's last barrier
     __syncthreads();                                  // the region becomes the row slab
     if (!active) return;
 
@@ -561,10 +557,7 @@ __device__ __forceinline__ void top2_merge(int& m1, int& m2, int s1, int s2) {
 // swapped), overwriting their rowres entries before match_rows2_kernel reads them. out: rowres[p][j] = {v1, 0, u, 0}.
 template <int KS, bool BOUND = false>
 __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
-                                                                   int wgs_per_pair, uint4* __restrict__ rowres, int row_stride, int prio) {
-    if (prio == 1) __builtin_amdgcn_s_setprio(1);  // (A/B switch EACHAM_EXP_SWEEP_PRIO: workgroup-uniform, off by default)
-    else if (prio == 2) __builtin_amdgcn_s_setprio(2);
-    else if (prio == 3) __builtin_amdgcn_s_setprio(3);
+                                                                   int wgs_per_pair, uint4* __restrict__ rowres, int row_stride) {
     constexpr int NSUB = 2;
     constexpr int TILE_V4 = KS * 64;
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
@@ -977,9 +970,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
 // faster at 256-D / 128-D). But the pair loop of apps/sfm/main.cpp:111,133-142 only ever looks at column t = m12[q] of a
 // row q that passed the ratio test: with |mutual| > min_mutual >= min_dir - 1 the two direction thresholds are implied
 // (every mutual match is in m12 and in m21), so a pair with no more than min_mutual passing rows is dead, and for the
-// others the column top-2 is needed for the passing rows' best columns only. Three small kernels replace K2:
-//   R  match_rows_kernel       per pair: merge the row results, ratio test, ordered list of the passing rows (candidates),
-//                              one work item per 64 candidates of a live pair
+// others the column top-2 is needed for the passing rows' best columns only. Small kernels replace K2:
+//   R  match_rows2_kernel      per pair: ratio test, ordered list of the passing rows (candidates); match_argmin_kernel finds
+//                              their columns and settles what it can, match_colpick_kernel lists the rest, 64 per work item
 //   V  match_colverify_kernel  per item: d2 of 64 candidate columns against ALL rows of the query frame on the int8 MFMA
 //                              with the operands swapped (candidates = B operand, one per lane), top-2 VALUES per column
 //   F  match_finalize2_kernel  per pair: keep candidate (q, t) iff column t passes the ratio test with minimum d2(q, t);
@@ -1007,65 +1000,6 @@ __device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave /* [FI
 
 constexpr int VER_GROUPS = 2;                 // 32-candidate groups per wave: one fetched A fragment feeds two MFMA chains
 constexpr int VER_CANDS = 32 * VER_GROUPS;    // candidates per work item
-
-// rowcand[p][j] = {stored column of row j's best, d2} if stored row j passes the ratio test, else {~0, 0};
-// candlist[p][i] = stored row of the i-th passing row (ascending j); state[p] = {passing rows, live, 0, 0}
-__global__ __launch_bounds__(FIN_THREADS) void match_rows_kernel(
-    const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int col_chunks,
-    int row_stride, double ratio, int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand,
-    int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items, int* __restrict__ n_items, int exp_all) {
-    __shared__ int s_wave[FIN_THREADS / 64];
-    __shared__ int s_item0;
-    const int tid = threadIdx.x;
-    const int p = blockIdx.x;
-    const int2 pr = pairs[p];
-    const FrameDev A = frames[pr.x], B = frames[pr.y];
-    const int A_even = A.meta[0], A_tiles = A.meta[1], B_tiles = B.meta[1];
-    constexpr unsigned PAD_V = 2u * PADH;
-    const int nchunks = (B_tiles + CHUNK_TILES - 1) / CHUNK_TILES;
-    uint2* rc = rowcand + (size_t)p * row_stride;
-    int* cl = candlist + (size_t)p * row_stride;
-    int base = 0;
-    for (int j0 = 0; j0 < 32 * A_tiles; j0 += FIN_THREADS) {
-        const int j = j0 + tid;
-        bool ok = false;
-        unsigned col = 0;
-        int d2 = 0;
-        if (j < 32 * A_tiles && A.orig[j] >= 0) {
-            unsigned v1 = 0xffffffffu, v2 = 0xffffffffu;
-            for (int ch = 0; ch < nchunks; ++ch) {  // ascending columns; strict '<' keeps the lower column on ties
-                const uint4 e = rowres[((size_t)p * col_chunks + ch) * row_stride + j];
-                if (e.x < v1) {
-                    v2 = umin(v1, e.z);
-                    v1 = e.x;
-                    col = e.y;
-                } else {
-                    v2 = umin(v2, e.x);
-                }
-            }
-            const unsigned pa = (j >> 5) >= A_even ? 1u : 0u;
-            d2 = (int)(v1 + pa) - 2;
-            ok = v2 < PAD_V && ratio_pass(d2, (int)(v2 + pa) - 2, ratio);  // pad second => < 2 train rows
-            if (exp_all) ok = true;  // (diagnostic: every row a candidate — the candidate pass then sweeps the whole pair)
-        }
-        if (j < 32 * A_tiles) rc[j] = ok ? make_uint2(col, (unsigned)d2) : make_uint2(0xffffffffu, 0u);
-        int total;
-        const int rank = block_rank(ok, tid, s_wave, total);
-        if (ok) cl[base + rank] = j;
-        base += total;
-    }
-    // main.cpp:111,142: an edge needs |m12| >= min_dir and |mutual| > min_mutual, and mutual is a subset of m12
-    const bool live = (mode == 0 && base >= min_dir && base > min_mutual) || exp_all;
-    const int groups = (base + VER_CANDS - 1) / VER_CANDS;
-    if (tid == 0) {
-        state[p] = make_int4(base, live ? 1 : 0, 0, 0);
-        if (live) s_item0 = atomicAdd(n_items, groups);
-    }
-    if (live) {  // workgroup-uniform
-        __syncthreads();
-        for (int g = tid; g < groups; g += FIN_THREADS) items[s_item0 + g] = make_int2(p, g);
-    }
-}
 
 // Behind the BOUND form of the sweep (match_sweep_kernel<KS, true>): rowres[p][j] = {v1, 0, u, 0} with u an upper bound of the row's
 // second-smallest value. A row that fails the ratio test against u fails it against the truth and stays as it is (match_rows2_kernel
@@ -1108,8 +1042,10 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
 }
 
 // The rows kernel of the operand-swapped sweep (match_sweep_kernel): rowres carries the TILE of a row's minimum, not its column.
-// Besides what match_rows_kernel does, the passing rows of a pair that goes on are grouped by that tile (bytile[p][..], a counting
-// sort in LDS) and one argmin item is appended per (tile, <= 32 rows) — match_argmin_kernel turns the tile into the column.
+// rowcand[p][j] = {tile of row j's best, d2} if stored row j passes the ratio test, else {~0, 0}; candlist[p][i] = stored row of the
+// i-th passing row (ascending j); state[p] = {passing rows, live, L(p), 0}. The passing rows of a pair that goes on are grouped by
+// that tile (bytile[p][..], a counting sort in LDS) and one argmin item is appended per (tile, <= 32 rows) — match_argmin_kernel
+// turns the tile into the column.
 // state[p].z = L(p), a lower bound of d2(q', t) for every real row q' and every column t that is not q''s own best column: the
 // smallest of d2_1 over the rows that are no candidates (their minimum bounds ALL their distances; under the bound form of the sweep
 // their third word is no runner-up, so only the first is used) and of d2_2 over the candidates (exact {v1, tile, v2} in both forms:
@@ -1119,7 +1055,7 @@ constexpr int AITEM_SHARED = 1 << 16;   // aitems[..].y: the tile, plus this fla
 __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand, int* __restrict__ candlist, int* __restrict__ bytile,
-    int4* __restrict__ state, int4* __restrict__ aitems, int* __restrict__ n_aitems, int exp_all) {
+    int4* __restrict__ state, int4* __restrict__ aitems, int* __restrict__ n_aitems) {
     __shared__ int s_wave[FIN_THREADS / 64];
     __shared__ int s_cnt[MAX_TILES], s_pos[MAX_TILES], s_grp[MAX_TILES];
     __shared__ int s_scan[FIN_THREADS], s_scan2[FIN_THREADS];
@@ -1148,7 +1084,6 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
             d2 = (int)(e.x + pa) - 2;
             ok = e.z < PAD_V && ratio_pass(d2, (int)(e.z + pa) - 2, ratio);  // pad second => < 2 train rows
             low = imin(low, ok ? (int)(e.z + pa) - 2 : d2);   // (a row without a real minimum gives a negative value: nothing is settled then)
-            if (exp_all) ok = e.x < PAD_V;
         }
         if (j < 32 * A_tiles) rc[j] = ok ? make_uint2(tile, (unsigned)d2) : make_uint2(0xffffffffu, 0u);
         if (ok) atomicAdd(&s_cnt[tile], 1);
@@ -1158,7 +1093,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
         base += total;
     }
     // main.cpp:111,142: an edge needs |m12| >= min_dir and |mutual| > min_mutual, and mutual is a subset of m12
-    const bool live = (mode == 0 && base >= min_dir && base > min_mutual) || (exp_all && base > 0);
+    const bool live = mode == 0 && base >= min_dir && base > min_mutual;
     const bool want_col = live || (mode == 1 && base > 0);   // directed lists need the column of every passing row
     atomicMin(&s_low, low);
     __syncthreads();
@@ -1332,7 +1267,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_colpick_kernel(const int* _
 // time: 27 VALU operations per 16 distances (the sweep needs 48) under 8 MFMAs — the kernel is bound by the matrix pipe,
 // which the sweep (bound by the VALU port) leaves idle more than half of the time. Rows of the two parity classes are kept
 // apart (a tile has one parity) and joined when 2H + pa is formed. candlist is the pair's list of stored rows, state[p] word
-// count_word its length: every passing row (match_rows_kernel), or the ones match_argmin_kernel left unresolved (match_colpick_kernel).
+// count_word its length: every passing row (match_rows2_kernel), or the ones match_argmin_kernel left unresolved (match_colpick_kernel).
 // ROWS = true: the same pass with the frames' roles swapped — the candidates are stored ROWS of the query frame (candlist holds them
 // directly), the train frame's tiles stream — for the rows the bound form of the sweep (match_sweep_kernel<KS, true>) could not
 // finish: their exact {v1 = 2H + pb minimum, first tile holding it, v2} go to rowres[p][j], what match_rows2_kernel reads. A wave
@@ -1578,6 +1513,14 @@ static int ks_for_dim(int dim) {
     return 8;
 }
 
+// f(std::integral_constant<int, KS>) for the KS of the resident frames (ks_for_dim: 2, 4 or 8)
+template <class F>
+static void with_ks(int ks, F&& f) {
+    if (ks == 2) f(std::integral_constant<int, 2>{});
+    else if (ks == 4) f(std::integral_constant<int, 4>{});
+    else f(std::integral_constant<int, 8>{});
+}
+
 static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim) {
     if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
     if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
@@ -1719,18 +1662,6 @@ static int next_batch(const MatchPlan& pl, int first, int npairs) {
     return nb;
 }
 
-template <int KS>
-static void launch_tile(eacham_ctx* ctx, const MatchPlan& pl, const int2* pairs_dev, int nb, char* ws, bool col) {
-    if (!col)  // the sweep without its column direction: the candidate-only pass follows (or nothing, for directed lists)
-        match_tile_kernel<KS, MATCH_NSUB, false><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, ctx->stream>>>(
-            ctx->frame_table_dev, pairs_dev, pl.wgs_per_pair, pl.col_chunks, (uint4*)(ws + pl.off_rowres),
-            (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
-    else
-        match_tile_kernel<KS, MATCH_NSUB, true><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, ctx->stream>>>(
-            ctx->frame_table_dev, pairs_dev, pl.wgs_per_pair, pl.col_chunks, (uint4*)(ws + pl.off_rowres),
-            (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
-}
-
 // Core driver. mode 0 = mutual (CSR out), mode 1 = directed single pair (fixed-stride out in ws).
 static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir,
                      int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
@@ -1749,7 +1680,7 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     // redundant once |mutual| > min_mutual >= min_dir - 1, so only the columns that are some passing row's best are ever
     // looked at (candidate-only pass); directed lists need no column at all. Callers that ask for the per-pair statistics
     // (|m12|, |m21|) or use other thresholds get every column's top-2 from the sweep itself, as before.
-    const bool full_cols = ctx->match_full_columns || (mode == 0 && (stats_dev != nullptr || (long long)min_mutual < (long long)min_dir - 1));
+    const bool full_cols = mode == 0 && (stats_dev != nullptr || (long long)min_mutual < (long long)min_dir - 1);
     MatchPlan pl = make_plan(ctx, npairs, full_cols);
     rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
@@ -1776,30 +1707,24 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
         char* ws = (char*)ctx->ws + (size_t)slot * pl.slot_bytes;
         const int2* pb = pairs_dev + first;
         if (b >= pl.slots) EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st1, ctx->ev_fin[slot], 0));  // slot free again
-        const bool row_sweep = !full_cols && !ctx->match_tile_sweep;   // the operand-swapped row sweep (match_sweep_kernel): the default of the lean form
-        // its BOUND form + the exact pass over the rows it could not finish: up to 128-D, where the sweep is bound by its epilogue's
-        // VALU work (S200 at 128-D +5 %, the 1000-frame KITTI stand-in +12 %); at 256-D the sweep is bound by the matrix pipe and gains
-        // 4 % while the exact pass (one more stream of the train frame per pair beside the next sweep) costs the step 4-8 %
-        // (profiles/r05_match_bound_sweep_ab.txt)
-        const bool bound_sweep = row_sweep && (ctx->match_sweep_form == 2 || (ctx->match_sweep_form == 0 && ctx->ks_common <= 4));
+        // The lean form sweeps rows with match_sweep_kernel. Its BOUND form + the exact pass over the rows it could not finish: up to
+        // 128-D, where the sweep is bound by its epilogue's VALU work (S200 at 128-D +5 %, the 1000-frame KITTI stand-in +12 %); at
+        // 256-D the sweep is bound by the matrix pipe and gains 4 % while the exact pass (one more stream of the train frame per pair
+        // beside the next sweep) costs the step 4-8 % (profiles/r05_match_bound_sweep_ab.txt)
+        const bool bound_sweep = !full_cols && (ctx->match_sweep_form == 2 || (ctx->match_sweep_form == 0 && ctx->ks_common <= 4));
+        uint4* rowres = (uint4*)(ws + pl.off_rowres);
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
-            const bool col = full_cols && !ctx->exp_no_coltop2;
-            if (row_sweep) {
-                switch (ctx->ks_common) {
-#define EACHAM_SWEEP(KS_, BOUND_) match_sweep_kernel<KS_, BOUND_><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, (uint4*)(ws + pl.off_rowres), pl.row_stride, ctx->exp_sweep_prio)
-                    case 2: if (bound_sweep) EACHAM_SWEEP(2, true); else EACHAM_SWEEP(2, false); break;
-                    case 4: if (bound_sweep) EACHAM_SWEEP(4, true); else EACHAM_SWEEP(4, false); break;
-                    default: if (bound_sweep) EACHAM_SWEEP(8, true); else EACHAM_SWEEP(8, false); break;
-#undef EACHAM_SWEEP
-                }
-            } else {
-                switch (ctx->ks_common) {
-                    case 2: launch_tile<2>(ctx, pl, pb, nb, ws, col); break;
-                    case 4: launch_tile<4>(ctx, pl, pb, nb, ws, col); break;
-                    default: launch_tile<8>(ctx, pl, pb, nb, ws, col); break;
-                }
-            }
+            with_ks(ctx->ks_common, [&](auto ks) {
+                constexpr int KS = decltype(ks)::value;
+                if (full_cols)
+                    match_tile_kernel<KS><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, st1>>>(
+                        ctx->frame_table_dev, pb, pl.wgs_per_pair, pl.col_chunks, rowres, (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
+                else if (bound_sweep)
+                    match_sweep_kernel<KS, true><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
+                else
+                    match_sweep_kernel<KS, false><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
+            });
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
@@ -1809,10 +1734,8 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st2);
             if (full_cols) {
                 match_finalize_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(
-                    ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres),
-                    (const uint2*)(ws + pl.off_colpart), pl.col_chunks, pl.wb_stride, pl.row_stride, ratio, min_dir,
-                    min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt,
-                    stats_dev ? stats_dev + first : nullptr);
+                    ctx->frame_table_dev, pb, rowres, (const uint2*)(ws + pl.off_colpart), pl.col_chunks, pl.wb_stride, pl.row_stride, ratio,
+                    min_dir, min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
             } else {
                 uint2* rowcand = (uint2*)(ws + pl.off_rowcand);
                 int* candlist = (int*)(ws + pl.off_candlist);
@@ -1820,53 +1743,32 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                 int4* state = (int4*)(ws + pl.off_state);
                 int2* items = (int2*)(ws + pl.off_items);
                 int* n_items = (int*)(ws + pl.off_nitems);
+                int* n_pre = n_items + 8;
                 int* n_aitems = n_items + 16;
-                const int* vlist = candlist;   // what match_colverify_kernel<KS> runs over: every passing row (state[p].x of them) ...
-                int vword = 0;
+                int* bytile = (int*)(ws + pl.off_bytile);
+                int4* aitems = (int4*)(ws + pl.off_aitems);
+                int* openlist = (int*)(ws + pl.off_openlist);
+                // persistent workgroups over an item list (its length is only known on the device): one round of the chip
+                const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
+                const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
-                if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
-                    int* n_pre = n_items + 8;
-                    match_rowpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres), pl.row_stride, ratio,
-                                                                      candlist, state, items, n_pre);
-                    const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
-                    switch (ctx->ks_common) {
-                        case 2: match_colverify_kernel<2, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
-                        case 4: match_colverify_kernel<4, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
-                        default: match_colverify_kernel<8, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre, pl.row_stride, 0, nullptr, (uint4*)(ws + pl.off_rowres)); break;
+                with_ks(ctx->ks_common, [&](auto ks) {
+                    constexpr int KS = decltype(ks)::value;
+                    if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
+                        match_rowpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre);
+                        match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
+                                                                                        pl.row_stride, 0, nullptr, rowres);
                     }
-                }
-                if (row_sweep) {
-                    int* bytile = (int*)(ws + pl.off_bytile);
-                    int4* aitems = (int4*)(ws + pl.off_aitems);
-                    match_rows2_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres), pl.row_stride, ratio,
-                                                                    min_dir, min_mutual, mode, rowcand, candlist, bytile, state, aitems, n_aitems,
-                                                                    ctx->exp_all_candidates ? 1 : 0);
-                    const int settle = ctx->match_colprune && !ctx->exp_all_candidates ? 1 : 0;
-                    const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
-                    switch (ctx->ks_common) {
-                        case 2: match_argmin_kernel<2><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
-                        case 4: match_argmin_kernel<4><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
-                        default: match_argmin_kernel<8><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride, mode == 0 ? colres : nullptr, state, ratio, settle); break;
-                    }
-                    if (mode == 0) {   // the candidates the arg-min pass could not settle: the list and the items of the column pass
-                        int* openlist = (int*)(ws + pl.off_openlist);
+                    match_rows2_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
+                                                                    rowcand, candlist, bytile, state, aitems, n_aitems);
+                    match_argmin_kernel<KS><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride,
+                                                                   mode == 0 ? colres : nullptr, state, ratio, ctx->match_colprune ? 1 : 0);
+                    if (mode == 0) {   // the candidates the arg-min pass could not settle (state[p].w of them): listed, then the column pass
                         match_colpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(candlist, colres, state, pl.row_stride, openlist, items, n_items, colprune_totals(ctx));
-                        vlist = openlist, vword = 3;   // ... or the unresolved ones (state[p].w)
+                        match_colverify_kernel<KS><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, openlist, state, items, n_items,
+                                                                                  pl.row_stride, 3, colres);
                     }
-                } else {
-                    match_rows_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, (const uint4*)(ws + pl.off_rowres), pl.col_chunks,
-                                                                   pl.row_stride, ratio, min_dir, min_mutual, mode, rowcand, candlist, state,
-                                                                   items, n_items, ctx->exp_all_candidates ? 1 : 0);
-                }
-                if (mode == 0) {
-                    // persistent workgroups over the item list (its length is only known on the device): one round of the chip
-                    const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
-                    switch (ctx->ks_common) {
-                        case 2: match_colverify_kernel<2><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
-                        case 4: match_colverify_kernel<4><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
-                        default: match_colverify_kernel<8><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, vlist, state, items, n_items, pl.row_stride, vword, colres); break;
-                    }
-                }
+                });
                 match_finalize2_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
                                                                           min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt);
             }
@@ -2059,7 +1961,7 @@ int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int3
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (npairs < 0 || !n_batches || cap < 0 || (cap > 0 && !starts)) return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_debug_batches");
     if (ctx->kind_common == 1) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the fp32 path plans its batches on its own");
-    const bool full_cols = ctx->match_full_columns || with_stats != 0;
+    const bool full_cols = with_stats != 0;
     MatchPlan pl = make_plan(ctx, std::max(npairs, 1), full_cols);
     int b = 0;
     for (int first = 0, nb = 0; first < npairs; first += nb, ++b) {

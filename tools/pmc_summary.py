@@ -2,7 +2,7 @@
 """Summarise rocprofv3 --pmc counter_collection.csv files: mean per dispatch of a kernel."""
 import csv, sys, glob, collections
 pat = sys.argv[1]
-kern = sys.argv[2] if len(sys.argv) > 2 else "match_tile_kernel"
+kern = sys.argv[2] if len(sys.argv) > 2 else "match_sweep_kernel"
 for fn in sorted(glob.glob(pat, recursive=True)):
     acc = collections.defaultdict(list)
     with open(fn) as f:
