@@ -101,7 +101,6 @@ struct eacham_ctx {
                               // totals {settled, verified} of the last matching call's candidate columns (eacham_match_debug_colprune)
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
     int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip)
-    void* last_matches = nullptr;  // per-pair match lists of the last run (directed API reads them back)
     void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
     int table16_cap = 0;
     long long dot16_fallback_pairs = 0;  // pairs of the last screened call that ran the fp32 tile kernel (eacham_match_debug_dot_screen)

@@ -321,40 +321,21 @@ extern "C" int eacham_graph_best_pair(eacham_ctx* ctx, int n_frames, const int32
             if (q[k] >= n1 || t[k] >= n2) return ctx->fail(EACHAM_ERR_INVALID, "graph_best_pair: match %lld of pair %d is out of range", k, p);
     }
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + bytes); return o; };
-    const size_t o_pairs = take(sizeof(int) * 2 * (size_t)npairs), o_cnt = take(sizeof(int) * (size_t)npairs);
-    const size_t o_off = take(sizeof(long long) * (size_t)npairs), o_q = take(sizeof(unsigned) * (size_t)n_edges);
-    const size_t o_t = take(sizeof(unsigned) * (size_t)n_edges), o_valid = take((size_t)n_frames), o_excl = take((size_t)n_frames);
-    const size_t o_kpo = take(sizeof(long long) * ((size_t)n_frames + 1)), o_h3 = take((size_t)n_kp);
-    const size_t o_ec = take(sizeof(unsigned) * 2 * (size_t)npairs), o_best = take(sizeof(unsigned) * 4);
-    if (int rc = ensure_io(ctx, off)) return rc;
-    char* base = (char*)ctx->io;
     hipStream_t st = ctx->stream;
-    auto up = [&](size_t o, const void* src, size_t bytes) {
-        return bytes ? hipMemcpyAsync(base + o, src, bytes, hipMemcpyHostToDevice, st) : hipSuccess;
-    };
-    EACHAM_HIP_TRY(ctx, up(o_pairs, pairs, sizeof(int) * 2 * (size_t)npairs));
-    EACHAM_HIP_TRY(ctx, up(o_cnt, counts, sizeof(int) * (size_t)npairs));
-    EACHAM_HIP_TRY(ctx, up(o_off, offsets, sizeof(long long) * (size_t)npairs));
-    EACHAM_HIP_TRY(ctx, up(o_q, q, sizeof(unsigned) * (size_t)n_edges));
-    EACHAM_HIP_TRY(ctx, up(o_t, t, sizeof(unsigned) * (size_t)n_edges));
-    EACHAM_HIP_TRY(ctx, up(o_valid, valid, (size_t)n_frames));
-    if (excluded) EACHAM_HIP_TRY(ctx, up(o_excl, excluded, (size_t)n_frames));
-    EACHAM_HIP_TRY(ctx, up(o_kpo, kp_offsets, sizeof(long long) * ((size_t)n_frames + 1)));
-    EACHAM_HIP_TRY(ctx, up(o_h3, kp_has3d, (size_t)n_kp));
-    graph_edge_counts_kernel<<<npairs, GT, 0, st>>>((const int2*)(base + o_pairs), (const int*)(base + o_cnt),
-                                                     (const long long*)(base + o_off), (const unsigned*)(base + o_q),
-                                                     (const unsigned*)(base + o_t), (const long long*)(base + o_kpo),
-                                                     (const unsigned char*)(base + o_h3), (unsigned*)(base + o_ec));
-    graph_best_pair_kernel<<<1, 1024, 0, st>>>((const int2*)(base + o_pairs), npairs, (const int*)(base + o_cnt),
-                                               (const unsigned*)(base + o_ec), (const unsigned char*)(base + o_valid),
-                                               excluded ? (const unsigned char*)(base + o_excl) : nullptr,
-                                               (unsigned*)(base + o_best));
+    IoStage io(ctx, st);
+    const auto h_pairs = io.in<int2>(pairs, (size_t)npairs);
+    const auto h_cnt = io.in<int>(counts, (size_t)npairs);
+    const auto h_off = io.in<long long>(offsets, (size_t)npairs);
+    const auto h_q = io.in<unsigned>(q, (size_t)n_edges), h_t = io.in<unsigned>(t, (size_t)n_edges);
+    const auto h_valid = io.in<unsigned char>(valid, (size_t)n_frames), h_excl = io.in<unsigned char>(excluded, (size_t)n_frames);
+    const auto h_kpo = io.in<long long>(kp_offsets, (size_t)n_frames + 1);
+    const auto h_h3 = io.in<unsigned char>(kp_has3d, (size_t)n_kp);
+    const auto h_ec = io.out<unsigned>(edge_counts, 2 * (size_t)npairs);   // always computed; a null edge_counts is not brought back
+    const auto h_best = io.out<unsigned>(best, 3);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    graph_edge_counts_kernel<<<npairs, GT, 0, st>>>(d(h_pairs), d(h_cnt), d(h_off), d(h_q), d(h_t), d(h_kpo), d(h_h3), d(h_ec));
+    graph_best_pair_kernel<<<1, 1024, 0, st>>>(d(h_pairs), npairs, d(h_cnt), d(h_ec), d(h_valid), excluded ? d(h_excl) : nullptr, d(h_best));
     EACHAM_HIP_TRY(ctx, hipGetLastError());
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(best, base + o_best, sizeof(unsigned) * 3, hipMemcpyDeviceToHost, st));
-    if (edge_counts)
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(edge_counts, base + o_ec, sizeof(unsigned) * 2 * (size_t)npairs, hipMemcpyDeviceToHost, st));
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
-    return EACHAM_OK;
+    return io.finish();
 }

@@ -1662,7 +1662,7 @@ static int next_batch(const MatchPlan& pl, int first, int npairs) {
     return nb;
 }
 
-// Core driver. mode 0 = mutual (CSR out), mode 1 = directed single pair (fixed-stride out in ws).
+// Core driver, CSR over the pairs out. mode 0 = mutual + thresholds, mode 1 = directed lists.
 static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir,
                      int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
                      uint2* edges_dev, long long edge_cap, long long* total_dev, int4* stats_dev) {
@@ -1684,7 +1684,6 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     MatchPlan pl = make_plan(ctx, npairs, full_cols);
     rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
-    ctx->last_matches = (char*)ctx->ws + pl.off_matches;
     const size_t fin_smem = (size_t)(full_cols ? 2 : 1) * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024) {
         if (full_cols) EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
@@ -1728,8 +1727,7 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
-        const bool csr = offsets_dev != nullptr;  // mode 1 without offsets: the single directed pair of eacham_match_pair
-        int* cnt = csr ? counts_dev + first : counts_dev;
+        int* cnt = counts_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st2);
             if (full_cols) {
@@ -1772,11 +1770,9 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                 match_finalize2_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
                                                                           min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt);
             }
-            if (csr) {
-                scan_counts_kernel<<<1, 1024, 0, st2>>>(cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-                compact_edges_kernel<<<nb, 256, 0, st2>>>((const uint2*)(ws + pl.off_matches), cnt, offsets_dev + first,
-                                                          pl.row_stride, edges_dev, edge_cap);
-            }
+            scan_counts_kernel<<<1, 1024, 0, st2>>>(cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
+            compact_edges_kernel<<<nb, 256, 0, st2>>>((const uint2*)(ws + pl.off_matches), cnt, offsets_dev + first,
+                                                      pl.row_stride, edges_dev, edge_cap);
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_fin[slot], st2));
         EACHAM_HIP_TRY(ctx, hipGetLastError());
@@ -1799,6 +1795,99 @@ static int check_pairs_host(eacham_ctx* ctx, const int32_t* pairs, int npairs) {
         int f = pairs[i];
         if (f < 0 || (size_t)f >= ctx->frames.size() || ctx->frames[f].n < 0)
             return ctx->fail(EACHAM_ERR_INVALID, "pair %d references frame %d which is not resident", i / 2, f);
+    }
+    return EACHAM_OK;
+}
+
+// Every host-pointer matching call runs its body through this: null context, the context's lock, its device, and nothing thrown
+// (std::vector on an absurd capacity) leaves extern "C".
+template <class Body>
+static int match_entry(eacham_ctx* ctx, Body body) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    try {
+        return body();
+    } catch (const std::exception& e) {
+        return ctx->fail(EACHAM_ERR_INVALID, "matcher: %s", e.what());
+    } catch (...) {
+        return ctx->fail(EACHAM_ERR_INVALID, "matcher: unknown exception");
+    }
+}
+
+// What a host-pointer call runs: the L2 ratio test on the resident frames (int8 or float), the dot-product form on float
+// frames (matcher_dot.hip), or that form behind the fp16 screen (matcher_dot16.hip; mutual only).
+enum MatchForm { MATCH_L2, MATCH_DOT, MATCH_DOT_SCREENED };
+
+// Host pointers in, CSR over the pairs out: mode 0 = mutual + thresholds, mode 1 = directed lists. `thresh` is the ratio of the
+// L2 form or the minimum score of the dot forms, which also fill out_score.
+static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pairs, int npairs, double thresh, int min_dir,
+                            int min_mutual, int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t,
+                            float* out_score, int64_t cap, int64_t* out_total, int32_t* stats) {
+    const bool dot = form != MATCH_L2;
+    if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
+        return ctx->fail(EACHAM_ERR_INVALID, dot ? "bad arguments to the dot-product matcher" : "bad arguments to match_all_pairs");
+    int rc = check_pairs_host(ctx, pairs, npairs);
+    if (rc) return rc;
+    if (!dot) {
+        rc = check_integer_flag(ctx);
+        if (rc) return rc;
+    } else if (npairs > 0 && ctx->kind_common != 1) {
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are int8");
+    }
+    *out_total = 0;
+    if (npairs == 0) {
+        if (offsets) offsets[0] = 0;
+        return EACHAM_OK;
+    }
+    if (dot) {
+        rc = sync_frame_table(ctx);
+        if (rc) return rc;
+    }
+    std::vector<int32_t> pairs_fb;   // the screened form's second pair list
+    int n_fallback = 0;
+    if (form == MATCH_DOT_SCREENED) {
+        pairs_fb.resize((size_t)npairs * 2);
+        rc = prepare_match_dot_screened(ctx, pairs, npairs, pairs_fb.data(), &n_fallback);
+        if (rc) return rc;
+    }
+    long long total = 0;
+    IoStage io(ctx, ctx->stream);
+    const auto h_pairs = io.in<int2>(pairs, (size_t)npairs), h_fb = io.in<int2>(pairs_fb.data(), pairs_fb.size() / 2);
+    const auto h_counts = io.out<int>(counts, (size_t)npairs);
+    const auto h_offsets = io.out<long long>(offsets, (size_t)npairs + 1), h_total = io.out<long long>(&total, 1);
+    IoArray<int4> h_stats{0};
+    if (stats) h_stats = io.out<int4>(stats, (size_t)npairs);
+    // device-only: as results they would pin cap elements and come back whole, where only `total` of them are wanted
+    const auto h_edges = io.scratch<uint2>((size_t)cap);
+    const auto h_scores = io.scratch<float>(dot ? (size_t)cap : 0);
+    IoDev d;
+    rc = io.upload(d);
+    if (rc) return rc;
+    int4* stats_dev = stats ? d(h_stats) : nullptr;   // null selects the lean form in run_match
+    if (form == MATCH_DOT_SCREENED)
+        rc = run_match_dot_screened(ctx, d(h_pairs), d(h_fb), pairs_fb.data(), npairs, n_fallback, (float)thresh, min_dir, min_mutual,
+                                    d(h_counts), d(h_offsets), d(h_edges), d(h_scores), cap, d(h_total), stats_dev);
+    else if (form == MATCH_DOT)
+        rc = run_match_dot(ctx, d(h_pairs), npairs, (float)thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
+                           d(h_scores), cap, d(h_total), stats_dev);
+    else
+        rc = run_match(ctx, d(h_pairs), npairs, thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges), cap, d(h_total),
+                       stats_dev);
+    if (rc) return rc;
+    rc = io.finish();
+    if (rc) return rc;
+    *out_total = total;
+    if (total > cap) return ctx->fail(EACHAM_ERR_CAPACITY, "%lld matches but capacity %lld", total, (long long)cap);
+    if (total > 0) {
+        // The one direct copy beside IoStage: how many edges there are is known only now, and exactly that many come back.
+        std::vector<uint2> tmp((size_t)total);
+        EACHAM_HIP_TRY(ctx, hipMemcpy(tmp.data(), d(h_edges), sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost));
+        for (long long k = 0; k < total; ++k) {
+            out_q[k] = tmp[k].x;
+            out_t[k] = tmp[k].y;
+        }
+        if (out_score) EACHAM_HIP_TRY(ctx, hipMemcpy(out_score, d(h_scores), sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
     }
     return EACHAM_OK;
 }
@@ -1843,40 +1932,6 @@ int eacham_frame_rows(eacham_ctx* ctx, int frame_id) {
     return ctx->frames[frame_id].n;
 }
 
-int eacham_match_pair(eacham_ctx* ctx, int f1, int f2, double ratio, uint32_t* out_q, uint32_t* out_t,
-                      int cap, int* out_count) {
-    if (!ctx) return EACHAM_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    if (!out_count || cap < 0 || (cap > 0 && (!out_q || !out_t))) return ctx->fail(EACHAM_ERR_INVALID, "null output");
-    int32_t pr[2] = {f1, f2};
-    int rc = check_pairs_host(ctx, pr, 1);
-    if (rc) return rc;
-    rc = check_integer_flag(ctx);
-    if (rc) return rc;
-    rc = ensure_io(ctx, 256);
-    if (rc) return rc;
-    int2* pairs_dev = (int2*)ctx->io;
-    int* count_dev = (int*)((char*)ctx->io + 64);
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(pairs_dev, pr, sizeof(pr), hipMemcpyHostToDevice, ctx->stream));
-    rc = run_match(ctx, pairs_dev, 1, ratio, 0, 0, /*mode=*/1, count_dev, nullptr, nullptr, 0, nullptr, nullptr);
-    if (rc) return rc;
-    int count = 0;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&count, count_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *out_count = count;
-    if (count > cap) return ctx->fail(EACHAM_ERR_CAPACITY, "%d matches but capacity %d", count, cap);
-    if (count > 0) {
-        std::vector<uint2> tmp(count);
-        EACHAM_HIP_TRY(ctx, hipMemcpy(tmp.data(), ctx->last_matches, sizeof(uint2) * count, hipMemcpyDeviceToHost));
-        for (int k = 0; k < count; ++k) {
-            out_q[k] = tmp[k].x;
-            out_t[k] = tmp[k].y;
-        }
-    }
-    return EACHAM_OK;
-}
-
 int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int npairs, double ratio,
                                int min_dir, int min_mutual, int32_t* counts_dev, int64_t* offsets_dev,
                                uint32_t* edges_dev, int64_t edge_cap, int64_t* total_dev,
@@ -1892,68 +1947,26 @@ int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int np
                      (int4*)stats_dev);
 }
 
-// host pointers in, CSR over the pairs out: mode 0 = mutual + thresholds, mode 1 = directed lists
-static int match_pairs_host(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int min_dir,
-                            int min_mutual, int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q,
-                            uint32_t* out_t, int64_t cap, int64_t* out_total, int32_t* stats) {
-    if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
-        return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_all_pairs");
-    int rc = check_pairs_host(ctx, pairs, npairs);
-    if (rc) return rc;
-    rc = check_integer_flag(ctx);
-    if (rc) return rc;
-    *out_total = 0;
-    if (npairs == 0) {
-        if (offsets) offsets[0] = 0;
-        return EACHAM_OK;
-    }
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o_pairs = 0;
-    size_t o_counts = align(o_pairs + (size_t)npairs * 2 * sizeof(int32_t));
-    size_t o_offsets = align(o_counts + (size_t)npairs * sizeof(int32_t));
-    size_t o_total = align(o_offsets + (size_t)(npairs + 1) * sizeof(int64_t));
-    size_t o_stats = align(o_total + sizeof(int64_t));
-    size_t o_edges = align(o_stats + (size_t)npairs * 4 * sizeof(int32_t));
-    size_t bytes = o_edges + (size_t)cap * sizeof(uint2);
-    rc = ensure_io(ctx, bytes);
-    if (rc) return rc;
-    char* io = (char*)ctx->io;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs, pairs, (size_t)npairs * 2 * sizeof(int32_t),
-                                       hipMemcpyHostToDevice, ctx->stream));
-    rc = run_match(ctx, (const int2*)(io + o_pairs), npairs, ratio, min_dir, min_mutual, mode,
-                   (int*)(io + o_counts), (long long*)(io + o_offsets), (uint2*)(io + o_edges), cap,
-                   (long long*)(io + o_total), stats ? (int4*)(io + o_stats) : nullptr);
-    if (rc) return rc;
-    long long total = 0;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&total, io + o_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(counts, io + o_counts, (size_t)npairs * sizeof(int32_t),
-                                       hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(offsets, io + o_offsets, (size_t)(npairs + 1) * sizeof(int64_t),
-                                       hipMemcpyDeviceToHost, ctx->stream));
-    if (stats)
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(stats, io + o_stats, (size_t)npairs * 4 * sizeof(int32_t),
-                                           hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *out_total = total;
-    if (total > cap) return ctx->fail(EACHAM_ERR_CAPACITY, "%lld matches but capacity %lld", total, (long long)cap);
-    if (total > 0) {
-        std::vector<uint2> tmp((size_t)total);
-        EACHAM_HIP_TRY(ctx, hipMemcpy(tmp.data(), io + o_edges, sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost));
-        for (long long k = 0; k < total; ++k) {
-            out_q[k] = tmp[k].x;
-            out_t[k] = tmp[k].y;
-        }
-    }
-    return EACHAM_OK;
+int eacham_match_pair(eacham_ctx* ctx, int f1, int f2, double ratio, uint32_t* out_q, uint32_t* out_t,
+                      int cap, int* out_count) {
+    return match_entry(ctx, [&]() -> int {
+        if (!out_count || cap < 0 || (cap > 0 && (!out_q || !out_t))) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+        const int32_t pr[2] = {f1, f2};
+        int32_t count = 0;
+        int64_t offsets[2] = {0, 0}, total = 0;
+        const int rc = match_pairs_host(ctx, MATCH_L2, pr, 1, ratio, 0, 0, 1, &count, offsets, out_q, out_t, nullptr, cap, &total, nullptr);
+        if (rc == EACHAM_OK || rc == EACHAM_ERR_CAPACITY) *out_count = (int)total;
+        return rc;
+    });
 }
 
 int eacham_match_all_pairs(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int min_dir,
                            int min_mutual, int32_t* counts, int64_t* offsets, uint32_t* out_q,
                            uint32_t* out_t, int64_t cap, int64_t* out_total, int32_t* stats) {
-    if (!ctx) return EACHAM_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return match_pairs_host(ctx, pairs, npairs, ratio, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, cap, out_total, stats);
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_L2, pairs, npairs, ratio, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, nullptr, cap,
+                                out_total, stats);
+    });
 }
 
 int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int32_t* starts, int cap, int* n_batches, int* n_slots) {
@@ -1988,103 +2001,20 @@ int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* veri
 
 int eacham_match_pairs_directed(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int32_t* counts,
                                 int64_t* offsets, uint32_t* out_q, uint32_t* out_t, int64_t cap, int64_t* out_total) {
-    if (!ctx) return EACHAM_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    return match_pairs_host(ctx, pairs, npairs, ratio, 0, 0, 1, counts, offsets, out_q, out_t, cap, out_total, nullptr);
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_L2, pairs, npairs, ratio, 0, 0, 1, counts, offsets, out_q, out_t, nullptr, cap, out_total, nullptr);
+    });
 }
 
-// ---- dot-product form (matcher_dot.hip): host pointers in, CSR over the pairs + scores out ----
-static int match_pairs_dot_host(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
-                                int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score,
-                                int64_t cap, int64_t* out_total, int32_t* stats, bool screened = false) {
-    if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
-        return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to the dot-product matcher");
-    int rc = check_pairs_host(ctx, pairs, npairs);
-    if (rc) return rc;
-    if (npairs > 0 && ctx->kind_common != 1)
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are int8");
-    *out_total = 0;
-    if (npairs == 0) {
-        if (offsets) offsets[0] = 0;
-        return EACHAM_OK;
-    }
-    rc = sync_frame_table(ctx);
-    if (rc) return rc;
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t o_pairs = 0;
-    const size_t o_counts = align(o_pairs + (size_t)npairs * 2 * sizeof(int32_t));
-    const size_t o_offsets = align(o_counts + (size_t)npairs * sizeof(int32_t));
-    const size_t o_total = align(o_offsets + (size_t)(npairs + 1) * sizeof(int64_t));
-    const size_t o_stats = align(o_total + sizeof(int64_t));
-    const size_t o_edges = align(o_stats + (size_t)npairs * 4 * sizeof(int32_t));
-    const size_t o_scores = align(o_edges + (size_t)cap * sizeof(uint2));
-    const size_t o_pairs_fb = align(o_scores + (size_t)cap * sizeof(float));  // the screened form's second pair list
-    rc = ensure_io(ctx, screened ? o_pairs_fb + (size_t)npairs * 2 * sizeof(int32_t) : o_pairs_fb);
-    if (rc) return rc;
-    char* io = (char*)ctx->io;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs, pairs, (size_t)npairs * 2 * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-    if (screened) {
-        std::vector<int32_t> pairs_fb((size_t)npairs * 2);
-        int n_fallback = 0;
-        rc = prepare_match_dot_screened(ctx, pairs, npairs, pairs_fb.data(), &n_fallback);
-        if (rc) return rc;
-        // (pageable source: the copy is staged before hipMemcpyAsync returns)
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(io + o_pairs_fb, pairs_fb.data(), pairs_fb.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        rc = run_match_dot_screened(ctx, (const int2*)(io + o_pairs), (const int2*)(io + o_pairs_fb), pairs_fb.data(), npairs, n_fallback,
-                                    min_score, min_dir, min_mutual, (int*)(io + o_counts), (long long*)(io + o_offsets),
-                                    (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
-                                    stats ? (int4*)(io + o_stats) : nullptr);
-    } else {
-        rc = run_match_dot(ctx, (const int2*)(io + o_pairs), npairs, min_score, min_dir, min_mutual, mode, (int*)(io + o_counts),
-                           (long long*)(io + o_offsets), (uint2*)(io + o_edges), (float*)(io + o_scores), cap, (long long*)(io + o_total),
-                           stats ? (int4*)(io + o_stats) : nullptr);
-    }
-    if (rc) return rc;
-    long long total = 0;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&total, io + o_total, sizeof(total), hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(counts, io + o_counts, (size_t)npairs * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(offsets, io + o_offsets, (size_t)(npairs + 1) * sizeof(int64_t), hipMemcpyDeviceToHost, ctx->stream));
-    if (stats)
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(stats, io + o_stats, (size_t)npairs * 4 * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
-    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    *out_total = total;
-    if (total > cap) return ctx->fail(EACHAM_ERR_CAPACITY, "%lld matches but capacity %lld", total, (long long)cap);
-    if (total > 0) {
-        std::vector<uint2> tmp((size_t)total);
-        EACHAM_HIP_TRY(ctx, hipMemcpy(tmp.data(), io + o_edges, sizeof(uint2) * (size_t)total, hipMemcpyDeviceToHost));
-        for (long long k = 0; k < total; ++k) {
-            out_q[k] = tmp[k].x;
-            out_t[k] = tmp[k].y;
-        }
-        if (out_score) EACHAM_HIP_TRY(ctx, hipMemcpy(out_score, io + o_scores, sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
-    }
-    return EACHAM_OK;
-}
-
-// Nothing may leave extern "C" (std::vector throws on an absurd capacity): the three entry points run their body through this.
-extern "C++" template <class Body>
-static int dot_entry(eacham_ctx* ctx, Body body) {
-    if (!ctx) return EACHAM_ERR_INVALID;
-    std::lock_guard<std::mutex> lock(ctx->mu);
-    (void)hipSetDevice(ctx->device);
-    try {
-        return body();
-    } catch (const std::exception& e) {
-        return ctx->fail(EACHAM_ERR_INVALID, "dot-product matcher: %s", e.what());
-    } catch (...) {
-        return ctx->fail(EACHAM_ERR_INVALID, "dot-product matcher: unknown exception");
-    }
-}
-
+// ---- dot-product form (matcher_dot.hip): CSR over the pairs + scores out ----
 int eacham_match_pair_dot(eacham_ctx* ctx, int f1, int f2, float min_score, uint32_t* out_q, uint32_t* out_t, float* out_score,
                           int cap, int* out_count) {
-    return dot_entry(ctx, [&]() -> int {
+    return match_entry(ctx, [&]() -> int {
         if (!out_count) return ctx->fail(EACHAM_ERR_INVALID, "null output");
         const int32_t pr[2] = {f1, f2};
         int32_t count = 0;
         int64_t offsets[2] = {0, 0}, total = 0;
-        const int rc = match_pairs_dot_host(ctx, pr, 1, min_score, 0, 0, 1, &count, offsets, out_q, out_t, out_score, cap, &total, nullptr);
+        const int rc = match_pairs_host(ctx, MATCH_DOT, pr, 1, min_score, 0, 0, 1, &count, offsets, out_q, out_t, out_score, cap, &total, nullptr);
         if (rc == EACHAM_OK || rc == EACHAM_ERR_CAPACITY) *out_count = (int)total;
         return rc;
     });
@@ -2093,26 +2023,26 @@ int eacham_match_pair_dot(eacham_ctx* ctx, int f1, int f2, float min_score, uint
 int eacham_match_pairs_directed_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int32_t* counts,
                                     int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap,
                                     int64_t* out_total) {
-    return dot_entry(ctx, [&]() -> int {
-        return match_pairs_dot_host(ctx, pairs, npairs, min_score, 0, 0, 1, counts, offsets, out_q, out_t, out_score, cap, out_total, nullptr);
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_DOT, pairs, npairs, min_score, 0, 0, 1, counts, offsets, out_q, out_t, out_score, cap, out_total, nullptr);
     });
 }
 
 int eacham_match_all_pairs_dot(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
                                int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score, int64_t cap,
                                int64_t* out_total, int32_t* stats) {
-    return dot_entry(ctx, [&]() -> int {
-        return match_pairs_dot_host(ctx, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
-                                    out_total, stats);
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_DOT, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
+                                out_total, stats);
     });
 }
 
 int eacham_match_all_pairs_dot_screened(eacham_ctx* ctx, const int32_t* pairs, int npairs, float min_score, int min_dir, int min_mutual,
                                         int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, float* out_score,
                                         int64_t cap, int64_t* out_total, int32_t* stats) {
-    return dot_entry(ctx, [&]() -> int {
-        return match_pairs_dot_host(ctx, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score, cap,
-                                    out_total, stats, true);
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_DOT_SCREENED, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score,
+                                cap, out_total, stats);
     });
 }
 

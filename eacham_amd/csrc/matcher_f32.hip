@@ -338,7 +338,6 @@ int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double rat
     int rc = ensure_workspace(ctx, total);
     if (rc) return rc;
     char* ws = (char*)ctx->ws;
-    ctx->last_matches = ws + off_matches;
     const size_t fin_smem = (size_t)2 * row_stride * sizeof(int);
     if (fin_smem > 48 * 1024)
         EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
@@ -355,17 +354,14 @@ int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double rat
                 default: match_tile_f32_kernel<128><<<nb * wgs_per_pair, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, wgs_per_pair, rr, cp, wb_stride, row_stride); break;
             }
         }
-        const bool csr = offsets_dev != nullptr;  // mode 1 without offsets: the single directed pair of eacham_match_pair
-        int* cnt = csr ? counts_dev + first : counts_dev;
+        int* cnt = counts_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
             match_finalize_f32_kernel<<<nb, FIN_T, fin_smem, ctx->stream>>>(
                 ctx->frame_table_dev, pb, (const int4*)(ws + off_rowres), (const int4*)(ws + off_colpart), wb_stride, row_stride,
                 ratio, min_dir, min_mutual, mode, (uint2*)(ws + off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
-            if (csr) {
-                launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-                launch_compact_edges(ctx, nb, (const uint2*)(ws + off_matches), cnt, offsets_dev + first, row_stride, edges_dev, edge_cap);
-            }
+            launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
+            launch_compact_edges(ctx, nb, (const uint2*)(ws + off_matches), cnt, offsets_dev + first, row_stride, edges_dev, edge_cap);
         }
         EACHAM_HIP_TRY(ctx, hipGetLastError());
     }

@@ -25,6 +25,23 @@ def test_matches_oracle(ctx, n_frames, seed):
         assert got == want and np.array_equal(ec, wec)
 
 
+def test_matches_oracle_without_edge_counts(ctx):
+    """edge_counts = NULL (with and without an excluded mask) on the smallest graph: the same best pair, nothing else written."""
+    pairs, counts, offsets, q, t, valid, has3d, excluded = scenario(5, 0)
+    pairs, counts, offsets = np.ascontiguousarray(pairs, np.int32), np.ascontiguousarray(counts, np.int32), np.ascontiguousarray(offsets, np.int64)
+    q, t = np.ascontiguousarray(q, np.uint32), np.ascontiguousarray(t, np.uint32)
+    valid8 = np.ascontiguousarray(valid, np.uint8)
+    kp_offsets, flat = G.pack_has3d(has3d)
+    for ex in (None, excluded):
+        ex8 = None if ex is None else np.ascontiguousarray(ex, np.uint8)
+        best = np.full(4, 77, np.uint32)
+        rc = ctx._L.eacham_graph_best_pair(ctx.handle, 5, pairs.ctypes.data, len(pairs), counts.ctypes.data, offsets.ctypes.data, q.ctypes.data,
+                                           t.ctypes.data, valid8.ctypes.data, None if ex8 is None else ex8.ctypes.data, kp_offsets.ctypes.data,
+                                           flat.ctypes.data, None, best.ctypes.data)
+        want, _ = O.graph_best_pair(5, pairs, counts, offsets, q, t, valid, has3d, ex)
+        assert rc == capi.OK and tuple(int(b) for b in best[:3]) == want and best[3] == 77
+
+
 @pytest.mark.parametrize("n_frames,seed", [(9, 1), (40, 3), (64, 4)])
 def test_resident_graph_follows_the_state_frame_by_frame(ctx, n_frames, seed):
     """eacham_graph_create / _set_frame / _query: the graph uploaded once, the loop's state changes applied frame by frame —

@@ -130,6 +130,35 @@ def test_job_cut_into_more_than_one_launch():
         assert np.array_equal(dq[sl], wq) and np.array_equal(dt[sl], wt) and np.array_equal(_bits(ds[sl]), _bits(ws)), p
 
 
+def _repetition(short, idx):
+    """The CSR (counts, offsets, q, t, scores, stats) of the pairs of `short` in the order `idx`."""
+    per = lambda k: [short[k][short[1][p]:short[1][p + 1]] for p in range(len(short[0]))]     # noqa: E731
+    counts = short[0][idx]
+    return (counts, np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]).astype(np.int64),
+            *(np.concatenate([per(k)[i] for i in idx]) for k in (2, 3, 4)), None if short[5] is None else short[5][idx])
+
+
+def test_packed_and_direct_results_in_one_call():
+    """IoStage::PACK_MAX (eacham_amd/csrc/context.hpp) is 256 KiB = 262 144 B. At 33 000 pairs the counts (132 000 B) travel through
+    the pinned mirror, the offsets (264 008 B) and the stats (528 000 B) lie above it and take their own direct copy: the 12 ordered
+    pairs of four 40-row frames (two 32-row tiles, the second mostly padding), repeated cyclically, must give the 12-pair call's
+    results (all of them packed) repeated, byte for byte, with the offsets their running sum."""
+    descs = DC.float_frames(32, [40] * 4, 25, 311)
+    ordered = DC.ordered_pairs(4)
+    idx = np.arange(33000) % 12
+    want = R.match_all_pairs(descs, ordered, DC.MIN_SCORE, 0, -1)
+    assert (want[0] > 0).all() and want[0].min() < 40
+    with HipContext(0) as ctx:
+        _upload(ctx, descs)
+        for stats in (True, False):
+            short = ctx.match_all_pairs_dot(ordered, DC.MIN_SCORE, 0, -1, stats=stats)
+            _same(short[:5], want[:5], f"12 pairs, stats={stats}")
+            assert np.array_equal(short[5], want[5]) if stats else short[5] is None
+            long = ctx.match_all_pairs_dot(ordered[idx], DC.MIN_SCORE, 0, -1, stats=stats)
+            for name, g, w in zip(["counts", "offsets", "q", "t", "scores", "stats"], long, _repetition(short, idx)):
+                assert (g is None and w is None) or np.ascontiguousarray(g).tobytes() == np.ascontiguousarray(w).tobytes(), (name, stats)
+
+
 def test_error_paths():
     descs = DC.scene("d64")
     with HipContext(0) as ctx:
@@ -169,7 +198,7 @@ def test_error_paths():
 
 
 def test_l2_float_path_is_unchanged_by_a_dot_call():
-    """Shared workspace and last_matches state: an L2 call on the same resident float frames returns what it returned before."""
+    """Shared workspace state: an L2 call on the same resident float frames returns what it returned before."""
     descs = DC.scene("d128")
     pairs = synth.all_pairs(len(descs))
     with HipContext(0) as ctx:

@@ -169,6 +169,30 @@ def test_many_tiny_pairs_in_one_launch():
         assert np.array_equal(st[p], wst), p
 
 
+def test_packed_and_direct_results_in_one_call():
+    """IoStage::PACK_MAX (eacham_amd/csrc/context.hpp) is 256 KiB = 262 144 B. At 33 000 pairs the counts (132 000 B) travel through
+    the pinned mirror; the two pair lists and the offsets (264 000 B, 264 008 B) and the stats (528 000 B) lie above it and take their
+    own direct copy. The 12 ordered pairs of four 40-row frames (two 32-row tiles, the second mostly padding), repeated cyclically,
+    must give the exact call's bytes and the reference's 12-pair results repeated, with the offsets their running sum."""
+    descs = DC.float_frames(32, [40] * 4, 25, 311)
+    ordered = DC.ordered_pairs(4)
+    idx = np.arange(33000) % 12
+    want = R.match_all_pairs(descs, ordered, DC.MIN_SCORE, 0, -1)
+    assert (want[0] > 0).all() and want[0].min() < 40
+    per = lambda k: [want[k][want[1][p]:want[1][p + 1]] for p in range(12)]     # noqa: E731
+    rep = (want[0][idx], np.concatenate([[0], np.cumsum(want[0][idx], dtype=np.int64)]).astype(np.int64),
+           *(np.concatenate([per(k)[i] for i in idx]) for k in (2, 3, 4)), want[5][idx])
+    with HipContext(0) as ctx:
+        _upload(ctx, descs)
+        _same_bytes(ctx.match_all_pairs_dot(ordered, DC.MIN_SCORE, 0, -1, screened=True), want, "12 pairs, screened")
+        got = ctx.match_all_pairs_dot(ordered[idx], DC.MIN_SCORE, 0, -1, screened=True)
+        _same_bytes(got, rep, "33 000 pairs, screened, vs the repetition")
+        _same_bytes(got, ctx.match_all_pairs_dot(ordered[idx], DC.MIN_SCORE, 0, -1), "33 000 pairs, screened, vs the exact call")
+        lean = ctx.match_all_pairs_dot(ordered[idx], DC.MIN_SCORE, 0, -1, stats=False, screened=True)
+        assert lean[5] is None
+        _same_bytes(lean[:5], rep[:5], "33 000 pairs, screened, without stats")
+
+
 def test_repeat_and_order_independence():
     descs, pairs = _scenes()["a_d128"]
     with HipContext(0) as ctx:

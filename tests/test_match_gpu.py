@@ -527,3 +527,118 @@ def test_documented_limits_are_errors_not_wrong_answers(hip_ctx):
         hip_ctx.upload_descriptors_f32(2, np.zeros((16385, 32), np.float32))
     assert e.value.code == capi.ERR_UNSUPPORTED
     hip_ctx.clear_descriptors()
+
+
+# ---- the staging of the host-pointer calls (IoStage, eacham_amd/csrc/context.hpp) --------------------------------
+# IoStage::PACK_MAX is 256 KiB = 262 144 B. At 33 000 pairs the counts (4 B a pair: 132 000 B) travel through the pinned mirror,
+# while the offsets (8 B a pair + 8: 264 008 B) and the stats (16 B a pair: 528 000 B) lie above it and take their own direct copy.
+STAGING_PAIRS = 33000
+ORDERED_12 = np.array([(i, j) for i in range(4) for j in range(4) if i != j], np.int32)
+
+
+def _staging_frames():
+    """Four frames of 40 rows x 32-D, integer-valued (two 32-row tiles, the second mostly padding): frame f holds noisy copies of the
+    first 24 - 3 f of the same rows and unrelated ones, in an order of its own, so that the pairs' counts differ."""
+    base = synth.random_u8_descriptors(24, 32, 77, 0)
+    out = []
+    for f in range(4):
+        m = 24 - 3 * f
+        rows = np.concatenate([np.clip(base[:m] + np.rint(3 * synth.rng_normal(77, 10 + f, (m, 32))), 0, 255),
+                               synth.random_u8_descriptors(40 - m, 32, 77, 1 + f)])
+        out.append(np.ascontiguousarray(rows[synth.rng_permutation(77, f, 40)], np.float32))
+    return out
+
+
+def _directed_raw(ctx, pairs, cap, ratio=0.8):
+    """eacham_match_pairs_directed as it stands: (rc, counts, offsets, q, t, total); q and t hold the sentinel 77 where unwritten."""
+    import ctypes as C
+    pairs = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+    counts, offsets = np.zeros(len(pairs), np.int32), np.zeros(len(pairs) + 1, np.int64)
+    q, t = np.full(max(cap, 1), 77, np.uint32), np.full(max(cap, 1), 77, np.uint32)
+    total = C.c_int64(-1)
+    rc = ctx._L.eacham_match_pairs_directed(ctx.handle, pairs.ctypes.data, len(pairs), ratio, counts.ctypes.data, offsets.ctypes.data,
+                                            q.ctypes.data, t.ctypes.data, cap, C.byref(total))
+    return rc, counts, offsets, q, t, total.value
+
+
+def _assert_repetition(long, short, what):
+    """The CSR of the 12 pairs repeated cyclically to the length of `long`, byte for byte."""
+    n = len(long[0])
+    idx = np.arange(n) % len(short[0])
+    assert long[0].tobytes() == short[0][idx].tobytes(), f"{what}: counts"
+    assert long[1].tobytes() == np.concatenate([[0], np.cumsum(short[0][idx], dtype=np.int64)]).astype(np.int64).tobytes(), f"{what}: offsets"
+    for k in (2, 3):
+        per_pair = [short[k][short[1][p]:short[1][p + 1]] for p in range(len(short[0]))]
+        assert long[k].tobytes() == np.concatenate([per_pair[i] for i in idx]).tobytes(), f"{what}: edges {k}"
+    if short[4] is not None:
+        assert long[4].tobytes() == short[4][idx].tobytes(), f"{what}: stats"
+    else:
+        assert long[4] is None
+
+
+def test_packed_and_direct_results_in_one_call(hip_ctx):
+    descs = _staging_frames()
+    pairs = ORDERED_12[np.arange(STAGING_PAIRS) % 12]
+    _upload(hip_ctx, descs)
+    want = O.match_all_pairs(descs, ORDERED_12, min_dir=1, min_mutual=0)
+    assert (want[0] > 0).all() and len(set(want[0].tolist())) > 2          # every pair an edge list, of several lengths
+    short = hip_ctx.match_all_pairs(ORDERED_12, min_dir=1, min_mutual=0)
+    _assert_csr_equal(short, want)
+    _assert_repetition(hip_ctx.match_all_pairs(pairs, min_dir=1, min_mutual=0), short, "with stats")
+    lean = hip_ctx.match_all_pairs(ORDERED_12, min_dir=1, min_mutual=0, stats=False)
+    assert lean[4] is None
+    _assert_csr_equal(lean[:4], want[:4])
+    _assert_repetition(hip_ctx.match_all_pairs(pairs, min_dir=1, min_mutual=0, stats=False), lean, "lean form")
+    # the directed lists
+    rc, c, o, q, t, total = _directed_raw(hip_ctx, ORDERED_12, 12 * 40)
+    assert rc == capi.OK and total == o[-1] == c.sum()
+    for p, (a, b) in enumerate(ORDERED_12):
+        qo, to = O.match_directed(descs[a], descs[b])
+        assert np.array_equal(q[o[p]:o[p + 1]], qo) and np.array_equal(t[o[p]:o[p + 1]], to), (a, b)
+    rc, lc, lo, lq, lt, ltotal = _directed_raw(hip_ctx, pairs, STAGING_PAIRS * 40)
+    assert rc == capi.OK and ltotal == lo[-1]
+    _assert_repetition((lc, lo, lq[:ltotal], lt[:ltotal], None), (c, o, q[:total], t[:total], None), "directed")
+    hip_ctx.clear_descriptors()
+
+
+def test_capacity_on_the_int8_calls(hip_ctx):
+    """cap below the true total: EACHAM_ERR_CAPACITY, the true total, counts and offsets as an uncapped call gives them, q and t
+    untouched; and the context then serves an uncapped call."""
+    import ctypes as C
+    descs = _staging_frames()
+    _upload(hip_ctx, descs)
+    L = hip_ctx._L
+    want = hip_ctx.match_all_pairs(ORDERED_12, min_dir=1, min_mutual=0)
+    true_total = int(want[1][-1])
+    assert true_total > 3
+    for with_stats in (True, False):
+        counts, offsets = np.full(12, -7, np.int32), np.full(13, -7, np.int64)
+        q, t = np.full(3, 77, np.uint32), np.full(3, 77, np.uint32)
+        st = np.full((12, 4), -7, np.int32)
+        total = C.c_int64(-7)
+        rc = L.eacham_match_all_pairs(hip_ctx.handle, ORDERED_12.ctypes.data, 12, 0.8, 1, 0, counts.ctypes.data, offsets.ctypes.data,
+                                      q.ctypes.data, t.ctypes.data, 3, C.byref(total), st.ctypes.data if with_stats else None)
+        assert rc == capi.ERR_CAPACITY and b"capacity" in L.eacham_last_error(hip_ctx.handle)
+        assert total.value == true_total and np.array_equal(counts, want[0]) and np.array_equal(offsets, want[1])
+        assert (q == 77).all() and (t == 77).all()
+        assert np.array_equal(st, want[4]) if with_stats else (st == -7).all()
+        _assert_csr_equal(hip_ctx.match_all_pairs(ORDERED_12, min_dir=1, min_mutual=0), want)
+    # the directed lists
+    rc, c_ok, o_ok, q_ok, t_ok, total_ok = _directed_raw(hip_ctx, ORDERED_12, 12 * 40)
+    assert rc == capi.OK and total_ok > 3
+    rc, c, o, q, t, total = _directed_raw(hip_ctx, ORDERED_12, 3)
+    assert rc == capi.ERR_CAPACITY and total == total_ok and np.array_equal(c, c_ok) and np.array_equal(o, o_ok)
+    assert (q == 77).all() and (t == 77).all()
+    rc, c, o, q, t, total = _directed_raw(hip_ctx, ORDERED_12, 12 * 40)
+    assert rc == capi.OK and total == total_ok and np.array_equal(c, c_ok) and np.array_equal(o, o_ok)
+    assert np.array_equal(q[:total], q_ok[:total]) and np.array_equal(t[:total], t_ok[:total])
+    # one pair
+    qo, to = O.match_directed(descs[0], descs[1])
+    assert len(qo) > 3
+    q, t, cnt = np.full(3, 77, np.uint32), np.full(3, 77, np.uint32), C.c_int(-7)
+    rc = L.eacham_match_pair(hip_ctx.handle, 0, 1, 0.8, q.ctypes.data, t.ctypes.data, 3, C.byref(cnt))
+    assert rc == capi.ERR_CAPACITY and cnt.value == len(qo) and (q == 77).all() and (t == 77).all()
+    assert b"capacity" in L.eacham_last_error(hip_ctx.handle)
+    q, t = hip_ctx.match_pair(0, 1)
+    assert np.array_equal(q, qo) and np.array_equal(t, to)
+    hip_ctx.clear_descriptors()

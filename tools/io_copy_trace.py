@@ -1,4 +1,4 @@
-"""Each of the nine staged entry points once after a warm-up pass, a host-to-device copy of SEP bytes between two calls, for a
+"""Each of the staged entry points once after a warm-up pass, a host-to-device copy of SEP bytes between two calls, for a
 memory-copy trace of its own:
 
     rocprofv3 --memory-copy-trace --output-format csv -d <dir> -- python tools/io_copy_trace.py
@@ -17,7 +17,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 SEP = 7777
 NAMES = ["solve_minimal", "solve_pnp", "score_hypotheses", "triangulate_tracks", "reprojection_errors", "two_view_points",
-         "two_view_batch", "lmeds_batch", "graph_set_frames"]
+         "two_view_batch", "lmeds_batch", "graph_set_frames", "match_all_pairs", "match_all_pairs_nostats", "match_pair",
+         "graph_best_pair", "(second context: float frames, warm-up)", "match_all_pairs_dot"]
 
 
 def calls():
@@ -37,6 +38,9 @@ def calls():
     first = np.asarray(tr["track_ptr"][:-1])[np.diff(tr["track_ptr"]) > 0]
     uv1, uv2, K, Ts = _two_view_case(seed=5, n=2000)
     pairs, counts, offsets, q, t, valid, has3d, _ = scenario(40, 3)
+    import dot_cases as DC
+    u8, _ = synth.make_frame_descriptors(synth.make_scene(4, 1200, 4, seed=9), 300, 128, seed=9)
+    f32, ordered = DC.scene("d64"), DC.ordered_pairs(4)
     sep_src = torch.zeros(SEP, dtype=torch.uint8)
     with HipContext(0) as ctx:
         rg = G.ResidentGraph(ctx, 40, pairs, counts, offsets, q, t, [len(a) for a in has3d])
@@ -50,7 +54,13 @@ def calls():
                lambda: tri.two_view_points(ctx, uv1, uv2, K, Ts, 4.0, 0.0175, True),
                lambda: ctx.two_view_batch(tc["uv1"], tc["uv2"], tc["K"], tc["rules"], tc["transforms"], tc["max_err"], tc["min_angle"]),
                lambda: ctx.lmeds_batch("homography", lc["uv1"], lc["uv2"], lc["samples"], lc["K"]),
-               lambda: rg.set_frames(list(range(7)), [valid[f] for f in range(7)], [has3d[f] for f in range(7)])]
+               lambda: rg.set_frames(list(range(7)), [valid[f] for f in range(7)], [has3d[f] for f in range(7)]),
+               lambda: ctx.match_all_pairs(ordered, 0.8, 1, 0),
+               lambda: ctx.match_all_pairs(ordered, 0.8, 1, 0, stats=False),
+               lambda: ctx.match_pair(0, 1),
+               lambda: G.best_pair_for_valid(ctx, 40, pairs, counts, offsets, q, t, valid, has3d)]
+        for f, d in enumerate(u8):
+            ctx.upload_descriptors(f, d)
         for f in fns:
             f()
         for f in fns:
@@ -60,6 +70,13 @@ def calls():
         sep_src.cuda()
         torch.cuda.synchronize()
         rg.close()
+    with HipContext(0) as ctx:           # float frames cannot be resident beside int8 ones: a context of its own
+        for f, d in enumerate(f32):
+            ctx.upload_descriptors_f32(f, d)
+        for _ in range(2):               # the warm-up call closes the segment of the context change, the second call is the one counted
+            ctx.match_all_pairs_dot(ordered, 0.5, 0, -1)
+            sep_src.cuda()
+            torch.cuda.synchronize()
 
 
 def table(d):

@@ -1,4 +1,4 @@
-"""Every output of the nine host-pointer entry points that stage through IoStage, as raw bytes, for a before/after run of two
+"""Every output of the host-pointer entry points that stage through IoStage, as raw bytes, for a before/after run of two
 builds of the library (EACHAM_HIP_LIB selects the build; each build needs a process of its own):
 
     EACHAM_HIP_LIB=<parent build> python tools/io_layout_outputs.py --dump /tmp/parent.npz
@@ -9,7 +9,10 @@ Inputs: the cases of tests/two_view_batch_cases.py (eacham_two_view_batch, and e
 cases of tests/lmeds_batch_cases.py in their three variants (eacham_lmeds_batch, and eacham_solve_minimal +
 eacham_score_hypotheses problem by problem), tests/test_tri_oracle.py's two-view case (seed 5, 2000 matches, both angle rules), one
 synth.make_tracks scene (eacham_triangulate_tracks, eacham_reprojection_errors), one PnP batch (eacham_solve_pnp,
-eacham_score_hypotheses) and the resident graph after eacham_graph_set_frames (its query's answer)."""
+eacham_score_hypotheses), the resident graph after eacham_graph_set_frames (its query's answer), eacham_graph_best_pair on the
+same scenario (with and without an excluded mask) and the seven matching calls: eacham_match_pair / _match_all_pairs (with and
+without stats) / _match_pairs_directed on int8 frames and on float frames, the four dot-product calls on the float frames, each on
+a 12-pair list and on a list long enough for the direct copies (33 000 pairs)."""
 import argparse
 import os
 import sys
@@ -94,13 +97,59 @@ def dump(path):
                 put(f"graph_set_frames/{lo}", np.array(rg.query(), np.int64), np.array(rg.query(np.nonzero(excluded)[0]), np.int64))
         finally:
             rg.close()
+        for ex in (None, excluded):
+            best, ec = G.best_pair_for_valid(ctx, 40, pairs, counts, offsets, q, t, valid, has3d, ex, want_edge_counts=True)
+            put(f"graph_best_pair/{int(ex is not None)}", np.array(best, np.int64), ec)
+    matching(put)
     np.savez(path, **out)
     print(f"{len(out)} arrays, {sum(a.size for a in out.values())} bytes -> {path}")
 
 
+def matching(put):
+    """The seven host-pointer matching calls (eacham_amd/csrc/matcher.hip), each build in a context of its own per descriptor kind."""
+    import ctypes as C
+    from eacham_amd import HipContext, synth
+    import dot_cases as DC
+    ordered = DC.ordered_pairs(4)
+    long = ordered[np.arange(33000) % 12]
+
+    def directed(ctx, pr):
+        counts, offsets = np.zeros(len(pr), np.int32), np.zeros(len(pr) + 1, np.int64)
+        cap = 300 * len(pr)
+        q, t, total = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32), C.c_int64(0)
+        pr = np.ascontiguousarray(pr, np.int32)
+        ctx._check(ctx._L.eacham_match_pairs_directed(ctx.handle, pr.ctypes.data, len(pr), 0.8, counts.ctypes.data, offsets.ctypes.data,
+                                                      q.ctypes.data, t.ctypes.data, cap, C.byref(total)))
+        return counts, offsets, q[:total.value], t[:total.value]
+
+    sc = synth.make_scene(4, 1200, 4, seed=9)
+    u8, _ = synth.make_frame_descriptors(sc, 300, 128, seed=9)
+    f32 = DC.float_frames(64, [300, 237, 150, 97], 80, 101)
+    for kind, descs in (("i8", u8), ("f32", f32)):
+        with HipContext(0) as ctx:
+            for f, d in enumerate(descs):
+                (ctx.upload_descriptors if kind == "i8" else ctx.upload_descriptors_f32)(f, d)
+            for a, b in ordered:
+                put(f"match_pair/{kind}/{a}_{b}", *ctx.match_pair(int(a), int(b)))
+            for tag, pr in (("12", ordered), ("33000", long if kind == "i8" else long[:6000])):
+                for md, mm in ((30, 30), (1, 0)):
+                    put(f"match_all_pairs/{kind}/{tag}/{md}_{mm}", *ctx.match_all_pairs(pr, 0.8, md, mm))
+                    put(f"match_all_pairs_nostats/{kind}/{tag}/{md}_{mm}", *ctx.match_all_pairs(pr, 0.8, md, mm, stats=False)[:4])
+                put(f"match_pairs_directed/{kind}/{tag}", *directed(ctx, pr))
+            if kind == "f32":
+                for a, b in ordered:
+                    put(f"match_pair_dot/{a}_{b}", *ctx.match_pair_dot(int(a), int(b), 0.5))
+                for tag, pr in (("12", ordered), ("6000", long[:6000])):
+                    put(f"match_pairs_directed_dot/{tag}", *ctx.match_pairs_directed_dot(pr, 0.5))
+                    for screened in (False, True):
+                        name = "match_all_pairs_dot_screened" if screened else "match_all_pairs_dot"
+                        put(f"{name}/{tag}", *ctx.match_all_pairs_dot(pr, 0.5, 0, -1, screened=screened))
+                        put(f"{name}_nostats/{tag}", *ctx.match_all_pairs_dot(pr, 0.5, 5, 5, stats=False, screened=screened)[:5])
+
+
 def compare(a_path, b_path, out_path):
     a, b = np.load(a_path), np.load(b_path)
-    lines = [f"Outputs of the nine staged entry points, parent build against this one, as raw bytes ({os.path.basename(a_path)} vs {os.path.basename(b_path)})"]
+    lines = [f"Outputs of the staged entry points, parent build against this one, as raw bytes ({os.path.basename(a_path)} vs {os.path.basename(b_path)})"]
     groups = {}
     bad = sorted(set(a.files) ^ set(b.files))
     for k in sorted(set(a.files) & set(b.files)):

@@ -1,10 +1,29 @@
 """Rate of the drop-in FeatureMatcherHip::Match under the reference's own call pattern (apps/sfm/main.cpp:84-109: one
 std::async(&Match) per ORDERED pair from a pool of threads on one shared instance), next to the batch entry point.
-  python3 tools/match_async_rate.py [frames] [kpts] [dim] [threads]"""
+  python3 tools/match_async_rate.py [frames] [kpts] [dim] [threads]
+  python3 tools/match_async_rate.py --pair [calls]    only the wall time of one eacham_match_pair call on a 600 x 128-D pair
+                                                      (EACHAM_HIP_LIB selects the build, for a before/after run)"""
 import os, struct, subprocess, sys, tempfile, time
 sys.path.insert(0, os.getcwd())
 import numpy as np
 from eacham_amd import synth, HipContext
+
+if len(sys.argv) > 1 and sys.argv[1] == "--pair":
+    calls = int(sys.argv[2]) if len(sys.argv) > 2 else 400
+    sc = synth.make_scene(2, 1200, 2, seed=9)
+    descs, _ = synth.make_frame_descriptors(sc, 600, 128, seed=9)
+    with HipContext(0) as ctx:
+        for f, d in enumerate(descs):
+            ctx.upload_descriptors(f, d)
+        for _ in range(50):
+            n = len(ctx.match_pair(0, 1)[0])
+        dts = []
+        for _ in range(calls):
+            t0 = time.perf_counter(); ctx.match_pair(0, 1); dts.append(time.perf_counter() - t0)
+    dts = np.sort(dts) * 1e6
+    print(f"eacham_match_pair 600 x 128-D, {n} matches, {calls} calls: median {dts[len(dts) // 2]:.1f} us, mean {dts.mean():.1f} us, "
+          f"p10 {dts[len(dts) // 10]:.1f} us, p90 {dts[len(dts) * 9 // 10]:.1f} us")
+    sys.exit(0)
 
 F = int(sys.argv[1]) if len(sys.argv) > 1 else 48
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 2000
