@@ -649,11 +649,9 @@ __device__ __forceinline__ void eliminate_observations_block(const BaDev& D, dou
             et[3 * a + 1] = m1 * e0 + m2 * e1;
             et[3 * a + 2] = m3 * e0 + m4 * e1 + m5 * e2;
         }
-#ifndef EXP_NO_ET_STORE  // (knock-out, timing only: what the 72 MB store costs)
         double2* out = reinterpret_cast<double2*>(D.Et + 18 * (size_t)p);
 #pragma unroll
         for (int k = 0; k < 9; ++k) out[k] = double2{et[2 * k], et[2 * k + 1]};
-#endif
     }
     mfma_d4 acc = {0.0, 0.0, 0.0, 0.0};
     double *sa = stA[wave], *sb = stB[wave];
@@ -754,11 +752,7 @@ __global__ __launch_bounds__(TPB) void ba_schur_pairs(BaDev D) {
         for (int it = 0; it < 18; ++it) {
             const int c = 64 * it + lane, r = c / 9, piece = c - 9 * r;  // piece of row r = side (r & 1) of entry r >> 1
             const int rx = __shfl(pr.x, r >> 1), ry = __shfl(pr.y, r >> 1);
-#ifdef EXP_PAIRS_LOCAL  // (knock-out, timing only: every row comes from a 74 KB window — the gathers as if Et sat in LDS / L1)
-            const double* src = D.Et + 18 * (size_t)(((r & 1) ? ry : rx) & 511) + 2 * piece;
-#else
             const double* src = D.Et + 18 * (size_t)((r & 1) ? ry : rx) + 2 * piece;
-#endif
             __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                              (__attribute__((address_space(3))) void*)(buf + 128 * it), 16, 0, 0);
         }
@@ -1019,9 +1013,6 @@ __global__ __launch_bounds__(TPB, 4 - NR) void ba_schur_groups(BaDev D, double l
     }
     __syncthreads();
     // ---- phase B: the slices, one per lane ----
-#ifdef EXP_GRP_NO_B  // (knock-out, timing only)
-    if (lambda > -1.0) return;
-#endif
     for (int c = wave; c < G.nchunks; c += TPB / 64) {
         // (requesting the first chunk's record, lane words and entries before phase 0 — they need only the group record — was
         // measured: 75.4 against 72.6 us, and four spilled registers in the 256-row form)
@@ -1065,9 +1056,6 @@ __global__ __launch_bounds__(TPB, 4 - NR) void ba_schur_groups(BaDev D, double l
         auto fold_step = [&](auto DC) {
             constexpr int d = decltype(DC)::value;
             const bool take = after >= d;
-#ifdef EXP_GRP_NO_FOLD  // (knock-out, timing only)
-            if (lambda > -1.0) return;
-#endif
             if (!__ballot(take)) return;  // (wave-uniform: nobody in this chunk reaches that far — chunks of one-lane segments skip all three)
 #pragma unroll
             for (int k = 0; k < 36; ++k) {
@@ -3688,6 +3676,87 @@ __device__ __forceinline__ T ge_block_scan(T v, T* lds, T* total) {  // exclusiv
     __syncthreads();
     return incl - v;
 }
+// A run of L entries of one block as lanes: L > 4 gives ceil(L / GRP_SLICE) lanes of L / n (+ 1) entries, in the "long" region of
+// the group's lane list; a shorter run is one lane of the "short" region behind it. f(offset in the run, length, long?) per lane.
+template <class F>
+__device__ __forceinline__ void ge_run_lanes(int L, F&& f) {
+    const bool lng = L > 4;
+    const int n = lng ? (L + GRP_SLICE - 1) / GRP_SLICE : L > 0 ? 1 : 0;
+    const int each = lng ? L / n : L, more = lng ? L % n : 0;   // (a short run pays no division)
+    for (int q = 0, at = 0; q < n; ++q) {
+        const int len = each + (q < more ? 1 : 0);
+        f(at, len, lng);
+        at += len;
+    }
+}
+// From the lane list to everything but the entries, for both entry kernels: steps per chunk, segments, the PASS 0 hand-off;
+// in PASS 1 the group record, the chunk table, the lane records and the (key, where) list of the segments. lane_id[l] names
+// the block of lane l (equal identity = same block; block_key turns a head's identity into the block key), lane_len[l] its
+// entries; base = the group's {first chunk, first uint4-row, first segment} (PASS 1). Leaves chunk_ent0 / chunk_n4
+// (workgroup-shared, GE_MAXE / 64 each) for the caller's entry-writing loop; true = the kernel is done (PASS 0).
+template <int PASS, class KeyOf>
+__device__ __forceinline__ bool ge_lanes_tail(const uint32_t* lane_id, const unsigned char* lane_len, int nlanes, int ne, int* scan_buf,
+                                              int* chunk_ent0, int* chunk_n4, const prim::I3 base, int g, BaGroup* __restrict__ groups,
+                                              prim::I3* __restrict__ counts, BaChunk* __restrict__ chunks,
+                                              uint32_t* __restrict__ laneinfo, uint32_t* __restrict__ seg_key, uint32_t* __restrict__ seg_where,
+                                              int seg_off, KeyOf&& block_key) {
+    const int tid = threadIdx.x, nchunks = (nlanes + 63) / 64;
+    // thread c < nchunks: longest lane of chunk c (nchunks <= GE_MAXE / 64 = 128 <= GE_THREADS)
+    int my_n4 = 0;
+    if (tid < nchunks) {
+        int longest = 0;
+        for (int l = 64 * tid; l < min(nlanes, 64 * tid + 64); ++l) longest = max(longest, (int)lane_len[l]);
+        my_n4 = (longest + 3) / 4;
+    }
+    int tot_n4 = 0;
+    const int off_n4 = ge_block_scan<int>(my_n4, scan_buf, &tot_n4);
+    if (tid < nchunks) chunk_ent0[tid] = off_n4, chunk_n4[tid] = my_n4;
+    // segment heads: lane li is a head iff (li - h0) % GRP_SEG == 0, h0 = first lane of its block at or after the row start
+    int my_heads = 0;
+    const int lper = (nlanes + GE_THREADS - 1) / GE_THREADS;
+    const int l0 = min(tid * lper, nlanes), l1 = min(l0 + lper, nlanes);
+    for (int li = l0; li < l1; ++li) {
+        const uint32_t id = lane_id[li];
+        int h = li;
+        const int cs = li & ~(GRP_ROW - 1);   // a segment stays inside its row of 16 lanes
+        while (h > cs && lane_id[h - 1] == id) --h;
+        if (((li - h) % GRP_SEG) == 0) ++my_heads;
+    }
+    int tot_heads = 0;
+    const int off_heads = ge_block_scan<int>(my_heads, scan_buf, &tot_heads);
+    if (PASS == 0) {
+        if (tid == 0) counts[g] = prim::I3{nchunks, tot_n4, tot_heads};
+        return true;
+    }
+    __syncthreads();
+    // ---- PASS 1: write ----
+    if (tid == 0) {
+        groups[g].chunk0 = base.a; groups[g].nchunks = nchunks; groups[g].n_entries = ne; groups[g].n_segments = tot_heads;
+    }
+    if (tid < nchunks) chunks[base.a + tid] = BaChunk{base.b + chunk_ent0[tid], chunk_n4[tid]};
+    // lanes: records + segment list
+    int hs = off_heads;
+    for (int li = l0; li < l1; ++li) {
+        const uint32_t id = lane_id[li];
+        const int cs = li & ~(GRP_ROW - 1), ce = min(nlanes, cs + GRP_ROW);
+        int h = li;
+        while (h > cs && lane_id[h - 1] == id) --h;
+        h += (li - h) / GRP_SEG * GRP_SEG;
+        int e = h;
+        while (e < ce && e < h + GRP_SEG && lane_id[e] == id) ++e;
+        uint32_t info = (uint32_t)(e - 1 - li) << 28;
+        const size_t where = (size_t)64 * base.a + li;
+        if (li == h) {
+            seg_key[seg_off + base.c + hs] = block_key(id);
+            seg_where[seg_off + base.c + hs] = (uint32_t)where;
+            ++hs;
+            info |= 1u;  // (prep_grp_slots writes the slot)
+        }
+        laneinfo[where] = info;
+    }
+    for (int li = nlanes + tid; li < 64 * nchunks; li += GE_THREADS) laneinfo[(size_t)64 * base.a + li] = 0;
+    return false;
+}
 template <int PASS>
 __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries(int emax /* power of two >= the group bound on entries */, int nc, int R, const GrpCounters* __restrict__ gc, BaGroup* __restrict__ groups,
                                                                const int2* __restrict__ rowinfo, const int* __restrict__ lmrow,
@@ -3775,9 +3844,7 @@ __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries(int emax /* power
         if (i > 0 && (words[i - 1] >> 31) == key) continue;
         int e = i + 1;
         while (e < ne && (words[e] >> 31) == key) ++e;
-        const int L = e - i;
-        if (L > 4) lanes_long += (L + GRP_SLICE - 1) / GRP_SLICE;
-        else lanes_short += 1;
+        ge_run_lanes(e - i, [&](int, int, bool lng) { lanes_long += lng ? 1 : 0, lanes_short += lng ? 0 : 1; });
     }
     int tot_long = 0, tot_short = 0;
     const int off_long = ge_block_scan<int>(lanes_long, scan_buf, &tot_long);
@@ -3790,80 +3857,20 @@ __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries(int emax /* power
             if (i > 0 && (words[i - 1] >> 31) == key) continue;
             int e = i + 1;
             while (e < ne && (words[e] >> 31) == key) ++e;
-            const int L = e - i;
-            if (L > 4) {
-                const int n = (L + GRP_SLICE - 1) / GRP_SLICE;
-                for (int q = 0, at = i; q < n; ++q) {
-                    const int len = L / n + (q < L % n ? 1 : 0);
-                    lane_first[ll] = (unsigned short)at, lane_len[ll] = (unsigned char)len, lane_key[ll] = (uint32_t)key;
-                    at += len, ++ll;
-                }
-            } else {
-                lane_first[ls] = (unsigned short)i, lane_len[ls] = (unsigned char)L, lane_key[ls] = (uint32_t)key;
-                ++ls;
-            }
+            ge_run_lanes(e - i, [&](int at, int len, bool lng) {
+                const int l = lng ? ll : ls;
+                ll += lng ? 1 : 0, ls += lng ? 0 : 1;
+                lane_first[l] = (unsigned short)(i + at), lane_len[l] = (unsigned char)len, lane_key[l] = (uint32_t)key;
+            });
         }
     }
     __syncthreads();
-    // ---- chunks: steps per chunk, segments ----
-    // thread c < nchunks: longest lane of chunk c (nchunks <= GE_MAXE / 64 = 128 <= GE_THREADS)
-    int my_n4 = 0;
-    if (tid < nchunks) {
-        int longest = 0;
-        for (int l = 64 * tid; l < min(nlanes, 64 * tid + 64); ++l) longest = max(longest, (int)lane_len[l]);
-        my_n4 = (longest + 3) / 4;
-    }
-    int tot_n4 = 0;
-    const int off_n4 = ge_block_scan<int>(my_n4, scan_buf, &tot_n4);
+    // ---- chunks, segments, lane records (a lane's block = its key) ----
     __shared__ int s_chunk_ent0[GE_MAXE / 64], s_chunk_n4[GE_MAXE / 64];
-    if (tid < nchunks) s_chunk_ent0[tid] = off_n4, s_chunk_n4[tid] = my_n4;
-    // segment heads: lane li is a head iff (li - h0) % GRP_SEG == 0, h0 = first lane of its key at or after the chunk start
-    int my_heads = 0;
-    const int lper = (nlanes + GE_THREADS - 1) / GE_THREADS;
-    const int l0 = tid * lper, l1 = min(l0 + lper, nlanes);
-    for (int li = l0; li < l1; ++li) {
-        const uint32_t key = lane_key[li];
-        int h = li;
-        const int cs = li & ~(GRP_ROW - 1);   // a segment stays inside its row of 16 lanes
-        while (h > cs && lane_key[h - 1] == key) --h;
-        if (((li - h) % GRP_SEG) == 0) ++my_heads;
-    }
-    int tot_heads = 0;
-    const int off_heads = ge_block_scan<int>(my_heads, scan_buf, &tot_heads);
-    if (PASS == 0) {
-        if (tid == 0) counts[g] = prim::I3{nchunks, tot_n4, tot_heads};
+    const prim::I3 base = PASS == 0 ? prim::I3{0, 0, 0} : bases[g];   // {first chunk, first uint4-row, first segment}
+    if (ge_lanes_tail<PASS>(lane_key, lane_len, nlanes, ne, scan_buf, s_chunk_ent0, s_chunk_n4, base, g, groups, counts, chunks, laneinfo,
+                            seg_key, seg_where, seg_off, [](uint32_t key) { return key; }))
         return;
-    }
-    __syncthreads();
-    // ---- PASS 1: write ----
-    const prim::I3 base = bases[g];   // {first chunk, first uint4-row, first segment}
-    if (tid == 0) {
-        groups[g].chunk0 = base.a; groups[g].nchunks = nchunks; groups[g].n_entries = ne; groups[g].n_segments = tot_heads;
-    }
-    if (tid < nchunks) chunks[base.a + tid] = BaChunk{base.b + s_chunk_ent0[tid], s_chunk_n4[tid]};
-    // lanes: records + segment list
-    {
-        int hs = off_heads;
-        for (int li = l0; li < l1; ++li) {
-            const uint32_t key = lane_key[li];
-            const int cs = li & ~(GRP_ROW - 1), ce = min(nlanes, cs + GRP_ROW);
-            int h = li;
-            while (h > cs && lane_key[h - 1] == key) --h;
-            h += (li - h) / GRP_SEG * GRP_SEG;
-            int e = h;
-            while (e < ce && e < h + GRP_SEG && lane_key[e] == key) ++e;
-            uint32_t info = (uint32_t)(e - 1 - li) << 28;
-            const size_t where = (size_t)64 * base.a + li;
-            if (li == h) {
-                seg_key[seg_off + base.c + hs] = key;
-                seg_where[seg_off + base.c + hs] = (uint32_t)where;
-                ++hs;
-                info |= 1u;  // (prep_grp_slots writes the slot)
-            }
-            laneinfo[where] = info;
-        }
-        for (int li = nlanes + tid; li < 64 * nchunks; li += GE_THREADS) laneinfo[(size_t)64 * base.a + li] = 0;
-    }
     // entries: [chunk][step][lane][4], null beyond a slice
     const uint32_t null_ent = (uint32_t)R | ((uint32_t)R << 16);
     for (int c = 0; c < nchunks; ++c) {
@@ -3884,8 +3891,9 @@ __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries(int emax /* power
 // kernel above serves the others): with the group's cameras numbered locally in ascending order, the run of block (la, lb) is
 // the landmarks that see both — M[la] & M[lb] for per-camera bit masks over the group's <= 128 landmarks — in ascending
 // landmark order, which IS the (block key, emission index) order of the definition. Pairs are walked in key order by strips,
-// lanes / chunks / segments follow from scans as above, and a lane's entries are read off the mask (the bits from its start
-// position on; the two rows by a search through the landmark's few rows). 0.56 ms per pass on S200 with the bitonic sort,
+// their runs cut into lanes by ge_run_lanes, the lane list handed to ge_lanes_tail (a lane's identity is its pair's index;
+// the block key of a head comes from the pair's two cameras), and a lane's entries are read off the mask (the bits from its
+// start position on; the two rows by a search through the landmark's few rows). 0.56 ms per pass on S200 with the bitonic sort,
 // the per-group time here is a small sort of the <= 512 row cameras and a few scans.
 __device__ __forceinline__ int gf_pairs_before(int la, int U) { return la * U - la * (la - 1) / 2; }
 template <int PASS>
@@ -3979,8 +3987,7 @@ __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries_fast(int lane_cap
         for (int q = q0; q < q1; ++q) {
             const int L = run_len(la, lb);
             my_entries += L;
-            if (L > 4) lanes_long += (L + GRP_SLICE - 1) / GRP_SLICE;
-            else if (L > 0) lanes_short += 1;
+            ge_run_lanes(L, [&](int, int, bool lng) { lanes_long += lng ? 1 : 0, lanes_short += lng ? 0 : 1; });
             if (++lb == U) ++la, lb = la;
         }
     }
@@ -3993,80 +4000,25 @@ __global__ __launch_bounds__(GE_THREADS) void prep_grp_entries_fast(int lane_cap
         int la, lb, ll = off_long, ls = tot_long + off_short;
         pair_of(q0, la, lb);
         for (int q = q0; q < q1; ++q) {
-            const int L = run_len(la, lb);
-            if (L > 4) {
-                const int n = (L + GRP_SLICE - 1) / GRP_SLICE;
-                for (int k = 0, at = 0; k < n; ++k) {
-                    const int len = L / n + (k < L % n ? 1 : 0);
-                    lane_q[ll] = (uint32_t)q, lane_at[ll] = (unsigned char)at, lane_len[ll] = (unsigned char)len;
-                    at += len, ++ll;
-                }
-            } else if (L > 0) {
-                lane_q[ls] = (uint32_t)q, lane_at[ls] = 0, lane_len[ls] = (unsigned char)L;
-                ++ls;
-            }
+            ge_run_lanes(run_len(la, lb), [&](int at, int len, bool lng) {
+                const int l = lng ? ll : ls;
+                ll += lng ? 1 : 0, ls += lng ? 0 : 1;
+                lane_q[l] = (uint32_t)q, lane_at[l] = (unsigned char)at, lane_len[l] = (unsigned char)len;
+            });
             if (++lb == U) ++la, lb = la;
         }
     }
     __syncthreads();
-    // ---- chunks and segments, as in the general kernel (a lane's block = its pair) ----
-    int my_n4 = 0;
-    if (tid < nchunks) {
-        int longest = 0;
-        for (int l = 64 * tid; l < min(nlanes, 64 * tid + 64); ++l) longest = max(longest, (int)lane_len[l]);
-        my_n4 = (longest + 3) / 4;
-    }
-    int tot_n4 = 0;
-    const int off_n4 = ge_block_scan<int>(my_n4, scan_buf, &tot_n4);
-    if (tid < nchunks) s_chunk_ent0[tid] = off_n4, s_chunk_n4[tid] = my_n4;
-    int my_heads = 0;
-    const int lper = (nlanes + GE_THREADS - 1) / GE_THREADS;
-    const int l0 = min(tid * lper, nlanes), l1 = min(l0 + lper, nlanes);
-    for (int li = l0; li < l1; ++li) {
-        const uint32_t q = lane_q[li];
-        int h = li;
-        const int cs = li & ~(GRP_ROW - 1);   // a segment stays inside its row of 16 lanes
-        while (h > cs && lane_q[h - 1] == q) --h;
-        if (((li - h) % GRP_SEG) == 0) ++my_heads;
-    }
-    int tot_heads = 0;
-    const int off_heads = ge_block_scan<int>(my_heads, scan_buf, &tot_heads);
-    if (PASS == 0) {
-        if (tid == 0) counts[g] = prim::I3{nchunks, tot_n4, tot_heads};
-        return;
-    }
-    __syncthreads();
-    // ---- PASS 1: write ----
-    const prim::I3 base = bases[g];   // {first chunk, first uint4-row, first segment}
-    if (tid == 0) {
-        groups[g].chunk0 = base.a; groups[g].nchunks = nchunks; groups[g].n_entries = ne; groups[g].n_segments = tot_heads;
-    }
-    if (tid < nchunks) chunks[base.a + tid] = BaChunk{base.b + s_chunk_ent0[tid], s_chunk_n4[tid]};
+    // ---- chunks, segments, lane records (a lane's block = its pair; the key of a head's block from the pair's two cameras) ----
     const uint32_t W = (uint32_t)nc + 1;
-    {
-        int hs = off_heads;
-        for (int li = l0; li < l1; ++li) {
-            const uint32_t q = lane_q[li];
-            const int cs = li & ~(GRP_ROW - 1), ce = min(nlanes, cs + GRP_ROW);
-            int h = li;
-            while (h > cs && lane_q[h - 1] == q) --h;
-            h += (li - h) / GRP_SEG * GRP_SEG;
-            int e = h;
-            while (e < ce && e < h + GRP_SEG && lane_q[e] == q) ++e;
-            uint32_t info = (uint32_t)(e - 1 - li) << 28;
-            const size_t where = (size_t)64 * base.a + li;
-            if (li == h) {
-                int la, lb;
-                pair_of((int)q, la, lb);
-                seg_key[seg_off + base.c + hs] = (uint32_t)ucam[la] * W + (uint32_t)ucam[lb];
-                seg_where[seg_off + base.c + hs] = (uint32_t)where;
-                ++hs;
-                info |= 1u;  // (prep_grp_slots writes the slot)
-            }
-            laneinfo[where] = info;
-        }
-        for (int li = nlanes + tid; li < 64 * nchunks; li += GE_THREADS) laneinfo[(size_t)64 * base.a + li] = 0;
-    }
+    const prim::I3 base = PASS == 0 ? prim::I3{0, 0, 0} : bases[g];   // {first chunk, first uint4-row, first segment}
+    if (ge_lanes_tail<PASS>(lane_q, lane_len, nlanes, ne, scan_buf, s_chunk_ent0, s_chunk_n4, base, g, groups, counts, chunks, laneinfo,
+                            seg_key, seg_where, seg_off, [&](uint32_t q) {
+                                int la, lb;
+                                pair_of((int)q, la, lb);
+                                return (uint32_t)ucam[la] * W + (uint32_t)ucam[lb];
+                            }))
+        return;
     // entries, a lane per thread: the landmarks of the run from position lane_at on; the two rows by a search through the landmark's rows
     const uint32_t null_ent = (uint32_t)R | ((uint32_t)R << 16);
     for (int li = tid; li < 64 * nchunks; li += GE_THREADS) {
@@ -4443,6 +4395,25 @@ struct BaDevicePrep {
         return EACHAM_OK;
     }
 
+    // One pass of the entries kernel over `ngrid` groups: the general form (it sorts every group's entries) when some landmark
+    // sees a camera twice, the sort-free form otherwise. The first pass raises the LDS limit of both passes of the form it takes.
+    template <int PASS>
+    int launch_grp_entries(int ngrid, prim::I3* counts, const prim::I3* bases, BaChunk* chunks, uint32_t* ent, uint32_t* laneinfo,
+                           uint32_t* seg_key, uint32_t* seg_where, int seg_off) {
+        const bool general = hg.any_dup != 0;
+        const int cap = general ? g_emax : GRP_ENT_PER_ROW * R;   // the kernel's first argument: entries (a power of two) / lanes
+        const size_t lds = general ? grp_entries_lds_bytes(cap, R) : grp_entries_fast_lds_bytes(cap, R);
+        const auto pass0 = general ? prep_grp_entries<0> : prep_grp_entries_fast<0>;
+        const auto pass1 = general ? prep_grp_entries<1> : prep_grp_entries_fast<1>;
+        if (PASS == 0) {
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)pass0, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)pass1, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        }
+        (PASS == 0 ? pass0 : pass1)<<<ngrid, GE_THREADS, lds, st>>>(cap, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, counts, bases, chunks, ent,
+                                                                     laneinfo, seg_key, seg_where, seg_off);
+        return EACHAM_OK;
+    }
+
     // ---- the landmark-major structure (ba_groups.hpp steps 2-4 on the device), first half: groups, padded per-group arrays,
     // the counting pass over every group's entries ----
     int groups_first() {
@@ -4472,17 +4443,7 @@ struct BaDevicePrep {
             prep_grp_records<<<(unsigned)((ng_max + TPB - 1) / TPB), TPB, 0, st>>>(gcnt, tg_lm0, grstart, tg_groups);
             prep_grp_fill<<<gnu, TPB, 0, st>>>(nu, nc, R, R0g, g_sorted, gcstart, grstart, tg_lm0, lm_ptr, obs_cam, obs_uv, tg_lmid, tg_lmrow, tg_rowinfo, tg_uv);
         }
-        if (hg.any_dup) {  // the general form: sorts every group's entries
-            const size_t ge_lds = grp_entries_lds_bytes(g_emax, R);
-            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
-            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ge_lds));
-            prep_grp_entries<0><<<ng_max, GE_THREADS, ge_lds, st>>>(g_emax, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, tg_counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        } else {
-            const size_t gf_lds = grp_entries_fast_lds_bytes(GRP_ENT_PER_ROW * R, R);
-            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries_fast<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
-            EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)prep_grp_entries_fast<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)gf_lds));
-            prep_grp_entries_fast<0><<<ng_max, GE_THREADS, gf_lds, st>>>(GRP_ENT_PER_ROW * R, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, tg_counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
-        }
+        TRY(launch_grp_entries<0>(ng_max, tg_counts, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0));
         prim::exclusive_scan<prim::I3>(st, tg_counts, tg_bases, ng_max, tg_ws, &gcnt->totals);
         // ---- read-back 2: groups, chunks, entry rows, segments ----
         EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&hg, gcnt, sizeof(hg), hipMemcpyDeviceToHost, st));
@@ -4520,12 +4481,7 @@ struct BaDevicePrep {
         }));
         const int n_mand = 2 * nc + 1;
         prep_grp_mandatory<<<(unsigned)((n_mand + TPB - 1) / TPB), TPB, 0, st>>>(nc, ikA, iwA);
-        if (ngf > 0) {
-            if (hg.any_dup)
-                prep_grp_entries<1><<<ngf, GE_THREADS, grp_entries_lds_bytes(g_emax, R), st>>>(g_emax, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, nullptr, tg_bases, sg_chunks, sg_ent, sg_laneinfo, ikA, iwA, n_mand);
-            else
-                prep_grp_entries_fast<1><<<ngf, GE_THREADS, grp_entries_fast_lds_bytes(GRP_ENT_PER_ROW * R, R), st>>>(GRP_ENT_PER_ROW * R, nc, R, gcnt, tg_groups, tg_rowinfo, tg_lmrow, nullptr, tg_bases, sg_chunks, sg_ent, sg_laneinfo, ikA, iwA, n_mand);
-        }
+        if (ngf > 0) TRY(launch_grp_entries<1>(ngf, nullptr, tg_bases, sg_chunks, sg_ent, sg_laneinfo, ikA, iwA, n_mand));
         const int w_i = prim::radix_sort_pairs<uint32_t>(st, ikA, iwA, ikB, iwB, n_items, bits_for((long long)(nc + 1) * (nc + 1)), isort_ws);
         const uint32_t *skey = w_i ? ikB : ikA, *swhere = w_i ? iwB : iwA;
         const unsigned git = (unsigned)((n_items + TPB - 1) / TPB);

@@ -196,3 +196,32 @@ def test_every_accepted_group_size_builds_the_same_structure(rows):
     finally:
         for ctx in pair:
             ctx.close()
+
+
+@pytest.mark.parametrize("repeat", [False, True], ids=["fast", "general"])
+@pytest.mark.parametrize("rows", [64, 252, 508])
+def test_long_runs_cut_into_slices_and_segments_by_both_entry_kernels(rows, repeat):
+    """Five cameras and three observations per landmark: a 508-row group holds about 120 landmarks, so a block's run inside a
+    group is several slices long and the diagonal blocks exceed 64 entries — lanes are sliced, segments are cut at GRP_SEG
+    lanes and some cross a row of GRP_ROW lanes. As it is the scene takes the sort-free entries kernel of ba.hip; with five
+    observations repeated (a camera sees a landmark twice) every group goes through the general, sorting one. Both must
+    build the host form's structure at every group size; `_group_rows` holds the case to the groups (not the pair lists)."""
+    A = _arrays(31, 5, 300, 3)
+    if repeat:
+        A.obs_cam = np.concatenate([A.obs_cam, A.obs_cam[:5]]).astype(np.uint32)
+        A.obs_point = np.concatenate([A.obs_point, A.obs_point[:5]]).astype(np.uint32)
+        A.obs_uv = np.concatenate([A.obs_uv, A.obs_uv[:5] + 0.7])
+    pair = _ctx_pair_with(EACHAM_BA_SCHUR="groups", EACHAM_BA_GROUP_ROWS=str(rows))
+    try:
+        for ctx in pair:
+            pb = ba.PreparedBA(ctx, A)
+            try:
+                assert _group_rows(pb) == rows
+            finally:
+                pb.close()
+        _same_step(pair, A)
+        if rows == 508:
+            _same_run(pair, A)
+    finally:
+        for ctx in pair:
+            ctx.close()
