@@ -26,6 +26,7 @@ KERNEL_SCORE = 7
 SCORE_ESSENTIAL, SCORE_HOMOGRAPHY, SCORE_PNP = 0, 1, 2
 SOLVE_HOMOGRAPHY4, SOLVE_ESSENTIAL5 = 0, 1
 TWOVIEW_POSES, TWOVIEW_SOLUTIONS = 0, 1
+SAMPLING_OPENCV, SAMPLING_COUNTER = 0, 1
 
 
 class EachamError(RuntimeError):
@@ -113,6 +114,10 @@ def lib() -> C.CDLL:
         L.eacham_tracks_build.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
         L.eacham_graph_tracks.argtypes = [vp, vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
         L.eacham_tracks_debug_last.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(C.c_float)]
+    if hasattr(L, "eacham_graph_verify"):  # (likewise)
+        L.eacham_graph_set_keypoints.argtypes = [vp, vp]
+        L.eacham_graph_verify.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+        L.eacham_graph_tracks_verified.argtypes = [vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
     L.eacham_reprojection_errors.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.eacham_profile_enable.argtypes = [vp, i32]
     L.eacham_profile_reset.argtypes = [vp]

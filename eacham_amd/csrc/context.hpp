@@ -173,6 +173,14 @@ struct eacham_graph {
     long long* kp_offsets = nullptr;
     long long* src_offsets = nullptr;    // per edge: where its match list began in the caller's arrays
     std::vector<long long> kp_offsets_h;
+    // what the geometric verification adds (graph_verify.hip: a PROBLEM is a caller pair, in the caller's order)
+    int npairs = 0;                      // caller pairs, those without matches included
+    std::vector<int> pair_counts_h;      // [npairs] the caller's counts
+    long long* pair_ptr = nullptr;       // [npairs + 1] where each caller pair's matches begin in the packed lists (a pair without matches owns none)
+    double* xy = nullptr;                // [n_kp x 2] pixel coordinates (eacham_graph_set_keypoints), an allocation of its own
+    bool has_xy = false;
+    unsigned char* keep_mask = nullptr;  // [n_src] the inlier mask a verify call retained, an allocation of its own
+    bool has_keep = false;
 };
 
 #define EACHAM_HIP_TRY(ctx, expr)                                                              \
@@ -292,6 +300,31 @@ private:
         return EACHAM_OK;
     }
 };
+// lmeds_batch.hip: the launch sequence of eacham_lmeds_batch on device pointers — solve every sample, scan the root counts, score
+// every candidate (keys in LDS up to SC_MAX_LDS points, in error rows beyond, by max_n), select per problem. The host-pointer entry
+// and eacham_graph_verify (graph_verify.hip) both call it. S = the samples sample_ptr[P] names; the scratch arrays may be larger.
+struct LmedsLaunch {
+    int kind, P;                 // EACHAM_SOLVE_*, problems (> 0)
+    long long S, max_n;          // samples in this call; the largest problem with at least a minimal sample's worth of points
+    int score_grid;              // lmeds_score_grid(...): the workgroups of the scorer, and the rows `rows` holds beyond SC_MAX_LDS
+    const long long *point_ptr, *sample_ptr;
+    const double *a, *b, *K;     // K: device copy of fx fy cx cy; has_K says whether the caller gave one
+    bool has_K;
+    const int* sample_idx;
+    // scratch: 9 x S x maxm, S, S, S, 1, scan_ws_elems(S), S x maxm, need_rows ? score_grid x max_n : 0
+    double* cand_models;
+    int *n_models, *first, *sample_problem, *total, *scan_ws;
+    float *cand_medians, *rows;
+    // results, per problem (masks: per point, in the layout of a / b)
+    double* models;
+    float *medians, *thresholds;
+    int* inliers;
+    unsigned char* masks;
+    int *winner, *n_candidates;
+};
+int lmeds_score_grid(long long cand_cap, long long max_n);
+bool lmeds_needs_rows(long long max_n);
+int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L);
 int sync_frame_table(eacham_ctx* ctx);
 // copies `pairs` into the workspace tail with every pair that names a missing frame redirected to the empty
 // stand-in entry frames[n_frames] (and flags it); returns the sanitised device pointer in *out

@@ -127,7 +127,9 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     std::vector<long long> e_off, e_src;   // e_src: where the edge's match list began in the caller's arrays (the index space of a `keep` mask)
     std::vector<unsigned> e_q, e_t;
     long long n_src = 0;
+    std::vector<long long> pair_ptr((size_t)npairs + 1, 0);
     for (int p = 0; p < npairs; ++p) {
+        pair_ptr[p + 1] = pair_ptr[p] + std::max(counts[p], 0);
         const int f1 = pairs[2 * p], f2 = pairs[2 * p + 1];
         if (f1 < 0 || f2 < 0 || f1 >= n_frames || f2 >= n_frames)
             return ctx->fail(EACHAM_ERR_INVALID, "graph_create: pair %d names frame %d/%d of %d", p, f1, f2, n_frames);
@@ -156,6 +158,8 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     g->n_kp = kp_offsets[n_frames];
     g->n_src = n_src;
     g->kp_offsets_h.assign(kp_offsets, kp_offsets + n_frames + 1);
+    g->npairs = npairs;
+    g->pair_counts_h.assign(counts, counts + npairs);
     (void)hipSetDevice(ctx->device);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 8)); return o; };
@@ -164,7 +168,7 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     const size_t o_t = take(sizeof(unsigned) * (size_t)g->n_matches), o_valid = take((size_t)n_frames), o_excl = take((size_t)n_frames);
     const size_t o_kpo = take(sizeof(long long) * ((size_t)n_frames + 1)), o_h3 = take((size_t)g->n_kp);
     const size_t o_ec = take(sizeof(unsigned) * 2 * (size_t)g->n_edges), o_best = take(sizeof(unsigned) * 4);
-    const size_t o_src = take(sizeof(long long) * (size_t)g->n_edges);
+    const size_t o_src = take(sizeof(long long) * (size_t)g->n_edges), o_pptr = take(sizeof(long long) * ((size_t)npairs + 1));
     if (hipMalloc((void**)&g->dev, off) != hipSuccess) {
         delete g;
         return ctx->fail(EACHAM_ERR_HIP, "graph_create: allocating %zu bytes failed", off);
@@ -175,13 +179,15 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     g->excluded = (unsigned char*)(base + o_excl); g->kp_offsets = (long long*)(base + o_kpo); g->has3d = (unsigned char*)(base + o_h3);
     g->edge_counts = (unsigned*)(base + o_ec); g->best = (unsigned*)(base + o_best);
     g->src_offsets = (long long*)(base + o_src);
+    g->pair_ptr = (long long*)(base + o_pptr);
     hipStream_t st = ctx->stream;
     bool ok = hipMemsetAsync(base, 0, off, st) == hipSuccess;
     auto up = [&](void* dst, const void* src, size_t bytes) { return !bytes || hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st) == hipSuccess; };
     ok = ok && up(g->pairs, e_pairs.data(), sizeof(int) * e_pairs.size()) && up(g->counts, e_counts.data(), sizeof(int) * e_counts.size()) &&
          up(g->offsets, e_off.data(), sizeof(long long) * e_off.size()) && up(g->q, e_q.data(), sizeof(unsigned) * e_q.size()) &&
          up(g->t, e_t.data(), sizeof(unsigned) * e_t.size()) && up(g->kp_offsets, kp_offsets, sizeof(long long) * ((size_t)n_frames + 1)) &&
-         up(g->src_offsets, e_src.data(), sizeof(long long) * e_src.size());
+         up(g->src_offsets, e_src.data(), sizeof(long long) * e_src.size()) &&
+         up(g->pair_ptr, pair_ptr.data(), sizeof(long long) * pair_ptr.size());
     ok = ok && hipStreamSynchronize(st) == hipSuccess;   // (the host vectors die here)
     if (!ok) {
         (void)hipFree(g->dev);
@@ -199,6 +205,8 @@ extern "C" void eacham_graph_destroy(eacham_graph* g) {
         (void)hipSetDevice(g->ctx->device);
         (void)hipStreamSynchronize(g->ctx->stream);
         if (g->dev) (void)hipFree(g->dev);
+        if (g->xy) (void)hipFree(g->xy);
+        if (g->keep_mask) (void)hipFree(g->keep_mask);
     }
     delete g;
 }

@@ -1,0 +1,271 @@
+// graph_verify.hip — LMedS verification of every edge of a RESIDENT match graph (eacham_graph_set_keypoints, eacham_graph_verify), gfx950.
+//
+// What a caller of eacham_lmeds_batch does on the host for a whole graph — walk the matches and gather (uv1, uv2) per pair, draw
+// every pair's minimal samples, pack and upload 32 bytes per match plus the sample lists, download a mask byte per match and upload
+// it again as the `keep` of eacham_graph_tracks — happens here where the graph lives. A PROBLEM is a caller pair of
+// eacham_graph_create, in the caller's order; its points are the pair's matches in the caller's order.
+//
+//   gv_gather           flat over the packed matches: the edge by prim::segment_of over the packed offsets, a = xy[kp_offsets[f1] + q],
+//                       b = xy[kp_offsets[f2] + t] into the call's scratch (doubles copied, nothing computed)
+//   gv_draw_counter     a thread per (pair, sample): counter_sample (include/eacham/CvSampling.hpp), the function draw_samples calls
+//   gv_draw_opencv      a thread per pair — the stream restarts from (uint64)-1 for every pair and every draw depends on the ones
+//                       before it: `iterations` cv_get_subset calls of at most 1000 attempts, for the homography with
+//                       cv_check_subset_homography on the pair's gathered points converted to float, as lmeds_samples does it; a
+//                       pair stops where getSubset gives up
+//                       both write the fixed-stride `samples` (npairs x iterations x m, -1 behind a pair's count) and the counts
+//   prim::exclusive_scan of the counts (npairs + 1 entries, the last 0) -> sample_ptr;  gv_compact -> the packed sample_idx
+//   lmeds_launch        (lmeds_batch.hip) the lb_* kernels, unchanged, on these device arrays; the per-problem results land in caller-pair
+//                       order, the mask in the packed order of the points
+//   gv_scatter_mask     the mask byte of packed match k of edge e to src_offsets[e] + k: the index space of the q / t the graph was made
+//                       from, which is what eacham_graph_tracks takes as `keep` (bytes that belong to no pair: zero)
+//
+// READ-BACKS. The number of samples is known on the host — (pairs with n >= m) x iterations — except under the OpenCV stream for the
+// homography, where checkSubset can make getSubset give up: then the total (8 bytes) is read back once through the pinned mirror.
+// The scratch is sized by the host-known bound either way; the launches cover exactly sample_ptr[npairs] samples.
+#include "context.hpp"
+#include "devprim.hpp"
+#include "../../include/eacham/CvSampling.hpp"
+
+#include <climits>
+#include <exception>
+
+namespace eacham {
+namespace {
+
+constexpr int GV = 256;
+constexpr int GV_PAIR = 64;   // gv_draw_opencv: a thread per pair
+
+__device__ __forceinline__ long long gv_gid(int block) { return (long long)blockIdx.x * block + threadIdx.x; }
+
+__global__ __launch_bounds__(GV) void gv_gather_kernel(long long n_matches, const int2* __restrict__ pairs, int n_edges,
+                                                       const long long* __restrict__ offsets, const unsigned* __restrict__ q,
+                                                       const unsigned* __restrict__ t, const long long* __restrict__ kp_offsets,
+                                                       const double2* __restrict__ xy, double2* __restrict__ a, double2* __restrict__ b) {
+    const long long k = gv_gid(GV);
+    if (k >= n_matches) return;
+    const int2 pr = pairs[prim::segment_of(offsets, n_edges, k)];
+    a[k] = xy[kp_offsets[pr.x] + q[k]];
+    b[k] = xy[kp_offsets[pr.y] + t[k]];
+}
+
+// every pair with n >= M gets exactly `iterations` samples; the grid has max(iterations, 1) threads per pair so that the counts are
+// written when no sample is asked for
+template <int M>
+__global__ __launch_bounds__(GV) void gv_draw_counter_kernel(int P, int iterations, const long long* __restrict__ pair_ptr,
+                                                             const unsigned long long* __restrict__ seeds, int* __restrict__ samples,
+                                                             int* __restrict__ n_samples, long long* __restrict__ cnt) {
+    const int per = iterations > 0 ? iterations : 1;
+    const long long g = gv_gid(GV);
+    if (g >= (long long)P * per) return;
+    const int p = (int)(g / per), it = (int)(g % per);
+    const long long n = pair_ptr[p + 1] - pair_ptr[p];
+    if (it == 0) {
+        const int c = n >= M ? iterations : 0;
+        n_samples[p] = c;
+        cnt[p] = c;
+        if (p == 0) cnt[P] = 0;
+    }
+    if (it >= iterations) return;
+    int32_t idx[M];
+#pragma unroll
+    for (int k = 0; k < M; ++k) idx[k] = -1;
+    if (n >= M) hip::counter_sample((int)n, M, seeds ? (uint64_t)seeds[p] : 12345ull, it, idx);
+#pragma unroll
+    for (int k = 0; k < M; ++k) samples[g * M + k] = idx[k];
+}
+
+template <int M, bool HOMOGRAPHY>
+__global__ __launch_bounds__(GV_PAIR) void gv_draw_opencv_kernel(int P, int iterations, const long long* __restrict__ pair_ptr,
+                                                                 const double* __restrict__ a, const double* __restrict__ b,
+                                                                 int* __restrict__ samples, int* __restrict__ n_samples,
+                                                                 long long* __restrict__ cnt) {
+    const long long p = gv_gid(GV_PAIR);
+    if (p >= P) return;
+    const long long base = pair_ptr[p], n = pair_ptr[p + 1] - base;
+    int* out = samples + (size_t)p * iterations * M;
+    int done = 0;
+    if (n >= M) {
+        const double* pa = a + 2 * base;
+        const double* pb = b + 2 * base;
+        hip::CvRNG rng(0xffffffffffffffffull);
+        for (; done < iterations; ++done) {
+            int32_t idx[M];
+            const bool found = hip::cv_get_subset(rng, (int)n, M, idx, 1000, [&](const int32_t* s) {
+                if constexpr (!HOMOGRAPHY) {
+                    return true;
+                } else {
+                    float fa[8], fb[8];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        fa[2 * k] = (float)pa[2 * (size_t)s[k]], fa[2 * k + 1] = (float)pa[2 * (size_t)s[k] + 1];
+                        fb[2 * k] = (float)pb[2 * (size_t)s[k]], fb[2 * k + 1] = (float)pb[2 * (size_t)s[k] + 1];
+                    }
+                    return hip::cv_check_subset_homography(fa, fb, 4);
+                }
+            });
+            if (!found) break;
+#pragma unroll
+            for (int k = 0; k < M; ++k) out[done * M + k] = idx[k];
+        }
+    }
+    for (int i = done * M; i < iterations * M; ++i) out[i] = -1;
+    n_samples[p] = done;
+    cnt[p] = done;
+    if (p == 0) cnt[P] = 0;
+}
+
+// sample `it` of pair p, if the pair has that many, to its place in the packed list the lb_* kernels read
+template <int M>
+__global__ __launch_bounds__(GV) void gv_compact_kernel(int P, int iterations, const long long* __restrict__ sample_ptr,
+                                                        const int* __restrict__ samples, int* __restrict__ sample_idx) {
+    const long long g = gv_gid(GV);
+    if (g >= (long long)P * iterations) return;
+    const int p = (int)(g / iterations), it = (int)(g % iterations);
+    const long long s0 = sample_ptr[p];
+    if (it >= sample_ptr[p + 1] - s0) return;
+#pragma unroll
+    for (int k = 0; k < M; ++k) sample_idx[(s0 + it) * M + k] = samples[g * M + k];
+}
+
+__global__ __launch_bounds__(GV) void gv_scatter_mask_kernel(long long n_matches, int n_edges, const long long* __restrict__ offsets,
+                                                             const long long* __restrict__ src_offsets,
+                                                             const unsigned char* __restrict__ packed, unsigned char* __restrict__ out) {
+    const long long k = gv_gid(GV);
+    if (k >= n_matches) return;
+    const int e = prim::segment_of(offsets, n_edges, k);
+    out[src_offsets[e] + (k - offsets[e])] = packed[k];
+}
+
+inline unsigned gv_blocks(long long n, int block) { return (unsigned)((n + block - 1) / block); }
+
+template <class Body>
+int verify_entry(eacham_ctx* ctx, const char* what, Body body) {   // nothing may leave extern "C"
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    try {
+        return body();
+    } catch (const std::exception& e) {
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: %s", what, e.what());
+    } catch (...) {
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: unknown exception", what);
+    }
+}
+
+}  // namespace
+}  // namespace eacham
+
+using namespace eacham;
+
+extern "C" int eacham_graph_set_keypoints(eacham_graph* g, const double* xy) {
+    if (!g) return EACHAM_ERR_INVALID;
+    eacham_ctx* ctx = g->ctx;
+    return verify_entry(ctx, "graph_set_keypoints", [&]() -> int {
+        if (g->n_kp > 0 && !xy) return ctx->fail(EACHAM_ERR_INVALID, "graph_set_keypoints: null xy for a graph with %lld keypoints", g->n_kp);
+        EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const size_t bytes = 2 * sizeof(double) * (size_t)g->n_kp;
+        if (!g->xy) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->xy, std::max<size_t>(bytes, 16)));
+        g->has_xy = g->has_keep = false;   // new coordinates: a mask retained for the old ones says nothing about them
+        if (bytes) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(g->xy, xy, bytes, hipMemcpyHostToDevice, ctx->stream));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the caller's buffer may die when this call returns)
+        g->has_xy = true;
+        return EACHAM_OK;
+    });
+}
+
+extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
+                                   double* models, float* medians, float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner,
+                                   int32_t* n_candidates, int32_t* n_samples, int32_t* samples) {
+    if (!g) return EACHAM_ERR_INVALID;
+    eacham_ctx* ctx = g->ctx;
+    return verify_entry(ctx, "graph_verify", [&]() -> int {
+        if (!g->has_xy) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: the graph has no keypoint coordinates (eacham_graph_set_keypoints)");
+        if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown kind %d", kind);
+        if (sampling != EACHAM_SAMPLING_OPENCV && sampling != EACHAM_SAMPLING_COUNTER)
+            return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown sampling %d", sampling);
+        if (iterations < 0) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: negative iterations");
+        const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4;
+        const int P = g->npairs, m = homography ? 4 : 5, maxm = homography ? 1 : 10;
+        if (P == 0) return EACHAM_OK;
+        long long n_ok = 0, max_n = 0;   // pairs with a minimal sample's worth of matches; the largest of them
+        for (int p = 0; p < P; ++p)
+            if (g->pair_counts_h[p] >= m) ++n_ok, max_n = std::max<long long>(max_n, g->pair_counts_h[p]);
+        const long long NP = g->n_matches, S_cap = n_ok * iterations, slots = (long long)P * iterations;
+        if (NP > INT_MAX / 2 || P == INT_MAX || slots * m > INT_MAX || S_cap * maxm > INT_MAX)
+            return ctx->fail(EACHAM_ERR_CAPACITY, "graph_verify: %lld points / %d pairs x %d samples in one call", NP, P, iterations);
+        EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (retain && !g->keep_mask) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->keep_mask, std::max<size_t>((size_t)g->n_src, 16)));
+        const bool need_rows = lmeds_needs_rows(max_n), count_known = !(homography && sampling == EACHAM_SAMPLING_OPENCV);
+        const long long cand_cap = S_cap * maxm;
+        const int score_grid = lmeds_score_grid(cand_cap, max_n);
+        hipStream_t st = ctx->stream;
+        IoStage io(ctx, st);
+        const auto h_total = io.out<long long>(nullptr, 1);   // first: offset 0, always inside the pinned mirror
+        const auto h_om = io.out<double>(models, 9 * (size_t)P);
+        const auto h_omed = io.out<float>(medians, (size_t)P), h_othr = io.out<float>(thresholds, (size_t)P);
+        const auto h_oinl = io.out<int>(inliers, (size_t)P), h_owin = io.out<int>(winner, 3 * (size_t)P), h_onc = io.out<int>(n_candidates, (size_t)P);
+        const auto h_ons = io.out<int>(n_samples, (size_t)P), h_osamp = io.out<int>(samples, (size_t)slots * m);
+        const auto h_omask = io.out<unsigned char>(masks, (size_t)g->n_src);
+        const auto h_K = io.in<double>(K, 4);
+        const auto h_seeds = io.in<unsigned long long>(seeds, (size_t)P);
+        const auto h_a = io.scratch<double2>((size_t)NP), h_b = io.scratch<double2>((size_t)NP);
+        const auto h_cnt = io.scratch<long long>((size_t)P + 1), h_sp = io.scratch<long long>((size_t)P + 1);
+        const auto h_spws = io.scratch<long long>(prim::scan_ws_elems((size_t)P + 1));
+        const auto h_i = io.scratch<int>((size_t)S_cap * m);
+        const auto h_m = io.scratch<double>(9 * (size_t)cand_cap);
+        const auto h_n = io.scratch<int>((size_t)S_cap), h_first = io.scratch<int>((size_t)S_cap), h_sprob = io.scratch<int>((size_t)S_cap);
+        const auto h_tot = io.scratch<int>(1), h_ws = io.scratch<int>(prim::scan_ws_elems((size_t)S_cap));
+        const auto h_cmed = io.scratch<float>((size_t)cand_cap);
+        const auto h_rows = io.scratch<float>(need_rows ? (size_t)score_grid * (size_t)max_n : 0);
+        const auto h_pmask = io.scratch<unsigned char>((size_t)NP);
+        IoDev d;
+        if (int rc = io.upload(d)) return rc;
+        const double* d_a = (const double*)d(h_a);
+        const double* d_b = (const double*)d(h_b);
+        {   // (profiling: the gather, the draws and the mask's scatter count with the scorer's stage, as the LMedS kernels do)
+            ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+            if (NP > 0)
+                gv_gather_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->pairs, g->n_edges, g->offsets, g->q, g->t, g->kp_offsets, (const double2*)g->xy,
+                                                                   d(h_a), d(h_b));
+            if (sampling == EACHAM_SAMPLING_COUNTER) {
+                const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
+                const unsigned long long* d_seeds = seeds ? d(h_seeds) : nullptr;
+                if (homography) gv_draw_counter_kernel<4><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+                else gv_draw_counter_kernel<5><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+            } else {
+                const unsigned grid = gv_blocks(P, GV_PAIR);
+                if (homography) gv_draw_opencv_kernel<4, true><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+                else gv_draw_opencv_kernel<5, false><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+            }
+            prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
+            if (slots > 0) {
+                if (homography) gv_compact_kernel<4><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+                else gv_compact_kernel<5><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+            }
+        }
+        EACHAM_HIP_TRY(ctx, hipGetLastError());
+        long long S = S_cap;
+        if (!count_known) {
+            const size_t at = io.lay.off[h_total.k];
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->io_host + at, d(h_total), sizeof(long long), hipMemcpyDeviceToHost, st));
+            EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+            S = *(volatile const long long*)((char*)ctx->io_host + at);
+            if (S < 0 || S > S_cap) return ctx->fail(EACHAM_ERR_HIP, "graph_verify: %lld samples drawn, at most %lld possible", S, S_cap);
+        }
+        const LmedsLaunch L{kind, P, S, max_n, score_grid, g->pair_ptr, d(h_sp), d_a, d_b, d(h_K), K != nullptr, d(h_i),
+                            d(h_m), d(h_n), d(h_first), d(h_sprob), d(h_tot), d(h_ws), d(h_cmed), d(h_rows),
+                            d(h_om), d(h_omed), d(h_othr), d(h_oinl), d(h_pmask), d(h_owin), d(h_onc)};
+        if (int rc = lmeds_launch(ctx, st, L)) return rc;
+        {
+            ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+            if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemsetAsync(d(h_omask), 0, (size_t)g->n_src, st));
+            if (NP > 0) gv_scatter_mask_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->n_edges, g->offsets, g->src_offsets, d(h_pmask), d(h_omask));
+            EACHAM_HIP_TRY(ctx, hipGetLastError());
+            if (retain) {
+                g->has_keep = false;
+                if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(g->keep_mask, d(h_omask), (size_t)g->n_src, hipMemcpyDeviceToDevice, st));
+            }
+        }
+        if (int rc = io.finish()) return rc;
+        if (retain) g->has_keep = true;
+        return EACHAM_OK;
+    });
+}

@@ -253,6 +253,50 @@ constexpr int LB_SCORE_GRID = 4096;      // workgroups striding over the candida
 constexpr int LB_SCORE_GRID_ROWS = 1024; // ... when each carries an error row of the largest problem (> SC_MAX_LDS points)
 
 }  // namespace
+
+bool lmeds_needs_rows(long long max_n) { return max_n > SC_MAX_LDS; }
+int lmeds_score_grid(long long cand_cap, long long max_n) {
+    return (int)std::max<long long>(1, std::min<long long>(cand_cap, lmeds_needs_rows(max_n) ? LB_SCORE_GRID_ROWS : LB_SCORE_GRID));
+}
+
+int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L) {
+    const int P = L.P, maxm = L.kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
+    const long long S = L.S, max_n = L.max_n;
+    const bool need_rows = lmeds_needs_rows(max_n);
+    const double* d_K = L.has_K ? L.K : nullptr;
+    const int normalise = L.has_K && L.kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
+    ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+    if (S > 0) {
+        const unsigned grid = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
+        if (L.kind == EACHAM_SOLVE_HOMOGRAPHY4)
+            lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.point_ptr, L.sample_ptr, P, L.a, L.b, (int)S, L.sample_idx, L.cand_models, L.n_models,
+                                                                  L.sample_problem);
+        else
+            lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.point_ptr, L.sample_ptr, P, L.a, L.b, L.K, L.has_K ? 1 : 0, (int)S, L.sample_idx,
+                                                                  L.cand_models, L.n_models, L.sample_problem);
+    }
+    prim::exclusive_scan<int>(st, L.n_models, L.first, (int)S, L.scan_ws, L.total);   // (no samples: *total = 0)
+    const size_t smem = sizeof(unsigned) * (size_t)std::max<long long>(1, std::min<long long>(max_n, SC_MAX_LDS));
+#define EACHAM_LB_LAUNCH(KIND)                                                                                                                     \
+    do {                                                                                                                                           \
+        if (S > 0) {                                                                                                                               \
+            if (smem > 48 * 1024)                                                                                                                  \
+                EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)lb_score_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
+            lb_score_kernel<KIND><<<L.score_grid, SC_BLOCK, smem, st>>>(L.point_ptr, L.a, L.b, d_K, normalise, (int)S, L.first, L.total,           \
+                                                                        L.sample_problem, L.cand_models, maxm, L.cand_medians,                     \
+                                                                        need_rows ? L.rows : nullptr, (size_t)max_n);                              \
+        }                                                                                                                                          \
+        lb_select_kernel<KIND><<<P, SC_BLOCK, 0, st>>>(L.point_ptr, L.sample_ptr, L.a, L.b, d_K, normalise, (int)S, L.first, L.total,              \
+                                                       L.cand_models, maxm, L.cand_medians, L.models, L.medians, L.thresholds, L.inliers,          \
+                                                       L.masks, L.winner, L.n_candidates);                                                         \
+    } while (0)
+    if (L.kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_LB_LAUNCH(0);
+    else EACHAM_LB_LAUNCH(1);
+#undef EACHAM_LB_LAUNCH
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    return EACHAM_OK;
+}
+
 }  // namespace eacham
 
 using namespace eacham;
@@ -284,9 +328,9 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
                 return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: problem %d: sample index %d of %lld points", p, (int)sample_idx[k], n);
     }
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const bool need_rows = max_n > SC_MAX_LDS;
+    const bool need_rows = lmeds_needs_rows(max_n);
     const long long cand_cap = S * maxm;
-    const int score_grid = (int)std::max<long long>(1, std::min<long long>(cand_cap, need_rows ? LB_SCORE_GRID_ROWS : LB_SCORE_GRID));
+    const int score_grid = lmeds_score_grid(cand_cap, max_n);
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
     const auto h_om = io.out<double>(models, 9 * (size_t)P);
@@ -304,38 +348,9 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
     const auto h_rows = io.scratch<float>(need_rows ? (size_t)score_grid * (size_t)max_n : 0);
     IoDev d;
     if (int rc = io.upload(d)) return rc;
-    const long long *d_pp = d(h_pp), *d_sp = d(h_sp);
-    const double *d_a = d(h_a), *d_b = d(h_b), *d_K = K ? d(h_K) : nullptr;
-    double* d_m = d(h_m);
-    int *d_n = d(h_n), *d_first = d(h_first), *d_sprob = d(h_sprob), *d_tot = d(h_tot);
-    float* d_cmed = d(h_cmed);
-    const int normalise = K && kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
-    {
-        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
-        if (S > 0) {
-            const unsigned grid = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
-            if (kind == EACHAM_SOLVE_HOMOGRAPHY4)
-                lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, (int)S, d(h_i), d_m, d_n, d_sprob);
-            else
-                lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d_pp, d_sp, P, d_a, d_b, d(h_K), K ? 1 : 0, (int)S, d(h_i), d_m, d_n, d_sprob);
-        }
-        prim::exclusive_scan<int>(st, d_n, d_first, (int)S, d(h_ws), d_tot);   // (no samples: *total = 0)
-        const size_t smem = sizeof(unsigned) * (size_t)std::max<long long>(1, std::min<long long>(max_n, SC_MAX_LDS));
-#define EACHAM_LB_LAUNCH(KIND)                                                                                                                     \
-    do {                                                                                                                                           \
-        if (S > 0) {                                                                                                                               \
-            if (smem > 48 * 1024)                                                                                                                  \
-                EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)lb_score_kernel<KIND>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem)); \
-            lb_score_kernel<KIND><<<score_grid, SC_BLOCK, smem, st>>>(d_pp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_sprob, d_m, maxm, \
-                                                                      d_cmed, need_rows ? d(h_rows) : nullptr, (size_t)max_n);                \
-        }                                                                                                                                          \
-        lb_select_kernel<KIND><<<P, SC_BLOCK, 0, st>>>(d_pp, d_sp, d_a, d_b, d_K, normalise, (int)S, d_first, d_tot, d_m, maxm, d_cmed,             \
-                                                       d(h_om), d(h_omed), d(h_othr), d(h_oinl), d(h_omask), d(h_owin), d(h_onc));                 \
-    } while (0)
-        if (kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_LB_LAUNCH(0);
-        else EACHAM_LB_LAUNCH(1);
-#undef EACHAM_LB_LAUNCH
-    }
-    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    const LmedsLaunch L{kind, P, S, max_n, score_grid, d(h_pp), d(h_sp), d(h_a), d(h_b), d(h_K), K != nullptr, d(h_i),
+                        d(h_m), d(h_n), d(h_first), d(h_sprob), d(h_tot), d(h_ws), d(h_cmed), d(h_rows),
+                        d(h_om), d(h_omed), d(h_othr), d(h_oinl), d(h_omask), d(h_owin), d(h_onc)};
+    if (int rc = lmeds_launch(ctx, st, L)) return rc;
     return io.finish();
 }

@@ -418,32 +418,52 @@ extern "C" int eacham_tracks_build(eacham_ctx* ctx, int n_frames, const int32_t*
     });
 }
 
+// eacham_graph_tracks / eacham_graph_tracks_verified: `keep_dev` is a mask already on the device (the one a verify call retained), else
+// `keep` is the caller's host array or null
+static int graph_tracks_run(eacham_graph* gr, const uint8_t* keep, const unsigned char* keep_dev, int min_len, int conflict_policy, int64_t cap_obs,
+                            int32_t cap_tracks, int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame, uint32_t* obs_kp,
+                            uint8_t* track_flags, int32_t* node_track) {
+    eacham_ctx* ctx = gr->ctx;
+    const TracksOut out{cap_obs, cap_tracks, n_tracks, n_obs, track_ptr, obs_frame, obs_kp, track_flags};
+    if (int rc = tracks_check_common(ctx, min_len, conflict_policy, cap_obs, cap_tracks, out)) return rc;
+    if (gr->n_kp > INT_MAX || gr->n_matches > INT_MAX)
+        return ctx->fail(EACHAM_ERR_CAPACITY, "graph_tracks: %lld nodes and %lld matches, at most 2^31 - 1 of each in one call", gr->n_kp, gr->n_matches);
+    if (gr->n_matches == 0 || gr->n_kp == 0) return tracks_empty(ctx, gr->n_kp, out, node_track);
+    if (int rc = tracks_check_sort(ctx, gr->n_kp, gr->n_matches)) return rc;
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const TracksPlan pl(gr->n_kp, gr->n_matches);
+    ctx->tracks_round_cap = pl.round_cap;
+    IoStage io(ctx, ctx->stream);
+    const auto h_words = io.out<int>(nullptr, N_WORDS);
+    const auto h_nt = io.out<int>(node_track, (size_t)gr->n_kp);
+    const auto h_keep = io.in<unsigned char>(keep, keep && !keep_dev ? (size_t)gr->n_src : 0);
+    const auto h_sc = io.scratch<char>(pl.total);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    // the resident match lists are packed in edge order (offsets); src_offsets says where each began in the arrays `keep` indexes
+    const TracksGraphDev g{gr->n_frames, gr->n_edges, gr->n_kp, gr->n_matches, gr->pairs, gr->offsets, gr->offsets, gr->src_offsets,
+                           gr->kp_offsets, gr->q, gr->t, keep_dev ? keep_dev : keep ? d(h_keep) : nullptr};
+    return tracks_run(ctx, io, pl, g, d(h_words), io.lay.off[h_words.k], d(h_nt), d(h_sc), min_len, conflict_policy, out);
+}
+
 extern "C" int eacham_graph_tracks(eacham_graph* gr, const uint8_t* keep, int min_len, int conflict_policy, int64_t cap_obs,
                                    int32_t cap_tracks, int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame,
                                    uint32_t* obs_kp, uint8_t* track_flags, int32_t* node_track) {
     if (!gr) return EACHAM_ERR_INVALID;
-    eacham_ctx* ctx = gr->ctx;
-    return tracks_entry(ctx, [&]() -> int {
-        const TracksOut out{cap_obs, cap_tracks, n_tracks, n_obs, track_ptr, obs_frame, obs_kp, track_flags};
-        if (int rc = tracks_check_common(ctx, min_len, conflict_policy, cap_obs, cap_tracks, out)) return rc;
-        if (gr->n_kp > INT_MAX || gr->n_matches > INT_MAX)
-            return ctx->fail(EACHAM_ERR_CAPACITY, "graph_tracks: %lld nodes and %lld matches, at most 2^31 - 1 of each in one call", gr->n_kp, gr->n_matches);
-        if (gr->n_matches == 0 || gr->n_kp == 0) return tracks_empty(ctx, gr->n_kp, out, node_track);
-        if (int rc = tracks_check_sort(ctx, gr->n_kp, gr->n_matches)) return rc;
-        EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const TracksPlan pl(gr->n_kp, gr->n_matches);
-        ctx->tracks_round_cap = pl.round_cap;
-        IoStage io(ctx, ctx->stream);
-        const auto h_words = io.out<int>(nullptr, N_WORDS);
-        const auto h_nt = io.out<int>(node_track, (size_t)gr->n_kp);
-        const auto h_keep = io.in<unsigned char>(keep, keep ? (size_t)gr->n_src : 0);
-        const auto h_sc = io.scratch<char>(pl.total);
-        IoDev d;
-        if (int rc = io.upload(d)) return rc;
-        // the resident match lists are packed in edge order (offsets); src_offsets says where each began in the arrays `keep` indexes
-        const TracksGraphDev g{gr->n_frames, gr->n_edges, gr->n_kp, gr->n_matches, gr->pairs, gr->offsets, gr->offsets, gr->src_offsets,
-                               gr->kp_offsets, gr->q, gr->t, keep ? d(h_keep) : nullptr};
-        return tracks_run(ctx, io, pl, g, d(h_words), io.lay.off[h_words.k], d(h_nt), d(h_sc), min_len, conflict_policy, out);
+    return tracks_entry(gr->ctx, [&]() -> int {
+        return graph_tracks_run(gr, keep, nullptr, min_len, conflict_policy, cap_obs, cap_tracks, n_tracks, n_obs, track_ptr, obs_frame, obs_kp,
+                                track_flags, node_track);
+    });
+}
+
+extern "C" int eacham_graph_tracks_verified(eacham_graph* gr, int min_len, int conflict_policy, int64_t cap_obs, int32_t cap_tracks,
+                                            int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame, uint32_t* obs_kp,
+                                            uint8_t* track_flags, int32_t* node_track) {
+    if (!gr) return EACHAM_ERR_INVALID;
+    return tracks_entry(gr->ctx, [&]() -> int {
+        if (!gr->has_keep) return gr->ctx->fail(EACHAM_ERR_INVALID, "graph_tracks_verified: no verify call has retained a mask in this graph");
+        return graph_tracks_run(gr, nullptr, gr->keep_mask, min_len, conflict_policy, cap_obs, cap_tracks, n_tracks, n_obs, track_ptr, obs_frame,
+                                obs_kp, track_flags, node_track);
     });
 }
 

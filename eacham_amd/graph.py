@@ -8,6 +8,8 @@ i.e. the two Graph::Connect calls of apps/sfm/main.cpp:144-145.
 """
 from __future__ import annotations
 
+from typing import NamedTuple
+
 import numpy as np
 
 from .matcher import HipContext
@@ -47,6 +49,41 @@ def best_pair_for_valid(ctx: HipContext, n_frames: int, pairs, counts, offsets, 
     return (out, ec) if want_edge_counts else out
 
 
+SAMPLINGS = {"opencv": 0, "counter": 1}
+
+
+class GraphVerify(NamedTuple):
+    """eacham_graph_verify: the LmedsBatch fields per caller pair, the mask in the caller's match index space, the samples drawn."""
+    models: np.ndarray        # [npairs, 9] float64: the winning model as solved (zeros: none)
+    medians: np.ndarray       # [npairs] float32 (NaN: none)
+    thresholds: np.ndarray    # [npairs] float32
+    inliers: np.ndarray       # [npairs] int32
+    masks: np.ndarray         # [n_src] uint8, indexed like the q / t the graph was made from: the `keep` of ResidentGraph.tracks
+    winner: np.ndarray        # [npairs, 3] int32: candidate, sample, root (-1 -1 -1: none)
+    n_candidates: np.ndarray  # [npairs] int32
+    n_samples: np.ndarray     # [npairs] int32: the samples each pair used
+    samples: np.ndarray | None  # [npairs, iterations, m] int32, -1 behind a pair's n_samples (want_samples)
+
+
+def lmeds_iterations(kind: str, max_iters: int | None = None, confidence: float | None = None) -> int:
+    """The samples LMeDSPointSetRegistrator::run asks for, as twoview_detail::lmeds computes them: RANSACUpdateNumIters at an
+    assumed outlier ratio of 0.45, at least 3, at most max_iters. Defaults: the reference's calls (essential 1000 / 0.99 -> 89,
+    homography 100 / 0.999 -> 72)."""
+    import math
+    essential = kind.startswith("essential")
+    m = 5 if essential else 4
+    max_iters = (1000 if essential else 100) if max_iters is None else int(max_iters)
+    p = min(max((0.99 if essential else 0.999) if confidence is None else float(confidence), 0.0), 1.0)
+    tiny = np.finfo(np.float64).tiny
+    num, denom = max(1.0 - p, tiny), 1.0 - (1.0 - 0.45) ** m
+    if denom < tiny:
+        n = 0
+    else:
+        ln, ld = math.log(num), math.log(denom)
+        n = max_iters if ld >= 0 or -ln >= max_iters * (-ld) else int(math.floor(ln / ld + 0.5))
+    return max(min(max_iters, max(n, 3)), 0)
+
+
 class ResidentGraph:
     """eacham_graph_create / _set_frame / _query: the match graph uploaded once, the per-frame state set frame by frame,
     the query two small kernels — what the incremental loop of apps/sfm/main.cpp:188-214 uses after every frame it adds."""
@@ -66,6 +103,58 @@ class ResidentGraph:
                                               q.ctypes.data, t.ctypes.data, kpo.ctypes.data, C.byref(h)))
         self._h = h
         self._n_nodes, self._n_matches = int(kpo[-1]), int(counts[counts > 0].sum())
+        self._npairs = int(pairs.shape[0])
+        ends = offsets[:counts.size] + counts    # (offsets may carry the CSR's closing entry)
+        self._n_src = int(ends[counts > 0].max()) if (counts > 0).any() else 0   # the length of a `keep` mask
+
+    def set_keypoints(self, xy):
+        """eacham_graph_set_keypoints: the pixel coordinates of every keypoint, frame-major ([total keypoints, 2], or a list of
+        per-frame [n_f, 2] arrays). Uploaded once; a later call replaces them and drops a retained mask."""
+        if isinstance(xy, (list, tuple)):
+            xy = np.concatenate([np.asarray(a, dtype=np.float64).reshape(-1, 2) for a in xy]) if len(xy) else np.zeros((0, 2))
+        xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1, 2)
+        if xy.shape[0] != self._n_nodes:
+            raise ValueError(f"xy has {xy.shape[0]} rows, the graph {self._n_nodes} keypoints")
+        self.ctx._check(self.ctx._L.eacham_graph_set_keypoints(self._h, xy.ctypes.data if xy.size else None))
+
+    def verify(self, kind: str, K=None, sampling: str = "opencv", iterations: int | None = None, seeds=None, retain: bool = False,
+               want_samples: bool = False) -> GraphVerify:
+        """eacham_graph_verify: LMedS ("essential" with K = fx fy cx cy or None for normalised points, or "homography") for every
+        pair of the graph, gathered, sampled and solved on the device. iterations defaults to lmeds_iterations(kind); seeds: one
+        per pair for sampling="counter" (None: 12345). retain=True keeps the mask on the device for tracks_verified()."""
+        from . import capi
+        homography = kind.startswith("homography")
+        if not homography and not kind.startswith("essential"):
+            raise ValueError(f"unknown kind {kind!r}")
+        k, m = (capi.SOLVE_HOMOGRAPHY4, 4) if homography else (capi.SOLVE_ESSENTIAL5, 5)
+        its = lmeds_iterations(kind) if iterations is None else int(iterations)
+        return self._verify_raw(k, m, K, SAMPLINGS[sampling], its, seeds, retain, want_samples)
+
+    def _verify_raw(self, k: int, m: int, K, sampling: int, its: int, seeds, retain: bool, want_samples: bool, preset=None) -> GraphVerify:
+        """The call itself on integer codes (nothing is checked here: the library's own checks answer). preset: a value every
+        output array is filled with beforehand (tests of the error paths)."""
+        P = self._npairs
+        K4 = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != P:
+            raise ValueError("one seed per pair")
+        fill = 0 if preset is None else preset
+        models = np.full((P, 9), fill, dtype=np.float64)
+        med, thr = np.full(P, fill, dtype=np.float32), np.full(P, fill, dtype=np.float32)
+        inl, nc, ns = np.full(P, fill, dtype=np.int32), np.full(P, fill, dtype=np.int32), np.full(P, fill, dtype=np.int32)
+        win = np.full((P, 3), fill, dtype=np.int32)
+        masks = np.full(self._n_src, fill, dtype=np.uint8)
+        samples = np.full((P, max(its, 0), m), fill, dtype=np.int32) if want_samples else None
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data   # noqa: E731
+        self.ctx._check(self.ctx._L.eacham_graph_verify(
+            self._h, k, ptr(K4), sampling, its, ptr(sd), int(bool(retain)), ptr(models), ptr(med), ptr(thr), ptr(inl), ptr(masks), ptr(win),
+            ptr(nc), ptr(ns), ptr(samples)))
+        return GraphVerify(models, med, thr, inl, masks, win, nc, ns, samples)
+
+    def tracks_verified(self, min_len: int = 2, conflict_policy: int = 0, cap_obs=None, cap_tracks=None):
+        """eacham_graph_tracks_verified: tracks() with the mask the last verify(retain=True) left on the device; nothing is uploaded."""
+        from .tracks import graph_tracks_verified
+        return graph_tracks_verified(self.ctx, self._h, self._n_nodes, self._n_matches, min_len, conflict_policy, cap_obs, cap_tracks)
 
     def tracks(self, keep=None, min_len: int = 2, conflict_policy: int = 0, cap_obs=None, cap_tracks=None):
         """eacham_graph_tracks: the multi-view tracks of the resident graph (eacham_amd/tracks.py); only `keep` — a byte per match,

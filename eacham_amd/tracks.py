@@ -110,6 +110,16 @@ def graph_tracks(ctx: HipContext, graph_handle, n_nodes: int, n_matches: int, ke
     return out.result()
 
 
+def graph_tracks_verified(ctx: HipContext, graph_handle, n_nodes: int, n_matches: int, min_len: int = 2, conflict_policy: int = CONFLICT_FLAG,
+                          cap_obs: int | None = None, cap_tracks: int | None = None) -> Tracks:
+    """eacham_graph_tracks_verified: the tracks of a resident graph under the mask its last verify(retain=True) left on the device
+    (ResidentGraph.tracks_verified calls this)."""
+    bound_obs, bound_tracks = output_bounds(n_nodes, n_matches)
+    out = _Out(n_nodes, bound_obs if cap_obs is None else cap_obs, bound_tracks if cap_tracks is None else cap_tracks)
+    ctx._check(ctx._L.eacham_graph_tracks_verified(graph_handle, int(min_len), int(conflict_policy), *out.args()))
+    return out.result()
+
+
 def last_call_info(ctx: HipContext) -> dict:
     """eacham_tracks_debug_last: rounds of the last track-building call on this context, their cap, its read-backs of status words,
     and the device time by HIP events (-1 unless profiling is enabled on the context)."""
@@ -118,4 +128,4 @@ def last_call_info(ctx: HipContext) -> dict:
     return {"rounds": int(r.value), "round_cap": int(cap.value), "readbacks": int(rb.value), "kernel_ms": float(ms.value)}
 
 
-__all__ = ["Tracks", "build_tracks", "graph_tracks", "last_call_info", "output_bounds", "kp_offsets_of", "CONFLICT_FLAG", "CONFLICT_DROP"]
+__all__ = ["Tracks", "build_tracks", "graph_tracks", "graph_tracks_verified", "last_call_info", "output_bounds", "kp_offsets_of", "CONFLICT_FLAG", "CONFLICT_DROP"]

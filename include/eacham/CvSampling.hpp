@@ -23,6 +23,16 @@
 #include <cstdint>
 #include <vector>
 
+// The streams below are stated ONCE for the host and for the kernels that draw on the device (eacham_amd/csrc/graph_verify.hip):
+// EACHAM_HD marks what both compile; the unroll hint lets the 4 - 5 indices of a subset stay in registers there.
+#if defined(__HIPCC__)
+#define EACHAM_HD __host__ __device__
+#define EACHAM_UNROLL _Pragma("unroll")
+#else
+#define EACHAM_HD
+#define EACHAM_UNROLL
+#endif
+
 namespace eacham {
 namespace hip {
 
@@ -33,21 +43,23 @@ enum class Sampling {
 
 struct CvRNG {   // cv::RNG (core/include/opencv2/core.hpp, core/operations.hpp)
     uint64_t state;
-    explicit CvRNG(uint64_t s = 0xffffffffu) : state(s ? s : 0xffffffffu) {}
-    unsigned next() {
+    EACHAM_HD explicit CvRNG(uint64_t s = 0xffffffffu) : state(s ? s : 0xffffffffu) {}
+    EACHAM_HD unsigned next() {
         state = (uint64_t)(unsigned)state * 4164903690u + (unsigned)(state >> 32);
         return (unsigned)state;
     }
-    int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
+    EACHAM_HD int uniform(int a, int b) { return a == b ? a : (int)(next() % (unsigned)(b - a) + a); }
 };
 
 namespace cvsampling_detail {
 
 // haveCollinearPoints (fundam.cpp): only the LAST point of the subset is tested against the lines through two earlier ones
-inline bool have_collinear_points(const float* p /* count x 2 */, int count) {
+EACHAM_HD inline bool have_collinear_points(const float* p /* count x 2 */, int count) {
     const int i = count - 1;
+    EACHAM_UNROLL
     for (int j = 0; j < i; ++j) {
         const double dx1 = p[2 * j] - p[2 * i], dy1 = p[2 * j + 1] - p[2 * i + 1];   // (float differences, widened)
+        EACHAM_UNROLL
         for (int k = 0; k < j; ++k) {
             const double dx2 = p[2 * k] - p[2 * i], dy2 = p[2 * k + 1] - p[2 * i + 1];
             if (std::fabs(dx2 * dy1 - dy2 * dx1) <= FLT_EPSILON * (std::fabs(dx1) + std::fabs(dy1) + std::fabs(dx2) + std::fabs(dy2))) return true;
@@ -55,19 +67,20 @@ inline bool have_collinear_points(const float* p /* count x 2 */, int count) {
     }
     return false;
 }
-inline double det3(const double* m) {
+EACHAM_HD inline double det3(const double* m) {
     return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
 }
 
 }  // namespace cvsampling_detail
 
 // HomographyEstimatorCallback::checkSubset for a subset of `count` correspondences (src, dst: count x 2, cv::Point2f values)
-inline bool cv_check_subset_homography(const float* src, const float* dst, int count) {
+EACHAM_HD inline bool cv_check_subset_homography(const float* src, const float* dst, int count) {
     using namespace cvsampling_detail;
     if (have_collinear_points(src, count) || have_collinear_points(dst, count)) return false;
     if (count == 4) {
-        static const int tt[4][3] = {{0, 1, 2}, {1, 2, 3}, {0, 2, 3}, {0, 1, 3}};
+        constexpr int tt[4][3] = {{0, 1, 2}, {1, 2, 3}, {0, 2, 3}, {0, 1, 3}};
         int negative = 0;
+        EACHAM_UNROLL
         for (int i = 0; i < 4; ++i) {
             const int* t = tt[i];
             const double A[9] = {src[2 * t[0]], src[2 * t[0] + 1], 1.0, src[2 * t[1]], src[2 * t[1] + 1], 1.0, src[2 * t[2]], src[2 * t[2] + 1], 1.0};
@@ -82,12 +95,14 @@ inline bool cv_check_subset_homography(const float* src, const float* dst, int c
 // One getSubset call: m distinct indices out of n into idx[0..m). `check(idx)` is the callback's checkSubset (may be empty).
 // Returns false when maxAttempts subsets were refused (the registrator then stops: found == false).
 template <class Check>
-inline bool cv_get_subset(CvRNG& rng, int n, int m, int32_t* idx, int maxAttempts, Check check) {
+EACHAM_HD inline bool cv_get_subset(CvRNG& rng, int n, int m, int32_t* idx, int maxAttempts, Check check) {
     for (int iters = 0; iters < maxAttempts; ++iters) {
+        EACHAM_UNROLL
         for (int i = 0; i < m; ++i) {
             int v = rng.uniform(0, n);
             for (;;) {
                 bool dup = false;
+                EACHAM_UNROLL
                 for (int j = 0; j < i; ++j) dup = dup || idx[j] == v;
                 if (!dup) break;
                 v = rng.uniform(0, n);
@@ -97,6 +112,31 @@ inline bool cv_get_subset(CvRNG& rng, int n, int m, int32_t* idx, int maxAttempt
         if (check(idx)) return true;
     }
     return false;
+}
+
+// ---- the library's counter-based stream (Sampling::Counter): splitmix64 of (seed, sample, draw) ----
+EACHAM_HD inline uint64_t mix(uint64_t x) {
+    x += 0x9E3779B97F4A7C15ull;
+    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+// sample number `sample` of the stream of `seed`: m distinct indices out of n (n >= m) into idx[0..m)
+EACHAM_HD inline void counter_sample(int n, int m, uint64_t seed, int sample, int32_t* idx) {
+    uint64_t ctr = 0;
+    EACHAM_UNROLL
+    for (int k = 0; k < m; ++k) {
+        for (;;) {
+            const int v = (int)(mix(seed * 0x100000001B3ull + ((uint64_t)sample << 20) + ctr++) % (uint64_t)n);
+            bool dup = false;
+            EACHAM_UNROLL
+            for (int j = 0; j < k; ++j) dup = dup || idx[j] == v;
+            if (!dup) {
+                idx[k] = v;
+                break;
+            }
+        }
+    }
 }
 
 }  // namespace hip

@@ -572,6 +572,8 @@ public:
                                       g.q.data(), g.t.data(), kpo.data(), &h_));
         nodes_ = kpo.back();
         for (int32_t c : g.counts) matches_ += c > 0 ? c : 0;
+        counts_.assign(g.counts.begin(), g.counts.begin() + (long)pairs.size());
+        offsets_.assign(g.offsets.begin(), g.offsets.begin() + (long)pairs.size());
     }
     ~ResidentMatchGraph() { eacham_graph_destroy(h_); }
     ResidentMatchGraph(const ResidentMatchGraph&) = delete;
@@ -605,10 +607,19 @@ public:
     // The multi-view tracks of the graph (eacham_graph_tracks; defined in TracksHip.hpp): keep = optional byte per match, indexed like
     // the q and t the graph was made from.
     struct Tracks Tracks(const uint8_t* keep = nullptr, int min_len = 2, int conflict_policy = 0);
+    // The handle and what the graph was made from, for the calls that live in other headers (GraphVerifyHip.hpp)
+    eacham_graph* get() const { return h_; }
+    Context& context() const { return ctx_; }
+    int64_t nodes() const { return nodes_; }
+    int64_t matches() const { return matches_; }
+    const std::vector<int32_t>& counts() const { return counts_; }     // per caller pair
+    const std::vector<int64_t>& offsets() const { return offsets_; }   // per caller pair: where its matches begin in q / t (and in a mask)
 private:
     Context& ctx_;
     eacham_graph* h_ = nullptr;
     int64_t nodes_ = 0, matches_ = 0;
+    std::vector<int32_t> counts_;
+    std::vector<int64_t> offsets_;
 };
 
 }  // namespace hip

@@ -101,24 +101,11 @@ inline void svd3(const Mat3& A, Mat3& U, Vec3& S, Mat3& V) {
         for (int r = 0; r < 3; ++r) U[3 * r + k] = u[k][r];
 }
 
-// counter-based sample indices (splitmix64): sample s = m distinct indices out of n
-inline uint64_t mix(uint64_t x) {
-    x += 0x9E3779B97F4A7C15ull;
-    x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-    x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
+// counter-based sample indices (CvSampling.hpp: mix, counter_sample): sample s = m distinct indices out of n
+using ::eacham::hip::mix;
 inline std::vector<int32_t> draw_samples(int n, int m, int count, uint64_t seed, int first = 0) {   // samples first .. first + count - 1
     std::vector<int32_t> idx((size_t)count * m);
-    for (int s = 0; s < count; ++s) {
-        uint64_t ctr = 0;
-        for (int k = 0; k < m;) {
-            const int v = (int)(mix(seed * 0x100000001B3ull + ((uint64_t)(first + s) << 20) + ctr++) % (uint64_t)n);
-            bool dup = false;
-            for (int j = 0; j < k; ++j) dup = dup || idx[(size_t)s * m + j] == v;
-            if (!dup) idx[(size_t)s * m + k++] = v;
-        }
-    }
+    for (int s = 0; s < count; ++s) counter_sample(n, m, seed, first + s, &idx[(size_t)s * m]);
     return idx;
 }
 

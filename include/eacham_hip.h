@@ -621,6 +621,48 @@ int eacham_tracks_build(eacham_ctx* ctx, int n_frames, const int32_t* pairs, int
 int eacham_graph_tracks(eacham_graph* graph, const uint8_t* keep, int min_len, int conflict_policy, int64_t cap_obs,
                         int32_t cap_tracks, int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame,
                         uint32_t* obs_kp, uint8_t* track_flags, int32_t* node_track);
+/* ---- geometric verification of a resident match graph ----------------------------------------------------------
+ * eacham_lmeds_batch for every pair of a graph made by eacham_graph_create, without the graph's matches leaving the device:
+ * the correspondences are gathered, the minimal samples drawn and the LMedS kernels run where the graph lives; the inlier mask
+ * comes out in the layout eacham_graph_tracks takes as `keep`, and can stay on the device for it.
+ *
+ * eacham_graph_set_keypoints: xy holds kp_offsets[n_frames] rows of 2 doubles (pixels), frame-major in the kp_offsets layout the
+ * graph was created with. Uploaded once into memory the graph owns (eacham_graph_destroy frees it). A second call replaces the
+ * coordinates and drops a retained mask. EACHAM_ERR_INVALID: a null xy while the graph has keypoints. */
+int eacham_graph_set_keypoints(eacham_graph* graph, const double* xy);
+/* eacham_graph_verify: PROBLEM p is caller pair p of eacham_graph_create (every per-pair output has npairs entries), its points
+ * the pair's matches in the caller's order: a[i] = xy[kp_offsets[f1] + q[i]], b[i] = xy[kp_offsets[f2] + t[i]].
+ *   kind         EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5; K as in eacham_lmeds_batch (4 doubles on the host, NULL =
+ *                already normalised; read by the essential kind only)
+ *   sampling     EACHAM_SAMPLING_OPENCV: per pair cv::RNG((uint64)-1), getSubset with at most 1000 attempts per subset and, for
+ *                the homography, checkSubset on the pair's points as floats; a pair stops where getSubset gives up.
+ *                EACHAM_SAMPLING_COUNTER: the counter-based stream, seeded per pair by seeds[p] (seeds == NULL: 12345 for every
+ *                pair; the OpenCV stream does not read seeds). Both are the functions of include/eacham/CvSampling.hpp that the
+ *                host's lmeds_samples / draw_samples call, compiled for the device.
+ *   iterations   the samples LMedS asks for per pair, computed once by the caller as lmeds() does:
+ *                min(maxIters, max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3))
+ *   retain       != 0: this call's mask stays in the graph (replacing an earlier one) for eacham_graph_tracks_verified
+ * Outputs (each optional): models .. n_candidates as eacham_lmeds_batch returns them, per caller pair; masks: n_src bytes (n_src =
+ * max over pairs of offsets[p] + counts[p]) in the index space of the q / t given to eacham_graph_create — match i of pair p at
+ * offsets[p] + i, bytes that belong to no pair zero: exactly the `keep` of eacham_graph_tracks; n_samples: the samples each pair
+ * used; samples: npairs x iterations x m int32 at a fixed stride, slots behind a pair's n_samples = -1.
+ * A pair with counts[p] == 0, with fewer than m matches or with no samples gets the "none" record of eacham_lmeds_batch.
+ * Byte for byte the host composition: gather, lmeds_samples / draw_samples per pair, eacham_lmeds_batch. The match lists of
+ * different pairs must not overlap in the caller's arrays.
+ * EACHAM_ERR_INVALID (before anything is launched or written): keypoints not set, unknown kind or sampling, negative iterations.
+ * EACHAM_ERR_CAPACITY: more than (2^31 - 1) / 2 matches, npairs x iterations x m or the candidates beyond 2^31 - 1.
+ * Scratch during a call: 33 bytes per match, iterations x m x 4 bytes per pair twice over, and what eacham_lmeds_batch needs
+ * for its samples; retained: one byte per n_src. */
+#define EACHAM_SAMPLING_OPENCV 0
+#define EACHAM_SAMPLING_COUNTER 1
+int eacham_graph_verify(eacham_graph* graph, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
+                        double* models, float* medians, float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner,
+                        int32_t* n_candidates, int32_t* n_samples, int32_t* samples);
+/* eacham_graph_tracks with the mask the last eacham_graph_verify(retain != 0) left in the graph as `keep`: nothing is uploaded.
+ * Byte for byte eacham_graph_tracks(graph, masks of that verify call, ...). EACHAM_ERR_INVALID if no mask is retained. */
+int eacham_graph_tracks_verified(eacham_graph* graph, int min_len, int conflict_policy, int64_t cap_obs, int32_t cap_tracks,
+                                 int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame, uint32_t* obs_kp,
+                                 uint8_t* track_flags, int32_t* node_track);
 /* Diagnostic: how the context's last track-building call ran (any pointer may be NULL). rounds = hook-and-compress rounds until
  * one changed nothing (that one included; 0 if the call had no kept edge), round_cap = the bound it is held to,
  * 2 * ceil(log2(touched-node bound)) + 1 with the bound min(nodes, 2 x matches), readbacks = device-to-host read-backs of status words (one per batch of rounds, one
