@@ -1,14 +1,21 @@
-// devprim.hpp — the two data-parallel primitives the device-side problem construction of the bundle adjuster is made of
-// (ba.hip, eacham_ba_prepare): an exclusive prefix sum and a STABLE least-significant-digit radix sort of (key, value)
-// pairs, hand-written for gfx950 (64-wide wavefronts: the in-tile ranks of the sort come from wave ballots).
+// devprim.hpp — the data-parallel primitives under the device-side constructions: an exclusive prefix sum, a STABLE
+// least-significant-digit radix sort of (key, value) pairs and the search for the segment that owns an item, hand-written for
+// gfx950 (64-wide wavefronts: the in-tile ranks of the sort come from wave ballots). Five users: ba.hip (eacham_ba_prepare:
+// seven sorts, a dozen scans over int, long long and I3), tracks.hip, lmeds_batch.hip, graph_verify.hip, and, through
+// segment_of, triangulate.hip / pnp_batch.hip.
 //
-// Why stable matters here: RefineBA's graph construction (modules/sfm/reconstruction/BundleAdjuster.cpp:57-178) visits
+// Why stable matters: RefineBA's graph construction (modules/sfm/reconstruction/BundleAdjuster.cpp:57-178) visits
 // landmarks and observers in a fixed order, and every fp64 sum of the solver runs in the order of these lists — a stable sort
 // reproduces the order a sequential host loop produces, so the device-built structure is bit-identical with the host-built
-// one (tests/test_ba_gpu.py holds them against each other) and two runs are bit-identical with each other.
+// one and two runs are bit-identical with each other; a track's observations stay ascending for the same reason.
 //
-// Everything is enqueued on the caller's stream; nothing synchronises. More than one translation unit includes this file (ba.hip,
-// lmeds_batch.hip): the kernels are templates or static. Workspace sizes are given by the *_ws_elems helpers.
+// What all of them rely on — the scan is exact, the sort is a stable permutation by the low key_bits only, neither writes
+// outside the buffers scan_ws_elems / radix_ws_ints size — is held directly, outside every product, by
+// tests/test_devprim_gpu.py (tests/cpp/devprim_driver.hip: exact references, guards around every buffer) and, for the
+// workspace sizes, tests/test_devprim_host.py.
+//
+// Everything is enqueued on the caller's stream; nothing synchronises. More than one translation unit includes this file:
+// the kernels are templates or static. Workspace sizes are given by scan_ws_elems / radix_ws_ints.
 #pragma once
 
 #include <hip/hip_runtime.h>
