@@ -112,7 +112,7 @@ int sync_frame_table(eacham_ctx* ctx) {
     std::vector<FrameDev> tab(need + 1);
     {   // entry [need]: an empty frame that invalid device-side pairs are redirected to
         FrameDev& e = tab[need];
-        e.frag = nullptr; e.norm = nullptr; e.normb = nullptr;
+        e.frag = nullptr; e.norm = nullptr; e.normb = nullptr; e.screen = nullptr;
         e.orig = ctx->flag_dev + 16; e.pos = ctx->flag_dev + 16; e.meta = ctx->flag_dev + 8;
         e.n = 0; e.ntiles = 0; e.resident = 1;
     }
@@ -124,6 +124,7 @@ int sync_frame_table(eacham_ctx* ctx) {
         tab[i].orig = f.orig;
         tab[i].pos = f.pos;
         tab[i].meta = f.meta;
+        tab[i].screen = f.screen;
         tab[i].n = f.n < 0 ? 0 : f.n;
         tab[i].ntiles = f.n < 0 ? 0 : f.ntiles;
         tab[i].resident = f.n < 0 ? 0 : 1;
@@ -247,7 +248,7 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
     ctx->device = device_id;
     ctx->match_no_overlap = getenv("EACHAM_NO_OVERLAP") != nullptr;
     if (const char* v = getenv("EACHAM_MATCH_COLPRUNE")) ctx->match_colprune = strcmp(v, "0") != 0;
-    if (const char* v = getenv("EACHAM_MATCH_SWEEP_FORM")) ctx->match_sweep_form = !strcmp(v, "exact") ? 1 : !strcmp(v, "bound") ? 2 : 0;
+    if (const char* v = getenv("EACHAM_MATCH_SWEEP_FORM")) ctx->match_sweep_form = !strcmp(v, "exact") ? 1 : !strcmp(v, "bound") ? 2 : !strcmp(v, "screen") ? 3 : 0;
     if (const char* b = getenv("EACHAM_MATCH_BUDGET_MB")) {
         const int v = atoi(b);
         if (v >= 16 && v <= 65536) ctx->match_budget_mb = v;

@@ -32,6 +32,8 @@ struct FrameDev {
     const int* orig;   // int8: stored position -> caller's row (-1 = padding)
     const int* pos;    // int8: caller's row -> stored position
     const int* meta;   // int8: {tiles of the even class, tiles in use}; written by the upload kernels
+    const int4* screen;  // int8 frames above 128-D: the FP6 image of the screen sweep (matcher.hip, match_screen.hpp), at the same stored
+                         // positions and tiles: [ntiles][4 k-steps]{64 x 16 B | 64 x 8 B} | |M|^2 / 2 as float [32 ntiles] | s_r [32 ntiles] | {E}; else null
     int n;             // real rows
     int ntiles;        // allocated 32-row tiles (upper bound of meta[1] for int8 frames)
     int resident;      // 0: no descriptors uploaded under this id (device-side pair lists naming it are neutralised)
@@ -44,6 +46,7 @@ struct FrameHost {
     int* orig = nullptr;
     int* pos = nullptr;
     int* meta = nullptr;
+    int4* screen = nullptr;  // the FP6 image of a frame above 128-D: the tail of frag's allocation
     int n = -1;  // -1 = not resident
     int dim = 0;
     int ks = 0;
@@ -98,7 +101,9 @@ struct eacham_ctx {
     bool frame_table_dirty = true;
     int* flag_dev = nullptr;  // [0] = non-integer descriptor seen, [1] = a device-side pair list named a frame that is not
                               // resident, [8..9] = meta of the empty stand-in frame (zeros), [16..] scratch, [32..35] = the two 64-bit
-                              // totals {settled, verified} of the last matching call's candidate columns (eacham_match_debug_colprune)
+                              // totals {settled, verified} of the last matching call's candidate columns (eacham_match_debug_colprune),
+                              // [40..51] = the tally of the screened dot-product form, [52..55] = the two 64-bit totals {real query rows,
+                              // rows left open} of the last matching call's screen sweeps (eacham_match_debug_screen)
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
     int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip)
     void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
@@ -131,8 +136,9 @@ struct eacham_ctx {
                               // Any other value means 0: the retired =dense (docs/HISTORY.md) now gives a local window its default, the pair lists
     int ba_ordering = 0;  // EACHAM_BA_ORDERING=natural|rcm|nd read ONCE at eacham_ctx_create (diagnostic override of
                           // eacham_ba_problem.ordering == AUTO); nothing on the solve path reads the environment
-    int match_sweep_form = 0;         // EACHAM_MATCH_SWEEP_FORM=exact|bound (diagnostic A/B, tests): the lean form's row sweep keeps every row's exact top-2 (1), or
-                                      // runs its bound form + the exact pass over the rows left open (2); 0 = by descriptor dimension (bound up to 128-D)
+    int match_sweep_form = 0;         // EACHAM_MATCH_SWEEP_FORM=exact|bound|screen (diagnostic A/B, tests): the lean form's row sweep keeps every row's exact top-2 (1),
+                                      // runs its bound form + the exact pass over the rows left open (2), or screens the rows on the FP6 image where the frames
+                                      // have one, with the same exact pass (3); 0 = by descriptor dimension (bound up to 128-D, screen above)
     bool match_colprune = true;       // EACHAM_MATCH_COLPRUNE=0 (A/B, tests): no candidate column is settled from the sweep's row minima, all go to match_colverify_kernel
     int match_budget_mb = 1024;     // EACHAM_MATCH_BUDGET_MB (diagnostic: workspace budget of one batch of pairs), read at create
     bool match_no_overlap = false;  // EACHAM_NO_OVERLAP (diagnostic: finalize on the tile kernel's stream), read at create

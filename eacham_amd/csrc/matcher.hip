@@ -26,6 +26,7 @@
 // 1, which no ratio <= 1 accepts), so no row index is carried through the column reduction.
 // A running top-2 costs two VALU ops:  m2 = med3(m1, m2, key); m1 = min(m1, key).
 #include "context.hpp"
+#include "match_screen.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -157,6 +158,54 @@ __global__ void quantize_kernel(const float* __restrict__ src, int dim, int KS, 
     }
     const v4i out = {(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
     frag[((size_t)tile * KS + ks) * 64 + h * 32 + r] = out;
+}
+
+// U4 (frames above 128-D): the FP6 image of the screen sweep (match_screen.hpp), thread per stored row and 32 dimensions. A tile of
+// 32 rows is 6 KiB: per K = 64 step a 16-byte plane and an 8-byte plane of 64 lanes (lane = 32 * ((k % 64) / 32) + row % 32 holds the
+// 32 codes of k % 32 ascending, 24 bytes), so the LDS-DMA pieces of the sweep's ring stay 1 KiB and a lane's operand is two aligned
+// reads. msq (zeroed) gathers |M|^2, sr (zeroed) s_r = sum (x - x~)^2.
+constexpr float SCREEN_PAD = 8388608.0f;     // 2^23: exact in f32, above any n / 2 (n <= 256 * 120^2) and any partial sum of a real row
+constexpr int SCREEN_KS = 4;                 // K = 64 steps of a 256-D row
+constexpr int SCREEN_STEP_BYTES = 1536, SCREEN_TILE_BYTES = SCREEN_KS * SCREEN_STEP_BYTES;
+__global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, int npad, const int* __restrict__ orig,
+                                       char* __restrict__ image, int* __restrict__ msq, int* __restrict__ sr) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= npad * 2 * SCREEN_KS) return;
+    const int j = idx / (2 * SCREEN_KS), ch = idx % (2 * SCREEN_KS);
+    const int ks = ch >> 1, h = ch & 1, tile = j >> 5, r = j & 31;
+    const int row = orig[j];
+    int m2 = 0, err = 0;
+    unsigned char codes[32];
+#pragma unroll
+    for (int e = 0; e < 32; ++e) {
+        const int k = ks * 64 + h * 32 + e;
+        int code = 0;   // padded dimensions and padding rows: code 0, nothing towards a distance
+        if (row >= 0 && k < dim) {
+            const int x = min(max((int)src[(size_t)row * dim + k], 0), 255);   // (a value out of range fails the call elsewhere)
+            code = screen::encode(x);
+            const int m = screen::decode(code), d = x - screen::reconstruct(code);
+            m2 += m * m;
+            err += d * d;
+        }
+        codes[e] = (unsigned char)code;
+    }
+    uint32_t w[6];
+    screen::pack32(codes, w);
+    char* tb = image + (size_t)tile * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES;
+    const int lane = 32 * h + r;
+    *reinterpret_cast<v4i*>(tb + 16 * lane) = v4i{(int)w[0], (int)w[1], (int)w[2], (int)w[3]};
+    *reinterpret_cast<int2*>(tb + 1024 + 8 * lane) = make_int2((int)w[4], (int)w[5]);
+    if (m2) atomicAdd(&msq[j], m2);
+    if (err) atomicAdd(&sr[j], err);
+}
+// U5: hm = |M|^2 / 2 as float in msq's place (the C-init of the row as a train row, added once as a query row; padding rows:
+// SCREEN_PAD, above every real value), eb[0] = the largest s_r of a real row.
+__global__ void finish_screen_kernel(int npad, const int* __restrict__ orig, int* __restrict__ msq, const int* __restrict__ sr, int* __restrict__ eb) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= npad) return;
+    const bool real_row = orig[j] >= 0;
+    reinterpret_cast<float*>(msq)[j] = real_row ? 0.5f * (float)msq[j] : SCREEN_PAD;
+    if (real_row) atomicMax(eb, sr[j]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -836,6 +885,275 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 }
 
 // ------------------------------------------------------------------------------------------------
+// K1s: the SCREEN form of the row sweep above 128-D — match_sweep_kernel<8, true> on the FP6 image of the frames (match_screen.hpp).
+//
+// At 256-D the int8 sweep is bound by the matrix pipe (16 v_mfma_i32_32x32x32_i8 per wave-tile). v_mfma_scale_f32_32x32x64_f8f6f4
+// with e2m3 operands takes twice the K in the same cycles: 8 per wave-tile over the quantised rows. The train tile is the A operand,
+// the wave's 64 query rows the B operand with their sign bits flipped; both scale operands are 2^3 (one register), so a product is the
+// integer -M_a M_b and, with |M_b|^2 / 2 as the C-init, an accumulator holds |M_b|^2 / 2 - M_a.M_b: every partial sum is a multiple of
+// 1/2 below 2^22, exact in f32 in any order. |M_a|^2 / 2 is added once after the sweep: n = |M_a - M_b|^2 is twice the sum.
+// The epilogue is the bound form's: four running minima per sub-tile (two v_min3_f32 per group and tile). Nothing here depends on the
+// parity of a norm, so there is no class boundary; the sixteen disjoint subsets of a query row are (tile parity, group of four
+// accumulators, lane half). Their smallest is n1, their second smallest u bounds the runner-up from above, and the tail turns them
+// into L1 <= the true minimum and U2 >= the true runner-up (screen::lower_d2 / upper_d2 with the row's s and the train frame's E).
+// out: rowres[p][j] = {L1 - pa + 2, 0, U2 - pa + 2, n1}: the bound form's slot and encoding ((e.x + pa) - 2 decodes to L1), so
+// match_rowpick_kernel lists the rows that do not fail the ratio test on (L1, U2), match_colverify_kernel<8, true> overwrites them
+// with exact {v1, tile, v2}, and match_rows2_kernel fails the others on the same two numbers (L1 is a valid lower bound for its L(p)).
+// A row without a real minimum, or whose minima fill one subset only, carries the bound form's padding values. The fourth word
+// (n1, ~0 without one) is read by eacham_match_debug_screen_pair only.
+// LDS-DMA ring (three slots of 6 KiB), just-in-time fragment ring, double-buffered accumulators and the six-tiles-per-trip loop are
+// match_sweep_kernel's; a fragment is 24 bytes, two LDS reads.
+// ------------------------------------------------------------------------------------------------
+typedef int v2i __attribute__((ext_vector_type(2)));
+typedef int v6i __attribute__((ext_vector_type(6)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef float v16f __attribute__((ext_vector_type(16)));
+__device__ __forceinline__ void lds_read_frag64(v2i& dst, unsigned addr, int offset_bytes) {
+    asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(offset_bytes));
+}
+__device__ __forceinline__ float fmin3(float a, float b, float c) {
+    float d;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
+    return d;
+}
+struct ScreenFrag { v4i lo; v2i hi; };   // a lane's 32 codes of one K = 64 step
+__device__ __forceinline__ v8i screen_operand(const ScreenFrag& f) { return v8i{f.lo[0], f.lo[1], f.lo[2], f.lo[3], f.hi[0], f.hi[1], 0, 0}; }
+
+__global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
+                                                                     int wgs_per_pair, uint4* __restrict__ rowres, int row_stride) {
+    constexpr int NSUB = 2, KS = SCREEN_KS;
+    constexpr int TILE_V4 = SCREEN_TILE_BYTES / 16;
+    constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
+    constexpr float BIGF = 3.0e38f;
+    constexpr int SCALE = (int)0x82828282u;   // E8M0 2^3 in every byte, both operands: e2m3 numbers become the integers M, products -M_a M_b
+    __shared__ v4i sB[3][TILE_V4];
+    __shared__ __attribute__((aligned(16))) float sHb[3][32];  // |M_b|^2 / 2 of the tile in the same ring slot: the C-init of its chains
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int h = lane >> 5;
+    const int rb = blockIdx.x % wgs_per_pair;
+    const int p = blockIdx.x / wgs_per_pair;
+    const int2 pr = pairs[p];
+    const FrameDev A = frames[pr.x], B = frames[pr.y];
+    const int A_even = ((gint_t)A.meta)[0], A_tiles = ((gint_t)A.meta)[1];
+    const int T = ((gint_t)B.meta)[1];
+    if (rb * (ROWS_WG / 32) >= A_tiles) return;  // workgroup-uniform
+    const int wb = rb * WAVES + wave;
+    const bool active = NSUB * wb < A_tiles;
+    typedef const __attribute__((address_space(1))) char* gbytes_t;
+    typedef const float __attribute__((address_space(1)))* gfloat_t;
+    const gbytes_t Aimg = (gbytes_t)A.screen, Bimg = (gbytes_t)B.screen;
+    const gfloat_t Am2 = (gfloat_t)(Aimg + (size_t)A.ntiles * SCREEN_TILE_BYTES), Bm2 = (gfloat_t)(Bimg + (size_t)B.ntiles * SCREEN_TILE_BYTES);
+    const int wbc = active ? wb : 0;
+
+    v6i a[NSUB][KS];   // this wave's 64 query rows, sign bits flipped: the B operand (a lane = a query row of the sub-tile)
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const gbytes_t tb = Aimg + (size_t)(NSUB * wbc + s) * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES;
+            const v4i lo = *(const v4i __attribute__((address_space(1)))*)(tb + 16 * lane);
+            const v2i hi = *(const v2i __attribute__((address_space(1)))*)(tb + 1024 + 8 * lane);
+            // the sign bit of code e is bit 6 e + 5: a pattern of period three words
+            a[s][ks] = v6i{lo[0] ^ 0x20820820, lo[1] ^ 0x08208208, lo[2] ^ (int)0x82082082u, lo[3] ^ 0x20820820, hi[0] ^ 0x08208208, hi[1] ^ (int)0x82082082u};
+        }
+    float xm[2][NSUB][4];  // [tile parity][sub-tile][group]: the minimum over accumulators 4 g .. 4 g + 3 of the tiles of that parity
+#pragma unroll
+    for (int q = 0; q < 2; ++q)
+#pragma unroll
+        for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) xm[q][s][g] = BIGF;
+
+    static_assert(TILE_V4 % 64 == 0, "a tile is a whole number of 1 KiB pieces");
+    constexpr int PIECES = TILE_V4 / 64;
+    constexpr int PPW = (PIECES + WAVES - 1) / WAVES;
+    // (the lane offsets of the staging and of the constants' load are kept opaque: added to the frame's base ahead of the loop they
+    // would be held as two 64-bit per-lane addresses through the sweep)
+    unsigned stage_off = (unsigned)(wave * PPW * 64 + lane) * 16u, hb_off = (unsigned)tid * 4u;
+    auto stage_tile = [&](int tile, int slot) {
+        const gbytes_t base = Bimg + (size_t)tile * SCREEN_TILE_BYTES;
+        asm volatile("" : "+v"(stage_off));
+#pragma unroll
+        for (int i = 0; i < PPW; ++i) {
+            const int piece = wave * PPW + i;
+            if (piece < PIECES)
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + stage_off + i * 1024),
+                                                 (__attribute__((address_space(3))) void*)(&sB[slot][piece * 64]), 16, 0, 0);
+        }
+    };
+    if (T > 0) {
+        stage_tile(0, 0);
+        stage_tile(min(1, T - 1), 1);
+        stage_tile(min(2, T - 1), 2);
+        if (tid < 96) sHb[tid >> 5][tid & 31] = Bm2[32 * min(tid >> 5, T - 1) + (tid & 31)];
+    }
+    __builtin_amdgcn_s_waitcnt(0);
+    __syncthreads();
+
+    // C-init of a chain on the tile in ring slot `slot`: accumulator r is train row (r & 3) + 8 (r >> 2) + 4 h
+    // (the lane's address in slot 0 is one opaque register, slot and group immediate offsets: derived from h at every use it kept h
+    // and the lane alive through the sweep, spilled)
+    typedef const v4f __attribute__((address_space(3)))* lds_v4f_t;
+    lds_v4f_t hb_lane = (lds_v4f_t)(const __attribute__((address_space(3))) void*)&sHb[0][4 * h];
+    asm volatile("" : "+v"(hb_lane));
+    auto cinit_of = [&](int slot) {
+        v16f c;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const v4f q = hb_lane[8 * slot + 2 * g];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) c[4 * g + k] = q[k];
+        }
+        return c;
+    };
+    auto mfma = [&](const ScreenFrag& b, const v6i& q, const v16f& c) {
+        const v8i q8 = __builtin_shufflevector(q, q, 0, 1, 2, 3, 4, 5, -1, -1);
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, SCALE, 0, SCALE);
+    };
+    v16f accA[NSUB], accB[NSUB];
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accA[s][r] = 0.0f, accB[s][r] = 0.0f;
+    ScreenFrag bq[3];  // fragment ring: step i of the ks sequence lives in bq[i % 3]
+    const char* sBb = reinterpret_cast<const char*>(&sB[0][0]);
+    auto read_plain = [&](int slot, int ks) {
+        ScreenFrag f;
+        f.lo = *reinterpret_cast<const v4i*>(sBb + slot * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 16 * lane);
+        f.hi = *reinterpret_cast<const v2i*>(sBb + slot * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 1024 + 8 * lane);
+        return f;
+    };
+#pragma unroll
+    for (int i = 0; i < 3; ++i) bq[i].lo = v4i{0, 0, 0, 0}, bq[i].hi = v2i{0, 0};
+    if (T > 0 && active) {
+        const v16f c0 = cinit_of(0);
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+            const ScreenFrag b0 = read_plain(0, ks);
+#pragma unroll
+            for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
+        }
+        bq[0] = read_plain(1, 0);   // the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never read)
+        bq[1] = read_plain(1, 1);
+#pragma unroll
+        for (int s = 0; s < NSUB; ++s) accB[s] = cinit_of(1);
+    }
+    __syncthreads();   // slot 0 is staged into again by the first call below
+    // this lane's bytes in the two planes of slot 0, step 0: slot and step are immediate offsets of the reads
+    unsigned lds16 = lds_addr(sBb) + 16u * lane, lds8 = lds_addr(sBb) + 8u * lane;
+    asm volatile("" : "+v"(lds16), "+v"(lds8));
+    // keys of tile t handled by step ks of tile t + 1's MFMAs: all 32 within the first KS - 1 steps, so that the accumulators are
+    // free for tile t + 2's constants a step before the call's drain
+    auto key_lo = [](int ks) constexpr { return ks >= KS - 1 ? 32 : (32 * ks + KS - 2) / (KS - 1); };
+    // accumulators 4 g .. 4 g + 3 of sub-tile idx / 16 -> the running minimum of that group and tile parity, two at a time
+    auto consume = [&](const v16f(&cur)[NSUB], float(&m)[NSUB][4], const int idx) {
+        const int ph = idx / 16, eg = idx % 16;
+        if (eg & 1) m[ph][eg >> 2] = fmin3(m[ph][eg >> 2], cur[ph][eg - 1], cur[ph][eg]);
+    };
+    // One call: epilogue of tile t (held in `cur`), MFMAs of tile t + 1 into `nxt`, tile t + 3 staged into tile t's ring slot, the
+    // first fragments and the constants of tile t + 2 fetched at the end and drained before the call's barrier (match_sweep_kernel).
+    auto tile = [&](auto PHc, auto SLc, auto PARc, const int t) {
+        constexpr int PH = decltype(PHc)::value, SL = decltype(SLc)::value, PAR = decltype(PARc)::value;
+        constexpr int slot_nxt = (SL + 1) % 3, slot_nn = (SL + 2) % 3;
+        v16f(&cur)[NSUB] = PAR ? accB : accA;
+        v16f(&nxt)[NSUB] = PAR ? accA : accB;
+        const int t3 = min(t + 3, T - 1);
+        asm volatile("" : "+v"(hb_off));
+        const float hb_new = (tid < 32) ? *reinterpret_cast<gfloat_t>(reinterpret_cast<gbytes_t>(Bm2 + 32 * t3) + hb_off) : 0.0f;   // lands during this call; stored to the ring before the barrier
+        stage_tile(t3, SL);
+        if (active) {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                // the fragment of step ks has landed (the two reads of step ks + 1 may be in flight)
+                asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bq[(ks + PH) % 3].lo), "+v"(bq[(ks + PH) % 3].hi));
+                const int j = ks + 2;
+                lds_read_frag(bq[(j + PH) % 3].lo, lds16, (j < KS ? slot_nxt : slot_nn) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES);
+                lds_read_frag64(bq[(j + PH) % 3].hi, lds8, (j < KS ? slot_nxt : slot_nn) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES + 1024);
+#pragma unroll
+                for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(bq[(ks + PH) % 3], a[s][ks], nxt[s]);
+#pragma unroll
+                for (int idx = key_lo(ks); idx < key_lo(ks + 1); ++idx) {
+                    consume(cur, xm[PAR], idx);
+                    if (idx % 16 == 15) cur[idx / 16] = cinit_of(slot_nn);   // done with these accumulators: tile t + 2's constants, for the next call's chains
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi));
+        }
+        if (tid < 32) sHb[SL][tid] = hb_new;
+        __syncthreads();
+    };
+    // the last tile has nothing to issue and nothing to stage: its epilogue alone (which accumulators hold it is its parity)
+    auto last = [&](auto PARc) {
+        constexpr int PAR = decltype(PARc)::value;
+        v16f(&cur)[NSUB] = PAR ? accB : accA;
+        if (active) {
+#pragma unroll
+            for (int idx = 0; idx < 32; ++idx) consume(cur, xm[PAR], idx);
+        }
+    };
+    if (T > 0) {
+        constexpr int ADV = KS % 3;
+        const int TM = T - 1;
+        int t = 0;
+        auto run = [&](auto K6c, int tt) {
+            constexpr int K6 = decltype(K6c)::value;
+            tile(std::integral_constant<int, (K6 * ADV) % 3>{}, std::integral_constant<int, K6 % 3>{}, std::integral_constant<int, K6 % 2>{}, tt);
+        };
+        for (; t + 6 <= TM; t += 6) {
+            run(std::integral_constant<int, 0>{}, t);
+            run(std::integral_constant<int, 1>{}, t + 1);
+            run(std::integral_constant<int, 2>{}, t + 2);
+            run(std::integral_constant<int, 3>{}, t + 3);
+            run(std::integral_constant<int, 4>{}, t + 4);
+            run(std::integral_constant<int, 5>{}, t + 5);
+        }
+        if (t < TM) run(std::integral_constant<int, 0>{}, t);
+        if (t + 1 < TM) run(std::integral_constant<int, 1>{}, t + 1);
+        if (t + 2 < TM) run(std::integral_constant<int, 2>{}, t + 2);
+        if (t + 3 < TM) run(std::integral_constant<int, 3>{}, t + 3);
+        if (t + 4 < TM) run(std::integral_constant<int, 4>{}, t + 4);
+        if (TM & 1) last(std::integral_constant<int, 1>{});
+        else last(std::integral_constant<int, 0>{});
+    }
+    if (!active) return;
+    // join the partner lane (the same query row against the other half of every tile's train rows) and the tile parities: the two
+    // smallest of the sixteen subset minima, then the bounds
+    const gint_t Asr = (gint_t)(Am2 + 32 * (size_t)A.ntiles);
+    const int e_b = T > 0 ? ((gint_t)(Bm2 + 64 * (size_t)B.ntiles))[0] : 0;
+    uint4* rr = rowres + (size_t)p * row_stride + ROWS_WAVE * wb;
+    const int lane_t = (int)((lds16 - lds_addr(sBb)) >> 4), cl_t = lane_t & 31, h_t = lane_t >> 5;   // (the lane, from what the sweep kept)
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s) {
+        const int j = ROWS_WAVE * wb + 32 * s + cl_t;
+        const float ma = Am2[j];
+        float v1 = BIGF, v2 = BIGF;
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const float mine = xm[q][s][g], other = __shfl_xor(mine, 32);
+                v2 = fminf(v2, fmaxf(v1, mine)), v1 = fminf(v1, mine);
+                v2 = fminf(v2, fmaxf(v1, other)), v1 = fminf(v1, other);
+            }
+        if (h_t == 0) {
+            // a padding train row holds SCREEN_PAD or more, a subset that met no tile BIGF; real values stay below 2^21
+            const bool real_row = ma < 0.5f * SCREEN_PAD;
+            const bool real1 = real_row && v1 < 0.5f * SCREEN_PAD, real2 = real_row && v2 < 0.5f * SCREEN_PAD;
+            const unsigned pa = NSUB * wb + s >= A_even ? 1u : 0u;
+            const int s_a = Asr[j];
+            const unsigned n1 = real1 ? (unsigned)(2.0f * (v1 + ma)) : 0u, u = real2 ? (unsigned)(2.0f * (v2 + ma)) : 0u;
+            const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
+            const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
+            rr[32 * s + cl_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // K2: merge column partials, ratio test, mutual check, thresholds, ordered compaction
 // ------------------------------------------------------------------------------------------------
 
@@ -996,7 +1314,8 @@ constexpr int VER_CANDS = 32 * VER_GROUPS;    // candidates per work item
 // candidates of the pair (candlist, state[p].x = their number) and appends one item per 64 of them for match_colverify_kernel<KS, true>.
 __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
-    int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items, int* __restrict__ n_items) {
+    int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items, int* __restrict__ n_items,
+    unsigned long long* __restrict__ tally = nullptr) {
     __shared__ int s_wave[FIN_THREADS / 64];
     __shared__ int s_item0;
     const int tid = threadIdx.x;
@@ -1007,6 +1326,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     constexpr unsigned PAD_V = 2u * PADH;
     int* cl = candlist + (size_t)p * row_stride;
     int base = 0;
+    if (tally && tid == 0) atomicAdd(&tally[0], (unsigned long long)A.n);   // behind the screen sweep: {real query rows, rows left open} of the call
     for (int j0 = 0; j0 < 32 * A_tiles; j0 += FIN_THREADS) {
         const int j = j0 + tid;
         bool ok = false;
@@ -1024,6 +1344,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     if (tid == 0) {
         state[p] = make_int4(base, 0, 0, 0);
         s_item0 = groups ? atomicAdd(n_items, groups) : 0;
+        if (tally) atomicAdd(&tally[1], (unsigned long long)base);
     }
     __syncthreads();
     for (int g = tid; g < groups; g += FIN_THREADS) items[s_item0 + g] = make_int2(p, g);
@@ -1494,11 +1815,12 @@ __global__ void compact_edges_kernel(const uint2* __restrict__ matches, const in
 // host side
 // ------------------------------------------------------------------------------------------------
 
+// (up to 128-D a multiple of 16; above, any dimension: the upload kernels pad a row with centred zeros to the 256 of the class)
 static int ks_for_dim(int dim) {
-    if (dim <= 0 || dim > 256 || dim % 16) return 0;
-    if (dim <= 64) return 2;
-    if (dim <= 128) return 4;
-    return 8;
+    if (dim <= 0 || dim > 256) return 0;
+    if (dim > 128) return 8;
+    if (dim % 16) return 0;
+    return dim <= 64 ? 2 : 4;
 }
 
 // f(std::integral_constant<int, KS>) for the KS of the resident frames (ks_for_dim: 2, 4 or 8)
@@ -1513,7 +1835,7 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
     if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
     if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
     int ks = ks_for_dim(dim);
-    if (!ks) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "descriptor dim %d: need a multiple of 16, <= 256", dim);
+    if (!ks) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "descriptor dim %d: need a multiple of 16 up to 128, or 129..256", dim);
     if (ctx->ks_common && (ctx->ks_common != ks || ctx->kind_common != 0))
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32) and dim class");
     // each parity class is padded to whole tiles (at most one extra tile), the total to whole wave-blocks
@@ -1544,12 +1866,24 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
         int* s1 = f.norm + 5 * (size_t)npad;
         f.meta = f.norm + 6 * (size_t)npad;
         if (npad > 0) {
-            EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, (size_t)ntiles * ks * 64 * sizeof(int4)));
+            // above 128-D the FP6 image of the screen sweep follows the int8 fragments: image | |M|^2 | s_r | {E} (quantize_screen_kernel)
+            const size_t frag_bytes = (size_t)ntiles * ks * 64 * sizeof(int4);
+            const size_t screen_bytes = ks == 8 ? (size_t)ntiles * SCREEN_TILE_BYTES + (size_t)npad * 8 + 16 : 0;
+            EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, frag_bytes + screen_bytes));
             const long long sums = (long long)n * ((dim + 15) / 16);
             rowsum_kernel<<<(unsigned)((sums + 255) / 256), 256, 0, ctx->stream>>>(src_dev, n, dim, s2, s1, ctx->flag_dev);
             partition_kernel<<<1, 1024, 0, ctx->stream>>>(s2, s1, n, npad, group_rows, f.norm, f.normb, f.orig, f.pos, f.meta);
             const long long work = (long long)npad * ks * 2;
             quantize_kernel<<<(unsigned)((work + 255) / 256), 256, 0, ctx->stream>>>(src_dev, dim, ks, npad, f.orig, (v4i*)f.frag);
+            if (screen_bytes) {
+                char* img = (char*)f.frag + frag_bytes;
+                int* msq = (int*)(img + (size_t)ntiles * SCREEN_TILE_BYTES);   // becomes hm, floats
+                int* sr = msq + npad;
+                EACHAM_HIP_TRY(ctx, hipMemsetAsync(msq, 0, (size_t)npad * 8 + 16, ctx->stream));
+                quantize_screen_kernel<<<(npad * 2 * SCREEN_KS + 255) / 256, 256, 0, ctx->stream>>>(src_dev, dim, npad, f.orig, img, msq, sr);
+                finish_screen_kernel<<<(npad + 255) / 256, 256, 0, ctx->stream>>>(npad, f.orig, msq, sr, sr + npad);
+                f.screen = (int4*)img;
+            }
             EACHAM_HIP_TRY(ctx, hipGetLastError());
         }
     }
@@ -1578,6 +1912,15 @@ static int check_integer_flag(eacham_ctx* ctx) {
 
 // {settled, verified}: the candidate columns of the last matching call that match_argmin_kernel settled / that went to match_colverify_kernel
 static unsigned long long* colprune_totals(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 32); }
+// {real query rows, rows left open}: what the screen sweeps of the last matching call met / handed to the exact pass
+static unsigned long long* screen_tally(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 52); }
+// every resident frame with rows carries the FP6 image (all frames share one dim class, so this is ks_common == 8)
+static bool frames_have_screen(const eacham_ctx* ctx) {
+    if (ctx->kind_common != 0 || ctx->ks_common != 8) return false;
+    for (const auto& f : ctx->frames)
+        if (f.n > 0 && !f.screen) return false;
+    return true;
+}
 
 struct MatchPlan {
     int batch;       // pairs per launch
@@ -1684,6 +2027,11 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st1));        // inputs queued on the context stream
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_join, 0));
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(colprune_totals(ctx), 0, 2 * sizeof(unsigned long long), st2));
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 2 * sizeof(unsigned long long), st2));
+    // The row sweep of the lean form. EACHAM_MATCH_SWEEP_FORM forces the exact (1) or the bound form (2) at every dimension; screen (3)
+    // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
+    const int form = ctx->match_sweep_form;
+    const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job's last batch is cut short (an eighth of a full one),
     // so the exposed tail is that of ~1 500 pairs instead of ~10 000 (0.8 ms of a 21 ms S200 step).
@@ -1698,13 +2046,17 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
         // 128-D, where the sweep is bound by its epilogue's VALU work (S200 at 128-D +5 %, the 1000-frame KITTI stand-in +12 %); at
         // 256-D the sweep is bound by the matrix pipe and gains 4 % while the exact pass (one more stream of the train frame per pair
         // beside the next sweep) costs the step 4-8 % (profiles/r05_match_bound_sweep_ab.txt)
-        const bool bound_sweep = !full_cols && (ctx->match_sweep_form == 2 || (ctx->match_sweep_form == 0 && ctx->ks_common <= 4));
+        // above it the int8 sweep is bound by the matrix pipe, where the bound form gains nothing: there the rows are screened on the FP6
+        // matrix cores instead (match_screen_kernel, half the matrix cycles), with the same exact pass behind
+        const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
         uint4* rowres = (uint4*)(ws + pl.off_rowres);
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
             with_ks(ctx->ks_common, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value;
-                if (full_cols)
+                if (screen_sweep)
+                    match_screen_kernel<<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
+                else if (full_cols)
                     match_tile_kernel<KS><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, st1>>>(
                         ctx->frame_table_dev, pb, pl.wgs_per_pair, pl.col_chunks, rowres, (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
                 else if (bound_sweep)
@@ -1740,8 +2092,9 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
                 with_ks(ctx->ks_common, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value;
-                    if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
-                        match_rowpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre);
+                    if (bound_sweep || screen_sweep) {   // the rows the bound / screen form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
+                        match_rowpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre,
+                                                                          screen_sweep ? screen_tally(ctx) : nullptr);
                         match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
                                                                                         pl.row_stride, 0, nullptr, rowres);
                     }
@@ -1985,6 +2338,65 @@ int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* veri
     *settled = (int64_t)tot[0];
     *verified = (int64_t)tot[1];
     return EACHAM_OK;
+}
+
+int eacham_match_debug_screen(eacham_ctx* ctx, int64_t* rows, int64_t* open) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    if (!rows || !open) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+    unsigned long long tot[2] = {0, 0};
+    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpy(tot, screen_tally(ctx), sizeof(tot), hipMemcpyDeviceToHost));
+    *rows = (int64_t)tot[0];
+    *open = (int64_t)tot[1];
+    return EACHAM_OK;
+}
+
+int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1, int32_t* l1, int32_t* u2, int cap) {
+    return match_entry(ctx, [&]() -> int {
+        if (!n1 || !l1 || !u2 || cap < 0) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+        const int32_t pr[2] = {f1, f2};
+        int rc = check_pairs_host(ctx, pr, 1);
+        if (rc) return rc;
+        rc = check_integer_flag(ctx);
+        if (rc) return rc;
+        rc = sync_frame_table(ctx);
+        if (rc) return rc;
+        if (!frames_have_screen(ctx)) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the screen sweep needs int8 frames above 128-D");
+        const FrameHost& A = ctx->frames[f1];
+        if (cap < A.n) return ctx->fail(EACHAM_ERR_CAPACITY, "%d rows but capacity %d", A.n, cap);
+        if (A.n == 0) return EACHAM_OK;
+        MatchPlan pl = make_plan(ctx, 1, false);
+        rc = ensure_workspace(ctx, pl.total);
+        if (rc) return rc;
+        IoStage io(ctx, ctx->stream);
+        const auto h_pair = io.in<int2>(pr, 1);
+        IoDev d;
+        rc = io.upload(d);
+        if (rc) return rc;
+        uint4* rowres = (uint4*)((char*)ctx->ws + pl.off_rowres);
+        match_screen_kernel<<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride);
+        EACHAM_HIP_TRY(ctx, hipGetLastError());
+        rc = io.finish();
+        if (rc) return rc;
+        // the slots as the sweep wrote them, by stored row: back to the caller's rows
+        const int rows = 32 * A.tiles_used;
+        std::vector<uint4> res((size_t)rows);
+        std::vector<int> pos((size_t)A.n), meta(2);
+        EACHAM_HIP_TRY(ctx, hipMemcpy(res.data(), rowres, sizeof(uint4) * res.size(), hipMemcpyDeviceToHost));
+        EACHAM_HIP_TRY(ctx, hipMemcpy(pos.data(), A.pos, sizeof(int) * pos.size(), hipMemcpyDeviceToHost));
+        EACHAM_HIP_TRY(ctx, hipMemcpy(meta.data(), A.meta, sizeof(int) * 2, hipMemcpyDeviceToHost));
+        for (int q = 0; q < A.n; ++q) {
+            const int j = pos[q];
+            const uint4 e = res[j];
+            const unsigned pa = (j >> 5) >= meta[0] ? 1u : 0u;
+            n1[q] = e.w;
+            l1[q] = e.x == 0xffffffffu ? -1 : (int32_t)(e.x + pa) - 2;   // -1: no real minimum / no bound (the bound form's padding values)
+            u2[q] = e.z == 0xffffffffu ? -1 : (int32_t)(e.z + pa) - 2;
+        }
+        return EACHAM_OK;
+    });
 }
 
 int eacham_match_pairs_directed(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int32_t* counts,

@@ -152,6 +152,25 @@ class HipContext:
         self._check(self._L.eacham_match_debug_colprune(self._h, C.byref(s), C.byref(v)))
         return s.value, v.value
 
+    def match_screen(self):
+        """(rows, open): real query rows the screen sweeps of the last matching call met / rows their bound left open for the exact
+        pass (eacham_match_debug_screen); (0, 0) when the call ran another form of the row sweep."""
+        r, o = C.c_int64(0), C.c_int64(0)
+        self._check(self._L.eacham_match_debug_screen(self._h, C.byref(r), C.byref(o)))
+        return r.value, o.value
+
+    def match_screen_pair(self, f1: int, f2: int):
+        """(n1, L1, U2) per row of f1, as the screen sweep writes them for the ordered pair (f1, f2) before the exact pass
+        (eacham_match_debug_screen_pair): the smallest squared code difference, a lower bound of the row's smallest squared
+        distance, an upper bound of its second smallest (-1: a padding value)."""
+        n = max(self.frame_rows(f1), 1)
+        n1 = np.zeros(n, dtype=np.uint32)
+        l1 = np.zeros(n, dtype=np.int32)
+        u2 = np.zeros(n, dtype=np.int32)
+        self._check(self._L.eacham_match_debug_screen_pair(self._h, f1, f2, n1.ctypes.data, l1.ctypes.data, u2.ctypes.data, n))
+        k = self.frame_rows(f1)
+        return n1[:k], l1[:k], u2[:k]
+
     def match_pairs_directed(self, frames, ordered_pairs, ratio: float = RATIO, f32: bool = False) -> list:
         """Uploads `frames` (list of N x D matrices) as frames 0.. and runs every ordered pair (i, j) as one directed
         Match(frames[i], frames[j]) in ONE launch sequence; returns a list of {queryIdx: trainIdx} dicts."""

@@ -66,7 +66,8 @@ const char* eacham_version(void);
  * cv::Mat returned by FeatureExtractorSift::Extract, modules/base/features/FeatureExtractorSift.cpp:14-26)
  * and keeps it resident on the device in the kernel's fragment-major int8 layout.
  * Values must be integers in [0,255] (OpenCV SIFT descriptors are) —
- * otherwise EACHAM_ERR_NOT_INTEGER. dim must be a multiple of 16 and <= 256. n may be 0.
+ * otherwise EACHAM_ERR_NOT_INTEGER. dim must be a multiple of 16 up to 128, or any
+ * dimension from 129 to 256 (rows are padded with centred zeros to 256). n may be 0.
  * Re-uploading a frame id replaces it. */
 int eacham_upload_descriptors(eacham_ctx* ctx, int frame_id, const float* rowmajor, int n, int dim);
 /* Same, source already on the device (enqueued on the context stream; the integrality check is
@@ -145,6 +146,17 @@ int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int3
  * column pass (*verified); live pairs only. EACHAM_MATCH_COLPRUNE=0 at eacham_ctx_create sends every candidate down the column
  * pass (*settled = 0). Waits for the context's stream. */
 int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* verified);
+
+/* Debug getter (tests, A/B runs): the screen sweeps of the LAST matching call on this context (lean form, int8 frames above 128-D,
+ * EACHAM_MATCH_SWEEP_FORM unset or =screen): *rows = real query rows they met, *open = rows their bound could not fail and that
+ * went to the exact pass. Both 0 when the call ran another form. Waits for the context's stream. */
+int eacham_match_debug_screen(eacham_ctx* ctx, int64_t* rows, int64_t* open);
+
+/* Debug entry (tests): the screen sweep alone on the ordered pair (f1, f2), before any exact pass. Per row q of f1 (cap >= its rows):
+ * n1[q] = the smallest |M_q - M_t|^2 over the rows t of f2 on the FP6 grid (~0 without a real row), l1[q] <= the row's true
+ * smallest squared distance, u2[q] >= its true second smallest (-1 where the sweep wrote a padding value: no row, or the minima
+ * of one subset only). EACHAM_ERR_UNSUPPORTED unless the resident frames are int8 above 128-D. */
+int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1, int32_t* l1, int32_t* u2, int cap);
 
 /* ---- dot-product similarity for float descriptors, scores returned ----------------------------
  * The brute-force rule for SuperPoint-class descriptors (modules/onnx/lightglue/feature/Types.h:11-14): nearest neighbour
