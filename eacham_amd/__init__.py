@@ -4,6 +4,6 @@ The product is the HIP library behind include/eacham_hip.h (eacham_amd/csrc). Th
 thin host-side mirror of the reference interfaces used by tests and bench.py.
 """
 from .capi import EachamError  # noqa: F401
-from .matcher import FeatureMatcherDotHip, FeatureMatcherHip, HipContext, MIN_DIRECTED, MIN_MUTUAL, MIN_SCORE, RATIO  # noqa: F401
+from .matcher import FeatureMatcherDotHip, FeatureMatcherHammingHip, FeatureMatcherHip, HipContext, MIN_DIRECTED, MIN_MUTUAL, MIN_SCORE, RATIO  # noqa: F401
 from .graph import ResidentGraph  # noqa: F401
 from .tracks import Tracks, build_tracks  # noqa: F401

@@ -354,6 +354,7 @@ int eacham_clear_descriptors(eacham_ctx* ctx) {
     ctx->ks_common = 0;
     ctx->kind_common = 0;
     ctx->frame_table_dirty = true;
+    ctx->bits_table_dirty = true;
     return EACHAM_OK;
 }
 
@@ -367,6 +368,7 @@ void eacham_ctx_destroy(eacham_ctx* ctx) {
         free_frame_image16(f);
     }
     if (ctx->table16_dev) (void)hipFree(ctx->table16_dev);
+    if (ctx->bits_table_dev) (void)hipFree((void*)ctx->bits_table_dev);
     if (ctx->frame_table_dev) (void)hipFree(ctx->frame_table_dev);
     if (ctx->flag_dev) (void)hipFree(ctx->flag_dev);
     if (ctx->pairs_safe) (void)hipFree(ctx->pairs_safe);

@@ -47,6 +47,8 @@ struct FrameHost {
     int* pos = nullptr;
     int* meta = nullptr;
     int4* screen = nullptr;  // the FP6 image of a frame above 128-D: the tail of frag's allocation
+    unsigned* bits = nullptr;  // binary frames (matcher_ham.hip): the packed rows in the caller's order, 8 words per row, zero-padded;
+                               // the tail of norm's allocation. The kernels reach it through a table of its own, not through FrameDev
     int n = -1;  // -1 = not resident
     int dim = 0;
     int ks = 0;
@@ -105,7 +107,11 @@ struct eacham_ctx {
                               // [40..51] = the tally of the screened dot-product form, [52..55] = the two 64-bit totals {real query rows,
                               // rows left open} of the last matching call's screen sweeps (eacham_match_debug_screen)
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
-    int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip)
+    int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip), 2 = binary rows as int8
+                              // fragments of 0 / 255 (matcher_ham.hip): the int8 kernels under the Hamming predicate
+    const unsigned** bits_table_dev = nullptr;  // [frames + 1] the frames' packed rows (FrameHost::bits; null: none), rebuilt when dirty
+    int bits_table_cap = 0;
+    bool bits_table_dirty = true;
     void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
     int table16_cap = 0;
     long long dot16_fallback_pairs = 0;  // pairs of the last screened call that ran the fp32 tile kernel (eacham_match_debug_dot_screen)
@@ -363,6 +369,12 @@ int prepare_match_dot_screened(eacham_ctx* ctx, const int32_t* pairs, int npairs
 int run_match_dot_screened(eacham_ctx* ctx, const int2* pairs_dev, const int2* pairs_fb_dev, const int32_t* pairs_fb_host, int npairs,
                            int n_fallback, float min_score, int min_dir, int min_mutual, int* counts_dev, long long* offsets_dev,
                            uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev);
+// matcher_ham.hip: binary descriptors. The packed rows are expanded on the device to the 0 / 255 rows the int8 upload takes, kept
+// packed beside the frame, and give every emitted match its Hamming distance (popcount of the XOR, independent of the sweep).
+void launch_bits_expand(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, int dim, float* dst_dev);
+void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, unsigned* bits_dev);
+int hamming_distances(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const long long* offsets_dev, const long long* total_dev,
+                      const uint2* edges_dev, long long edge_cap, int* dist_dev);
 // matcher.hip
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);
 void launch_compact_edges(eacham_ctx* ctx, int nb, const uint2* matches, const int* counts, const long long* offsets,

@@ -1159,7 +1159,17 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
 
 // FeatureMatcherFlann.cpp:23 — `m[0].distance / m[1].distance < 0.8`: distances are
 // sqrtf(squared L2) in fp32, fp32 quotient, compared as double. d2 values are exact integers.
+//
+// metric = METRIC_HAMMING (binary frames, matcher_ham.hip): a bit is stored as 0 / 255, so d2 = 65025 h exactly, and
+// cv::BFMatcher(NORM_HAMMING) hands the same test the quotient (float)h0 / (float)h1 with no square root. h and 65025 h are
+// both exact in fp32, hence fdiv(d2_0, d2_1) is bit for bit fdiv(h0, h1): the Hamming test on the integers the kernels hold,
+// the bounds (no multiples of 65025) included. Like the L2 form it is monotone in both arguments, false on 0/0 and false
+// on a negative argument (the "no real minimum" values: sqrtf gives NaN there, the Hamming form says so).
+constexpr int METRIC_L2 = 0, METRIC_HAMMING = 1;
+// The kernels that test the ratio take the metric as a template argument: their L2 instantiations are the code they were before.
+template <int METRIC>
 __device__ __forceinline__ bool ratio_pass(int d2_best, int d2_second, double ratio) {
+    if (METRIC == METRIC_HAMMING) return d2_best >= 0 && d2_second >= 0 && (double)__fdiv_rn((float)d2_best, (float)d2_second) < ratio;
     float q = __fdiv_rn(__fsqrt_rn((float)d2_best), __fsqrt_rn((float)d2_second));
     return (double)q < ratio;  // 0/0 = NaN -> false
 }
@@ -1169,6 +1179,7 @@ constexpr int FIN_THREADS = 256;
 // mode 0: mutual matches + thresholds (apps/sfm/main.cpp:111-146); mode 1: directed list m12.
 // out_matches[p][k] = {q, t} sorted by q; counts[p]; stats[p] = {|m12|, |m21|, |mutual|, edge}.
 // Rows/columns are addressed by stored position inside; q and t leave in the caller's numbering.
+template <int METRIC>
 __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
     const uint4* __restrict__ rowres, const uint2* __restrict__ colpart, int col_chunks, int wb_stride,
@@ -1208,7 +1219,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
                 v1 = umin(v1, va);
             }
             const unsigned pb = (c >> 5) >= B_even ? 1u : 0u;
-            const bool ok = v2 < PAD_V && ratio_pass((int)(v1 + pb) - 2, (int)(v2 + pb) - 2, ratio);  // pad second => < 2 query rows
+            const bool ok = v2 < PAD_V && ratio_pass<METRIC>((int)(v1 + pb) - 2, (int)(v2 + pb) - 2, ratio);  // pad second => < 2 query rows
             d = ok ? (int)(v1 + pb) - 2 : -1;
             c21 += ok;
         }
@@ -1231,7 +1242,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
                 }
             }
             const unsigned pa = (j >> 5) >= A_even ? 1u : 0u;
-            const bool ok = v2 < PAD_V && ratio_pass((int)(v1 + pa) - 2, (int)(v2 + pa) - 2, ratio);  // pad second => < 2 train rows
+            const bool ok = v2 < PAD_V && ratio_pass<METRIC>((int)(v1 + pa) - 2, (int)(v2 + pa) - 2, ratio);  // pad second => < 2 train rows
             c12 += ok;
             // main.cpp:133-140: q is kept iff t's own best match is q, i.e. iff t passes the ratio
             // test (unique minimum for any ratio <= 1) and its minimum is d2(q, t)
@@ -1312,6 +1323,7 @@ constexpr int VER_CANDS = 32 * VER_GROUPS;    // candidates per work item
 // will fail it on the same two numbers); every other row with a real minimum is a candidate of the exact pass — also a row whose bound
 // is a padding value (its runner-up, if it has one, shares the minimum's subset: a train frame of two adjacent rows). Lists the
 // candidates of the pair (candlist, state[p].x = their number) and appends one item per 64 of them for match_colverify_kernel<KS, true>.
+template <int METRIC>
 __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items, int* __restrict__ n_items,
@@ -1333,7 +1345,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
         if (j < 32 * A_tiles && A.orig[j] >= 0) {
             const uint4 e = rowres[(size_t)p * row_stride + j];
             const unsigned pa = (j >> 5) >= A_even ? 1u : 0u;
-            ok = e.x < PAD_V && (e.z >= PAD_V || ratio_pass((int)(e.x + pa) - 2, (int)(e.z + pa) - 2, ratio));
+            ok = e.x < PAD_V && (e.z >= PAD_V || ratio_pass<METRIC>((int)(e.x + pa) - 2, (int)(e.z + pa) - 2, ratio));
         }
         int total;
         const int rank = block_rank(ok, tid, s_wave, total);
@@ -1361,6 +1373,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
 // every column but the best one is at least the runner-up). match_argmin_kernel settles candidate columns with it.
 constexpr int MAX_TILES = MAX_ROWS / 32;
 constexpr int AITEM_SHARED = 1 << 16;   // aitems[..].y: the tile, plus this flag when the pair has more than one item of that tile
+template <int METRIC>
 __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand, int* __restrict__ candlist, int* __restrict__ bytile,
@@ -1391,7 +1404,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
             const unsigned pa = (j >> 5) >= A_even ? 1u : 0u;
             tile = e.y;
             d2 = (int)(e.x + pa) - 2;
-            ok = e.z < PAD_V && ratio_pass(d2, (int)(e.z + pa) - 2, ratio);  // pad second => < 2 train rows
+            ok = e.z < PAD_V && ratio_pass<METRIC>(d2, (int)(e.z + pa) - 2, ratio);  // pad second => < 2 train rows
             low = imin(low, ok ? (int)(e.z + pa) - 2 : d2);   // (a row without a real minimum gives a negative value: nothing is settled then)
         }
         if (j < 32 * A_tiles) rc[j] = ok ? make_uint2(tile, (unsigned)d2) : make_uint2(0xffffffffu, 0u);
@@ -1462,7 +1475,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
 // (the reference needs two neighbours) and every candidate with !ratio_pass(v, lo) stay unresolved: colres[p][j].x = COL_OPEN,
 // match_colpick_kernel lists them for match_colverify_kernel, which decides them as before. settle = 0: every candidate unresolved.
 constexpr unsigned COL_OPEN = 0xffffffffu;
-template <int KS>
+template <int KS, int METRIC>
 __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
                                                           uint2* __restrict__ rowcand, const int* __restrict__ bytile,
                                                           const int4* __restrict__ aitems, const int* __restrict__ n_aitems, int row_stride,
@@ -1505,7 +1518,7 @@ __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __rest
         const int low = state[p].z;
         const int v = (int)rowcand[(size_t)p * row_stride + j].y;
         // (a pair whose L(p) cannot settle even this item's smallest candidate skips the walk)
-        const bool open = settle && !(it.y & AITEM_SHARED) && A.n >= 2 && cl < it.w && ratio_pass(v, low, ratio);
+        const bool open = settle && !(it.y & AITEM_SHARED) && A.n >= 2 && cl < it.w && ratio_pass<METRIC>(v, low, ratio);
         uint2 res = make_uint2(COL_OPEN, 0u);
         if (__ballot(open)) {   // wave-uniform
             const int pb = tile >= B.meta[0] ? 1 : 0;
@@ -1521,7 +1534,7 @@ __global__ __launch_bounds__(64) void match_argmin_kernel(const FrameDev* __rest
             lo = imin(lo, __shfl_xor(lo, 32));
             __syncthreads();
             const unsigned second = (unsigned)(lo - pb + 2);
-            if (open && ratio_pass(v, lo, ratio) && second < PAD_V) res = make_uint2((unsigned)(v - pb + 2), second);
+            if (open && ratio_pass<METRIC>(v, lo, ratio) && second < PAD_V) res = make_uint2((unsigned)(v - pb + 2), second);
         }
         if (h == 0 && cl < it.w) colres[(size_t)p * row_stride + j] = res;
     }
@@ -1718,6 +1731,7 @@ __global__ __launch_bounds__(WG_THREADS) void match_colverify_kernel(
 }
 
 // out_matches[p][k] = {q, t} sorted by q; counts[p] (mode 0: |mutual| if it exceeds min_mutual, else 0; mode 1: |m12|)
+template <int METRIC>
 __global__ __launch_bounds__(FIN_THREADS) void match_finalize2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint2* __restrict__ rowcand,
     const uint2* __restrict__ colres, const int4* __restrict__ state, int row_stride, double ratio, int min_mutual, int mode,
@@ -1750,7 +1764,7 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize2_kernel(
                 const uint2 v = cr[j];
                 const unsigned pb = (c.x >> 5) >= (unsigned)B_even ? 1u : 0u;
                 const int d1 = (int)(v.x + pb) - 2;
-                if (d1 == (int)c.y && v.y < PAD_V && ratio_pass(d1, (int)(v.y + pb) - 2, ratio)) keep = (int)c.x;
+                if (d1 == (int)c.y && v.y < PAD_V && ratio_pass<METRIC>(d1, (int)(v.y + pb) - 2, ratio)) keep = (int)c.x;
             }
         }
         keepcol[j] = keep;
@@ -1831,13 +1845,15 @@ static void with_ks(int ks, F&& f) {
     else f(std::integral_constant<int, 8>{});
 }
 
-static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim) {
+// kind 0: the caller's integer rows; kind 2 (binary frames): rows of 0 / 255 expanded from packed bits, which get 8 words per row
+// behind the per-row arrays for their packed copy (FrameHost::bits, filled by the caller)
+static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim, int kind = 0) {
     if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
     if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
     int ks = ks_for_dim(dim);
     if (!ks) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "descriptor dim %d: need a multiple of 16 up to 128, or 129..256", dim);
-    if (ctx->ks_common && (ctx->ks_common != ks || ctx->kind_common != 0))
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32) and dim class");
+    if (ctx->ks_common && (ctx->ks_common != ks || ctx->kind_common != kind))
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32 / binary) and dim class");
     // each parity class is padded to whole tiles (at most one extra tile), the total to whole wave-blocks
     const int group_rows = 32 * GROUP_TILES;
     const int ntiles = n > 0 ? ((n + 31) / 32 + 1 + GROUP_TILES - 1) / GROUP_TILES * GROUP_TILES : 0;
@@ -1855,8 +1871,8 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
     f.img16_ready = false;  // (an empty frame has no allocation, yet counts as imaged: the new rows need an image of their own)
     const int npad = ntiles * 32;
     {
-        // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[2]
-        const size_t ints = (size_t)6 * npad + 2;
+        // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[2]; binary frames only: + 6 unused (32-byte alignment) | the packed rows, 8 words each
+        const size_t ints = (size_t)6 * npad + 2 + (kind == 2 ? 6 + (size_t)8 * n : 0);
         EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.norm, ints * sizeof(int)));
         EACHAM_HIP_TRY(ctx, hipMemsetAsync(f.norm, 0, ints * sizeof(int), ctx->stream));
         f.normb = f.norm + npad;
@@ -1865,6 +1881,7 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
         int* s2 = f.norm + 4 * (size_t)npad;
         int* s1 = f.norm + 5 * (size_t)npad;
         f.meta = f.norm + 6 * (size_t)npad;
+        if (kind == 2) f.bits = (unsigned*)(f.norm + 6 * (size_t)npad + 8);   // 32-byte aligned: npad is a multiple of 32
         if (npad > 0) {
             // above 128-D the FP6 image of the screen sweep follows the int8 fragments: image | |M|^2 | s_r | {E} (quantize_screen_kernel)
             const size_t frag_bytes = (size_t)ntiles * ks * 64 * sizeof(int4);
@@ -1892,8 +1909,9 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
     f.ks = ks;
     f.ntiles = ntiles;
     ctx->ks_common = ks;
-    ctx->kind_common = 0;
+    ctx->kind_common = kind;
     ctx->frame_table_dirty = true;
+    ctx->bits_table_dirty = true;
     return EACHAM_OK;
 }
 
@@ -1916,7 +1934,7 @@ static unsigned long long* colprune_totals(eacham_ctx* ctx) { return (unsigned l
 static unsigned long long* screen_tally(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 52); }
 // every resident frame with rows carries the FP6 image (all frames share one dim class, so this is ks_common == 8)
 static bool frames_have_screen(const eacham_ctx* ctx) {
-    if (ctx->kind_common != 0 || ctx->ks_common != 8) return false;
+    if (ctx->kind_common == 1 || ctx->ks_common != 8) return false;
     for (const auto& f : ctx->frames)
         if (f.n > 0 && !f.screen) return false;
     return true;
@@ -1994,9 +2012,10 @@ static int next_batch(const MatchPlan& pl, int first, int npairs) {
 }
 
 // Core driver, CSR over the pairs out. mode 0 = mutual + thresholds, mode 1 = directed lists.
-static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir,
-                     int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
-                     uint2* edges_dev, long long edge_cap, long long* total_dev, int4* stats_dev) {
+template <int METRIC>
+static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir,
+                            int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
+                            uint2* edges_dev, long long edge_cap, long long* total_dev, int4* stats_dev, const int2** pairs_used) {
     int rc = sync_frame_table(ctx);
     if (rc) return rc;
     if (npairs <= 0) return EACHAM_OK;
@@ -2004,6 +2023,10 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
         return ctx->fail(EACHAM_ERR_INVALID, "ratio %g: mutual matching supports 0 < ratio <= 1 (the reference uses 0.8)", ratio);
     rc = sanitize_pairs(ctx, pairs_dev, npairs, &pairs_dev);  // a bad frame id in a device-side list must not reach the kernels
     if (rc) return rc;
+    if (pairs_used) *pairs_used = pairs_dev;   // the list the kernels ran on (what the Hamming distance kernel indexes the frames with)
+    if (METRIC != (ctx->kind_common == 2 ? METRIC_HAMMING : METRIC_L2))
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, ctx->kind_common == 2 ? "the resident frames are binary: use the _hamming entry points"
+                                                                       : "Hamming matching needs binary frames (eacham_upload_descriptors_bits)");
     if (ctx->kind_common == 1)
         return run_match_f32(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
                              edge_cap, total_dev, stats_dev);
@@ -2017,8 +2040,8 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     if (rc) return rc;
     const size_t fin_smem = (size_t)(full_cols ? 2 : 1) * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024) {
-        if (full_cols) EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
-        else EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
+        if (full_cols) EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_kernel<METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
+        else EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize2_kernel<METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
     }
     // Two streams: the tile kernels run back to back on the context stream; finalize, scan and
     // compaction of a batch run on stream2 beside the next batch's tile kernel (they are bound by
@@ -2071,7 +2094,7 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st2);
             if (full_cols) {
-                match_finalize_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(
+                match_finalize_kernel<METRIC><<<nb, FIN_THREADS, fin_smem, st2>>>(
                     ctx->frame_table_dev, pb, rowres, (const uint2*)(ws + pl.off_colpart), pl.col_chunks, pl.wb_stride, pl.row_stride, ratio,
                     min_dir, min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
             } else {
@@ -2093,14 +2116,14 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                 with_ks(ctx->ks_common, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value;
                     if (bound_sweep || screen_sweep) {   // the rows the bound / screen form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
-                        match_rowpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre,
+                        match_rowpick_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre,
                                                                           screen_sweep ? screen_tally(ctx) : nullptr);
                         match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
                                                                                         pl.row_stride, 0, nullptr, rowres);
                     }
-                    match_rows2_kernel<<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
+                    match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
                                                                     rowcand, candlist, bytile, state, aitems, n_aitems);
-                    match_argmin_kernel<KS><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride,
+                    match_argmin_kernel<KS, METRIC><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride,
                                                                    mode == 0 ? colres : nullptr, state, ratio, ctx->match_colprune ? 1 : 0);
                     if (mode == 0) {   // the candidates the arg-min pass could not settle (state[p].w of them): listed, then the column pass
                         match_colpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(candlist, colres, state, pl.row_stride, openlist, items, n_items, colprune_totals(ctx));
@@ -2108,7 +2131,7 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
                                                                                   pl.row_stride, 3, colres);
                     }
                 });
-                match_finalize2_kernel<<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
+                match_finalize2_kernel<METRIC><<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
                                                                           min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt);
             }
             scan_counts_kernel<<<1, 1024, 0, st2>>>(cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
@@ -2121,6 +2144,16 @@ static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double 
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st2));         // later work on the context stream sees the results
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st1, ctx->ev_join, 0));
     return EACHAM_OK;
+}
+
+static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int metric, int min_dir, int min_mutual, int mode,
+                     int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev, int4* stats_dev,
+                     const int2** pairs_used = nullptr) {
+    return metric == METRIC_HAMMING
+               ? run_match_metric<METRIC_HAMMING>(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
+                                                  edge_cap, total_dev, stats_dev, pairs_used)
+               : run_match_metric<METRIC_L2>(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
+                                             edge_cap, total_dev, stats_dev, pairs_used);
 }
 
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last) {
@@ -2158,18 +2191,22 @@ static int match_entry(eacham_ctx* ctx, Body body) {
 
 // What a host-pointer call runs: the L2 ratio test on the resident frames (int8 or float), the dot-product form on float
 // frames (matcher_dot.hip), or that form behind the fp16 screen (matcher_dot16.hip; mutual only).
-enum MatchForm { MATCH_L2, MATCH_DOT, MATCH_DOT_SCREENED };
+enum MatchForm { MATCH_L2, MATCH_DOT, MATCH_DOT_SCREENED, MATCH_HAMMING };
 
 // Host pointers in, CSR over the pairs out: mode 0 = mutual + thresholds, mode 1 = directed lists. `thresh` is the ratio of the
-// L2 form or the minimum score of the dot forms, which also fill out_score.
+// L2 and Hamming forms or the minimum score of the dot forms. out_val: one 4-byte value per match, the float score of the dot forms,
+// the int32 Hamming distance of the Hamming form (may be null), nothing in the L2 form.
 static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pairs, int npairs, double thresh, int min_dir,
                             int min_mutual, int mode, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t,
-                            float* out_score, int64_t cap, int64_t* out_total, int32_t* stats) {
-    const bool dot = form != MATCH_L2;
+                            void* out_val, int64_t cap, int64_t* out_total, int32_t* stats) {
+    const bool dot = form == MATCH_DOT || form == MATCH_DOT_SCREENED, ham = form == MATCH_HAMMING;
     if (npairs < 0 || (npairs > 0 && (!pairs || !counts || !offsets)) || !out_total || cap < 0 || (cap > 0 && (!out_q || !out_t)))
         return ctx->fail(EACHAM_ERR_INVALID, dot ? "bad arguments to the dot-product matcher" : "bad arguments to match_all_pairs");
     int rc = check_pairs_host(ctx, pairs, npairs);
     if (rc) return rc;
+    if (npairs > 0 && !dot && ham != (ctx->kind_common == 2))
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, ham ? "Hamming matching needs binary frames (eacham_upload_descriptors_bits)"
+                                                     : "the resident frames are binary: use the _hamming entry points");
     if (!dot) {
         rc = check_integer_flag(ctx);
         if (rc) return rc;
@@ -2201,21 +2238,26 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
     if (stats) h_stats = io.out<int4>(stats, (size_t)npairs);
     // device-only: as results they would pin cap elements and come back whole, where only `total` of them are wanted
     const auto h_edges = io.scratch<uint2>((size_t)cap);
-    const auto h_scores = io.scratch<float>(dot ? (size_t)cap : 0);
+    const auto h_vals = io.scratch<uint32_t>(dot || (ham && out_val) ? (size_t)cap : 0);   // 4 bytes per match: float scores or int32 distances
     IoDev d;
     rc = io.upload(d);
     if (rc) return rc;
     int4* stats_dev = stats ? d(h_stats) : nullptr;   // null selects the lean form in run_match
+    const int2* pairs_used = nullptr;   // the sanitised list run_match ran on
     if (form == MATCH_DOT_SCREENED)
         rc = run_match_dot_screened(ctx, d(h_pairs), d(h_fb), pairs_fb.data(), npairs, n_fallback, (float)thresh, min_dir, min_mutual,
-                                    d(h_counts), d(h_offsets), d(h_edges), d(h_scores), cap, d(h_total), stats_dev);
+                                    d(h_counts), d(h_offsets), d(h_edges), (float*)d(h_vals), cap, d(h_total), stats_dev);
     else if (form == MATCH_DOT)
         rc = run_match_dot(ctx, d(h_pairs), npairs, (float)thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
-                           d(h_scores), cap, d(h_total), stats_dev);
+                           (float*)d(h_vals), cap, d(h_total), stats_dev);
     else
-        rc = run_match(ctx, d(h_pairs), npairs, thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges), cap, d(h_total),
-                       stats_dev);
+        rc = run_match(ctx, d(h_pairs), npairs, thresh, ham ? METRIC_HAMMING : METRIC_L2, min_dir, min_mutual, mode, d(h_counts),
+                       d(h_offsets), d(h_edges), cap, d(h_total), stats_dev, &pairs_used);
     if (rc) return rc;
+    if (ham && out_val) {
+        rc = hamming_distances(ctx, pairs_used, npairs, d(h_offsets), d(h_total), d(h_edges), cap, (int*)d(h_vals));
+        if (rc) return rc;
+    }
     rc = io.finish();
     if (rc) return rc;
     *out_total = total;
@@ -2228,7 +2270,7 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
             out_q[k] = tmp[k].x;
             out_t[k] = tmp[k].y;
         }
-        if (out_score) EACHAM_HIP_TRY(ctx, hipMemcpy(out_score, d(h_scores), sizeof(float) * (size_t)total, hipMemcpyDeviceToHost));
+        if (out_val && (dot || ham)) EACHAM_HIP_TRY(ctx, hipMemcpy(out_val, d(h_vals), sizeof(uint32_t) * (size_t)total, hipMemcpyDeviceToHost));
     }
     return EACHAM_OK;
 }
@@ -2283,7 +2325,7 @@ int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int np
     if (npairs < 0 || (npairs > 0 && (!pairs_dev || !counts_dev || !offsets_dev || !total_dev)) ||
         edge_cap < 0 || (edge_cap > 0 && !edges_dev))
         return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_all_pairs_dev");
-    return run_match(ctx, (const int2*)pairs_dev, npairs, ratio, min_dir, min_mutual, 0, counts_dev,
+    return run_match(ctx, (const int2*)pairs_dev, npairs, ratio, METRIC_L2, min_dir, min_mutual, 0, counts_dev,
                      (long long*)offsets_dev, (uint2*)edges_dev, edge_cap, (long long*)total_dev,
                      (int4*)stats_dev);
 }
@@ -2443,6 +2485,99 @@ int eacham_match_all_pairs_dot_screened(eacham_ctx* ctx, const int32_t* pairs, i
     return match_entry(ctx, [&]() -> int {
         return match_pairs_host(ctx, MATCH_DOT_SCREENED, pairs, npairs, min_score, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_score,
                                 cap, out_total, stats);
+    });
+}
+
+// ---- binary descriptors under Hamming distance (matcher_ham.hip): CSR over the pairs + distances out ----
+// The packed rows (device pointer) become a resident binary frame: expanded to 0 / 255 floats in the staging buffer for the int8
+// upload kernels, padded with zero bits to the next legal dimension, and kept packed beside the frame for the distance kernel.
+static int upload_frame_bits(eacham_ctx* ctx, int frame_id, const unsigned char* packed_dev, int n, int bytes_per_row, size_t stage_off) {
+    const int dim = bytes_per_row <= 16 ? (8 * bytes_per_row + 15) / 16 * 16 : 8 * bytes_per_row;
+    if (n > 0) launch_bits_expand(ctx, packed_dev, n, bytes_per_row, dim, (float*)((char*)ctx->io + stage_off));
+    int rc = upload_frame(ctx, frame_id, (const float*)((char*)ctx->io + stage_off), n, dim, 2);
+    if (rc) return rc;
+    if (n > 0) launch_bits_store(ctx, packed_dev, n, bytes_per_row, ctx->frames[frame_id].bits);
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // orders reuse of the staging buffer (and of the caller's rows)
+    return EACHAM_OK;
+}
+static int check_bits_shape(eacham_ctx* ctx, const void* rows, int n, int bytes_per_row) {
+    if (n < 0 || bytes_per_row <= 0) return ctx->fail(EACHAM_ERR_INVALID, "bad descriptor shape %d x %d bytes", n, bytes_per_row);
+    if (n > 0 && !rows) return ctx->fail(EACHAM_ERR_INVALID, "null descriptor pointer");
+    if (bytes_per_row > 32) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "binary descriptors of %d bytes: this build supports <= 32 (256 bits)", bytes_per_row);
+    if (n > MAX_ROWS) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "frame has %d rows; this build supports <= %d", n, MAX_ROWS);
+    return EACHAM_OK;
+}
+static size_t bits_stage_bytes(int n, int bytes_per_row) {   // the expanded rows (a padded dimension is at most 8 bits per byte + 8)
+    return ((size_t)n * (8 * bytes_per_row + 8) * sizeof(float) + 255) & ~(size_t)255;
+}
+
+int eacham_upload_descriptors_bits_dev(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor_dev, int n, int bytes_per_row) {
+    return match_entry(ctx, [&]() -> int {
+        int rc = check_bits_shape(ctx, rowmajor_dev, n, bytes_per_row);
+        if (rc) return rc;
+        rc = ensure_io(ctx, std::max<size_t>(bits_stage_bytes(n, bytes_per_row), 256));
+        if (rc) return rc;
+        return upload_frame_bits(ctx, frame_id, rowmajor_dev, n, bytes_per_row, 0);
+    });
+}
+
+int eacham_upload_descriptors_bits(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor, int n, int bytes_per_row) {
+    return match_entry(ctx, [&]() -> int {
+        int rc = check_bits_shape(ctx, rowmajor, n, bytes_per_row);
+        if (rc) return rc;
+        // staging: the packed rows as they came (the only host-to-device copy), then the expanded rows
+        const size_t packed = ((size_t)n * bytes_per_row + 255) & ~(size_t)255;
+        rc = ensure_io(ctx, std::max<size_t>(packed + bits_stage_bytes(n, bytes_per_row), 256));
+        if (rc) return rc;
+        if (n > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(ctx->io, rowmajor, (size_t)n * bytes_per_row, hipMemcpyHostToDevice, ctx->stream));
+        return upload_frame_bits(ctx, frame_id, (const unsigned char*)ctx->io, n, bytes_per_row, packed);
+    });
+}
+
+int eacham_match_pair_hamming(eacham_ctx* ctx, int f1, int f2, double ratio, uint32_t* out_q, uint32_t* out_t, int32_t* out_dist,
+                              int cap, int* out_count) {
+    return match_entry(ctx, [&]() -> int {
+        if (!out_count) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+        const int32_t pr[2] = {f1, f2};
+        int32_t count = 0;
+        int64_t offsets[2] = {0, 0}, total = 0;
+        const int rc = match_pairs_host(ctx, MATCH_HAMMING, pr, 1, ratio, 0, 0, 1, &count, offsets, out_q, out_t, out_dist, cap, &total, nullptr);
+        if (rc == EACHAM_OK || rc == EACHAM_ERR_CAPACITY) *out_count = (int)total;
+        return rc;
+    });
+}
+
+int eacham_match_pairs_directed_hamming(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int32_t* counts,
+                                        int64_t* offsets, uint32_t* out_q, uint32_t* out_t, int32_t* out_dist, int64_t cap,
+                                        int64_t* out_total) {
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_HAMMING, pairs, npairs, ratio, 0, 0, 1, counts, offsets, out_q, out_t, out_dist, cap, out_total, nullptr);
+    });
+}
+
+int eacham_match_all_pairs_hamming(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio, int min_dir, int min_mutual,
+                                   int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, int32_t* out_dist, int64_t cap,
+                                   int64_t* out_total, int32_t* stats) {
+    return match_entry(ctx, [&]() -> int {
+        return match_pairs_host(ctx, MATCH_HAMMING, pairs, npairs, ratio, min_dir, min_mutual, 0, counts, offsets, out_q, out_t, out_dist, cap,
+                                out_total, stats);
+    });
+}
+
+int eacham_match_all_pairs_hamming_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual,
+                                       int32_t* counts_dev, int64_t* offsets_dev, uint32_t* edges_dev, int64_t edge_cap,
+                                       int64_t* total_dev, int32_t* stats_dev, int32_t* dist_dev) {
+    return match_entry(ctx, [&]() -> int {
+        if (npairs < 0 || (npairs > 0 && (!pairs_dev || !counts_dev || !offsets_dev || !total_dev)) || edge_cap < 0 ||
+            (edge_cap > 0 && !edges_dev))
+            return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_all_pairs_hamming_dev");
+        const int2* pairs_used = nullptr;
+        int rc = run_match(ctx, (const int2*)pairs_dev, npairs, ratio, METRIC_HAMMING, min_dir, min_mutual, 0, counts_dev, (long long*)offsets_dev,
+                           (uint2*)edges_dev, edge_cap, (long long*)total_dev, (int4*)stats_dev, &pairs_used);
+        if (rc || !dist_dev || npairs <= 0) return rc;
+        return hamming_distances(ctx, pairs_used, npairs, (const long long*)offsets_dev, (const long long*)total_dev, (const uint2*)edges_dev,
+                                 edge_cap, dist_dev);
     });
 }
 

@@ -249,6 +249,61 @@ class HipContext:
         self._check(self._L.eacham_match_debug_dot_coarse(self._h, f1, f2, s.ctypes.data if s.size else None, re.ctypes.data, ce.ctypes.data))
         return s, re[:n1], ce[:n2]
 
+    # ---- binary descriptors under Hamming distance, distances returned ----------------------
+    def upload_descriptors_bits(self, frame_id: int, rows: np.ndarray):
+        """Packed binary descriptors (ORB / BRIEF / AKAZE): an N x B uint8 matrix, B = 1..32 bytes per row."""
+        d = np.ascontiguousarray(rows, dtype=np.uint8)
+        if d.ndim != 2:
+            raise ValueError("binary descriptors must be an N x B uint8 matrix")
+        self._check(self._L.eacham_upload_descriptors_bits(self._h, frame_id, d.ctypes.data, d.shape[0], d.shape[1]))
+
+    def upload_descriptors_bits_dev(self, frame_id: int, dev_ptr: int, n: int, bytes_per_row: int):
+        self._check(self._L.eacham_upload_descriptors_bits_dev(self._h, frame_id, C.c_void_p(dev_ptr), n, bytes_per_row))
+
+    def match_pair_hamming(self, f1: int, f2: int, ratio: float = RATIO):
+        """(q, t, dist) of the directed match f1 -> f2 of two binary frames: BFMatcher(NORM_HAMMING) + the ratio test."""
+        cap = max(self.frame_rows(f1), 1)
+        q = np.empty(cap, dtype=np.uint32)
+        t = np.empty(cap, dtype=np.uint32)
+        d = np.empty(cap, dtype=np.int32)
+        cnt = C.c_int(0)
+        self._check(self._L.eacham_match_pair_hamming(self._h, f1, f2, ratio, q.ctypes.data, t.ctypes.data, d.ctypes.data, cap, C.byref(cnt)))
+        return q[:cnt.value].copy(), t[:cnt.value].copy(), d[:cnt.value].copy()
+
+    def _ham_buffers(self, pairs, cap):
+        pairs, npairs, cap, counts, offsets, q, t, _ = self._dot_buffers(pairs, cap)
+        return pairs, npairs, cap, counts, offsets, q, t, np.empty(max(cap, 1), dtype=np.int32)
+
+    def match_pairs_directed_hamming(self, ordered_pairs, ratio: float = RATIO, cap: int | None = None):
+        """Every ordered pair (i, j) of the RESIDENT binary frames as one directed Hamming match, in one launch sequence.
+        Returns (counts, offsets, q, t, dist): CSR over the pairs."""
+        pairs, npairs, cap, counts, offsets, q, t, d = self._ham_buffers(ordered_pairs, cap)
+        total = C.c_int64(0)
+        self._check(self._L.eacham_match_pairs_directed_hamming(self._h, pairs.ctypes.data, npairs, ratio, counts.ctypes.data,
+                                                                offsets.ctypes.data, q.ctypes.data, t.ctypes.data, d.ctypes.data, cap, C.byref(total)))
+        n = total.value
+        return counts, offsets, q[:n].copy(), t[:n].copy(), d[:n].copy()
+
+    def match_all_pairs_hamming(self, pairs, ratio: float = RATIO, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL,
+                                cap: int | None = None, stats: bool = True):
+        """The mutual form (eacham_match_all_pairs_hamming). Returns (counts, offsets, q, t, dist, stats)."""
+        pairs, npairs, cap, counts, offsets, q, t, d = self._ham_buffers(pairs, cap)
+        st = np.zeros((npairs, 4), dtype=np.int32) if stats else None
+        total = C.c_int64(0)
+        self._check(self._L.eacham_match_all_pairs_hamming(
+            self._h, pairs.ctypes.data, npairs, ratio, min_dir, min_mutual, counts.ctypes.data, offsets.ctypes.data,
+            q.ctypes.data, t.ctypes.data, d.ctypes.data, cap, C.byref(total), st.ctypes.data if stats else None))
+        n = total.value
+        return counts, offsets, q[:n].copy(), t[:n].copy(), d[:n].copy(), st
+
+    def match_all_pairs_hamming_dev(self, pairs_dev: int, npairs: int, counts_dev: int, offsets_dev: int,
+                                    edges_dev: int, edge_cap: int, total_dev: int, stats_dev: int = 0, dist_dev: int = 0,
+                                    ratio: float = RATIO, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL):
+        vp = C.c_void_p
+        self._check(self._L.eacham_match_all_pairs_hamming_dev(
+            self._h, vp(pairs_dev), npairs, ratio, min_dir, min_mutual, vp(counts_dev), vp(offsets_dev),
+            vp(edges_dev), edge_cap, vp(total_dev), vp(stats_dev) if stats_dev else None, vp(dist_dev) if dist_dev else None))
+
     def match_all_pairs_dev(self, pairs_dev: int, npairs: int, counts_dev: int, offsets_dev: int,
                             edges_dev: int, edge_cap: int, total_dev: int, stats_dev: int = 0,
                             ratio: float = RATIO, min_dir: int = MIN_DIRECTED, min_mutual: int = MIN_MUTUAL):
@@ -355,3 +410,30 @@ class FeatureMatcherDotHip:
 
     def LastScores(self) -> dict:
         return self._scores
+
+
+class FeatureMatcherHammingHip:
+    """Mirror of eacham::hip::FeatureMatcherHammingHip (include/eacham/FeatureMatcherHip.hpp): packed binary descriptors
+    (N x B uint8, cv::Mat CV_8U layout) matched under Hamming distance. `Match(d1, d2)` returns {queryIdx: trainIdx}: the
+    directed ratio-test match, or with `mutual` the pair's one-to-one matches; `LastDistances()` gives
+    {queryIdx: Hamming distance} of that call."""
+
+    def __init__(self, ratio: float = RATIO, mutual: bool = False, context: HipContext | None = None):
+        self.ratio = ratio
+        self.mutual = mutual
+        self.ctx = context or HipContext()
+        self._dist = {}
+
+    def Match(self, descriptor1: np.ndarray, descriptor2: np.ndarray) -> dict:
+        self.ctx.clear_descriptors()
+        self.ctx.upload_descriptors_bits(0, descriptor1)
+        self.ctx.upload_descriptors_bits(1, descriptor2)
+        if self.mutual:
+            _, _, q, t, d, _ = self.ctx.match_all_pairs_hamming([[0, 1]], self.ratio, 0, -1, stats=False)
+        else:
+            q, t, d = self.ctx.match_pair_hamming(0, 1, self.ratio)
+        self._dist = dict(zip(q.tolist(), d.tolist()))
+        return dict(zip(q.tolist(), t.tolist()))
+
+    def LastDistances(self) -> dict:
+        return self._dist

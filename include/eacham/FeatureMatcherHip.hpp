@@ -518,6 +518,118 @@ inline MatchGraphDot MatchAllPairsDot(Context& ctx, const std::vector<Descriptor
     return g;
 }
 
+// ---- binary descriptors under Hamming distance ---------------------------------------------------
+// Stands where cv::BFMatcher(NORM_HAMMING) + the ratio test of FeatureMatcherFlann.cpp:23 would stand for the ORB configurations of
+// the reference (config/ConfigTUM.json:27, ConfigKITTI.json, ConfigRealsense.json): packed rows of 1..32 bytes (the cv::Mat CV_8U
+// layout of ORB / BRIEF / AKAZE), distance = differing bits, q -> t0 kept iff (float)h0 / (float)h1 < ratio (eacham_match_*_hamming).
+struct BinaryDescriptorView {
+    const uint8_t* data = nullptr;
+    int rows = 0;
+    int bytes = 0;   // bytes per row
+};
+
+//   mutual = false: the directed match of Match(d1, d2), as FeatureMatcherHip; mutual = true: the pair's one-to-one matches.
+// Thread-safe like FeatureMatcherDotHip: one shared instance may be called from many threads, calls are served one at a time on the
+// instance's own context; no upload cache and no combining of concurrent callers (the batch call is MatchAllPairsHamming below).
+class FeatureMatcherHammingHip : public IFeatureMatcher<BinaryDescriptorView> {
+public:
+    using DistanceType = std::unordered_map<unsigned, int>;  // query index -> Hamming distance of its match
+
+    explicit FeatureMatcherHammingHip(double ratio = 0.8, bool mutual = false, int device = 0) : ratio_(ratio), mutual_(mutual), ctx_(device) {}
+
+    MatchType Match(const BinaryDescriptorView& d1, const BinaryDescriptorView& d2) override { return Match(d1, d2, nullptr); }
+
+    // The distances alongside (the form to use under concurrent callers).
+    MatchType Match(const BinaryDescriptorView& d1, const BinaryDescriptorView& d2, DistanceType* distances) {
+        std::lock_guard<std::mutex> lk(mu_);
+        const int n1 = d1.rows > 0 ? d1.rows : 0;
+        ctx_.check(eacham_clear_descriptors(ctx_.get()));   // (two calls may bring rows of different lengths)
+        ctx_.check(eacham_upload_descriptors_bits(ctx_.get(), 0, d1.data, d1.rows, d1.bytes));
+        ctx_.check(eacham_upload_descriptors_bits(ctx_.get(), 1, d2.data, d2.rows, d2.bytes));
+        std::vector<uint32_t> q((size_t)(n1 > 0 ? n1 : 1)), t(q.size());
+        std::vector<int32_t> h(q.size());
+        int64_t total = 0;
+        if (mutual_) {
+            const int32_t pair[2] = {0, 1};
+            int32_t count = 0;
+            int64_t offsets[2] = {0, 0};
+            ctx_.check(eacham_match_all_pairs_hamming(ctx_.get(), pair, 1, ratio_, 0, -1, &count, offsets, q.data(), t.data(), h.data(), n1,
+                                                      &total, nullptr));
+        } else {
+            int count = 0;
+            ctx_.check(eacham_match_pair_hamming(ctx_.get(), 0, 1, ratio_, q.data(), t.data(), h.data(), n1, &count));
+            total = count;
+        }
+        MatchType out;
+        out.reserve((size_t)total);
+        last_.clear();
+        for (int64_t k = 0; k < total; ++k) {
+            out.insert({q[k], t[k]});
+            last_.insert({q[k], (int)h[k]});
+        }
+        if (distances) *distances = last_;
+        return out;
+    }
+
+#ifdef EACHAM_HIP_HAVE_OPENCV
+    MatchType Match(const cv::Mat& d1, const cv::Mat& d2) {
+        if (d1.type() != CV_8U || d2.type() != CV_8U || !d1.isContinuous() || !d2.isContinuous())
+            throw std::runtime_error("eacham_hip: binary descriptors must be continuous CV_8U matrices");
+        return Match(BinaryDescriptorView{d1.ptr<uint8_t>(), d1.rows, d1.cols}, BinaryDescriptorView{d2.ptr<uint8_t>(), d2.rows, d2.cols});
+    }
+#endif
+
+    // Distances of the most recent Match() on this instance (a copy); under concurrent callers use the overload above.
+    DistanceType LastDistances() {
+        std::lock_guard<std::mutex> lk(mu_);
+        return last_;
+    }
+
+    Context& context() { return ctx_; }
+
+private:
+    double ratio_;
+    bool mutual_;
+    Context ctx_;
+    std::mutex mu_;
+    DistanceType last_;
+};
+
+struct MatchGraphHamming : MatchGraph {
+    std::vector<int32_t> distances;  // distances[k] = Hamming distance of q[k] -> t[k]
+};
+
+// MatchAllPairs for binary descriptors: rewrites the context's descriptor store (frame f -> id f), matches every pair in both
+// directions with the mutual check and the thresholds given. The graph is what GetBestPairForValid / ResidentMatchGraph take.
+inline MatchGraphHamming MatchAllPairsHamming(Context& ctx, const std::vector<BinaryDescriptorView>& frames,
+                                              const std::vector<std::pair<unsigned, unsigned>>& pairs, double ratio = 0.8,
+                                              int min_directed = 30, int min_mutual = 30) {
+    ctx.store_rewritten();
+    ctx.check(eacham_clear_descriptors(ctx.get()));
+    for (size_t f = 0; f < frames.size(); ++f)
+        ctx.check(eacham_upload_descriptors_bits(ctx.get(), (int)f, frames[f].data, frames[f].rows, frames[f].bytes));
+    std::vector<int32_t> flat(2 * pairs.size());
+    int64_t cap = 0;
+    for (size_t p = 0; p < pairs.size(); ++p) {
+        flat[2 * p] = (int32_t)pairs[p].first;
+        flat[2 * p + 1] = (int32_t)pairs[p].second;
+        cap += frames.at(pairs[p].first).rows;
+    }
+    MatchGraphHamming g;
+    g.counts.resize(pairs.size());
+    g.offsets.resize(pairs.size() + 1);
+    g.q.resize(cap > 0 ? cap : 1);
+    g.t.resize(g.q.size());
+    g.distances.resize(g.q.size());
+    int64_t total = 0;
+    ctx.check(eacham_match_all_pairs_hamming(ctx.get(), flat.data(), (int)pairs.size(), ratio, min_directed, min_mutual, g.counts.data(),
+                                             g.offsets.data(), g.q.data(), g.t.data(), g.distances.data(), cap, &total, nullptr));
+    g.q.resize(total);
+    g.t.resize(total);
+    g.distances.resize(total);
+    return g;
+}
+
 // ---- view-graph query on the CSR match graph ---------------------------------------------------
 // std::tuple<unsigned, unsigned, unsigned> Graph::GetBestPairForValid(const std::set<unsigned>& excluded)
 //     /root/reference/modules/sfm/data/Graph.h:59-106

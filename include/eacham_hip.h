@@ -219,6 +219,43 @@ int eacham_match_debug_dot_screen(eacham_ctx* ctx, int64_t out[7]);
  * stored norm bounds with the formula and rounding steps of the classify kernel. */
 int eacham_match_debug_dot_coarse(eacham_ctx* ctx, int f1, int f2, float* s_coarse, float* row_E, float* col_E);
 
+/* ---- binary descriptors under Hamming distance, distances returned -----------------------------
+ * ORB / BRIEF / AKAZE rows (the reference's TUM, KITTI and Realsense configurations name ORB; its 256-bit popcount distance is
+ * modules/base/tools/Tools3d.h:47-63), matched as cv::BFMatcher(NORM_HAMMING) + the ratio test of FeatureMatcherFlann.cpp:23
+ * would: distance = the number of differing bits, an integer stored as float, and q -> t0 is kept iff
+ *   (double)((float)h0 / (float)h1) < ratio        (no square root: 5 h0 = 4 h1 fails at 0.8; 0/0 fails; 0/h1 passes)
+ * Everything else — two nearest rows, ties -> the lower train index, output sorted by q, fewer than 2 train rows -> empty,
+ * thresholds, mutual check, ratio in (0, 1] for the mutual form, CSR layout, error codes, capacity — is word for word
+ * eacham_match_pair / eacham_match_pairs_directed / eacham_match_all_pairs[_dev]. The CSR output is what eacham_graph_* and
+ * eacham_tracks_build take.
+ * out_dist[k] (int32, may be NULL) = the Hamming distance of emitted match k, computed from the packed rows themselves.
+ *
+ * Upload: n rows of bytes_per_row bytes, packed (bit order is irrelevant to the distance), bytes_per_row in 1..32; above 32
+ * (more than 256 bits) EACHAM_ERR_UNSUPPORTED. Rows are padded with zero bits to the next dimension eacham_upload_descriptors
+ * accepts. The host-to-device copy is the packed bytes. Binary frames are a third kind: mixing them with int8 or fp32 frames in
+ * one context is EACHAM_ERR_UNSUPPORTED at upload (eacham_clear_descriptors resets the kind), the L2 and dot-product entry
+ * points return EACHAM_ERR_UNSUPPORTED on binary frames and the calls below return it on other frames.
+ * Limits: <= 256 bits, <= 16384 rows per frame. There is no sharded form. */
+int eacham_upload_descriptors_bits(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor, int n, int bytes_per_row);
+/* Same, source already on the device. */
+int eacham_upload_descriptors_bits_dev(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor_dev, int n, int bytes_per_row);
+int eacham_match_pair_hamming(eacham_ctx* ctx, int f1, int f2, double ratio,
+                              uint32_t* out_q, uint32_t* out_t, int32_t* out_dist, int cap, int* out_count);
+int eacham_match_pairs_directed_hamming(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio,
+                                        int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t,
+                                        int32_t* out_dist, int64_t cap, int64_t* out_total);
+int eacham_match_all_pairs_hamming(eacham_ctx* ctx, const int32_t* pairs, int npairs, double ratio,
+                                   int min_dir, int min_mutual,
+                                   int32_t* counts, int64_t* offsets,
+                                   uint32_t* out_q, uint32_t* out_t, int32_t* out_dist, int64_t cap, int64_t* out_total,
+                                   int32_t* stats);
+/* As eacham_match_all_pairs_dev; dist_dev: edge_cap int32 (one per entry of edges_dev that is written) or NULL. */
+int eacham_match_all_pairs_hamming_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int npairs, double ratio,
+                                       int min_dir, int min_mutual,
+                                       int32_t* counts_dev, int64_t* offsets_dev,
+                                       uint32_t* edges_dev, int64_t edge_cap, int64_t* total_dev,
+                                       int32_t* stats_dev, int32_t* dist_dev);
+
 /* ---- bundle adjustment: RefineBA (modules/sfm/reconstruction/BundleAdjuster.cpp:40-250) --------
  *
  * The caller (the C++ adapter in include/eacham/BundleAdjusterHip.hpp) performs the reference's
