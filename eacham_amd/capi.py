@@ -91,6 +91,11 @@ def lib() -> C.CDLL:
         L.eacham_match_pairs_directed_hamming.argtypes = [vp, vp, i32, dbl, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]
         L.eacham_match_all_pairs_hamming.argtypes = [vp, vp, i32, dbl, i32, i32, vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]
         L.eacham_match_all_pairs_hamming_dev.argtypes = [vp, vp, i32, dbl, i32, i32, vp, vp, vp, i64, vp, vp, vp]
+    if hasattr(L, "eacham_upload_descriptors_bits_wide"):  # (likewise)
+        L.eacham_upload_descriptors_bits_wide.argtypes = [vp, i32, vp, i32, i32]
+        L.eacham_upload_descriptors_bits_wide_dev.argtypes = [vp, i32, vp, i32, i32]
+        L.eacham_match_debug_hamming_wide_pair.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+        L.eacham_match_debug_hamming_wide.argtypes = [vp, C.POINTER(i64)]
     L.eacham_ba_solve.argtypes = [vp, vp, vp, vp]
     L.eacham_ba_prepare.argtypes = [vp, vp, C.POINTER(vp)]
     L.eacham_ba_run.argtypes = [vp, vp, vp, vp]

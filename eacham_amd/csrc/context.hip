@@ -252,6 +252,9 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
     if (const char* b = getenv("EACHAM_MATCH_BUDGET_MB")) {
         const int v = atoi(b);
         if (v >= 16 && v <= 65536) ctx->match_budget_mb = v;
+        // the wide Hamming path (matcher_ham_wide.hip) needs a few KiB per pair: it takes the same variable down to fractions of a MiB
+        const double mb = atof(b);
+        if (mb > 0.0 && mb <= 65536.0) ctx->wide_budget_bytes = (size_t)(mb * 1048576.0);
     }
     if (const char* m = getenv("EACHAM_BA_PREPARE")) ctx->ba_prepare_mode = !strcmp(m, "host") ? 1 : !strcmp(m, "device") ? 2 : 0;
     if (const char* m = getenv("EACHAM_BA_SCHUR")) ctx->ba_schur_mode = !strcmp(m, "pairs") ? 2 : !strcmp(m, "groups") ? 1 : 0;

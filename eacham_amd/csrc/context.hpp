@@ -108,10 +108,16 @@ struct eacham_ctx {
                               // rows left open} of the last matching call's screen sweeps (eacham_match_debug_screen)
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
     int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip), 2 = binary rows as int8
-                              // fragments of 0 / 255 (matcher_ham.hip): the int8 kernels under the Hamming predicate
+                              // fragments of 0 / 255 (matcher_ham.hip): the int8 kernels under the Hamming predicate, 3 = wide binary
+                              // rows as FP4 fragments of +-1 (matcher_ham_wide.hip): a Hamming sweep of their own
     const unsigned** bits_table_dev = nullptr;  // [frames + 1] the frames' packed rows (FrameHost::bits; null: none), rebuilt when dirty
     int bits_table_cap = 0;
     bool bits_table_dirty = true;
+    // wide binary frames (kind 3, matcher_ham_wide.hip): FrameHost::frag is the FP4 image, FrameHost::norm (FrameDev::norm) the packed
+    // rows at 16 words per row; every other per-row array is null. ks_common is their k-step count (1..8)
+    int wide_bytes_common = 0;           // bytes per row shared by the resident wide frames (meaningful while ks_common != 0)
+    size_t wide_budget_bytes = 0;        // EACHAM_MATCH_BUDGET_MB as this path reads it: any positive value, fractions included (0: match_budget_mb)
+    long long wide_debug[4] = {0, 0, 0, 0};  // {batches, pairs per batch, sweep launches, query rows swept} of the last wide matching call
     void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
     int table16_cap = 0;
     long long dot16_fallback_pairs = 0;  // pairs of the last screened call that ran the fp32 tile kernel (eacham_match_debug_dot_screen)
@@ -375,6 +381,12 @@ void launch_bits_expand(eacham_ctx* ctx, const unsigned char* packed_dev, int n,
 void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, unsigned* bits_dev);
 int hamming_distances(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const long long* offsets_dev, const long long* total_dev,
                       const uint2* edges_dev, long long edge_cap, int* dist_dev);
+// matcher_ham_wide.hip: binary rows of up to 64 bytes as a kind of their own (3), swept on the FP4 matrix cores
+int upload_frame_bits_wide(eacham_ctx* ctx, int frame_id, const unsigned char* packed_dev, int n, int bytes_per_row);
+int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
+                       int* counts_dev, long long* offsets_dev, uint2* edges_dev, int* dist_dev, long long edge_cap,
+                       long long* total_dev, int4* stats_dev, const int32_t* pairs_host);
+int ham_wide_debug_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap);
 // matcher.hip
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);
 void launch_compact_edges(eacham_ctx* ctx, int nb, const uint2* matches, const int* counts, const long long* offsets,

@@ -2024,9 +2024,12 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     rc = sanitize_pairs(ctx, pairs_dev, npairs, &pairs_dev);  // a bad frame id in a device-side list must not reach the kernels
     if (rc) return rc;
     if (pairs_used) *pairs_used = pairs_dev;   // the list the kernels ran on (what the Hamming distance kernel indexes the frames with)
-    if (METRIC != (ctx->kind_common == 2 ? METRIC_HAMMING : METRIC_L2))
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, ctx->kind_common == 2 ? "the resident frames are binary: use the _hamming entry points"
-                                                                       : "Hamming matching needs binary frames (eacham_upload_descriptors_bits)");
+    const bool binary = ctx->kind_common == 2 || ctx->kind_common == 3;
+    if (METRIC != (binary ? METRIC_HAMMING : METRIC_L2))
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, binary ? "the resident frames are binary: use the _hamming entry points"
+                                                        : "Hamming matching needs binary frames (eacham_upload_descriptors_bits)");
+    if (ctx->kind_common == 3)   // (the Hamming entry points hand wide frames to run_match_ham_wide before they get here)
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the resident frames are wide binary frames: the int8 kernels do not take them");
     if (ctx->kind_common == 1)
         return run_match_f32(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
                              edge_cap, total_dev, stats_dev);
@@ -2204,14 +2207,16 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
         return ctx->fail(EACHAM_ERR_INVALID, dot ? "bad arguments to the dot-product matcher" : "bad arguments to match_all_pairs");
     int rc = check_pairs_host(ctx, pairs, npairs);
     if (rc) return rc;
-    if (npairs > 0 && !dot && ham != (ctx->kind_common == 2))
+    const bool wide = ctx->kind_common == 3;   // wide binary frames (matcher_ham_wide.hip): the Hamming form on a sweep of their own
+    if (npairs > 0 && !dot && ham != (ctx->kind_common == 2 || wide))
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, ham ? "Hamming matching needs binary frames (eacham_upload_descriptors_bits)"
                                                      : "the resident frames are binary: use the _hamming entry points");
     if (!dot) {
-        rc = check_integer_flag(ctx);
+        rc = wide ? EACHAM_OK : check_integer_flag(ctx);
         if (rc) return rc;
     } else if (npairs > 0 && ctx->kind_common != 1) {
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are int8");
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are %s",
+                         ctx->kind_common == 0 ? "int8" : "binary");
     }
     *out_total = 0;
     if (npairs == 0) {
@@ -2250,11 +2255,14 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
     else if (form == MATCH_DOT)
         rc = run_match_dot(ctx, d(h_pairs), npairs, (float)thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
                            (float*)d(h_vals), cap, d(h_total), stats_dev);
+    else if (ham && wide)   // (the distances come with the compaction)
+        rc = run_match_ham_wide(ctx, d(h_pairs), npairs, thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
+                                out_val ? (int*)d(h_vals) : nullptr, cap, d(h_total), stats_dev, pairs);
     else
         rc = run_match(ctx, d(h_pairs), npairs, thresh, ham ? METRIC_HAMMING : METRIC_L2, min_dir, min_mutual, mode, d(h_counts),
                        d(h_offsets), d(h_edges), cap, d(h_total), stats_dev, &pairs_used);
     if (rc) return rc;
-    if (ham && out_val) {
+    if (ham && out_val && !wide) {
         rc = hamming_distances(ctx, pairs_used, npairs, d(h_offsets), d(h_total), d(h_edges), cap, (int*)d(h_vals));
         if (rc) return rc;
     }
@@ -2572,12 +2580,51 @@ int eacham_match_all_pairs_hamming_dev(eacham_ctx* ctx, const int32_t* pairs_dev
         if (npairs < 0 || (npairs > 0 && (!pairs_dev || !counts_dev || !offsets_dev || !total_dev)) || edge_cap < 0 ||
             (edge_cap > 0 && !edges_dev))
             return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_all_pairs_hamming_dev");
+        if (ctx->kind_common == 3)
+            return run_match_ham_wide(ctx, (const int2*)pairs_dev, npairs, ratio, min_dir, min_mutual, 0, counts_dev, (long long*)offsets_dev,
+                                      (uint2*)edges_dev, dist_dev, edge_cap, (long long*)total_dev, (int4*)stats_dev, nullptr);
         const int2* pairs_used = nullptr;
         int rc = run_match(ctx, (const int2*)pairs_dev, npairs, ratio, METRIC_HAMMING, min_dir, min_mutual, 0, counts_dev, (long long*)offsets_dev,
                            (uint2*)edges_dev, edge_cap, (long long*)total_dev, (int4*)stats_dev, &pairs_used);
         if (rc || !dist_dev || npairs <= 0) return rc;
         return hamming_distances(ctx, pairs_used, npairs, (const long long*)offsets_dev, (const long long*)total_dev, (const uint2*)edges_dev,
                                  edge_cap, dist_dev);
+    });
+}
+
+// ---- wide binary descriptors (matcher_ham_wide.hip): up to 64 bytes per row, a kind of their own behind the _hamming calls above ----
+int eacham_upload_descriptors_bits_wide_dev(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor_dev, int n, int bytes_per_row) {
+    return match_entry(ctx, [&]() -> int { return upload_frame_bits_wide(ctx, frame_id, rowmajor_dev, n, bytes_per_row); });
+}
+
+int eacham_upload_descriptors_bits_wide(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor, int n, int bytes_per_row) {
+    return match_entry(ctx, [&]() -> int {
+        // staging: the packed rows as they came, the only host-to-device copy. Nothing is copied for a shape upload_frame_bits_wide refuses
+        // (it tells which way; the pointer it is handed is then never read)
+        const bool copy = n > 0 && n <= MAX_ROWS && bytes_per_row > 0 && bytes_per_row <= 64 && rowmajor;
+        if (copy) {
+            const int rc = ensure_io(ctx, std::max<size_t>((size_t)n * bytes_per_row, 256));
+            if (rc) return rc;
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(ctx->io, rowmajor, (size_t)n * bytes_per_row, hipMemcpyHostToDevice, ctx->stream));
+        }
+        return upload_frame_bits_wide(ctx, frame_id, (const unsigned char*)(copy ? ctx->io : (const void*)rowmajor), n, bytes_per_row);
+    });
+}
+
+int eacham_match_debug_hamming_wide_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap) {
+    return match_entry(ctx, [&]() -> int {
+        const int32_t pr[2] = {f1, f2};
+        const int rc = check_pairs_host(ctx, pr, 1);
+        if (rc) return rc;
+        return ham_wide_debug_pair(ctx, f1, f2, best, h0, h1, cap);
+    });
+}
+
+int eacham_match_debug_hamming_wide(eacham_ctx* ctx, int64_t out[4]) {
+    return match_entry(ctx, [&]() -> int {
+        if (!out) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+        for (int i = 0; i < 4; ++i) out[i] = ctx->wide_debug[i];
+        return EACHAM_OK;
     });
 }
 

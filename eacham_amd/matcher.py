@@ -260,6 +260,30 @@ class HipContext:
     def upload_descriptors_bits_dev(self, frame_id: int, dev_ptr: int, n: int, bytes_per_row: int):
         self._check(self._L.eacham_upload_descriptors_bits_dev(self._h, frame_id, C.c_void_p(dev_ptr), n, bytes_per_row))
 
+    def upload_descriptors_bits_wide(self, frame_id: int, rows: np.ndarray):
+        """Packed binary descriptors of up to 64 bytes per row (BRISK, FREAK, AKAZE's 61-byte MLDB): an N x B uint8 matrix, a frame
+        of the wide kind; the match_*_hamming calls take it as they take the narrow kind."""
+        d = np.ascontiguousarray(rows, dtype=np.uint8)
+        if d.ndim != 2:
+            raise ValueError("binary descriptors must be an N x B uint8 matrix")
+        self._check(self._L.eacham_upload_descriptors_bits_wide(self._h, frame_id, d.ctypes.data, d.shape[0], d.shape[1]))
+
+    def upload_descriptors_bits_wide_dev(self, frame_id: int, dev_ptr: int, n: int, bytes_per_row: int):
+        self._check(self._L.eacham_upload_descriptors_bits_wide_dev(self._h, frame_id, C.c_void_p(dev_ptr), n, bytes_per_row))
+
+    def match_debug_hamming_wide_pair(self, f1: int, f2: int):
+        """(best, h0, h1) per row of f1: the wide sweep's own top-2 over the rows of f2 (eacham_match_debug_hamming_wide_pair)."""
+        n = self.frame_rows(f1)
+        best, h0, h1 = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(3))
+        self._check(self._L.eacham_match_debug_hamming_wide_pair(self._h, f1, f2, best.ctypes.data, h0.ctypes.data, h1.ctypes.data, n))
+        return best[:n], h0[:n], h1[:n]
+
+    def match_debug_hamming_wide(self) -> dict:
+        """{batches, pairs_per_batch, sweep_launches, query_rows} of the last matching call on wide frames."""
+        out = (C.c_int64 * 4)()
+        self._check(self._L.eacham_match_debug_hamming_wide(self._h, out))
+        return dict(zip(("batches", "pairs_per_batch", "sweep_launches", "query_rows"), (int(v) for v in out)))
+
     def match_pair_hamming(self, f1: int, f2: int, ratio: float = RATIO):
         """(q, t, dist) of the directed match f1 -> f2 of two binary frames: BFMatcher(NORM_HAMMING) + the ratio test."""
         cap = max(self.frame_rows(f1), 1)
@@ -414,7 +438,7 @@ class FeatureMatcherDotHip:
 
 class FeatureMatcherHammingHip:
     """Mirror of eacham::hip::FeatureMatcherHammingHip (include/eacham/FeatureMatcherHip.hpp): packed binary descriptors
-    (N x B uint8, cv::Mat CV_8U layout) matched under Hamming distance. `Match(d1, d2)` returns {queryIdx: trainIdx}: the
+    (N x B uint8, cv::Mat CV_8U layout, B up to 64) matched under Hamming distance. `Match(d1, d2)` returns {queryIdx: trainIdx}: the
     directed ratio-test match, or with `mutual` the pair's one-to-one matches; `LastDistances()` gives
     {queryIdx: Hamming distance} of that call."""
 
@@ -426,8 +450,11 @@ class FeatureMatcherHammingHip:
 
     def Match(self, descriptor1: np.ndarray, descriptor2: np.ndarray) -> dict:
         self.ctx.clear_descriptors()
-        self.ctx.upload_descriptors_bits(0, descriptor1)
-        self.ctx.upload_descriptors_bits(1, descriptor2)
+        # rows of 33..64 bytes are frames of the wide kind; up to 32 bytes the narrow kind, as before
+        wide = max(np.shape(descriptor1)[-1], np.shape(descriptor2)[-1]) > 32
+        upload = self.ctx.upload_descriptors_bits_wide if wide else self.ctx.upload_descriptors_bits
+        upload(0, descriptor1)
+        upload(1, descriptor2)
         if self.mutual:
             _, _, q, t, d, _ = self.ctx.match_all_pairs_hamming([[0, 1]], self.ratio, 0, -1, stats=False)
         else:

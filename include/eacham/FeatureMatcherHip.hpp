@@ -520,13 +520,22 @@ inline MatchGraphDot MatchAllPairsDot(Context& ctx, const std::vector<Descriptor
 
 // ---- binary descriptors under Hamming distance ---------------------------------------------------
 // Stands where cv::BFMatcher(NORM_HAMMING) + the ratio test of FeatureMatcherFlann.cpp:23 would stand for the ORB configurations of
-// the reference (config/ConfigTUM.json:27, ConfigKITTI.json, ConfigRealsense.json): packed rows of 1..32 bytes (the cv::Mat CV_8U
-// layout of ORB / BRIEF / AKAZE), distance = differing bits, q -> t0 kept iff (float)h0 / (float)h1 < ratio (eacham_match_*_hamming).
+// the reference (config/ConfigTUM.json:27, ConfigKITTI.json, ConfigRealsense.json): packed rows of 1..64 bytes (the cv::Mat CV_8U
+// layout of ORB / BRIEF / AKAZE / BRISK / FREAK), distance = differing bits, q -> t0 kept iff (float)h0 / (float)h1 < ratio (eacham_match_*_hamming).
 struct BinaryDescriptorView {
     const uint8_t* data = nullptr;
     int rows = 0;
     int bytes = 0;   // bytes per row
 };
+
+// Rows of 33..64 bytes (BRISK, FREAK, AKAZE's default MLDB) become frames of the wide kind (eacham_upload_descriptors_bits_wide, its
+// own sweep on the FP4 matrix cores behind the same matching calls); up to 32 bytes the narrow kind, as before. (A template, so that
+// the Hamming symbols are referenced only from code that uses them.)
+template <class View>
+inline int UploadBinaryFrame(eacham_ctx* ctx, int frame_id, const View& d, bool wide) {
+    return wide ? eacham_upload_descriptors_bits_wide(ctx, frame_id, d.data, d.rows, d.bytes)
+                : eacham_upload_descriptors_bits(ctx, frame_id, d.data, d.rows, d.bytes);
+}
 
 //   mutual = false: the directed match of Match(d1, d2), as FeatureMatcherHip; mutual = true: the pair's one-to-one matches.
 // Thread-safe like FeatureMatcherDotHip: one shared instance may be called from many threads, calls are served one at a time on the
@@ -544,8 +553,9 @@ public:
         std::lock_guard<std::mutex> lk(mu_);
         const int n1 = d1.rows > 0 ? d1.rows : 0;
         ctx_.check(eacham_clear_descriptors(ctx_.get()));   // (two calls may bring rows of different lengths)
-        ctx_.check(eacham_upload_descriptors_bits(ctx_.get(), 0, d1.data, d1.rows, d1.bytes));
-        ctx_.check(eacham_upload_descriptors_bits(ctx_.get(), 1, d2.data, d2.rows, d2.bytes));
+        const bool wide = d1.bytes > 32 || d2.bytes > 32;
+        ctx_.check(UploadBinaryFrame(ctx_.get(), 0, d1, wide));
+        ctx_.check(UploadBinaryFrame(ctx_.get(), 1, d2, wide));
         std::vector<uint32_t> q((size_t)(n1 > 0 ? n1 : 1)), t(q.size());
         std::vector<int32_t> h(q.size());
         int64_t total = 0;
@@ -606,8 +616,9 @@ inline MatchGraphHamming MatchAllPairsHamming(Context& ctx, const std::vector<Bi
                                               int min_directed = 30, int min_mutual = 30) {
     ctx.store_rewritten();
     ctx.check(eacham_clear_descriptors(ctx.get()));
-    for (size_t f = 0; f < frames.size(); ++f)
-        ctx.check(eacham_upload_descriptors_bits(ctx.get(), (int)f, frames[f].data, frames[f].rows, frames[f].bytes));
+    bool wide = false;
+    for (const auto& fr : frames) wide = wide || fr.bytes > 32;
+    for (size_t f = 0; f < frames.size(); ++f) ctx.check(UploadBinaryFrame(ctx.get(), (int)f, frames[f], wide));
     std::vector<int32_t> flat(2 * pairs.size());
     int64_t cap = 0;
     for (size_t p = 0; p < pairs.size(); ++p) {

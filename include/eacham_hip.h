@@ -256,6 +256,28 @@ int eacham_match_all_pairs_hamming_dev(eacham_ctx* ctx, const int32_t* pairs_dev
                                        uint32_t* edges_dev, int64_t edge_cap, int64_t* total_dev,
                                        int32_t* stats_dev, int32_t* dist_dev);
 
+/* ---- wide binary descriptors: up to 512 bits (BRISK, FREAK: 64 bytes; AKAZE's default MLDB: 61 bytes) ------------
+ * A fourth kind of resident frame (kind 3), matched by the four eacham_match_*_hamming calls above with exactly their
+ * results: the same two nearest rows, ties, predicate, sorting, mutual check, thresholds, stats and int32 distances. Behind
+ * them runs a sweep of its own on the FP4 matrix cores (csrc/matcher_ham_wide.hip): a bit is the E2M1 number +-1, every sum an
+ * integer below 2^24, so the sweep is exact with no screen and no second pass.
+ *
+ * Upload: n rows (0..16384) of bytes_per_row bytes (1..64), the most significant bit of a byte first (np.unpackbits' order;
+ * the distance does not depend on it). EACHAM_ERR_UNSUPPORTED: more than 64 bytes; more than 16384 rows; a context that holds
+ * frames of another kind (eacham_clear_descriptors resets the kind); a bytes_per_row other than that of the resident wide
+ * frames. EACHAM_ERR_INVALID: a bad shape or a null pointer. The host-to-device copy is the packed bytes. Rows of 32 bytes
+ * or fewer may be uploaded either way, eacham_upload_descriptors_bits or this; the results are the same bytes.
+ * The L2 and dot-product entry points return EACHAM_ERR_UNSUPPORTED on wide frames. There is no sharded form. */
+int eacham_upload_descriptors_bits_wide(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor, int n, int bytes_per_row);
+/* Same, source already on the device. */
+int eacham_upload_descriptors_bits_wide_dev(eacham_ctx* ctx, int frame_id, const uint8_t* rowmajor_dev, int n, int bytes_per_row);
+/* Test hook: the sweep's own top-2 of the ordered pair (f1, f2), per row of f1 in the caller's order, read from the buffer the
+ * tail reads: best[q] = the nearest train row (the lower index on a tie), h0[q] its distance, h1[q] the runner-up's. cap >= rows
+ * of f1 (EACHAM_ERR_CAPACITY); f2 needs two rows or more (EACHAM_ERR_INVALID). */
+int eacham_match_debug_hamming_wide_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap);
+/* out = {batches, pairs per batch, sweep launches, query rows swept} of the last matching call on wide frames. */
+int eacham_match_debug_hamming_wide(eacham_ctx* ctx, int64_t out[4]);
+
 /* ---- bundle adjustment: RefineBA (modules/sfm/reconstruction/BundleAdjuster.cpp:40-250) --------
  *
  * The caller (the C++ adapter in include/eacham/BundleAdjusterHip.hpp) performs the reference's
