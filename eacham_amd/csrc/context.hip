@@ -85,10 +85,50 @@ int sanitize_pairs(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const int
         ctx->pairs_safe_cap = cap;
     }
     sanitize_pairs_kernel<<<(npairs + 255) / 256, 256, 0, ctx->stream>>>(pairs_dev, npairs, ctx->frame_table_dev, (int)ctx->frames.size(),
-                                                                          ctx->pairs_safe, ctx->flag_dev + 1);
+                                                                          ctx->pairs_safe, &ctx->flag_dev->bad_pair);
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     *out = ctx->pairs_safe;
     return EACHAM_OK;
+}
+
+void release_frame(FrameHost& f) {
+    if (f.frag) (void)hipFree(f.frag);   // with what lies behind it: the FP6 image, a wide frame's packed rows
+    if (f.norm) (void)hipFree(f.norm);   // the other per-row arrays (and a narrow binary frame's packed rows) share the allocation
+    free_frame_image16(f);
+    f = FrameHost();
+}
+
+int open_frame_slot(eacham_ctx* ctx, int frame_id, FrameKind kind, int n, int max_rows, int ks, int wide_bytes, FrameHost** slot) {
+    static const char* const kind_name[] = {"int8", "f32", "binary", "wide binary"};
+    static const char* const kind_rows[] = {"a multiple of 16 up to 128, or 129..256 values", "1..256 values", "1..32 bytes", "1..64 bytes"};
+    if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
+    if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
+    if (!ks) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "%s descriptors: a row is %s", kind_name[kind], kind_rows[kind]);
+    if (n > max_rows) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "frame has %d rows; this build supports <= %d", n, max_rows);
+    if (ctx->ks_common && (ctx->kind_common != kind || ctx->ks_common != ks || ctx->wide_bytes_common != wide_bytes))
+        return ctx->fail(EACHAM_ERR_UNSUPPORTED,
+                         "all resident frames must share one descriptor kind (int8 / f32 / binary / wide binary), one dim class and, wide binary "
+                         "frames, the bytes per row: %s frames are resident, a %s frame cannot be matched against them",
+                         kind_name[ctx->kind_common], kind_name[kind]);
+    if ((size_t)frame_id >= ctx->frames.size()) ctx->frames.resize(frame_id + 1);
+    FrameHost& f = ctx->frames[frame_id];
+    if (f.frag || f.norm) EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    release_frame(f);
+    ctx->frame_table_dirty = ctx->bits_table_dirty = true;   // (also if the upload fails from here on: the tables name what was freed)
+    *slot = &f;
+    return EACHAM_OK;
+}
+
+void commit_frame(eacham_ctx* ctx, FrameHost& f, FrameKind kind, int n, int dim, int ks, int ntiles, int wide_bytes) {
+    f.n = n;
+    f.dim = dim;
+    f.ks = ks;
+    f.ntiles = ntiles;
+    ctx->ks_common = ks;
+    ctx->kind_common = kind;
+    ctx->wide_bytes_common = wide_bytes;
+    ctx->frame_table_dirty = true;
+    ctx->bits_table_dirty = true;
 }
 
 __global__ void gather_tiles_kernel(const FrameDev* __restrict__ frames, int n, int* __restrict__ used) {
@@ -113,7 +153,7 @@ int sync_frame_table(eacham_ctx* ctx) {
     {   // entry [need]: an empty frame that invalid device-side pairs are redirected to
         FrameDev& e = tab[need];
         e.frag = nullptr; e.norm = nullptr; e.normb = nullptr; e.screen = nullptr;
-        e.orig = ctx->flag_dev + 16; e.pos = ctx->flag_dev + 16; e.meta = ctx->flag_dev + 8;
+        e.orig = ctx->flag_dev->standin_rows; e.pos = ctx->flag_dev->standin_rows; e.meta = ctx->flag_dev->standin_meta;
         e.n = 0; e.ntiles = 0; e.resident = 1;
     }
     for (int i = 0; i < need; ++i) {
@@ -327,8 +367,8 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
         hipEventCreateWithFlags(&ctx->ev_fin[0], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_fin[1], hipEventDisableTiming) != hipSuccess ||
         hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming) != hipSuccess ||
-        hipMalloc((void**)&ctx->flag_dev, 64 * sizeof(int)) != hipSuccess ||
-        hipMemsetAsync(ctx->flag_dev, 0, 64 * sizeof(int), ctx->stream) != hipSuccess ||
+        hipMalloc((void**)&ctx->flag_dev, sizeof(FlagBlock)) != hipSuccess ||
+        hipMemsetAsync(ctx->flag_dev, 0, sizeof(FlagBlock), ctx->stream) != hipSuccess ||
         hipStreamSynchronize(ctx->stream) != hipSuccess)
         return bail();
     *out_ctx = ctx;
@@ -347,15 +387,11 @@ int eacham_clear_descriptors(eacham_ctx* ctx) {
     std::lock_guard<std::mutex> lock(ctx->mu);
     (void)hipSetDevice(ctx->device);
     EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    for (auto& f : ctx->frames) {
-        if (f.frag) (void)hipFree(f.frag);
-        if (f.norm) (void)hipFree(f.norm);
-        free_frame_image16(f);
-        f = FrameHost();
-    }
+    for (auto& f : ctx->frames) release_frame(f);
     ctx->frames.clear();
     ctx->ks_common = 0;
-    ctx->kind_common = 0;
+    ctx->kind_common = FRAME_INT8;
+    ctx->wide_bytes_common = 0;
     ctx->frame_table_dirty = true;
     ctx->bits_table_dirty = true;
     return EACHAM_OK;
@@ -365,11 +401,7 @@ void eacham_ctx_destroy(eacham_ctx* ctx) {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
     (void)hipStreamSynchronize(ctx->stream);
-    for (auto& f : ctx->frames) {
-        if (f.frag) (void)hipFree(f.frag);
-        if (f.norm) (void)hipFree(f.norm);
-        free_frame_image16(f);
-    }
+    for (auto& f : ctx->frames) release_frame(f);
     if (ctx->table16_dev) (void)hipFree(ctx->table16_dev);
     if (ctx->bits_table_dev) (void)hipFree((void*)ctx->bits_table_dev);
     if (ctx->frame_table_dev) (void)hipFree(ctx->frame_table_dev);
@@ -404,9 +436,9 @@ int eacham_ctx_sync(eacham_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     int bad = 0;
-    EACHAM_HIP_TRY(ctx, hipMemcpy(&bad, ctx->flag_dev + 1, sizeof(int), hipMemcpyDeviceToHost));
+    EACHAM_HIP_TRY(ctx, hipMemcpy(&bad, &ctx->flag_dev->bad_pair, sizeof(int), hipMemcpyDeviceToHost));
     if (bad) {
-        EACHAM_HIP_TRY(ctx, hipMemset(ctx->flag_dev + 1, 0, sizeof(int)));
+        EACHAM_HIP_TRY(ctx, hipMemset(&ctx->flag_dev->bad_pair, 0, sizeof(int)));
         return ctx->fail(EACHAM_ERR_INVALID, "a device-side pair list named a frame that is not resident (those pairs produced no match)");
     }
     return EACHAM_OK;

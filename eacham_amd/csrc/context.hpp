@@ -8,6 +8,7 @@
 
 #include <algorithm>
 #include <cstdarg>
+#include <cstddef>
 #include <cstring>
 #include <cstdint>
 #include <cstdio>
@@ -20,6 +21,33 @@
 #include "io_layout.hpp"
 
 namespace eacham {
+
+// What the resident frames hold. All frames of a context are of one kind (eacham_ctx::kind_common) and one k-step class.
+enum FrameKind {
+    FRAME_INT8 = 0,       // int8 fragments (matcher.hip)
+    FRAME_F32 = 1,        // fp32 fragments (matcher_f32.hip)
+    FRAME_BITS = 2,       // binary rows as int8 fragments of 0 / 255 (matcher_ham.hip): the int8 kernels under the Hamming predicate
+    FRAME_BITS_WIDE = 3,  // wide binary rows as FP4 fragments of +-1 (matcher_ham_wide.hip): a Hamming sweep of their own
+};
+
+// The context's small block of device words (eacham_ctx::flag_dev), zeroed at create. Kernels receive plain pointers to its members.
+struct FlagBlock {
+    int not_integer;                  // a non-integer descriptor was seen by an int8 upload
+    int bad_pair;                     // a device-side pair list named a frame that is not resident
+    int pad0[6];
+    int standin_meta[8];              // meta of the empty stand-in frame (zeros)
+    int standin_rows[16];             // its orig / pos (zeros, never indexed: the frame has no row)
+    unsigned long long colprune[2];   // {settled, verified} candidate columns of the last matching call (eacham_match_debug_colprune)
+    int pad1[4];
+    unsigned long long dot16[6];      // the tally of the screened dot-product form
+    unsigned long long screen[2];     // {real query rows, rows left open} of the last call's screen sweeps (eacham_match_debug_screen)
+    int pad2[8];
+};
+static_assert(offsetof(FlagBlock, bad_pair) == 1 * sizeof(int) && offsetof(FlagBlock, standin_meta) == 8 * sizeof(int) &&
+                  offsetof(FlagBlock, standin_rows) == 16 * sizeof(int) && offsetof(FlagBlock, colprune) == 32 * sizeof(int) &&
+                  offsetof(FlagBlock, dot16) == 40 * sizeof(int) && offsetof(FlagBlock, screen) == 52 * sizeof(int) &&
+                  sizeof(FlagBlock) == 64 * sizeof(int),
+              "the block's words stay where the kernels and the debug calls have always found them");
 
 // Descriptor of one resident frame as the kernels see it (device-side table entry).
 // int8 frames are stored PARITY-SORTED: rows whose centred squared norm is even come first (stable),
@@ -47,15 +75,16 @@ struct FrameHost {
     int* pos = nullptr;
     int* meta = nullptr;
     int4* screen = nullptr;  // the FP6 image of a frame above 128-D: the tail of frag's allocation
-    unsigned* bits = nullptr;  // binary frames (matcher_ham.hip): the packed rows in the caller's order, 8 words per row, zero-padded;
-                               // the tail of norm's allocation. The kernels reach it through a table of its own, not through FrameDev
+    unsigned* bits = nullptr;  // binary frames: the packed rows in the caller's order, zero-padded to 8 words per row (matcher_ham.hip: the
+                               // tail of norm's allocation) or 16 (matcher_ham_wide.hip: the tail of frag's). The kernels reach it through
+                               // a table of its own (eacham_ctx::bits_table_dev), not through FrameDev
     int n = -1;  // -1 = not resident
     int dim = 0;
     int ks = 0;
     int ntiles = 0;      // allocated tiles
     int tiles_used = 0;  // tiles in use (<= ntiles), known after sync_frame_table
     // fp16 image of an fp32 frame (matcher_dot16.hip): one allocation, fragments | norm bounds | {max bound, flag}; built on the
-    // frame's first screened call, freed wherever frag is (free_frame_image16)
+    // frame's first screened call, freed with frag (release_frame)
     void* img16 = nullptr;
     bool img16_ready = false;   // built (or nothing to build: an empty frame)
     bool img16_bad = false;     // holds a value that is not finite or beyond the fp16 range: its pairs run the fp32 tile kernel
@@ -101,21 +130,15 @@ struct eacham_ctx {
     eacham::FrameDev* frame_table_dev = nullptr;
     int frame_table_cap = 0;
     bool frame_table_dirty = true;
-    int* flag_dev = nullptr;  // [0] = non-integer descriptor seen, [1] = a device-side pair list named a frame that is not
-                              // resident, [8..9] = meta of the empty stand-in frame (zeros), [16..] scratch, [32..35] = the two 64-bit
-                              // totals {settled, verified} of the last matching call's candidate columns (eacham_match_debug_colprune),
-                              // [40..51] = the tally of the screened dot-product form, [52..55] = the two 64-bit totals {real query rows,
-                              // rows left open} of the last matching call's screen sweeps (eacham_match_debug_screen)
+    eacham::FlagBlock* flag_dev = nullptr;   // the flags, the stand-in frame's arrays and the tallies of the debug calls
     int ks_common = 0;        // k-step class shared by all resident frames (0 = none yet)
-    int kind_common = 0;      // 0 = int8 fragments (matcher.hip), 1 = fp32 fragments (matcher_f32.hip), 2 = binary rows as int8
-                              // fragments of 0 / 255 (matcher_ham.hip): the int8 kernels under the Hamming predicate, 3 = wide binary
-                              // rows as FP4 fragments of +-1 (matcher_ham_wide.hip): a Hamming sweep of their own
+    eacham::FrameKind kind_common = eacham::FRAME_INT8;   // their kind (meaningful while ks_common != 0)
     const unsigned** bits_table_dev = nullptr;  // [frames + 1] the frames' packed rows (FrameHost::bits; null: none), rebuilt when dirty
     int bits_table_cap = 0;
     bool bits_table_dirty = true;
-    // wide binary frames (kind 3, matcher_ham_wide.hip): FrameHost::frag is the FP4 image, FrameHost::norm (FrameDev::norm) the packed
-    // rows at 16 words per row; every other per-row array is null. ks_common is their k-step count (1..8)
-    int wide_bytes_common = 0;           // bytes per row shared by the resident wide frames (meaningful while ks_common != 0)
+    // wide binary frames (matcher_ham_wide.hip): FrameHost::frag is the FP4 image with the packed rows (FrameHost::bits, 16 words per
+    // row) behind it; every per-row array of FrameDev is null. ks_common is their k-step count (1..8)
+    int wide_bytes_common = 0;           // bytes per row shared by the resident wide frames (0: the frames are of another kind)
     size_t wide_budget_bytes = 0;        // EACHAM_MATCH_BUDGET_MB as this path reads it: any positive value, fractions included (0: match_budget_mb)
     long long wide_debug[4] = {0, 0, 0, 0};  // {batches, pairs per batch, sweep launches, query rows swept} of the last wide matching call
     void* table16_dev = nullptr;   // device table of the frames' fp16 images (matcher_dot16.hip), rebuilt by every screened call
@@ -348,6 +371,17 @@ int sync_frame_table(eacham_ctx* ctx);
 // stand-in entry frames[n_frames] (and flags it); returns the sanitised device pointer in *out
 int sanitize_pairs(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const int2** out);
 
+// The life of a frame slot (context.hip), the same under every kind's upload.
+// open_frame_slot: what every upload checks before it allocates, in the order the error codes have always had — the id and the row
+// count (INVALID), then what this build does not take (UNSUPPORTED): ks == 0 says the uploader found no class for the row size,
+// n > max_rows, a kind, class or (wide frames) bytes per row other than the resident frames'. Then the table grows to hold the id
+// and whatever the slot held is released behind a synchronisation. *slot is the empty slot; nothing changed if the call fails.
+int open_frame_slot(eacham_ctx* ctx, int frame_id, FrameKind kind, int n, int max_rows, int ks, int wide_bytes, FrameHost** slot);
+// the only place that frees a frame's allocations (frag, norm and what shares them, the fp16 image); the caller has synchronised
+void release_frame(FrameHost& f);
+// hands the finished frame over: its shape, the context's common kind / class / wide row bytes, both device tables marked stale
+void commit_frame(eacham_ctx* ctx, FrameHost& f, FrameKind kind, int n, int dim, int ks, int ntiles, int wide_bytes);
+
 // matcher_f32.hip
 int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim);
 int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
@@ -376,16 +410,18 @@ int run_match_dot_screened(eacham_ctx* ctx, const int2* pairs_dev, const int2* p
                            int n_fallback, float min_score, int min_dir, int min_mutual, int* counts_dev, long long* offsets_dev,
                            uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev);
 // matcher_ham.hip: binary descriptors. The packed rows are expanded on the device to the 0 / 255 rows the int8 upload takes, kept
-// packed beside the frame, and give every emitted match its Hamming distance (popcount of the XOR, independent of the sweep).
+// packed beside the frame (both binary kinds: 8 or 16 words per row), and give every emitted match its Hamming distance (popcount
+// of the XOR, independent of the sweep): hamming_distances is the one place that computes it, for the frames of either kind.
 void launch_bits_expand(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, int dim, float* dst_dev);
-void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, unsigned* bits_dev);
+void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, int words_per_row, unsigned* bits_dev);
 int hamming_distances(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const long long* offsets_dev, const long long* total_dev,
                       const uint2* edges_dev, long long edge_cap, int* dist_dev);
-// matcher_ham_wide.hip: binary rows of up to 64 bytes as a kind of their own (3), swept on the FP4 matrix cores
+// matcher_ham_wide.hip: binary rows of up to 64 bytes as a kind of their own, swept on the FP4 matrix cores. *pairs_used: the
+// sanitised list the kernels ran on (what hamming_distances indexes the frames with)
 int upload_frame_bits_wide(eacham_ctx* ctx, int frame_id, const unsigned char* packed_dev, int n, int bytes_per_row);
 int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
-                       int* counts_dev, long long* offsets_dev, uint2* edges_dev, int* dist_dev, long long edge_cap,
-                       long long* total_dev, int4* stats_dev, const int32_t* pairs_host);
+                       int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
+                       int4* stats_dev, const int32_t* pairs_host, const int2** pairs_used);
 int ham_wide_debug_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap);
 // matcher.hip
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);

@@ -27,6 +27,7 @@
 // A running top-2 costs two VALU ops:  m2 = med3(m1, m2, key); m1 = min(m1, key).
 #include "context.hpp"
 #include "match_screen.hpp"
+#include "match_tail.hpp"
 
 #include <algorithm>
 #include <climits>
@@ -1174,8 +1175,6 @@ __device__ __forceinline__ bool ratio_pass(int d2_best, int d2_second, double ra
     return (double)q < ratio;  // 0/0 = NaN -> false
 }
 
-constexpr int FIN_THREADS = 256;
-
 // mode 0: mutual matches + thresholds (apps/sfm/main.cpp:111-146); mode 1: directed list m12.
 // out_matches[p][k] = {q, t} sorted by q; counts[p]; stats[p] = {|m12|, |m21|, |mutual|, edge}.
 // Rows/columns are addressed by stored position inside; q and t leave in the caller's numbering.
@@ -1194,7 +1193,6 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
     int* keepcol = smem;           // [row_stride] by stored row: stored column of the kept match or -1
     int* bwd = smem + row_stride;  // [row_stride] by stored column: d2 of the column's best if it passes the ratio test, else -1
     __shared__ int s_cnt[3];
-    __shared__ int s_scan[FIN_THREADS];
     if (tid < 3) s_cnt[tid] = 0;
     __syncthreads();
     constexpr unsigned PAD_V = 2u * PADH;  // v = 2H + parity of anything involving a padding row/column
@@ -1254,31 +1252,10 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
     atomicAdd(&s_cnt[1], c21);
     __syncthreads();
 
-    // ordered compaction over the caller's q in chunks of FIN_THREADS
-    uint2* out = out_matches + (size_t)p * row_stride;
-    int base = 0;
-    for (int q0 = 0; q0 < A.n; q0 += FIN_THREADS) {
-        const int q = q0 + tid;
-        const int t = q < A.n ? keepcol[A.pos[q]] : -1;
-        const bool keep = t >= 0;
-        s_scan[tid] = keep;
-        __syncthreads();
-        for (int off = 1; off < FIN_THREADS; off <<= 1) {  // Hillis-Steele inclusive scan
-            int v = tid >= off ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        if (keep) out[base + s_scan[tid] - 1] = make_uint2((unsigned)q, (unsigned)B.orig[t]);
-        base += s_scan[FIN_THREADS - 1];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        int n12 = s_cnt[0], n21 = s_cnt[1];
-        bool edge = n12 >= min_dir && n21 >= min_dir && base > min_mutual;  // main.cpp:111,142
-        counts[p] = mode == 1 ? base : (edge ? base : 0);
-        if (stats) stats[p] = make_int4(n12, n21, base, edge ? 1 : 0);
-    }
+    // (by stored position inside, the caller's numbering out)
+    const int base = compact_kept_rows(
+        A.n, tid, out_matches + (size_t)p * row_stride, [&](int q) { return keepcol[A.pos[q]]; }, [&](int t) { return B.orig[t]; });
+    if (tid == 0) write_pair_result(p, mode, s_cnt[0], s_cnt[1], base, min_dir, min_mutual, counts, stats);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1295,25 +1272,6 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize_kernel(
 //   F  match_finalize2_kernel  per pair: keep candidate (q, t) iff column t passes the ratio test with minimum d2(q, t);
 //                              ordered compaction in the caller's row order, threshold
 // ------------------------------------------------------------------------------------------------
-
-// exclusive rank of this thread's flag among the workgroup's flags (thread order) + the workgroup's total
-__device__ __forceinline__ int block_rank(bool flag, int tid, int* s_wave /* [FIN_THREADS / 64] */, int& total) {
-    const unsigned long long bal = __ballot(flag);
-    const int lane = tid & 63, wave = tid >> 6;
-    const int in_wave = __popcll(bal & ((1ull << lane) - 1ull));
-    if (lane == 0) s_wave[wave] = __popcll(bal);
-    __syncthreads();
-    int before = 0, all = 0;
-#pragma unroll
-    for (int w = 0; w < FIN_THREADS / 64; ++w) {
-        const int c = s_wave[w];
-        before += w < wave ? c : 0;
-        all += c;
-    }
-    __syncthreads();
-    total = all;
-    return before + in_wave;
-}
 
 constexpr int VER_GROUPS = 2;                 // 32-candidate groups per wave: one fetched A fragment feeds two MFMA chains
 constexpr int VER_CANDS = 32 * VER_GROUPS;    // candidates per work item
@@ -1737,7 +1695,6 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize2_kernel(
     const uint2* __restrict__ colres, const int4* __restrict__ state, int row_stride, double ratio, int min_mutual, int mode,
     uint2* __restrict__ out_matches, int* __restrict__ counts) {
     extern __shared__ int smem[];
-    __shared__ int s_wave[FIN_THREADS / 64];
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
     const int4 st = state[p];
@@ -1770,16 +1727,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_finalize2_kernel(
         keepcol[j] = keep;
     }
     __syncthreads();
-    uint2* out = out_matches + (size_t)p * row_stride;
-    int base = 0;
-    for (int q0 = 0; q0 < A.n; q0 += FIN_THREADS) {  // ordered compaction over the caller's q
-        const int q = q0 + tid;
-        const int t = q < A.n ? keepcol[A.pos[q]] : -1;
-        int total;
-        const int rank = block_rank(t >= 0, tid, s_wave, total);
-        if (t >= 0) out[base + rank] = make_uint2((unsigned)q, (unsigned)B.orig[t]);
-        base += total;
-    }
+    // (by stored position inside, the caller's numbering out)
+    const int base = compact_kept_rows(
+        A.n, tid, out_matches + (size_t)p * row_stride, [&](int q) { return keepcol[A.pos[q]]; }, [&](int t) { return B.orig[t]; });
     if (tid == 0) counts[p] = mode == 1 ? base : (base > min_mutual ? base : 0);  // main.cpp:142
 }
 
@@ -1845,34 +1795,20 @@ static void with_ks(int ks, F&& f) {
     else f(std::integral_constant<int, 8>{});
 }
 
-// kind 0: the caller's integer rows; kind 2 (binary frames): rows of 0 / 255 expanded from packed bits, which get 8 words per row
+// FRAME_INT8: the caller's integer rows; FRAME_BITS: rows of 0 / 255 expanded from packed bits, which get 8 words per row
 // behind the per-row arrays for their packed copy (FrameHost::bits, filled by the caller)
-static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim, int kind = 0) {
-    if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
-    if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
-    int ks = ks_for_dim(dim);
-    if (!ks) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "descriptor dim %d: need a multiple of 16 up to 128, or 129..256", dim);
-    if (ctx->ks_common && (ctx->ks_common != ks || ctx->kind_common != kind))
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32 / binary) and dim class");
+static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim, FrameKind kind = FRAME_INT8) {
+    const int ks = ks_for_dim(dim);
+    FrameHost* slot = nullptr;
+    if (int rc = open_frame_slot(ctx, frame_id, kind, n, MAX_ROWS, ks, 0, &slot)) return rc;
+    FrameHost& f = *slot;
     // each parity class is padded to whole tiles (at most one extra tile), the total to whole wave-blocks
     const int group_rows = 32 * GROUP_TILES;
     const int ntiles = n > 0 ? ((n + 31) / 32 + 1 + GROUP_TILES - 1) / GROUP_TILES * GROUP_TILES : 0;
-    if (n > MAX_ROWS)
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "frame has %d rows; this build supports <= %d", n, MAX_ROWS);
-    if ((size_t)frame_id >= ctx->frames.size()) ctx->frames.resize(frame_id + 1);
-    FrameHost& f = ctx->frames[frame_id];
-    if (f.frag || f.norm) {
-        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (f.frag) (void)hipFree(f.frag);
-        if (f.norm) (void)hipFree(f.norm);  // the other per-row arrays share the allocation
-        free_frame_image16(f);
-        f = FrameHost();
-    }
-    f.img16_ready = false;  // (an empty frame has no allocation, yet counts as imaged: the new rows need an image of their own)
     const int npad = ntiles * 32;
     {
         // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[2]; binary frames only: + 6 unused (32-byte alignment) | the packed rows, 8 words each
-        const size_t ints = (size_t)6 * npad + 2 + (kind == 2 ? 6 + (size_t)8 * n : 0);
+        const size_t ints = (size_t)6 * npad + 2 + (kind == FRAME_BITS ? 6 + (size_t)8 * n : 0);
         EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.norm, ints * sizeof(int)));
         EACHAM_HIP_TRY(ctx, hipMemsetAsync(f.norm, 0, ints * sizeof(int), ctx->stream));
         f.normb = f.norm + npad;
@@ -1881,14 +1817,14 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
         int* s2 = f.norm + 4 * (size_t)npad;
         int* s1 = f.norm + 5 * (size_t)npad;
         f.meta = f.norm + 6 * (size_t)npad;
-        if (kind == 2) f.bits = (unsigned*)(f.norm + 6 * (size_t)npad + 8);   // 32-byte aligned: npad is a multiple of 32
+        if (kind == FRAME_BITS) f.bits = (unsigned*)(f.norm + 6 * (size_t)npad + 8);   // 32-byte aligned: npad is a multiple of 32
         if (npad > 0) {
             // above 128-D the FP6 image of the screen sweep follows the int8 fragments: image | |M|^2 | s_r | {E} (quantize_screen_kernel)
             const size_t frag_bytes = (size_t)ntiles * ks * 64 * sizeof(int4);
             const size_t screen_bytes = ks == 8 ? (size_t)ntiles * SCREEN_TILE_BYTES + (size_t)npad * 8 + 16 : 0;
             EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, frag_bytes + screen_bytes));
             const long long sums = (long long)n * ((dim + 15) / 16);
-            rowsum_kernel<<<(unsigned)((sums + 255) / 256), 256, 0, ctx->stream>>>(src_dev, n, dim, s2, s1, ctx->flag_dev);
+            rowsum_kernel<<<(unsigned)((sums + 255) / 256), 256, 0, ctx->stream>>>(src_dev, n, dim, s2, s1, &ctx->flag_dev->not_integer);
             partition_kernel<<<1, 1024, 0, ctx->stream>>>(s2, s1, n, npad, group_rows, f.norm, f.normb, f.orig, f.pos, f.meta);
             const long long work = (long long)npad * ks * 2;
             quantize_kernel<<<(unsigned)((work + 255) / 256), 256, 0, ctx->stream>>>(src_dev, dim, ks, npad, f.orig, (v4i*)f.frag);
@@ -1904,24 +1840,17 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
             EACHAM_HIP_TRY(ctx, hipGetLastError());
         }
     }
-    f.n = n;
-    f.dim = dim;
-    f.ks = ks;
-    f.ntiles = ntiles;
-    ctx->ks_common = ks;
-    ctx->kind_common = kind;
-    ctx->frame_table_dirty = true;
-    ctx->bits_table_dirty = true;
+    commit_frame(ctx, f, kind, n, dim, ks, ntiles, 0);
     return EACHAM_OK;
 }
 
 static int check_integer_flag(eacham_ctx* ctx) {
-    if (ctx->kind_common == 1) return EACHAM_OK;  // fp32 frames take any value
+    if (ctx->kind_common == FRAME_F32) return EACHAM_OK;  // fp32 frames take any value
     int flag = 0;
-    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&flag, ctx->flag_dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&flag, &ctx->flag_dev->not_integer, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (flag) {
-        EACHAM_HIP_TRY(ctx, hipMemsetAsync(ctx->flag_dev, 0, sizeof(int), ctx->stream));
+        EACHAM_HIP_TRY(ctx, hipMemsetAsync(&ctx->flag_dev->not_integer, 0, sizeof(int), ctx->stream));
         return ctx->fail(EACHAM_ERR_NOT_INTEGER,
                          "descriptors must be integer-valued in [0,255] for the exact int8 path");
     }
@@ -1929,12 +1858,12 @@ static int check_integer_flag(eacham_ctx* ctx) {
 }
 
 // {settled, verified}: the candidate columns of the last matching call that match_argmin_kernel settled / that went to match_colverify_kernel
-static unsigned long long* colprune_totals(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 32); }
+static unsigned long long* colprune_totals(eacham_ctx* ctx) { return ctx->flag_dev->colprune; }
 // {real query rows, rows left open}: what the screen sweeps of the last matching call met / handed to the exact pass
-static unsigned long long* screen_tally(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 52); }
+static unsigned long long* screen_tally(eacham_ctx* ctx) { return ctx->flag_dev->screen; }
 // every resident frame with rows carries the FP6 image (all frames share one dim class, so this is ks_common == 8)
 static bool frames_have_screen(const eacham_ctx* ctx) {
-    if (ctx->kind_common == 1 || ctx->ks_common != 8) return false;
+    if (ctx->kind_common == FRAME_F32 || ctx->ks_common != 8) return false;
     for (const auto& f : ctx->frames)
         if (f.n > 0 && !f.screen) return false;
     return true;
@@ -2024,13 +1953,13 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     rc = sanitize_pairs(ctx, pairs_dev, npairs, &pairs_dev);  // a bad frame id in a device-side list must not reach the kernels
     if (rc) return rc;
     if (pairs_used) *pairs_used = pairs_dev;   // the list the kernels ran on (what the Hamming distance kernel indexes the frames with)
-    const bool binary = ctx->kind_common == 2 || ctx->kind_common == 3;
+    const bool binary = ctx->kind_common == FRAME_BITS || ctx->kind_common == FRAME_BITS_WIDE;
     if (METRIC != (binary ? METRIC_HAMMING : METRIC_L2))
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, binary ? "the resident frames are binary: use the _hamming entry points"
                                                         : "Hamming matching needs binary frames (eacham_upload_descriptors_bits)");
-    if (ctx->kind_common == 3)   // (the Hamming entry points hand wide frames to run_match_ham_wide before they get here)
+    if (ctx->kind_common == FRAME_BITS_WIDE)   // (run_match hands wide frames to run_match_ham_wide before they get here)
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the resident frames are wide binary frames: the int8 kernels do not take them");
-    if (ctx->kind_common == 1)
+    if (ctx->kind_common == FRAME_F32)
         return run_match_f32(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
                              edge_cap, total_dev, stats_dev);
     // Which form of the column direction: the reference's thresholds (30 / 30, main.cpp:111,142) make the direction counts
@@ -2151,7 +2080,10 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
 
 static int run_match(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int metric, int min_dir, int min_mutual, int mode,
                      int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev, int4* stats_dev,
-                     const int2** pairs_used = nullptr) {
+                     const int2** pairs_used = nullptr, const int32_t* pairs_host = nullptr) {
+    if (metric == METRIC_HAMMING && ctx->kind_common == FRAME_BITS_WIDE)   // the Hamming form on a sweep of its own (matcher_ham_wide.hip)
+        return run_match_ham_wide(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev, edge_cap,
+                                  total_dev, stats_dev, pairs_host, pairs_used);
     return metric == METRIC_HAMMING
                ? run_match_metric<METRIC_HAMMING>(ctx, pairs_dev, npairs, ratio, min_dir, min_mutual, mode, counts_dev, offsets_dev, edges_dev,
                                                   edge_cap, total_dev, stats_dev, pairs_used)
@@ -2207,16 +2139,16 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
         return ctx->fail(EACHAM_ERR_INVALID, dot ? "bad arguments to the dot-product matcher" : "bad arguments to match_all_pairs");
     int rc = check_pairs_host(ctx, pairs, npairs);
     if (rc) return rc;
-    const bool wide = ctx->kind_common == 3;   // wide binary frames (matcher_ham_wide.hip): the Hamming form on a sweep of their own
-    if (npairs > 0 && !dot && ham != (ctx->kind_common == 2 || wide))
+    const bool wide = ctx->kind_common == FRAME_BITS_WIDE;
+    if (npairs > 0 && !dot && ham != (ctx->kind_common == FRAME_BITS || wide))
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, ham ? "Hamming matching needs binary frames (eacham_upload_descriptors_bits)"
                                                      : "the resident frames are binary: use the _hamming entry points");
     if (!dot) {
-        rc = wide ? EACHAM_OK : check_integer_flag(ctx);
+        rc = wide ? EACHAM_OK : check_integer_flag(ctx);   // (no upload kernel of the wide kind raises the flag)
         if (rc) return rc;
-    } else if (npairs > 0 && ctx->kind_common != 1) {
+    } else if (npairs > 0 && ctx->kind_common != FRAME_F32) {
         return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are %s",
-                         ctx->kind_common == 0 ? "int8" : "binary");
+                         ctx->kind_common == FRAME_INT8 ? "int8" : "binary");
     }
     *out_total = 0;
     if (npairs == 0) {
@@ -2255,14 +2187,11 @@ static int match_pairs_host(eacham_ctx* ctx, MatchForm form, const int32_t* pair
     else if (form == MATCH_DOT)
         rc = run_match_dot(ctx, d(h_pairs), npairs, (float)thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
                            (float*)d(h_vals), cap, d(h_total), stats_dev);
-    else if (ham && wide)   // (the distances come with the compaction)
-        rc = run_match_ham_wide(ctx, d(h_pairs), npairs, thresh, min_dir, min_mutual, mode, d(h_counts), d(h_offsets), d(h_edges),
-                                out_val ? (int*)d(h_vals) : nullptr, cap, d(h_total), stats_dev, pairs);
     else
         rc = run_match(ctx, d(h_pairs), npairs, thresh, ham ? METRIC_HAMMING : METRIC_L2, min_dir, min_mutual, mode, d(h_counts),
-                       d(h_offsets), d(h_edges), cap, d(h_total), stats_dev, &pairs_used);
+                       d(h_offsets), d(h_edges), cap, d(h_total), stats_dev, &pairs_used, pairs);
     if (rc) return rc;
-    if (ham && out_val && !wide) {
+    if (ham && out_val) {
         rc = hamming_distances(ctx, pairs_used, npairs, d(h_offsets), d(h_total), d(h_edges), cap, (int*)d(h_vals));
         if (rc) return rc;
     }
@@ -2364,7 +2293,7 @@ int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int3
     if (!ctx) return EACHAM_ERR_INVALID;
     std::lock_guard<std::mutex> lock(ctx->mu);
     if (npairs < 0 || !n_batches || cap < 0 || (cap > 0 && !starts)) return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_debug_batches");
-    if (ctx->kind_common == 1) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the fp32 path plans its batches on its own");
+    if (ctx->kind_common == FRAME_F32) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the fp32 path plans its batches on its own");
     const bool full_cols = with_stats != 0;
     MatchPlan pl = make_plan(ctx, std::max(npairs, 1), full_cols);
     int b = 0;
@@ -2502,9 +2431,9 @@ int eacham_match_all_pairs_dot_screened(eacham_ctx* ctx, const int32_t* pairs, i
 static int upload_frame_bits(eacham_ctx* ctx, int frame_id, const unsigned char* packed_dev, int n, int bytes_per_row, size_t stage_off) {
     const int dim = bytes_per_row <= 16 ? (8 * bytes_per_row + 15) / 16 * 16 : 8 * bytes_per_row;
     if (n > 0) launch_bits_expand(ctx, packed_dev, n, bytes_per_row, dim, (float*)((char*)ctx->io + stage_off));
-    int rc = upload_frame(ctx, frame_id, (const float*)((char*)ctx->io + stage_off), n, dim, 2);
+    int rc = upload_frame(ctx, frame_id, (const float*)((char*)ctx->io + stage_off), n, dim, FRAME_BITS);
     if (rc) return rc;
-    if (n > 0) launch_bits_store(ctx, packed_dev, n, bytes_per_row, ctx->frames[frame_id].bits);
+    if (n > 0) launch_bits_store(ctx, packed_dev, n, bytes_per_row, 8, ctx->frames[frame_id].bits);
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // orders reuse of the staging buffer (and of the caller's rows)
     return EACHAM_OK;
@@ -2580,9 +2509,6 @@ int eacham_match_all_pairs_hamming_dev(eacham_ctx* ctx, const int32_t* pairs_dev
         if (npairs < 0 || (npairs > 0 && (!pairs_dev || !counts_dev || !offsets_dev || !total_dev)) || edge_cap < 0 ||
             (edge_cap > 0 && !edges_dev))
             return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_all_pairs_hamming_dev");
-        if (ctx->kind_common == 3)
-            return run_match_ham_wide(ctx, (const int2*)pairs_dev, npairs, ratio, min_dir, min_mutual, 0, counts_dev, (long long*)offsets_dev,
-                                      (uint2*)edges_dev, dist_dev, edge_cap, (long long*)total_dev, (int4*)stats_dev, nullptr);
         const int2* pairs_used = nullptr;
         int rc = run_match(ctx, (const int2*)pairs_dev, npairs, ratio, METRIC_HAMMING, min_dir, min_mutual, 0, counts_dev, (long long*)offsets_dev,
                            (uint2*)edges_dev, edge_cap, (long long*)total_dev, (int4*)stats_dev, &pairs_used);

@@ -13,6 +13,7 @@
 // comparison is a strict '>', so -inf and NaN similarities never win and never pass a threshold; ties resolve to the
 // lower index like every other path.
 #include "context.hpp"
+#include "match_tail.hpp"
 
 #include <algorithm>
 
@@ -150,8 +151,7 @@ __global__ __launch_bounds__(F_THREADS, 2) void match_tile_dot_kernel(
 }
 
 // ---- K2d: merge of the column partials, threshold, mutual check, thresholds, ordered compaction -------------
-constexpr int FIN_T = 256;
-__global__ __launch_bounds__(FIN_T) void match_finalize_dot_kernel(
+__global__ __launch_bounds__(FIN_THREADS) void match_finalize_dot_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const int2* __restrict__ rowres,
     const int2* __restrict__ colpart, int wb_stride, int row_stride, float min_score, int min_dir, int min_mutual,
     int mode, uint2* __restrict__ out_matches, int* __restrict__ counts, int4* __restrict__ stats) {
@@ -162,12 +162,11 @@ __global__ __launch_bounds__(FIN_T) void match_finalize_dot_kernel(
     int* fwd = smem;
     int* bwd = smem + row_stride;
     __shared__ int s_cnt[2];
-    __shared__ int s_scan[FIN_T];
     if (tid < 2) s_cnt[tid] = 0;
     __syncthreads();
     int c12 = 0, c21 = 0;
     const int na = A.n, nb = B.n;  // rows / columns at or beyond these are padding: never read
-    for (int q = tid; q < na; q += FIN_T) {
+    for (int q = tid; q < na; q += FIN_THREADS) {
         const int2 r = rowres[(size_t)p * row_stride + q];
         const bool ok = nb > 0 && __int_as_float(r.x) > min_score;  // strict; -inf ("no neighbour") never passes
         fwd[q] = ok ? r.y : -1;
@@ -175,7 +174,7 @@ __global__ __launch_bounds__(FIN_T) void match_finalize_dot_kernel(
     }
     if (mode == 0) {
         const int wbs = (na + 31) / 32;  // tiles of frame A that hold a real row
-        for (int c = tid; c < nb; c += FIN_T) {
+        for (int c = tid; c < nb; c += FIN_THREADS) {
             float v = EACHAM_NEG_INF;
             int r1 = -1;
             const int2* cp = colpart + (size_t)p * wb_stride * row_stride + c;
@@ -195,30 +194,11 @@ __global__ __launch_bounds__(FIN_T) void match_finalize_dot_kernel(
     atomicAdd(&s_cnt[0], c12);
     atomicAdd(&s_cnt[1], c21);
     __syncthreads();
-    uint2* out = out_matches + (size_t)p * row_stride;
-    int base = 0;
-    for (int q0 = 0; q0 < na; q0 += FIN_T) {
-        const int q = q0 + tid;
-        const int t = q < na ? fwd[q] : -1;
-        const bool keep = t >= 0 && (mode == 1 || bwd[t] == q);
-        s_scan[tid] = keep;
-        __syncthreads();
-        for (int off = 1; off < FIN_T; off <<= 1) {
-            const int v = tid >= off ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        if (keep) out[base + s_scan[tid] - 1] = make_uint2((unsigned)q, (unsigned)t);
-        base += s_scan[FIN_T - 1];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int n12 = s_cnt[0], n21 = s_cnt[1];
-        const bool edge = n12 >= min_dir && n21 >= min_dir && base > min_mutual;
-        counts[p] = mode == 1 ? base : (edge ? base : 0);
-        if (stats) stats[p] = make_int4(n12, n21, base, edge ? 1 : 0);
-    }
+    const int base = compact_kept_rows(na, tid, out_matches + (size_t)p * row_stride, [&](int q) {
+        const int t = fwd[q];
+        return t >= 0 && (mode == 1 || bwd[t] == q) ? t : -1;
+    });
+    if (tid == 0) write_pair_result(p, mode, s_cnt[0], s_cnt[1], base, min_dir, min_mutual, counts, stats);
 }
 
 // edges + scores of a launch into the CSR arrays; the score of (q, t) is the row result of q, still in the workspace
@@ -256,7 +236,7 @@ int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const int2* p
     {
         ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
         int* cnt = counts_dev + first;
-        match_finalize_dot_kernel<<<nb, FIN_T, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, cp, pl.wb_stride, pl.row_stride, min_score,
+        match_finalize_dot_kernel<<<nb, FIN_THREADS, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, cp, pl.wb_stride, pl.row_stride, min_score,
                                                                        min_dir, min_mutual, mode, mt, cnt, stats_dev ? stats_dev + first : nullptr);
         launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, is_last);
         compact_dot_kernel<<<nb, 256, 0, ctx->stream>>>(mt, rr, cnt, offsets_dev + first, pl.row_stride, edges_dev, scores_dev, edge_cap);

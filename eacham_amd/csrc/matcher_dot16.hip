@@ -500,7 +500,7 @@ static int sync_table16(eacham_ctx* ctx) {
     return EACHAM_OK;
 }
 
-static unsigned long long* dot16_tally(eacham_ctx* ctx) { return (unsigned long long*)(ctx->flag_dev + 40); }
+static unsigned long long* dot16_tally(eacham_ctx* ctx) { return ctx->flag_dev->dot16; }
 
 template <bool DUMP>
 static void launch_tile16(eacham_ctx* ctx, int grid, const int2* pb, const int2* fb, int empty, const MatchPlanF32& pl, int4* rr16,
@@ -608,7 +608,7 @@ extern "C" int eacham_match_debug_dot_coarse(eacham_ctx* ctx, int f1, int f2, fl
         for (int f : {f1, f2})
             if (f < 0 || (size_t)f >= ctx->frames.size() || ctx->frames[f].n < 0)
                 return ctx->fail(EACHAM_ERR_INVALID, "frame %d is not resident", f);
-        if (ctx->kind_common != 1)
+        if (ctx->kind_common != FRAME_F32)
             return ctx->fail(EACHAM_ERR_UNSUPPORTED, "dot-product matching needs float frames (eacham_upload_descriptors_f32); the resident frames are int8");
         const int n1 = ctx->frames[f1].n, n2 = ctx->frames[f2].n;
         if (n1 > 4096 || n2 > 4096) return ctx->fail(EACHAM_ERR_CAPACITY, "the coarse scores are for frames of <= 4096 rows (%d x %d)", n1, n2);

@@ -16,6 +16,7 @@
 // of 32 rows (D x 128 B) stream through a 2-slot LDS ring filled by LDS-DMA; the MFMA dominates
 // (D/2 instructions of 64 cycles per 32x32 tile), the (value, index) top-2 epilogue is minor.
 #include "context.hpp"
+#include "match_tail.hpp"
 
 #include <algorithm>
 
@@ -194,8 +195,7 @@ __device__ __forceinline__ bool ratio_pass_f32(float d2_best, float d2_second, d
     return (double)q < ratio;
 }
 
-constexpr int FIN_T = 256;
-__global__ __launch_bounds__(FIN_T) void match_finalize_f32_kernel(
+__global__ __launch_bounds__(FIN_THREADS) void match_finalize_f32_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const int4* __restrict__ rowres,
     const int4* __restrict__ colpart, int wb_stride, int row_stride, double ratio, int min_dir, int min_mutual,
     int mode, uint2* __restrict__ out_matches, int* __restrict__ counts, int4* __restrict__ stats) {
@@ -206,18 +206,17 @@ __global__ __launch_bounds__(FIN_T) void match_finalize_f32_kernel(
     int* fwd = smem;
     int* bwd = smem + row_stride;
     __shared__ int s_cnt[2];
-    __shared__ int s_scan[FIN_T];
     if (tid < 2) s_cnt[tid] = 0;
     __syncthreads();
     int c12 = 0, c21 = 0;
-    for (int q = tid; q < A.n; q += FIN_T) {
+    for (int q = tid; q < A.n; q += FIN_THREADS) {
         const int4 r = rowres[(size_t)p * row_stride + q];
         const float v1 = __int_as_float(r.x), v2 = __int_as_float(r.z);
         const bool ok = B.ntiles > 0 && v2 < INVALID_F && ratio_pass_f32(v1, v2, ratio);
         fwd[q] = ok ? r.y : -1;
         c12 += ok;
     }
-    for (int c = tid; c < B.n; c += FIN_T) {
+    for (int c = tid; c < B.n; c += FIN_THREADS) {
         float v1 = INIT_F, v2 = INIT_F;
         int r1 = -1;
         const int4* cp = colpart + (size_t)p * wb_stride * row_stride + c;
@@ -239,30 +238,11 @@ __global__ __launch_bounds__(FIN_T) void match_finalize_f32_kernel(
     atomicAdd(&s_cnt[0], c12);
     atomicAdd(&s_cnt[1], c21);
     __syncthreads();
-    uint2* out = out_matches + (size_t)p * row_stride;
-    int base = 0;
-    for (int q0 = 0; q0 < A.n; q0 += FIN_T) {
-        const int q = q0 + tid;
-        const int t = q < A.n ? fwd[q] : -1;
-        const bool keep = t >= 0 && (mode == 1 || bwd[t] == q);
-        s_scan[tid] = keep;
-        __syncthreads();
-        for (int off = 1; off < FIN_T; off <<= 1) {
-            const int v = tid >= off ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        if (keep) out[base + s_scan[tid] - 1] = make_uint2((unsigned)q, (unsigned)t);
-        base += s_scan[FIN_T - 1];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int n12 = s_cnt[0], n21 = s_cnt[1];
-        const bool edge = n12 >= min_dir && n21 >= min_dir && base > min_mutual;
-        counts[p] = mode == 1 ? base : (edge ? base : 0);
-        if (stats) stats[p] = make_int4(n12, n21, base, edge ? 1 : 0);
-    }
+    const int base = compact_kept_rows(A.n, tid, out_matches + (size_t)p * row_stride, [&](int q) {
+        const int t = fwd[q];
+        return t >= 0 && (mode == 1 || bwd[t] == q) ? t : -1;
+    });
+    if (tid == 0) write_pair_result(p, mode, s_cnt[0], s_cnt[1], base, min_dir, min_mutual, counts, stats);
 }
 
 // ---- host ------------------------------------------------------------------------------------------
@@ -272,25 +252,11 @@ static int d2_for_dim(int dim) {
 }
 
 int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n, int dim) {
-    if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
-    if (n < 0) return ctx->fail(EACHAM_ERR_INVALID, "negative row count");
     const int D2 = d2_for_dim(dim);
-    if (!D2) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "descriptor dim %d: need 1..256", dim);
-    if (ctx->ks_common && (ctx->kind_common != 1 || ctx->ks_common != D2))
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32) and dim class");
-    int ntiles = (n + 31) / 32;
-    ntiles = (ntiles + 3) / 4 * 4;
-    if (ntiles > 512) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "frame has %d rows; this build supports <= 16384", n);
-    if ((size_t)frame_id >= ctx->frames.size()) ctx->frames.resize(frame_id + 1);
-    FrameHost& f = ctx->frames[frame_id];
-    if (f.frag || f.norm) {
-        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (f.frag) (void)hipFree(f.frag);
-        if (f.norm) (void)hipFree(f.norm);
-        free_frame_image16(f);
-        f = FrameHost();
-    }
-    f.img16_ready = false;  // (an empty frame has no allocation, yet counts as imaged: the new rows need an image of their own)
+    FrameHost* slot = nullptr;
+    if (int rc = open_frame_slot(ctx, frame_id, FRAME_F32, n, 16384 /* 512 tiles */, D2, 0, &slot)) return rc;
+    FrameHost& f = *slot;
+    const int ntiles = ((n + 31) / 32 + 3) / 4 * 4;
     const int npad = ntiles * 32;
     if (npad > 0) {
         EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, (size_t)npad * D2 * 2 * sizeof(float)));
@@ -301,13 +267,7 @@ int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n,
         norm_f32_kernel<<<(npad + 255) / 256, 256, 0, ctx->stream>>>(src_dev, n, dim, npad, (float*)f.norm);
         EACHAM_HIP_TRY(ctx, hipGetLastError());
     }
-    f.n = n;
-    f.dim = dim;
-    f.ks = D2;
-    f.ntiles = ntiles;
-    ctx->ks_common = D2;
-    ctx->kind_common = 1;
-    ctx->frame_table_dirty = true;
+    commit_frame(ctx, f, FRAME_F32, n, dim, D2, ntiles, 0);
     return EACHAM_OK;
 }
 
@@ -357,7 +317,7 @@ int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double rat
         int* cnt = counts_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
-            match_finalize_f32_kernel<<<nb, FIN_T, fin_smem, ctx->stream>>>(
+            match_finalize_f32_kernel<<<nb, FIN_THREADS, fin_smem, ctx->stream>>>(
                 ctx->frame_table_dev, pb, (const int4*)(ws + off_rowres), (const int4*)(ws + off_colpart), wb_stride, row_stride,
                 ratio, min_dir, min_mutual, mode, (uint2*)(ws + off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
             launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);

@@ -13,7 +13,8 @@
 // What this file adds: the expansion of packed rows on the device (the host-to-device copy is the packed bytes), the resident
 // packed copy (8 words per row, reached through a table of its own so that FrameDev and the sweeps' argument loads stay as they
 // are), and the distance kernel: popcount of the XOR of the two packed rows of every emitted match, the DMatch.distance a
-// caller expects and an arithmetic path independent of the sweep.
+// caller expects and an arithmetic path independent of the sweep. The wide kind (matcher_ham_wide.hip, 16 words per row) stores
+// its packed rows with the same kernel, enters the same table and gets its distances from the same place.
 #include "context.hpp"
 #include "devprim.hpp"
 
@@ -32,11 +33,11 @@ __global__ void bits_expand_kernel(const unsigned char* __restrict__ packed, int
     for (int i = 0; i < 8; ++i) out[i] = (v >> (7 - i)) & 1u ? 255.0f : 0.0f;
 }
 
-// thread per (row, word): the packed row as 8 words, zero beyond bytes_per_row
-__global__ void bits_store_kernel(const unsigned char* __restrict__ packed, int n, int bytes_per_row, unsigned* __restrict__ bits) {
+// thread per (row, word): the packed row as `words` words (8: up to 256 bits, 16: the wide kind), zero beyond bytes_per_row
+__global__ void bits_store_kernel(const unsigned char* __restrict__ packed, int n, int bytes_per_row, int words, unsigned* __restrict__ bits) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * 8) return;
-    const int row = idx >> 3, w = idx & 7;
+    if (idx >= n * words) return;
+    const int row = idx / words, w = idx % words;
     unsigned v = 0u;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
@@ -47,7 +48,8 @@ __global__ void bits_store_kernel(const unsigned char* __restrict__ packed, int 
 }
 
 // dist[k] = popcount(row q of frame pairs[p].x ^ row t of frame pairs[p].y) for edge k = {q, t} of pair p, the pair found by
-// its offsets; k runs over the edges that were written (min(total, cap))
+// its offsets; k runs over the edges that were written (min(total, cap)). V4 = uint4s per packed row: 2 (8 words) or 4 (16, wide frames)
+template <int V4>
 __global__ void hamming_dist_kernel(const unsigned* const* __restrict__ table, const int2* __restrict__ pairs, int npairs,
                                     const long long* __restrict__ offsets, const long long* __restrict__ total,
                                     const uint2* __restrict__ edges, long long cap, int* __restrict__ dist) {
@@ -60,9 +62,12 @@ __global__ void hamming_dist_kernel(const unsigned* const* __restrict__ table, c
         const uint4* b = reinterpret_cast<const uint4*>(table[pr.y]);
         int h = -1;   // (a pair of the stand-in frame has no edge; nothing without packed rows is ever read)
         if (a && b) {
-            const uint4 a0 = a[2 * (size_t)e.x], a1 = a[2 * (size_t)e.x + 1], b0 = b[2 * (size_t)e.y], b1 = b[2 * (size_t)e.y + 1];
-            h = __popc(a0.x ^ b0.x) + __popc(a0.y ^ b0.y) + __popc(a0.z ^ b0.z) + __popc(a0.w ^ b0.w) + __popc(a1.x ^ b1.x) +
-                __popc(a1.y ^ b1.y) + __popc(a1.z ^ b1.z) + __popc(a1.w ^ b1.w);
+            h = 0;
+#pragma unroll
+            for (int w = 0; w < V4; ++w) {
+                const uint4 x = a[V4 * (size_t)e.x + w], y = b[V4 * (size_t)e.y + w];
+                h = h + __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
+            }
         }
         dist[k] = h;
     }
@@ -73,8 +78,8 @@ void launch_bits_expand(eacham_ctx* ctx, const unsigned char* packed_dev, int n,
     bits_expand_kernel<<<(unsigned)((work + 255) / 256), 256, 0, ctx->stream>>>(packed_dev, n, bytes_per_row, dim, dst_dev);
 }
 
-void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, unsigned* bits_dev) {
-    bits_store_kernel<<<(n * 8 + 255) / 256, 256, 0, ctx->stream>>>(packed_dev, n, bytes_per_row, bits_dev);
+void launch_bits_store(eacham_ctx* ctx, const unsigned char* packed_dev, int n, int bytes_per_row, int words_per_row, unsigned* bits_dev) {
+    bits_store_kernel<<<(n * words_per_row + 255) / 256, 256, 0, ctx->stream>>>(packed_dev, n, bytes_per_row, words_per_row, bits_dev);
 }
 
 // the table of the frames' packed rows, entry [frames] = the empty stand-in of sanitize_pairs
@@ -107,8 +112,10 @@ int hamming_distances(eacham_ctx* ctx, const int2* pairs_dev, int npairs, const 
     int rc = sync_bits_table(ctx);
     if (rc) return rc;
     const int grid = (int)std::min<long long>((edge_cap + 255) / 256, 2048);
-    hamming_dist_kernel<<<grid, 256, 0, ctx->stream>>>(ctx->bits_table_dev, pairs_dev, npairs, offsets_dev, total_dev, edges_dev, edge_cap,
-                                                      dist_dev);
+    if (ctx->kind_common == FRAME_BITS_WIDE)
+        hamming_dist_kernel<4><<<grid, 256, 0, ctx->stream>>>(ctx->bits_table_dev, pairs_dev, npairs, offsets_dev, total_dev, edges_dev, edge_cap, dist_dev);
+    else
+        hamming_dist_kernel<2><<<grid, 256, 0, ctx->stream>>>(ctx->bits_table_dev, pairs_dev, npairs, offsets_dev, total_dev, edges_dev, edge_cap, dist_dev);
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     return EACHAM_OK;
 }

@@ -22,11 +22,13 @@
 //
 // Resident image, per frame: [ntiles][KS][64] int4, KS = ceil(D / 64) in 1..8; lane l = 32 half + r of step s of tile t holds the 32
 // codes of bits 64 s + 32 half .. + 31 of row 32 t + r. A step of a tile is one 1 KiB piece: global_load_lds width 16 stages it.
-// The packed rows are kept too (16 words per row) and give every emitted match its distance by popcount, a path independent of
-// the sweep. Both live behind FrameHost::frag / ::norm, so the frame table, the sanitised pair list and the frees are the shared ones.
+// The packed rows are kept too (16 words per row, FrameHost::bits, behind the image in frag's allocation) and give every emitted
+// match its distance by popcount, a path independent of the sweep and shared with the narrow kind (hamming_distances, matcher_ham.hip).
+// The frame slot, the frame table, the sanitised pair list and the pair tail (match_tail.hpp) are the shared ones.
 //
 // Both directions: the sweep runs on (f1, f2) and on (f2, f1) — see DESIGN.md 3.7.
 #include "context.hpp"
+#include "match_tail.hpp"
 
 #include <algorithm>
 
@@ -46,7 +48,6 @@ constexpr float HW_PAD = 33554432.0f;            // 2^25: the C-init of a paddin
 constexpr float HW_KEY_END = 16777216.0f;        // 2^24: real keys lie below
 constexpr int HW_SCALE_TRAIN = (int)0x8c8c8c8cu; // E8M0 2^13 in every byte
 constexpr int HW_SCALE_QUERY = 0x7f7f7f7f;       // E8M0 2^0
-constexpr int HW_FIN_T = 256;
 
 // thread per (stored row, k-step, lane half): four bytes of the packed row -> four words of eight codes each. Bytes at or beyond
 // bytes_per_row and rows at or beyond n are the zero codes of the padding.
@@ -68,20 +69,6 @@ __global__ void ham_wide_image_kernel(const unsigned char* __restrict__ packed, 
         w[k] = word;
     }
     img[((size_t)(row >> 5) * ks + s) * 64 + 32 * half + (row & 31)] = make_int4((int)w[0], (int)w[1], (int)w[2], (int)w[3]);
-}
-
-// thread per (row, word): the packed row as 16 words, zero beyond bytes_per_row
-__global__ void ham_wide_store_kernel(const unsigned char* __restrict__ packed, int n, int bytes_per_row, unsigned* __restrict__ bits) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= n * 16) return;
-    const int row = idx >> 4, w = idx & 15;
-    unsigned v = 0u;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-        const int j = 4 * w + b;
-        if (j < bytes_per_row) v |= (unsigned)packed[(size_t)row * bytes_per_row + j] << (8 * b);
-    }
-    bits[idx] = v;
 }
 
 // ---- the sweep: rowres[(p ndir + dir)][q] = {smallest key, second smallest key} of query row q over the train frame's rows ----
@@ -220,7 +207,7 @@ __device__ __forceinline__ bool ham_wide_pass(float2 k, double ratio) {
 }
 
 // ---- the tail: decode, predicate, directed lists, mutual check + thresholds (mode 0), stats; block per pair ----
-__global__ __launch_bounds__(HW_FIN_T) void ham_wide_finalize_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
+__global__ __launch_bounds__(FIN_THREADS) void ham_wide_finalize_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
                                                                      const float2* __restrict__ rowres, int ndir, int row_stride,
                                                                      double ratio, int min_dir, int min_mutual, int mode,
                                                                      uint2* __restrict__ out_matches, int* __restrict__ counts,
@@ -232,12 +219,11 @@ __global__ __launch_bounds__(HW_FIN_T) void ham_wide_finalize_kernel(const Frame
     int* fwd = smem;
     int* bwd = smem + row_stride;
     __shared__ int s_cnt[2];
-    __shared__ int s_scan[HW_FIN_T];
     if (tid < 2) s_cnt[tid] = 0;
     __syncthreads();
     int c12 = 0, c21 = 0;
     const float2* r12 = rowres + (size_t)p * ndir * row_stride;
-    for (int q = tid; q < na; q += HW_FIN_T) {
+    for (int q = tid; q < na; q += FIN_THREADS) {
         const float2 k = r12[q];
         const bool ok = nb >= 2 && ham_wide_pass(k, ratio);
         fwd[q] = ok ? ((int)k.x & (HW_MAX_ROWS - 1)) : -1;
@@ -245,7 +231,7 @@ __global__ __launch_bounds__(HW_FIN_T) void ham_wide_finalize_kernel(const Frame
     }
     if (mode == 0) {
         const float2* r21 = r12 + row_stride;
-        for (int c = tid; c < nb; c += HW_FIN_T) {
+        for (int c = tid; c < nb; c += FIN_THREADS) {
             const float2 k = r21[c];
             const bool ok = na >= 2 && ham_wide_pass(k, ratio);
             bwd[c] = ok ? ((int)k.x & (HW_MAX_ROWS - 1)) : -1;
@@ -255,101 +241,34 @@ __global__ __launch_bounds__(HW_FIN_T) void ham_wide_finalize_kernel(const Frame
     atomicAdd(&s_cnt[0], c12);
     atomicAdd(&s_cnt[1], c21);
     __syncthreads();
-    uint2* out = out_matches + (size_t)p * row_stride;
-    int base = 0;
-    for (int q0 = 0; q0 < na; q0 += HW_FIN_T) {
-        const int q = q0 + tid;
-        const int t = q < na ? fwd[q] : -1;
-        const bool keep = t >= 0 && (mode == 1 || bwd[t] == q);
-        s_scan[tid] = keep;
-        __syncthreads();
-        for (int off = 1; off < HW_FIN_T; off <<= 1) {
-            const int v = tid >= off ? s_scan[tid - off] : 0;
-            __syncthreads();
-            s_scan[tid] += v;
-            __syncthreads();
-        }
-        if (keep) out[base + s_scan[tid] - 1] = make_uint2((unsigned)q, (unsigned)t);
-        base += s_scan[HW_FIN_T - 1];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int n12 = s_cnt[0], n21 = s_cnt[1];
-        const bool edge = n12 >= min_dir && n21 >= min_dir && base > min_mutual;
-        counts[p] = mode == 1 ? base : (edge ? base : 0);
-        if (stats) stats[p] = make_int4(n12, n21, base, edge ? 1 : 0);
-    }
-}
-
-// edges of a launch into the CSR arrays, with their distances: the popcount of the XOR of the two packed rows
-__global__ void ham_wide_compact_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint2* __restrict__ matches,
-                                        const int* __restrict__ counts, const long long* __restrict__ offsets, int row_stride,
-                                        uint2* __restrict__ edges, int* __restrict__ dist, long long edge_cap) {
-    const int p = blockIdx.x;
-    const int n = counts[p];
-    const long long off = offsets[p];
-    const int2 pr = pairs[p];
-    const uint4* a = reinterpret_cast<const uint4*>(frames[pr.x].norm);
-    const uint4* b = reinterpret_cast<const uint4*>(frames[pr.y].norm);
-    for (int k = threadIdx.x; k < n; k += blockDim.x)
-        if (off + k < edge_cap) {
-            const uint2 e = matches[(size_t)p * row_stride + k];
-            edges[off + k] = e;
-            if (dist) {
-                int hd = 0;
-#pragma unroll
-                for (int w = 0; w < 4; ++w) {
-                    const uint4 x = a[4 * (size_t)e.x + w], y = b[4 * (size_t)e.y + w];
-                    hd += __popc(x.x ^ y.x) + __popc(x.y ^ y.y) + __popc(x.z ^ y.z) + __popc(x.w ^ y.w);
-                }
-                dist[off + k] = hd;
-            }
-        }
+    const int base = compact_kept_rows(na, tid, out_matches + (size_t)p * row_stride, [&](int q) {
+        const int t = fwd[q];
+        return t >= 0 && (mode == 1 || bwd[t] == q) ? t : -1;
+    });
+    if (tid == 0) write_pair_result(p, mode, s_cnt[0], s_cnt[1], base, min_dir, min_mutual, counts, stats);
 }
 
 // ---- host ------------------------------------------------------------------------------------------
 int upload_frame_bits_wide(eacham_ctx* ctx, int frame_id, const unsigned char* packed_dev, int n, int bytes_per_row) {
-    if (frame_id < 0 || frame_id >= (1 << 20)) return ctx->fail(EACHAM_ERR_INVALID, "frame_id %d out of range", frame_id);
     if (n < 0 || bytes_per_row <= 0) return ctx->fail(EACHAM_ERR_INVALID, "bad descriptor shape %d x %d bytes", n, bytes_per_row);
     if (n > 0 && !packed_dev) return ctx->fail(EACHAM_ERR_INVALID, "null descriptor pointer");
-    if (bytes_per_row > HW_MAX_BYTES)
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "binary descriptors of %d bytes: this build supports <= %d (512 bits)", bytes_per_row, HW_MAX_BYTES);
-    if (n > HW_MAX_ROWS) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "frame has %d rows; this build supports <= %d", n, HW_MAX_ROWS);
-    if (ctx->ks_common && ctx->kind_common != 3)
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "all resident frames must share one descriptor kind (int8 / f32 / binary / wide binary)");
-    if (ctx->ks_common && ctx->wide_bytes_common != bytes_per_row)
-        return ctx->fail(EACHAM_ERR_UNSUPPORTED, "wide binary frames of %d bytes per row are resident: %d bytes per row cannot be matched against them",
-                         ctx->wide_bytes_common, bytes_per_row);
-    const int ks = (8 * bytes_per_row + 63) / 64;
+    const int ks = bytes_per_row <= HW_MAX_BYTES ? (8 * bytes_per_row + 63) / 64 : 0;
+    FrameHost* slot = nullptr;
+    if (int rc = open_frame_slot(ctx, frame_id, FRAME_BITS_WIDE, n, HW_MAX_ROWS, ks, bytes_per_row, &slot)) return rc;
+    FrameHost& f = *slot;
     const int ntiles = ((n + 31) / 32 + HW_NSUB - 1) / HW_NSUB * HW_NSUB;
-    if ((size_t)frame_id >= ctx->frames.size()) ctx->frames.resize(frame_id + 1);
-    FrameHost& f = ctx->frames[frame_id];
-    if (f.frag || f.norm) {
-        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        if (f.frag) (void)hipFree(f.frag);
-        if (f.norm) (void)hipFree(f.norm);
-        free_frame_image16(f);
-        f = FrameHost();
-    }
     const int npad = ntiles * 32;
     if (npad > 0) {
-        EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, (size_t)ntiles * ks * 64 * sizeof(int4)));
-        EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.norm, (size_t)n * 16 * sizeof(unsigned)));
-        f.bits = (unsigned*)f.norm;
+        // one allocation: the image (whole KiB) | the packed rows, 16 words each
+        const size_t img_bytes = (size_t)ntiles * ks * 64 * sizeof(int4);
+        EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.frag, img_bytes + (size_t)n * 16 * sizeof(unsigned)));
+        f.bits = (unsigned*)((char*)f.frag + img_bytes);
         const long long work = (long long)npad * ks * 2;
         ham_wide_image_kernel<<<(unsigned)((work + 255) / 256), 256, 0, ctx->stream>>>(packed_dev, n, bytes_per_row, ks, npad, f.frag);
-        ham_wide_store_kernel<<<(n * 16 + 255) / 256, 256, 0, ctx->stream>>>(packed_dev, n, bytes_per_row, f.bits);
+        launch_bits_store(ctx, packed_dev, n, bytes_per_row, 16, f.bits);
         EACHAM_HIP_TRY(ctx, hipGetLastError());
     }
-    f.n = n;
-    f.dim = 8 * bytes_per_row;
-    f.ks = ks;
-    f.ntiles = ntiles;
-    ctx->ks_common = ks;
-    ctx->kind_common = 3;
-    ctx->wide_bytes_common = bytes_per_row;
-    ctx->frame_table_dirty = true;
-    ctx->bits_table_dirty = true;
+    commit_frame(ctx, f, FRAME_BITS_WIDE, n, 8 * bytes_per_row, ks, ntiles, bytes_per_row);
     EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // orders reuse of the staging buffer (and of the caller's rows)
     return EACHAM_OK;
 }
@@ -395,11 +314,11 @@ void launch_ham_wide_sweep(eacham_ctx* ctx, const int2* pb, int nb, int ndir, co
 }
 }  // namespace
 
-// mode 0 = mutual + thresholds, mode 1 = directed lists; CSR over the pairs either way. dist_dev may be null; pairs_host (the same
-// list, checked, or null) only feeds the tally of eacham_match_debug_hamming_wide.
+// mode 0 = mutual + thresholds, mode 1 = directed lists; CSR over the pairs either way. pairs_host (the same list, checked, or
+// null) only feeds the tally of eacham_match_debug_hamming_wide; *pairs_used (may be null) is the list the kernels ran on.
 int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
-                       int* counts_dev, long long* offsets_dev, uint2* edges_dev, int* dist_dev, long long edge_cap,
-                       long long* total_dev, int4* stats_dev, const int32_t* pairs_host) {
+                       int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
+                       int4* stats_dev, const int32_t* pairs_host, const int2** pairs_used) {
     int rc = sync_frame_table(ctx);
     if (rc) return rc;
     if (npairs <= 0) return EACHAM_OK;
@@ -407,6 +326,7 @@ int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, doubl
         return ctx->fail(EACHAM_ERR_INVALID, "ratio %g: mutual matching supports 0 < ratio <= 1 (the reference uses 0.8)", ratio);
     rc = sanitize_pairs(ctx, pairs_dev, npairs, &pairs_dev);  // a bad frame id in a device-side list must not reach the kernels
     if (rc) return rc;
+    if (pairs_used) *pairs_used = pairs_dev;
     const HamWidePlan pl = plan_ham_wide(ctx, npairs);
     rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
@@ -427,11 +347,10 @@ int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, doubl
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
             int* cnt = counts_dev + first;
-            ham_wide_finalize_kernel<<<nb, HW_FIN_T, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, ndir, pl.row_stride, ratio, min_dir,
+            ham_wide_finalize_kernel<<<nb, FIN_THREADS, fin_smem, ctx->stream>>>(ctx->frame_table_dev, pb, rr, ndir, pl.row_stride, ratio, min_dir,
                                                                           min_mutual, mode, mt, cnt, stats_dev ? stats_dev + first : nullptr);
             launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-            ham_wide_compact_kernel<<<nb, 256, 0, ctx->stream>>>(ctx->frame_table_dev, pb, mt, cnt, offsets_dev + first, pl.row_stride, edges_dev,
-                                                                 dist_dev, edge_cap);
+            launch_compact_edges(ctx, nb, mt, cnt, offsets_dev + first, pl.row_stride, edges_dev, edge_cap);
         }
         EACHAM_HIP_TRY(ctx, hipGetLastError());
     }
@@ -448,7 +367,7 @@ int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, doubl
 // the sweep's own top-2 of the ordered pair (f1, f2), from the buffer the tail reads
 int ham_wide_debug_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap) {
     if (!best || !h0 || !h1 || cap < 0) return ctx->fail(EACHAM_ERR_INVALID, "null output");
-    if (ctx->kind_common != 3) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the wide Hamming sweep needs wide binary frames (eacham_upload_descriptors_bits_wide)");
+    if (ctx->kind_common != FRAME_BITS_WIDE) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the wide Hamming sweep needs wide binary frames (eacham_upload_descriptors_bits_wide)");
     const FrameHost &A = ctx->frames[f1], &B = ctx->frames[f2];
     if (B.n < 2) return ctx->fail(EACHAM_ERR_INVALID, "frame %d has %d rows: a top-2 needs two or more", f2, B.n);
     if (cap < A.n) return ctx->fail(EACHAM_ERR_CAPACITY, "%d rows but capacity %d", A.n, cap);

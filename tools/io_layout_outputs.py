@@ -10,9 +10,11 @@ cases of tests/lmeds_batch_cases.py in their three variants (eacham_lmeds_batch,
 eacham_score_hypotheses problem by problem), tests/test_tri_oracle.py's two-view case (seed 5, 2000 matches, both angle rules), one
 synth.make_tracks scene (eacham_triangulate_tracks, eacham_reprojection_errors), one PnP batch (eacham_solve_pnp,
 eacham_score_hypotheses), the resident graph after eacham_graph_set_frames (its query's answer), eacham_graph_best_pair on the
-same scenario (with and without an excluded mask) and the seven matching calls: eacham_match_pair / _match_all_pairs (with and
+same scenario (with and without an excluded mask) and the matching calls: eacham_match_pair / _match_all_pairs (with and
 without stats) / _match_pairs_directed on int8 frames and on float frames, the four dot-product calls on the float frames, each on
-a 12-pair list and on a list long enough for the direct copies (33 000 pairs)."""
+a 12-pair list and on a list long enough for the direct copies (33 000 pairs); the Hamming calls — pair, directed, all pairs with
+and without stats, and the device-pointer form with distances — on binary frames of 32 bytes per row and on wide ones of 64.
+--matching with --dump leaves out everything but the matching calls."""
 import argparse
 import os
 import sys
@@ -24,7 +26,24 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def dump(path):
+def dump(path, only_matching=False):
+    import torch
+    torch.cuda.init()   # (before the library touches the device: the device-pointer calls below hand it torch tensors)
+    out = {}
+
+    def put(name, *arrays):
+        for k, a in enumerate(arrays):
+            a = np.ascontiguousarray(a)
+            out[f"{name}/{k}"] = np.frombuffer(a.tobytes(), np.uint8)
+
+    if not only_matching:
+        staged(put)
+    matching(put)
+    np.savez(path, **out)
+    print(f"{len(out)} arrays, {sum(a.size for a in out.values())} bytes -> {path}")
+
+
+def staged(put):
     from eacham_amd import HipContext, score, synth, triangulate as tri
     from eacham_amd import graph as G
     import lmeds_batch_cases as LC
@@ -32,13 +51,6 @@ def dump(path):
     import two_view_batch_cases as TC
     from test_graph_oracle import scenario
     from test_tri_oracle import _two_view_case
-
-    out = {}
-
-    def put(name, *arrays):
-        for k, a in enumerate(arrays):
-            a = np.ascontiguousarray(a)
-            out[f"{name}/{k}"] = np.frombuffer(a.tobytes(), np.uint8)
 
     with HipContext(0) as ctx:
         for name, make in TC.CASES.items():
@@ -100,13 +112,10 @@ def dump(path):
         for ex in (None, excluded):
             best, ec = G.best_pair_for_valid(ctx, 40, pairs, counts, offsets, q, t, valid, has3d, ex, want_edge_counts=True)
             put(f"graph_best_pair/{int(ex is not None)}", np.array(best, np.int64), ec)
-    matching(put)
-    np.savez(path, **out)
-    print(f"{len(out)} arrays, {sum(a.size for a in out.values())} bytes -> {path}")
 
 
 def matching(put):
-    """The seven host-pointer matching calls (eacham_amd/csrc/matcher.hip), each build in a context of its own per descriptor kind."""
+    """The matching calls (eacham_amd/csrc/matcher.hip), each build in a context of its own per descriptor kind."""
     import ctypes as C
     from eacham_amd import HipContext, synth
     import dot_cases as DC
@@ -145,6 +154,36 @@ def matching(put):
                         name = "match_all_pairs_dot_screened" if screened else "match_all_pairs_dot"
                         put(f"{name}/{tag}", *ctx.match_all_pairs_dot(pr, 0.5, 0, -1, screened=screened))
                         put(f"{name}_nostats/{tag}", *ctx.match_all_pairs_dot(pr, 0.5, 5, 5, stats=False, screened=screened)[:5])
+    import torch
+    import ham_cases as HC
+    dev = torch.device("cuda", 0)
+    for kind, nbytes in (("bits", 32), ("wide", 64)):
+        descs = HC.binary_frames(nbytes, [300, 237, 150, 97], 120, 13)
+        with HipContext(0) as ctx:
+            for f, d in enumerate(descs):
+                (ctx.upload_descriptors_bits if kind == "bits" else ctx.upload_descriptors_bits_wide)(f, d)
+            for a, b in ordered:
+                put(f"match_pair_hamming/{kind}/{a}_{b}", *ctx.match_pair_hamming(int(a), int(b), 0.8))
+            for tag, pr in (("12", ordered), ("6000", long[:6000])):
+                put(f"match_pairs_directed_hamming/{kind}/{tag}", *ctx.match_pairs_directed_hamming(pr, 0.8))
+                for md, mm in ((30, 30), (1, 0)):
+                    put(f"match_all_pairs_hamming/{kind}/{tag}/{md}_{mm}", *ctx.match_all_pairs_hamming(pr, 0.8, md, mm))
+                    put(f"match_all_pairs_hamming_nostats/{kind}/{tag}/{md}_{mm}", *ctx.match_all_pairs_hamming(pr, 0.8, md, mm, stats=False)[:5])
+            cap = 300 * len(ordered)
+            with torch.cuda.stream(torch.cuda.ExternalStream(ctx.stream, device=dev)):
+                for with_stats in (True, False):
+                    pd = torch.from_numpy(np.ascontiguousarray(ordered)).to(dev)
+                    counts = torch.full((len(ordered),), -1, dtype=torch.int32, device=dev)
+                    offsets = torch.zeros(len(ordered) + 1, dtype=torch.int64, device=dev)
+                    total = torch.zeros(1, dtype=torch.int64, device=dev)
+                    edges = torch.zeros(2 * cap, dtype=torch.int32, device=dev)
+                    dist = torch.full((cap,), -7, dtype=torch.int32, device=dev)
+                    st = torch.zeros(4 * len(ordered), dtype=torch.int32, device=dev)
+                    ctx.sync()
+                    ctx.match_all_pairs_hamming_dev(pd.data_ptr(), len(ordered), counts.data_ptr(), offsets.data_ptr(), edges.data_ptr(), cap,
+                                                    total.data_ptr(), st.data_ptr() if with_stats else 0, dist.data_ptr(), ratio=0.8, min_dir=1, min_mutual=0)
+                    ctx.sync()
+                    put(f"match_all_pairs_hamming_dev/{kind}/{int(with_stats)}", *(x.cpu().numpy() for x in (counts, offsets, total, edges, dist, st)))
 
 
 def compare(a_path, b_path, out_path):
@@ -174,8 +213,9 @@ if __name__ == "__main__":
     ap.add_argument("--dump")
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--out")
+    ap.add_argument("--matching", action="store_true", help="with --dump: the matching calls only")
     args = ap.parse_args()
     if args.dump:
-        dump(args.dump)
+        dump(args.dump, args.matching)
         sys.exit(0)
     sys.exit(compare(args.compare[0], args.compare[1], args.out))
