@@ -5,96 +5,32 @@
 // winner — runs here for n_problems pairs with no host turn between the stages: the inputs go up once, the results come back
 // once, and the number of launches does not depend on n_problems.
 //
-//   lb_solve_h4 / lb_solve_e5   a wave per sample, SOLVE_WAVES samples per workgroup: the bodies of solve_h4_kernel / solve_e5_kernel
-//                               (solve_dev.hpp) on the sample's own problem, found by a binary search in sample_ptr (and left in
-//                               sample_problem[] for the stages below)
+//   solve_minimal_launch        (solve.hip, through solve_launch.hpp) the list instantiation of solve_h4_kernel / solve_e5_kernel — the
+//                               kernels eacham_solve_minimal launches, not a copy of them: a wave per sample on the sample's own
+//                               problem, found by a binary search in sample_ptr (and left in sample_problem[] for the stages below);
+//                               a problem with fewer points than a minimal sample has no candidates
 //   prim::exclusive_scan        of n_models over all samples (devprim.hpp: one launch up to 16 384 samples, three beyond): candidate c
 //                               of the flattened list (sample order, then root order) is root c - first[s] of the sample s with
 //                               first[s] <= c < first[s + 1] — the models stay where the solver wrote them, nothing is copied
 //   lb_score<KIND>              a workgroup per candidate over its own problem's points: score_one, the key transform and the radix
-//                               select of score_kernel (score_dev.hpp), so the medians are the same bits. The number of candidates
+//                               select of score_kernel (score_dev.hpp: block_median), so the medians are the same bits. The number of candidates
 //                               is only known on the device: a fixed grid strides over them. Keys live in LDS up to SC_MAX_LDS
 //                               points (dynamic LDS sized by the largest problem of the call) and in the workgroup's own error row
 //                               beyond it.
 //   lb_select<KIND>             a workgroup per problem: first smallest non-NaN median (strict < over ascending candidate index),
 //                               sigma and the threshold in fp64 in the host's order of operations, then the winner's errors
-//                               against the threshold: the mask bytes and the inlier count.
+//                               against the threshold: the mask bytes and the inlier count (score_dev.hpp: block_count).
+// The offset-table checks of the entry point keep their own wording ("not monotone", one message for both tables) and their own
+// order, so they are not pnp_batch.hip's check_table; the sample indices go through check_sample_idx (solve_launch.hpp).
 #include "context.hpp"
 #include "devprim.hpp"
 #include "score_dev.hpp"
-#include "solve_dev.hpp"
+#include "solve_launch.hpp"
 
 #include <climits>
 
 namespace eacham {
 namespace {
-
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_h4_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
-                                                                      int n_problems, const double* __restrict__ a, const double* __restrict__ b,
-                                                                      int n_samples, const int* __restrict__ idx, double* __restrict__ models,
-                                                                      int* __restrict__ n_models, int* __restrict__ sample_problem) {
-    __shared__ double LtL[SOLVE_WAVES][81], V[SOLVE_WAVES][81];
-    __shared__ JacRound R[SOLVE_WAVES];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int s = blockIdx.x * SOLVE_WAVES + wave;
-    if (s >= n_samples) return;
-    const int p = prim::segment_of(sample_ptr, n_problems, s);
-    const long long base = point_ptr[p];
-    if (lane == 0) sample_problem[s] = p;
-    if (point_ptr[p + 1] - base < 4) {   // (wave-uniform) a problem without a minimal sample's worth of points has no candidates
-        if (lane == 0) n_models[s] = 0;
-        return;
-    }
-    a += 2 * base, b += 2 * base;
-    double pa[8], pb[8], out[9];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = idx[(size_t)s * 4 + k];
-        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
-        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
-    }
-#pragma unroll
-    for (int k = 0; k < 9; ++k) out[k] = 0.0;
-    const int n = homography4_wave(pa, pb, out, LtL[wave], V[wave], R[wave]);
-    if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) models[9 * (size_t)s + k] = out[k];
-        n_models[s] = n;
-    }
-}
-
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void lb_solve_e5_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
-                                                                      int n_problems, const double* __restrict__ a, const double* __restrict__ b,
-                                                                      const double* __restrict__ K, int has_K, int n_samples, const int* __restrict__ idx,
-                                                                      double* __restrict__ models, int* __restrict__ n_models,
-                                                                      int* __restrict__ sample_problem) {
-    __shared__ E5Lds lds[SOLVE_WAVES];
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int s = blockIdx.x * SOLVE_WAVES + wave;
-    if (s >= n_samples) return;
-    const int p = prim::segment_of(sample_ptr, n_problems, s);
-    const long long base = point_ptr[p];
-    if (lane == 0) sample_problem[s] = p;
-    if (point_ptr[p + 1] - base < 5) {   // (wave-uniform)
-        if (lane == 0) n_models[s] = 0;
-        return;
-    }
-    a += 2 * base, b += 2 * base;
-    double pa[10], pb[10];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int i = idx[(size_t)s * 5 + k];
-        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
-        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
-    }
-    double fx = 1, fy = 1, cx = 0, cy = 0;
-    if (has_K) fx = K[0], fy = K[1], cx = K[2], cy = K[3];
-    double* dst = models + (size_t)s * 90;
-    for (int k = lane; k < 90; k += 64) dst[k] = 0.0;  // (this wave's own stores below follow in program order)
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    const int n = essential5_wave(pa, pb, has_K != 0, fx, fy, cx, cy, dst, lds[wave]);
-    if (lane == 0) n_models[s] = n;
-}
 
 // KIND 0 = essential (Sampson distance, fp64), 1 = homography (transfer error, fp32): score_one's kinds.
 // first[s] = candidates before sample s (the exclusive scan of n_models), *total = all of them; max_models = 10 / 1.
@@ -132,13 +68,7 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_score_kernel(const long long* __r
             else erow[i] = e;
         }
         __syncthreads();  // keys / the error row are complete (the row was written by this workgroup: visible after the barrier)
-        auto load = [&](int i) { return keys_in_lds ? keys[i] : fkey(erow[i]); };
-        const unsigned hi = radix_select(load, n, n / 2, hist, sh);
-        float med = fkey_inv(hi);
-        if (n % 2 == 0) {
-            const unsigned lo = radix_select(load, n, n / 2 - 1, hist, sh);
-            med = fmul(fadd(fkey_inv(lo), med), 0.5f);
-        }
+        const float med = block_median([&](int i) { return keys_in_lds ? keys[i] : fkey(erow[i]); }, n, hist, sh);
         if (threadIdx.x == 0) medians[c] = med;
         // (radix_select ends on a barrier: every read of this candidate's keys is done before the next one's are written)
     }
@@ -238,15 +168,8 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_select_kernel(const long long* __
         out_masks[base + i] = in;
         cnt += in;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_down(cnt, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int tot = 0;
-        for (int w = 0; w < SC_BLOCK / 64; ++w) tot += wsum[w];
-        out_inliers[p] = tot;
-    }
+    const int tot = block_count(cnt, wsum);
+    if (threadIdx.x == 0) out_inliers[p] = tot;
 }
 
 constexpr int LB_SCORE_GRID = 4096;      // workgroups striding over the candidates (~2 resident rounds of 256 CUs x 8)
@@ -267,13 +190,8 @@ int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L) {
     const int normalise = L.has_K && L.kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
     ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
     if (S > 0) {
-        const unsigned grid = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
-        if (L.kind == EACHAM_SOLVE_HOMOGRAPHY4)
-            lb_solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.point_ptr, L.sample_ptr, P, L.a, L.b, (int)S, L.sample_idx, L.cand_models, L.n_models,
-                                                                  L.sample_problem);
-        else
-            lb_solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.point_ptr, L.sample_ptr, P, L.a, L.b, L.K, L.has_K ? 1 : 0, (int)S, L.sample_idx,
-                                                                  L.cand_models, L.n_models, L.sample_problem);
+        solve_minimal_launch(st, MinimalLaunch{L.kind, SolveSeg{L.point_ptr, L.sample_ptr, P, L.sample_problem}, L.a, L.b, L.K, L.has_K, (int)S, L.sample_idx,
+                                               L.cand_models, L.n_models});
     }
     prim::exclusive_scan<int>(st, L.n_models, L.first, (int)S, L.scan_ws, L.total);   // (no samples: *total = 0)
     const size_t smem = sizeof(unsigned) * (size_t)std::max<long long>(1, std::min<long long>(max_n, SC_MAX_LDS));
@@ -323,9 +241,7 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
         const long long n = point_ptr[p + 1] - point_ptr[p];
         if (n < m) continue;   // its samples are not looked at: the problem gets the "none" record
         max_n = std::max(max_n, n);
-        for (long long k = sample_ptr[p] * m; k < sample_ptr[p + 1] * m; ++k)
-            if (sample_idx[k] < 0 || sample_idx[k] >= n)
-                return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: problem %d: sample index %d of %lld points", p, (int)sample_idx[k], n);
+        if (int rc = check_sample_idx(ctx, "lmeds_batch", p, sample_idx + sample_ptr[p] * m, (sample_ptr[p + 1] - sample_ptr[p]) * m, n)) return rc;
     }
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool need_rows = lmeds_needs_rows(max_n);

@@ -5,112 +5,28 @@
 // once, the results come back once, and the number of launches does not depend on n_problems.
 //
 // eacham_pnp_hypotheses_batch — one RANSAC round:
-//   pb_front        a wave per sample, SOLVE_WAVES samples per workgroup: the body of solve_pnp_front_kernel (epnp_front<false>,
-//                   solve_dev.hpp) on the sample's own problem, found by a binary search in sample_ptr (left in sample_problem[])
-//   pb_back         a lane per (sample, linearised start), blockIdx.y the start: the body of solve_pnp_back_kernel
-//   pb_count        a wave per sample: the first strictly smallest error of the three starts (solve_pnp_select_kernel's rule)
+//   solve_pnp_launch  (solve.hip, through solve_launch.hpp) the list instantiation of solve_pnp_front_kernel / solve_pnp_back_kernel — the
+//                   kernels eacham_solve_pnp launches, not a copy of them — on the sample's own problem, found by a binary search in
+//                   sample_ptr (left in sample_problem[])
+//   pb_count        a wave per sample: the first strictly smallest error of the three starts (pnp_first_smallest, solve_dev.hpp)
 //                   gives the model; score_one<PNP> over the problem's own points, a ballot and a popcount per 64 points,
 //                   gives its inlier count. The model passes from the choice to the count in registers.
 // eacham_pnp_refit_batch — the tail of solvePnPRansac:
 //   pb_refit        a workgroup per problem: scores the model, writes the mask, compacts the inlier indices IN ASCENDING ORDER
-//                   into the problem's own row of a workspace (ballot prefix: EPnP's sums run in row order), then the
-//                   three-wave body of solve_pnp_big_kernel runs on that row — for every size of the inlier set: with at most
-//                   64 rows a lane holds one term and the partials are added in lane order, which is the sequential sum of the
-//                   at-most-64-point form term by term.
+//                   into the problem's own row of a workspace (ballot prefix: EPnP's sums run in row order), then
+//                   pnp_refit_body (solve_dev.hpp: the function solve_pnp_big_kernel runs) on that row — for every size of the
+//                   inlier set: with at most 64 rows a lane holds one term and the partials are added in lane order, which is the
+//                   sequential sum of the at-most-64-point form term by term.
 #include "context.hpp"
-#include "devprim.hpp"
 #include "score_dev.hpp"
 #include "solve_dev.hpp"
+#include "solve_launch.hpp"
 
 #include <algorithm>
 #include <climits>
 
 namespace eacham {
 namespace {
-
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_front_kernel(const long long* __restrict__ point_ptr, const long long* __restrict__ sample_ptr,
-                                                                   int n_problems, const double* __restrict__ obj, const double* __restrict__ img,
-                                                                   const double* __restrict__ K, int sample_size, int n_samples,
-                                                                   const int* __restrict__ idx, double* __restrict__ frame,
-                                                                   int* __restrict__ sample_problem) {
-    __shared__ PnpLds lds[SOLVE_WAVES];
-    extern __shared__ double rows_dyn[];   // SOLVE_WAVES x sample_size x 24: the two rows of every point of a wave's sample
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int s = blockIdx.x * SOLVE_WAVES + wave;
-    if (s >= n_samples) return;
-    const int p = prim::segment_of(sample_ptr, n_problems, s);
-    const long long base = point_ptr[p];
-    if (lane == 0) sample_problem[s] = p;
-    double* rows = rows_dyn + (size_t)wave * 24 * sample_size;
-    const double K4[4] = {K[0], K[1], K[2], K[3]};
-    PnpFrame F;
-    PnpLds& S = lds[wave];
-    int ok = 0;
-    if (point_ptr[p + 1] - base >= sample_size)   // (wave-uniform) a problem without a sample's worth of points has no models
-        ok = epnp_front<false>(sample_size, idx + (size_t)s * sample_size, obj + 3 * base, img + 2 * base, K4, F, S, rows, nullptr);
-    const size_t ns = (size_t)n_samples;
-    double* dst = frame + s;
-    if (lane == 0) {
-        dst[PNP_F_VALID * ns] = ok ? 1.0 : 0.0;
-        if (ok) {
-#pragma unroll
-            for (int e = 0; e < 3; ++e) dst[e * ns] = F.c0[e], dst[(12 + e) * ns] = F.sc[e];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int e = 0; e < 3; ++e) dst[(3 + 3 * k + e) * ns] = F.ax[k][e];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) dst[(15 + q) * ns] = F.rho[q];
-        }
-    }
-    if (ok) {
-        if (lane < 48) dst[(PNP_F_EV + lane) * ns] = S.ev[lane];
-        if (lane < 60) dst[(PNP_F_L + lane) * ns] = S.L[lane];
-    }
-}
-
-template <int variant>
-__device__ __forceinline__ void pb_back_body(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
-                                             const double* __restrict__ img, const double* __restrict__ K, int sample_size, int n_samples,
-                                             const int* __restrict__ idx, const int* __restrict__ sample_problem,
-                                             const double* __restrict__ frame, double* __restrict__ tmp) {
-    const int s = blockIdx.x * 64 + threadIdx.x;
-    if (s >= n_samples) return;
-    const size_t ns = (size_t)n_samples;
-    const double* src = frame + s;
-    const double K4[4] = {K[0], K[1], K[2], K[3]};
-    double cand[12];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) cand[k] = 0.0;
-    double err = -1.0;
-    if (src[PNP_F_VALID * ns] != 0.0) {
-        PnpFrame F;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) F.c0[e] = src[e * ns], F.sc[e] = src[(12 + e) * ns];
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int e = 0; e < 3; ++e) F.ax[k][e] = src[(3 + 3 * k + e) * ns];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) F.rho[q] = src[(15 + q) * ns];
-        F.planar = F.sc[2] == 0.0;
-        const long long base = point_ptr[sample_problem[s]];
-        err = epnp_back_variant<true, variant>(sample_size, idx + (size_t)s * sample_size, obj + 3 * base, img + 2 * base, K4, F,
-                                               src + PNP_F_EV * ns, src + PNP_F_L * ns, ns, nullptr, cand);
-    }
-    double* dst = tmp + ((size_t)variant * ns + s) * 13;
-    dst[0] = err;
-#pragma unroll
-    for (int k = 0; k < 12; ++k) dst[1 + k] = cand[k];
-}
-__global__ __launch_bounds__(64) void pb_back_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
-                                                     const double* __restrict__ img, const double* __restrict__ K, int sample_size,
-                                                     int n_samples, const int* __restrict__ idx, const int* __restrict__ sample_problem,
-                                                     const double* __restrict__ frame, double* __restrict__ tmp) {
-    if (blockIdx.y == 0) pb_back_body<0>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);   // (workgroup-uniform)
-    else if (blockIdx.y == 1) pb_back_body<1>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);
-    else pb_back_body<2>(point_ptr, obj, img, K, sample_size, n_samples, idx, sample_problem, frame, tmp);
-}
 
 // A wave per sample: the choice among the three starts, then the count. models may be null (not wanted).
 __global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_count_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ obj,
@@ -122,12 +38,8 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_count_kernel(const long l
     const int lane = threadIdx.x & 63;
     const int s = blockIdx.x * SOLVE_WAVES + (threadIdx.x >> 6);
     if (s >= n_samples) return;
-    double best = -1.0;
-    int which = -1;
-    for (int v = 0; v < 3; ++v) {
-        const double err = tmp[((size_t)v * n_samples + s) * 13];
-        if (err >= 0.0 && (best < 0.0 || err < best)) best = err, which = v;
-    }
+    const size_t ns = (size_t)n_samples;
+    const int which = pnp_first_smallest(tmp[(size_t)s * 13], tmp[(ns + s) * 13], tmp[(2 * ns + s) * 13]);
     double M[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) M[k] = which >= 0 ? tmp[((size_t)which * n_samples + s) * 13 + 1 + k] : 0.0;
@@ -159,11 +71,7 @@ __global__ __launch_bounds__(PB_REFIT_BLOCK) void pb_refit_kernel(const long lon
                                                                  const double* __restrict__ models, const unsigned char* __restrict__ has_model,
                                                                  float threshold, unsigned char* __restrict__ mask, int* __restrict__ n_inliers,
                                                                  int* rows_all, double* __restrict__ refit, int* __restrict__ refit_ok) {
-    __shared__ PnpLds lds;
-    __shared__ double part[78 * 64];
-    __shared__ PnpFrame frame;
-    __shared__ int front_ok;
-    __shared__ double red[3][64], result[3][13];
+    __shared__ PnpRefitLds W;
     __shared__ int wcnt[PB_REFIT_BLOCK / 64];
     const int p = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long base = point_ptr[p];
@@ -198,39 +106,10 @@ __global__ __launch_bounds__(PB_REFIT_BLOCK) void pb_refit_kernel(const long lon
         __syncthreads();   // wcnt is read before the next trip writes it; after the last trip: rows[] is complete and visible
     }
     if (threadIdx.x == 0) n_inliers[p] = m;
-    if (threadIdx.x == 0) front_ok = 0;
-    __syncthreads();
-    if (m >= 5) {   // (workgroup-uniform) the body of solve_pnp_big_kernel on the row of inliers
-        if (wave == 0) {
-            PnpFrame F;
-            const int ok = epnp_front<true>(m, rows, obj, img, K4, F, lds, nullptr, part);
-            if (lane == 0) frame = F, front_ok = ok;
-        }
-        __syncthreads();
-        if (front_ok && wave < 3) {
-            const PnpFrame F = frame;
-            double cand[12];
-#pragma unroll
-            for (int k = 0; k < 12; ++k) cand[k] = 0.0;
-            double err;
-            if (wave == 0) err = epnp_back_variant<false, 0>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[0], cand);
-            else if (wave == 1) err = epnp_back_variant<false, 1>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[1], cand);
-            else err = epnp_back_variant<false, 2>(m, rows, obj, img, K4, F, lds.ev, lds.L, 1, red[2], cand);
-            if (lane == 0) {
-                result[wave][0] = err;
-#pragma unroll
-                for (int k = 0; k < 12; ++k) result[wave][1 + k] = cand[k];
-            }
-        }
-        __syncthreads();
-    }
+    int which = -1;
+    if (m >= 5) which = pnp_refit_body(m, rows, obj, img, K4, W);   // (workgroup-uniform) EPnP on the row of inliers
     if (threadIdx.x == 0) {
-        double best = -1.0;
-        int which = -1;
-        if (front_ok)
-            for (int v = 0; v < 3; ++v)
-                if (result[v][0] >= 0.0 && (best < 0.0 || result[v][0] < best)) best = result[v][0], which = v;
-        for (int k = 0; k < 12; ++k) refit[12 * (size_t)p + k] = which >= 0 ? result[which][1 + k] : 0.0;
+        for (int k = 0; k < 12; ++k) refit[12 * (size_t)p + k] = which >= 0 ? W.result[which][1 + k] : 0.0;
         refit_ok[p] = which >= 0 ? 1 : 0;
     }
 }
@@ -269,9 +148,7 @@ extern "C" int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, cons
     for (int p = 0; p < P; ++p) {
         const long long n = point_ptr[p + 1] - point_ptr[p];
         if (n < m) continue;   // its samples are not looked at: each gets n_models = 0
-        for (long long k = sample_ptr[p] * m; k < sample_ptr[p + 1] * m; ++k)
-            if (sample_idx[k] < 0 || sample_idx[k] >= n)
-                return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: sample index %d of %lld points", call, p, (int)sample_idx[k], n);
+        if (int rc = check_sample_idx(ctx, call, p, sample_idx + sample_ptr[p] * m, (sample_ptr[p + 1] - sample_ptr[p]) * m, n)) return rc;
     }
     if (S == 0) return EACHAM_OK;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -291,9 +168,7 @@ extern "C" int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, cons
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
         const unsigned gw = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
-        pb_front_kernel<<<gw, 64 * SOLVE_WAVES, sizeof(double) * SOLVE_WAVES * 24 * (size_t)m, st>>>(
-            d(h_pp), d(h_sp), P, d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_f), d(h_sprob));
-        pb_back_kernel<<<dim3((unsigned)((S + 63) / 64), 3), 64, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_sprob), d(h_f), d(h_t));
+        solve_pnp_launch(st, PnpLaunch{SolveSeg{d(h_pp), d(h_sp), P, d(h_sprob)}, d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_f), d(h_t)});
         pb_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), (int)S, d(h_sprob), d(h_t), threshold,
                                                          models ? d(h_m) : nullptr, d(h_n), d(h_c));
     }

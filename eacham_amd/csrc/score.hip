@@ -57,29 +57,15 @@ __global__ __launch_bounds__(SC_BLOCK) void score_kernel(int n, const double* __
         if (erow) erow[i] = e;
         if (keys_in_lds) keys[i] = fkey(e);
     }
-    // inlier count: shuffle tree per wave, then the waves in order (integers: exact in any order)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
-    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0 && counts) {
-        int tot = 0;
-        for (int w = 0; w < SC_BLOCK / 64; ++w) tot += wsum[w];
-        counts[m] = tot;
-    }
+    const int tot = block_count(c, wsum);
+    if (threadIdx.x == 0 && counts) counts[m] = tot;
     if (!medians) return;
     if (n == 0) {
         if (threadIdx.x == 0) medians[m] = __uint_as_float(0x7fc00000u);
         return;
     }
     __syncthreads();  // keys / the error row are complete (the row was written by this workgroup: visible after the barrier)
-    auto load = [&](int i) { return keys_in_lds ? keys[i] : fkey(erow[i]); };
-    const unsigned hi = radix_select(load, n, n / 2, hist, sh);
-    float med = fkey_inv(hi);
-    if (n % 2 == 0) {
-        const unsigned lo = radix_select(load, n, n / 2 - 1, hist, sh);
-        med = fmul(fadd(fkey_inv(lo), med), 0.5f);
-    }
+    const float med = block_median([&](int i) { return keys_in_lds ? keys[i] : fkey(erow[i]); }, n, hist, sh);
     if (threadIdx.x == 0) medians[m] = med;
 }
 

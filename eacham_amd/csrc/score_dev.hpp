@@ -1,6 +1,6 @@
 // score_dev.hpp — the device functions of the hypothesis scoring that more than one translation unit runs: the error one
 // model assigns to one correspondence (OpenCV 4.5.5's estimator callbacks, no fused operations), the order-preserving key of
-// a float and the block-wide radix select of the median. score.hip (eacham_score_hypotheses) and lmeds_batch.hip
+// a float, the block-wide radix select, the median over it (block_median) and the block's inlier count (block_count). score.hip (eacham_score_hypotheses) and lmeds_batch.hip
 // (eacham_lmeds_batch) inline the same bodies, so a model's errors and median are the same bits through either entry point.
 // Every includer is compiled with -ffp-contract=off (csrc/Makefile).
 #pragma once
@@ -91,6 +91,31 @@ __device__ unsigned radix_select(Load load, int n, int k, unsigned* hist /* [256
         __syncthreads();
     }
     return prefix;
+}
+
+// The median of the n > 0 keys as the float it stands for: the upper middle, averaged with the lower one when n is even.
+template <class Load>
+__device__ __forceinline__ float block_median(Load load, int n, unsigned* hist /* [256] LDS */, unsigned* sh /* [2] LDS */) {
+    const unsigned hi = radix_select(load, n, n / 2, hist, sh);
+    float med = fkey_inv(hi);
+    if (n % 2 == 0) {
+        const unsigned lo = radix_select(load, n, n / 2 - 1, hist, sh);
+        med = fmul(fadd(fkey_inv(lo), med), 0.5f);
+    }
+    return med;
+}
+
+// The sum of one count per thread, returned to thread 0 (integers: exact in any order): a shuffle tree per wave, then the waves in
+// order. Ends past a workgroup barrier.
+__device__ __forceinline__ int block_count(int c, int* wsum /* [SC_BLOCK / 64] LDS */) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = c;
+    __syncthreads();
+    int tot = 0;
+    if (threadIdx.x == 0)
+        for (int w = 0; w < SC_BLOCK / 64; ++w) tot += wsum[w];
+    return tot;
 }
 
 }  // namespace

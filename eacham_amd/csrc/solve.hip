@@ -20,13 +20,28 @@
 // A sample is ~10^4-10^5 flops of branchy fp64 with kilobytes of private state: latency-bound, no roofline claim; the
 // 1000 / 100 iterations the reference asks for are one launch.
 #include "context.hpp"
+#include "devprim.hpp"
 #include "solve_dev.hpp"
+#include "solve_launch.hpp"
 
-#include <algorithm>
 #include <cstdint>
 
 namespace eacham {
 namespace {
+
+// Every stage below is ONE kernel template with two instantiations: LIST = false, the one-problem calls of this file, and LIST = true,
+// the list calls (lmeds_batch.hip, pnp_batch.hip through solve_launch.hpp). What the list form adds is sample_segment() and nothing
+// else, so a sample gives the same bits through either and a change of a solver is made once.
+
+// LIST: the problem of sample s by a binary search in sample_ptr, left in sample_problem[s]; base = where its points begin. False: the
+// problem has fewer than m points, and its samples are not solved. (The one-problem calls have no such rule: they check the indices
+// against n_points on the host and solve whatever valid sample they are given, repeated indices on a 2-point problem included.)
+__device__ __forceinline__ bool sample_segment(const SolveSeg& g, int s, int m, long long& base) {
+    const int p = prim::segment_of(g.sample_ptr, g.n_problems, s);
+    base = g.point_ptr[p];
+    if ((threadIdx.x & 63) == 0) g.sample_problem[s] = p;
+    return g.point_ptr[p + 1] - base >= m;   // (wave-uniform)
+}
 
 // Samples of at most 64 points (the RANSAC loop's five-point samples) in two launches. Front: ONE WAVE per sample, SOLVE_WAVES samples
 // per workgroup (no workgroup barrier anywhere: waves return on their own), leaving the sample's frame — 130 doubles: c0 3, axes 9,
@@ -34,187 +49,152 @@ namespace {
 // frame[e * n_samples + s]: the back half's lanes read neighbouring words). Back: ONE LANE per sample. The back half is scalar work
 // with ~380 live registers: run by a whole wave per sample it held the kernel at one wave per SIMD and 64 lanes repeated every
 // operation (2.0 ms for 10 000 samples); by lanes, 10 000 samples are 157 waves. (The EPnP device code itself — epnp_front,
-// epnp_back_variant, the frame's layout — is in solve_dev.hpp: pnp_batch.hip runs the same bodies.)
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_pnp_front_kernel(const double* __restrict__ obj, const double* __restrict__ img,
+// epnp_back_variant, the frame's named offsets and its one pack — is in solve_dev.hpp; its one unpack is solve_pnp_back_body's.)
+template <bool LIST>
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_pnp_front_kernel(SolveSeg seg, const double* __restrict__ obj, const double* __restrict__ img,
                                                                           const double* __restrict__ K, int sample_size, int n_samples,
                                                                           const int* __restrict__ idx, double* __restrict__ frame) {
     __shared__ PnpLds lds[SOLVE_WAVES];
-    extern __shared__ double rows_dyn[];   // SOLVE_WAVES x min(sample_size, 64) x 24: the two rows of every point of a wave's sample
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    extern __shared__ double rows_dyn[];   // SOLVE_WAVES x sample_size x 24: the two rows of every point of a wave's sample
+    const int wave = threadIdx.x >> 6;
     const int s = blockIdx.x * SOLVE_WAVES + wave;
     if (s >= n_samples) return;
-    double* rows = rows_dyn + (size_t)wave * 24 * (sample_size < 64 ? sample_size : 64);
+    bool solve = true;
+    if constexpr (LIST) {
+        long long base;
+        solve = sample_segment(seg, s, sample_size, base);
+        obj += 3 * base, img += 2 * base;
+    }
+    double* rows = rows_dyn + (size_t)wave * 24 * sample_size;
     const double K4[4] = {K[0], K[1], K[2], K[3]};
     PnpFrame F;
     PnpLds& S = lds[wave];
-    const int ok = epnp_front<false>(sample_size, idx + (size_t)s * sample_size, obj, img, K4, F, S, rows, nullptr);
-    const size_t ns = (size_t)n_samples;
-    double* dst = frame + s;
-    if (lane == 0) {
-        dst[PNP_F_VALID * ns] = ok ? 1.0 : 0.0;
-        if (ok) {
-#pragma unroll
-            for (int e = 0; e < 3; ++e) dst[e * ns] = F.c0[e], dst[(12 + e) * ns] = F.sc[e];
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int e = 0; e < 3; ++e) dst[(3 + 3 * k + e) * ns] = F.ax[k][e];
-#pragma unroll
-            for (int q = 0; q < 6; ++q) dst[(15 + q) * ns] = F.rho[q];
-        }
-    }
-    if (ok) {
-        if (lane < 48) dst[(PNP_F_EV + lane) * ns] = S.ev[lane];
-        if (lane < 60) dst[(PNP_F_L + lane) * ns] = S.L[lane];
-    }
+    int ok = 0;
+    if (solve) ok = epnp_front<false>(sample_size, idx + (size_t)s * sample_size, obj, img, K4, F, S, rows, nullptr);
+    pnp_frame_pack(frame + s, (size_t)n_samples, ok, F, S);
 }
 
 // A lane per (sample, linearised start): blockIdx.y is the start (0..2), ONE launch — as one lane per sample with the three starts in
 // a row the kernel needed ~380 registers, spilled 122 of them (324 B of scratch per lane) and ran one wave per SIMD; as three launches
 // (one instantiation each) the starts waited for one another on the stream: 36 + 32 + 32 us per RANSAC chunk of the incremental loop,
-// where a chunk is four waves per start. The starts' errors and poses go to `tmp` ([start][sample][13]); solve_pnp_select_kernel
-// takes the first strictly smallest, as the CPU restatement's loop over the starts does.
-template <int variant>
+// where a chunk is four waves per start. The starts' errors and poses go to `tmp` ([start][sample][13]); pnp_first_smallest
+// (solve_pnp_select_kernel here, pb_count_kernel of pnp_batch.hip) takes the first strictly smallest, as the CPU restatement's loop
+// over the starts does.
+template <bool LIST, int variant>
 __device__ __forceinline__ void solve_pnp_back_body(const double* __restrict__ obj, const double* __restrict__ img,
                                                     const double* __restrict__ K, int sample_size, int n_samples,
                                                     const int* __restrict__ idx, const double* __restrict__ frame,
-                                                    double* __restrict__ tmp) {
+                                                    double* __restrict__ tmp, const SolveSeg& seg) {
     const int s = blockIdx.x * 64 + threadIdx.x;
     if (s >= n_samples) return;
     const size_t ns = (size_t)n_samples;
-    const double* src = frame + s;
     const double K4[4] = {K[0], K[1], K[2], K[3]};
     double cand[12];
 #pragma unroll
     for (int k = 0; k < 12; ++k) cand[k] = 0.0;
     double err = -1.0;
-    if (src[PNP_F_VALID * ns] != 0.0) {
+    const double* src = frame + s;
+    if (src[PNP_F_VALID * ns] != 0.0) {   // the frame's one unpack (its one pack: pnp_frame_pack, solve_dev.hpp)
         PnpFrame F;
 #pragma unroll
-        for (int e = 0; e < 3; ++e) F.c0[e] = src[e * ns], F.sc[e] = src[(12 + e) * ns];
+        for (int e = 0; e < 3; ++e) F.c0[e] = src[(PNP_F_C0 + e) * ns], F.sc[e] = src[(PNP_F_SC + e) * ns];
 #pragma unroll
         for (int k = 0; k < 3; ++k)
 #pragma unroll
-            for (int e = 0; e < 3; ++e) F.ax[k][e] = src[(3 + 3 * k + e) * ns];
+            for (int e = 0; e < 3; ++e) F.ax[k][e] = src[(PNP_F_AX + 3 * k + e) * ns];
 #pragma unroll
-        for (int q = 0; q < 6; ++q) F.rho[q] = src[(15 + q) * ns];
+        for (int q = 0; q < 6; ++q) F.rho[q] = src[(PNP_F_RHO + q) * ns];
         F.planar = F.sc[2] == 0.0;
-        const int* rows_idx = idx + (size_t)s * sample_size;
-        err = epnp_back_variant<true, variant>(sample_size, rows_idx, obj, img, K4, F, src + PNP_F_EV * ns, src + PNP_F_L * ns, ns, nullptr, cand);
+        if constexpr (LIST) {
+            const long long base = seg.point_ptr[seg.sample_problem[s]];
+            obj += 3 * base, img += 2 * base;
+        }
+        err = epnp_back_variant<true, variant>(sample_size, idx + (size_t)s * sample_size, obj, img, K4, F, src + PNP_F_EV * ns, src + PNP_F_L * ns, ns, nullptr, cand);
     }
     double* dst = tmp + ((size_t)variant * ns + s) * 13;
     dst[0] = err;
 #pragma unroll
     for (int k = 0; k < 12; ++k) dst[1 + k] = cand[k];
 }
+template <bool LIST>
 __global__ __launch_bounds__(64) void solve_pnp_back_kernel(const double* __restrict__ obj, const double* __restrict__ img,
                                                             const double* __restrict__ K, int sample_size, int n_samples,
                                                             const int* __restrict__ idx, const double* __restrict__ frame,
-                                                            double* __restrict__ tmp) {
-    if (blockIdx.y == 0) solve_pnp_back_body<0>(obj, img, K, sample_size, n_samples, idx, frame, tmp);        // (workgroup-uniform)
-    else if (blockIdx.y == 1) solve_pnp_back_body<1>(obj, img, K, sample_size, n_samples, idx, frame, tmp);
-    else solve_pnp_back_body<2>(obj, img, K, sample_size, n_samples, idx, frame, tmp);
+                                                            double* __restrict__ tmp, SolveSeg seg) {
+    if (blockIdx.y == 0) solve_pnp_back_body<LIST, 0>(obj, img, K, sample_size, n_samples, idx, frame, tmp, seg);        // (workgroup-uniform)
+    else if (blockIdx.y == 1) solve_pnp_back_body<LIST, 1>(obj, img, K, sample_size, n_samples, idx, frame, tmp, seg);
+    else solve_pnp_back_body<LIST, 2>(obj, img, K, sample_size, n_samples, idx, frame, tmp, seg);
 }
 __global__ __launch_bounds__(256) void solve_pnp_select_kernel(int n_samples, const double* __restrict__ tmp, double* __restrict__ models, int* __restrict__ n_models) {
     const int s = blockIdx.x * 256 + threadIdx.x;
     if (s >= n_samples) return;
-    double best = -1.0;
-    int which = -1;
-    for (int v = 0; v < 3; ++v) {
-        const double err = tmp[((size_t)v * n_samples + s) * 13];
-        if (err >= 0.0 && (best < 0.0 || err < best)) best = err, which = v;
-    }
-    for (int k = 0; k < 12; ++k) models[12 * (size_t)s + k] = which >= 0 ? tmp[((size_t)which * n_samples + s) * 13 + 1 + k] : 0.0;
+    const size_t ns = (size_t)n_samples;
+    const int which = pnp_first_smallest(tmp[(size_t)s * 13], tmp[(ns + s) * 13], tmp[(2 * ns + s) * 13]);
+    for (int k = 0; k < 12; ++k) models[12 * (size_t)s + k] = which >= 0 ? tmp[((size_t)which * ns + s) * 13 + 1 + k] : 0.0;
     n_models[s] = which >= 0 ? 1 : 0;
 }
 
-// samples of more than 64 points (the all-inlier refit): one workgroup of three waves per sample. Wave 0 runs the front half (a
-// partial M^T M per lane) and leaves the frame, the null vectors and the distance system in LDS; then every wave takes ONE
-// linearised start of the back half (its sums over the points spread over the wave's lanes, each wave with its own reduction
-// scratch) and thread 0 picks the first strictly smallest error — the order of epnp_back. One wave running the three starts in a row
-// was 234 us per refit of the incremental loop.
+// samples of more than 64 points (the all-inlier refit): one workgroup of three waves per sample runs pnp_refit_body (solve_dev.hpp),
+// as pb_refit_kernel of pnp_batch.hip does on its row of inliers.
 __global__ __launch_bounds__(192) void solve_pnp_big_kernel(const double* __restrict__ obj, const double* __restrict__ img,
                                                             const double* __restrict__ K, int sample_size, const int* __restrict__ idx,
                                                             double* __restrict__ models, int* __restrict__ n_models) {
-    __shared__ PnpLds lds;
-    __shared__ double part[78 * 64];
-    __shared__ PnpFrame frame;
-    __shared__ int front_ok;
-    __shared__ double red[3][64], result[3][13];
-    const int s = blockIdx.x, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    __shared__ PnpRefitLds W;
+    const int s = blockIdx.x;
     const double K4[4] = {K[0], K[1], K[2], K[3]};
-    const int* rows_idx = idx + (size_t)s * sample_size;
-    if (wave == 0) {
-        PnpFrame F;
-        const int n = epnp_front<true>(sample_size, rows_idx, obj, img, K4, F, lds, nullptr, part);
-        if (lane == 0) frame = F, front_ok = n;
-    }
-    __syncthreads();
-    if (front_ok) {   // (workgroup-uniform)
-        const PnpFrame F = frame;
-        double cand[12];
-#pragma unroll
-        for (int k = 0; k < 12; ++k) cand[k] = 0.0;
-        double err;
-        if (wave == 0) err = epnp_back_variant<false, 0>(sample_size, rows_idx, obj, img, K4, F, lds.ev, lds.L, 1, red[0], cand);
-        else if (wave == 1) err = epnp_back_variant<false, 1>(sample_size, rows_idx, obj, img, K4, F, lds.ev, lds.L, 1, red[1], cand);
-        else err = epnp_back_variant<false, 2>(sample_size, rows_idx, obj, img, K4, F, lds.ev, lds.L, 1, red[2], cand);
-        if (lane == 0) {
-            result[wave][0] = err;
-#pragma unroll
-            for (int k = 0; k < 12; ++k) result[wave][1 + k] = cand[k];
-        }
-    }
-    __syncthreads();
+    const int which = pnp_refit_body(sample_size, idx + (size_t)s * sample_size, obj, img, K4, W);
     if (threadIdx.x == 0) {
-        double best = -1.0;
-        int which = -1;
-        if (front_ok)
-            for (int v = 0; v < 3; ++v)
-                if (result[v][0] >= 0.0 && (best < 0.0 || result[v][0] < best)) best = result[v][0], which = v;
-        for (int k = 0; k < 12; ++k) models[12 * (size_t)s + k] = which >= 0 ? result[which][1 + k] : 0.0;
+        for (int k = 0; k < 12; ++k) models[12 * (size_t)s + k] = which >= 0 ? W.result[which][1 + k] : 0.0;
         n_models[s] = which >= 0 ? 1 : 0;
     }
 }
 
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_h4_kernel(const double* __restrict__ a, const double* __restrict__ b, int n_samples,
+template <bool LIST>
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_h4_kernel(SolveSeg seg, const double* __restrict__ a, const double* __restrict__ b, int n_samples,
                                                                    const int* __restrict__ idx, double* __restrict__ models, int* __restrict__ n_models) {
     __shared__ double LtL[SOLVE_WAVES][81], V[SOLVE_WAVES][81];
     __shared__ JacRound R[SOLVE_WAVES];
-    const int wave = threadIdx.x >> 6;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = blockIdx.x * SOLVE_WAVES + wave;
     if (s >= n_samples) return;
-    double pa[8], pb[8], out[9];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int i = idx[s * 4 + k];
-        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
-        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
+    if constexpr (LIST) {
+        long long base;
+        if (!sample_segment(seg, s, 4, base)) {   // no candidates
+            if (lane == 0) n_models[s] = 0;
+            return;
+        }
+        a += 2 * base, b += 2 * base;
     }
+    double pa[8], pb[8], out[9];
+    gather_sample<4>(idx + (size_t)s * 4, a, b, pa, pb);
 #pragma unroll
     for (int k = 0; k < 9; ++k) out[k] = 0.0;
     const int n = homography4_wave(pa, pb, out, LtL[wave], V[wave], R[wave]);
-    if ((threadIdx.x & 63) == 0) {
+    if (lane == 0) {
 #pragma unroll
         for (int k = 0; k < 9; ++k) models[9 * (size_t)s + k] = out[k];
         n_models[s] = n;
     }
 }
 
-__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_e5_kernel(const double* __restrict__ a, const double* __restrict__ b, const double* __restrict__ K,
-                                                                   int has_K, int n_samples, const int* __restrict__ idx, double* __restrict__ models,
-                                                                   int* __restrict__ n_models) {
+template <bool LIST>
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_e5_kernel(SolveSeg seg, const double* __restrict__ a, const double* __restrict__ b,
+                                                                   const double* __restrict__ K, int has_K, int n_samples, const int* __restrict__ idx,
+                                                                   double* __restrict__ models, int* __restrict__ n_models) {
     __shared__ E5Lds lds[SOLVE_WAVES];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int s = blockIdx.x * SOLVE_WAVES + wave;
     if (s >= n_samples) return;
-    double pa[10], pb[10];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-        const int i = idx[s * 5 + k];
-        pa[2 * k] = a[2 * (size_t)i]; pa[2 * k + 1] = a[2 * (size_t)i + 1];
-        pb[2 * k] = b[2 * (size_t)i]; pb[2 * k + 1] = b[2 * (size_t)i + 1];
+    if constexpr (LIST) {
+        long long base;
+        if (!sample_segment(seg, s, 5, base)) {   // no candidates
+            if (lane == 0) n_models[s] = 0;
+            return;
+        }
+        a += 2 * base, b += 2 * base;
     }
+    double pa[10], pb[10];
+    gather_sample<5>(idx + (size_t)s * 5, a, b, pa, pb);
     double fx = 1, fy = 1, cx = 0, cy = 0;
     if (has_K) fx = K[0], fy = K[1], cx = K[2], cy = K[3];
     double* dst = models + (size_t)s * 90;
@@ -225,6 +205,26 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_e5_kernel(const double
 }
 
 }  // namespace
+
+void solve_minimal_launch(hipStream_t st, const MinimalLaunch& L) {
+    const unsigned grid = (unsigned)((L.n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES);
+    const bool list = L.seg.point_ptr != nullptr;
+    if (L.kind == EACHAM_SOLVE_HOMOGRAPHY4)
+        (list ? solve_h4_kernel<true> : solve_h4_kernel<false>)<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.seg, L.a, L.b, L.n_samples, L.sample_idx, L.models, L.n_models);
+    else
+        (list ? solve_e5_kernel<true> : solve_e5_kernel<false>)<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.seg, L.a, L.b, L.K, L.has_K ? 1 : 0, L.n_samples, L.sample_idx,
+                                                                                                 L.models, L.n_models);
+}
+
+void solve_pnp_launch(hipStream_t st, const PnpLaunch& L) {
+    const bool list = L.seg.point_ptr != nullptr;
+    const unsigned gw = (unsigned)((L.n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES), gb = (unsigned)((L.n_samples + 63) / 64);
+    (list ? solve_pnp_front_kernel<true> : solve_pnp_front_kernel<false>)<<<gw, 64 * SOLVE_WAVES, sizeof(double) * SOLVE_WAVES * 24 * (size_t)L.sample_size, st>>>(
+        L.seg, L.obj, L.img, L.K, L.sample_size, L.n_samples, L.sample_idx, L.frame);
+    (list ? solve_pnp_back_kernel<true> : solve_pnp_back_kernel<false>)<<<dim3(gb, 3), 64, 0, st>>>(L.obj, L.img, L.K, L.sample_size, L.n_samples, L.sample_idx, L.frame,
+                                                                                                  L.tmp, L.seg);
+}
+
 }  // namespace eacham
 
 using namespace eacham;
@@ -238,9 +238,7 @@ extern "C" int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, con
         return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: null argument or negative size");
     if (n_samples == 0) return EACHAM_OK;
     const int m = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 4 : 5, maxm = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
-    for (long long k = 0; k < (long long)n_samples * m; ++k)
-        if (sample_idx[k] < 0 || sample_idx[k] >= n_points)
-            return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: sample index %d of %d points", (int)sample_idx[k], n_points);
+    if (int rc = check_sample_idx(ctx, "solve_minimal", -1, sample_idx, (long long)n_samples * m, n_points)) return rc;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
@@ -253,11 +251,7 @@ extern "C" int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, con
     if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
-        const unsigned grid = (unsigned)((n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES);
-        if (kind == EACHAM_SOLVE_HOMOGRAPHY4)
-            solve_h4_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d(h_a), d(h_b), n_samples, d(h_i), d(h_m), d(h_n));
-        else
-            solve_e5_kernel<<<grid, 64 * SOLVE_WAVES, 0, st>>>(d(h_a), d(h_b), d(h_K), K ? 1 : 0, n_samples, d(h_i), d(h_m), d(h_n));
+        solve_minimal_launch(st, MinimalLaunch{kind, SolveSeg{}, d(h_a), d(h_b), d(h_K), K != nullptr, n_samples, d(h_i), d(h_m), d(h_n)});
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     return io.finish();
@@ -272,9 +266,7 @@ extern "C" int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* obj
     if (n_samples == 0) return EACHAM_OK;
     if (sample_size < 5) return ctx->fail(EACHAM_ERR_INVALID, "solve_pnp: EPnP needs at least 5 points per sample, got %d", sample_size);
     const long long total = (long long)n_samples * sample_size;
-    for (long long k = 0; k < total; ++k)
-        if (sample_idx[k] < 0 || sample_idx[k] >= n_points)
-            return ctx->fail(EACHAM_ERR_INVALID, "solve_pnp: sample index %d of %d points", (int)sample_idx[k], n_points);
+    if (int rc = check_sample_idx(ctx, "solve_pnp", -1, sample_idx, total, n_points)) return rc;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
@@ -292,11 +284,7 @@ extern "C" int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* obj
         // Bit-identical with the CPU restatement either way: samples of at most 64 points — the RANSAC loop's — a wave per sample for the
         // shared front half, a lane per sample for the scalar back half; larger ones — the all-inlier refit — one wave for both.
         if (sample_size <= 64) {
-            solve_pnp_front_kernel<<<(unsigned)((n_samples + SOLVE_WAVES - 1) / SOLVE_WAVES), 64 * SOLVE_WAVES,
-                                     sizeof(double) * SOLVE_WAVES * 24 * (size_t)std::min(sample_size, 64), st>>>(
-                d(h_a), d(h_b), d(h_K), sample_size, n_samples, d(h_i), d(h_f));
-            const unsigned gb = (unsigned)((n_samples + 63) / 64);
-            solve_pnp_back_kernel<<<dim3(gb, 3), 64, 0, st>>>(d(h_a), d(h_b), d(h_K), sample_size, n_samples, d(h_i), d(h_f), d(h_t));
+            solve_pnp_launch(st, PnpLaunch{SolveSeg{}, d(h_a), d(h_b), d(h_K), sample_size, n_samples, d(h_i), d(h_f), d(h_t)});
             solve_pnp_select_kernel<<<(unsigned)((n_samples + 255) / 256), 256, 0, st>>>(n_samples, d(h_t), d(h_m), d(h_n));
         }
         else

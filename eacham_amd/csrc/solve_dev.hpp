@@ -1,8 +1,8 @@
 // solve_dev.hpp — the device functions of the minimal solvers that more than one translation unit runs: the homography
 // (4 points) and five-point (essential matrix) solvers by one wave per sample, EPnP's two halves, and the small dense algebra
-// under them. solve.hip (eacham_solve_minimal, eacham_solve_pnp), lmeds_batch.hip (eacham_lmeds_batch) and pnp_batch.hip
-// (eacham_pnp_hypotheses_batch, eacham_pnp_refit_batch) inline the same bodies, so a sample gives the same bits through
-// either entry point. Every includer is compiled with -ffp-contract=off (csrc/Makefile).
+// under them. solve.hip holds the solver kernels of every entry point (one template per stage, a one-problem and a list
+// instantiation: solve_launch.hpp); pnp_batch.hip includes this file for the refit body (pnp_refit_body) and the rule among
+// EPnP's three starts (pnp_first_smallest). Every includer is compiled with -ffp-contract=off (csrc/Makefile).
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -1154,7 +1154,93 @@ __device__ static double epnp_back_variant(int m, const int* idx, const double* 
 // The frame one sample leaves between the front and the back half of the at-most-64-point form — 130 doubles: c0 3, axes 9,
 // lengths 3, rho 6, null vectors 48, distance system 60, valid 1 — field-major in the batch (element e of sample s at
 // frame[e * n_samples + s]).
-constexpr int PNP_FRAME = 130, PNP_F_EV = 21, PNP_F_L = 69, PNP_F_VALID = 129;
+constexpr int PNP_FRAME = 130, PNP_F_C0 = 0, PNP_F_AX = 3, PNP_F_SC = 12, PNP_F_RHO = 15, PNP_F_EV = 21, PNP_F_L = 69, PNP_F_VALID = 129;
+
+// The front half's wave leaves its sample's frame at dst = frame + s (ns = n_samples: the stride of one element).
+__device__ __forceinline__ void pnp_frame_pack(double* dst, size_t ns, int ok, const PnpFrame& F, const PnpLds& S) {
+    const int lane = threadIdx.x & 63;
+    if (lane == 0) {
+        dst[PNP_F_VALID * ns] = ok ? 1.0 : 0.0;
+        if (ok) {
+#pragma unroll
+            for (int e = 0; e < 3; ++e) dst[(PNP_F_C0 + e) * ns] = F.c0[e], dst[(PNP_F_SC + e) * ns] = F.sc[e];
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+#pragma unroll
+                for (int e = 0; e < 3; ++e) dst[(PNP_F_AX + 3 * k + e) * ns] = F.ax[k][e];
+#pragma unroll
+            for (int q = 0; q < 6; ++q) dst[(PNP_F_RHO + q) * ns] = F.rho[q];
+        }
+    }
+    if (ok) {
+        if (lane < 48) dst[(PNP_F_EV + lane) * ns] = S.ev[lane];
+        if (lane < 60) dst[(PNP_F_L + lane) * ns] = S.L[lane];
+    }
+}
+// Which of EPnP's three linearised starts is the pose: the first strictly smallest non-negative error (the order of the CPU
+// restatement's loop over the starts), -1 = none gave a pose.
+__device__ __forceinline__ int pnp_first_smallest(double e0, double e1, double e2) {
+    const double e[3] = {e0, e1, e2};
+    double best = -1.0;
+    int which = -1;
+#pragma unroll
+    for (int v = 0; v < 3; ++v) {
+        const double err = e[v];
+        if (err >= 0.0 && (best < 0.0 || err < best)) best = err, which = v;
+    }
+    return which;
+}
+
+// EPnP on ONE row of any number of points (the all-inlier refit) by a workgroup of at least three waves. Wave 0 runs the front half
+// (a partial M^T M per lane) and leaves the frame, the null vectors and the distance system in LDS; then each of the waves 0..2 takes
+// ONE linearised start of the back half (its sums over the points spread over the wave's lanes, each wave with its own reduction
+// scratch) and thread 0 picks the start: its return value (-1..2; other threads: -1), the pose of start v in W.result[v][1..12].
+// With at most 64 rows a lane holds one term and the partials are added in lane order: the sequential sum of the at-most-64-point
+// form term by term. One wave running the three starts in a row was 234 us per refit of the incremental loop.
+struct PnpRefitLds {
+    PnpLds lds;
+    double part[78 * 64];
+    PnpFrame frame;
+    int front_ok;
+    double red[3][64], result[3][13];
+};
+__device__ __forceinline__ int pnp_refit_body(int m, const int* rows_idx, const double* obj, const double* img, const double* K4, PnpRefitLds& W) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    if (wave == 0) {
+        PnpFrame F;
+        const int ok = epnp_front<true>(m, rows_idx, obj, img, K4, F, W.lds, nullptr, W.part);
+        if (lane == 0) W.frame = F, W.front_ok = ok;
+    }
+    __syncthreads();
+    if (W.front_ok && wave < 3) {   // (front_ok is workgroup-uniform)
+        const PnpFrame F = W.frame;
+        double cand[12];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) cand[k] = 0.0;
+        double err;
+        if (wave == 0) err = epnp_back_variant<false, 0>(m, rows_idx, obj, img, K4, F, W.lds.ev, W.lds.L, 1, W.red[0], cand);
+        else if (wave == 1) err = epnp_back_variant<false, 1>(m, rows_idx, obj, img, K4, F, W.lds.ev, W.lds.L, 1, W.red[1], cand);
+        else err = epnp_back_variant<false, 2>(m, rows_idx, obj, img, K4, F, W.lds.ev, W.lds.L, 1, W.red[2], cand);
+        if (lane == 0) {
+            W.result[wave][0] = err;
+#pragma unroll
+            for (int k = 0; k < 12; ++k) W.result[wave][1 + k] = cand[k];
+        }
+    }
+    __syncthreads();
+    return threadIdx.x == 0 && W.front_ok ? pnp_first_smallest(W.result[0][0], W.result[1][0], W.result[2][0]) : -1;
+}
+
+// The minimal sample's M point pairs (idx: the sample's own row of indices into a / b) as x y x y ...
+template <int M>
+__device__ __forceinline__ void gather_sample(const int* __restrict__ idx, const double* __restrict__ a, const double* __restrict__ b, double* pa, double* pb) {
+#pragma unroll
+    for (int k = 0; k < M; ++k) {
+        const size_t i = (size_t)idx[k];
+        pa[2 * k] = a[2 * i]; pa[2 * k + 1] = a[2 * i + 1];
+        pb[2 * k] = b[2 * i]; pb[2 * k + 1] = b[2 * i + 1];
+    }
+}
 
 }  // namespace
 }  // namespace eacham

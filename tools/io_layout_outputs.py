@@ -10,11 +10,13 @@ cases of tests/lmeds_batch_cases.py in their three variants (eacham_lmeds_batch,
 eacham_score_hypotheses problem by problem), tests/test_tri_oracle.py's two-view case (seed 5, 2000 matches, both angle rules), one
 synth.make_tracks scene (eacham_triangulate_tracks, eacham_reprojection_errors), one PnP batch (eacham_solve_pnp,
 eacham_score_hypotheses), the resident graph after eacham_graph_set_frames (its query's answer), eacham_graph_best_pair on the
-same scenario (with and without an excluded mask) and the matching calls: eacham_match_pair / _match_all_pairs (with and
+same scenario (with and without an excluded mask), eacham_pnp_hypotheses_batch on the HYP_CASES of tests/pnp_batch_cases.py and
+eacham_pnp_refit_batch on its refit_case(), eacham_graph_verify on the graphs of tests/graph_verify_cases.py (both kinds, both sample
+streams) and the matching calls: eacham_match_pair / _match_all_pairs (with and
 without stats) / _match_pairs_directed on int8 frames and on float frames, the four dot-product calls on the float frames, each on
 a 12-pair list and on a list long enough for the direct copies (33 000 pairs); the Hamming calls — pair, directed, all pairs with
 and without stats, and the device-pointer form with distances — on binary frames of 32 bytes per row and on wide ones of 64.
---matching with --dump leaves out everything but the matching calls."""
+--matching with --dump leaves out everything but the matching calls, --staged the matching calls."""
 import argparse
 import os
 import sys
@@ -26,7 +28,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
-def dump(path, only_matching=False):
+def dump(path, only_matching=False, only_staged=False):
     import torch
     torch.cuda.init()   # (before the library touches the device: the device-pointer calls below hand it torch tensors)
     out = {}
@@ -38,15 +40,18 @@ def dump(path, only_matching=False):
 
     if not only_matching:
         staged(put)
-    matching(put)
+    if not only_staged:
+        matching(put)
     np.savez(path, **out)
     print(f"{len(out)} arrays, {sum(a.size for a in out.values())} bytes -> {path}")
 
 
 def staged(put):
     from eacham_amd import HipContext, score, synth, triangulate as tri
-    from eacham_amd import graph as G
+    from eacham_amd import capi, graph as G
+    import graph_verify_cases as GC
     import lmeds_batch_cases as LC
+    import pnp_batch_cases as PC
     import score_cases as SC
     import two_view_batch_cases as TC
     from test_graph_oracle import scenario
@@ -112,6 +117,26 @@ def staged(put):
         for ex in (None, excluded):
             best, ec = G.best_pair_for_valid(ctx, 40, pairs, counts, offsets, q, t, valid, has3d, ex, want_edge_counts=True)
             put(f"graph_best_pair/{int(ex is not None)}", np.array(best, np.int64), ec)
+        for name, make in PC.HYP_CASES.items():
+            c = make()
+            g = ctx.pnp_hypotheses_batch(c["X"], c["uv"], c["K"], c["samples"], PC.THR)
+            put(f"pnp_hypotheses_batch/{name}", *g.models, *g.n_models, *g.inlier_counts)
+        c = PC.refit_case()
+        g = ctx.pnp_refit_batch(c["X"], c["uv"], c["K"], c["models"], c["has_model"], PC.THR)
+        put("pnp_refit_batch", *g.masks, g.n_inliers, g.refit, g.refit_ok)
+        for name, its in (("small", 72), ("small", 89), ("large", 3), ("eight", 89)):
+            gr = getattr(GC, name)()
+            rg = G.ResidentGraph(ctx, gr["n_frames"], gr["pairs"], gr["counts"], gr["offsets"], gr["q"], gr["t"], gr["n_kp"])
+            try:
+                rg.set_keypoints(gr["xy"])
+                for kind, m in (("homography", 4), ("essential", 5)):
+                    for sampling in (capi.SAMPLING_OPENCV, capi.SAMPLING_COUNTER):
+                        got = rg._verify_raw(capi.SOLVE_HOMOGRAPHY4 if m == 4 else capi.SOLVE_ESSENTIAL5, m, GC.K4 if m == 5 else None, sampling, its,
+                                             gr["seeds"], False, True, preset=0x55)
+                        put(f"graph_verify/{name}/{its}/{kind}/{sampling}", got.models, got.medians, got.thresholds, got.inliers, got.masks,
+                            got.winner, got.n_candidates, got.n_samples, got.samples)
+            finally:
+                rg.close()
 
 
 def matching(put):
@@ -214,8 +239,9 @@ if __name__ == "__main__":
     ap.add_argument("--compare", nargs=2)
     ap.add_argument("--out")
     ap.add_argument("--matching", action="store_true", help="with --dump: the matching calls only")
+    ap.add_argument("--staged", action="store_true", help="with --dump: everything but the matching calls")
     args = ap.parse_args()
     if args.dump:
-        dump(args.dump, args.matching)
+        dump(args.dump, args.matching, args.staged)
         sys.exit(0)
     sys.exit(compare(args.compare[0], args.compare[1], args.out))
