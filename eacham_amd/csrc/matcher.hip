@@ -167,6 +167,7 @@ __global__ void quantize_kernel(const float* __restrict__ src, int dim, int KS, 
 // reads. msq (zeroed) gathers |M|^2, sr (zeroed) s_r = sum (x - x~)^2.
 constexpr float SCREEN_PAD = 8388608.0f;     // 2^23: exact in f32, above any n / 2 (n <= 256 * 120^2) and any partial sum of a real row
 constexpr int SCREEN_KS = 4;                 // K = 64 steps of a 256-D row
+constexpr int SCREEN_EXACT_KS = 8;           // int8 K = 32 steps of the same row: the exact pass behind the screen (frames_have_screen)
 constexpr int SCREEN_STEP_BYTES = 1536, SCREEN_TILE_BYTES = SCREEN_KS * SCREEN_STEP_BYTES;
 __global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, int npad, const int* __restrict__ orig,
                                        char* __restrict__ image, int* __restrict__ msq, int* __restrict__ sr) {
@@ -902,6 +903,9 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // with exact {v1, tile, v2}, and match_rows2_kernel fails the others on the same two numbers (L1 is a valid lower bound for its L(p)).
 // A row without a real minimum, or whose minima fill one subset only, carries the bound form's padding values. The fourth word
 // (n1, ~0 without one) is read by eacham_match_debug_screen_pair only.
+// openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
+// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane. match_openlist_kernel
+// turns the words of a pair (256 B where its rowres is 32 KB) into the candidate list.
 // LDS-DMA ring (three slots of 6 KiB), just-in-time fragment ring, double-buffered accumulators and the six-tiles-per-trip loop are
 // match_sweep_kernel's; a fragment is 24 bytes, two LDS reads.
 // ------------------------------------------------------------------------------------------------
@@ -918,11 +922,16 @@ __device__ __forceinline__ float fmin3(float a, float b, float c) {
     asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
+// the ratio test of the finalize kernels (defined with them below): the screen kernel's tail lists its open rows with it
+template <int METRIC>
+__device__ __forceinline__ bool ratio_pass(int d2_best, int d2_second, double ratio);
 struct ScreenFrag { v4i lo; v2i hi; };   // a lane's 32 codes of one K = 64 step
 __device__ __forceinline__ v8i screen_operand(const ScreenFrag& f) { return v8i{f.lo[0], f.lo[1], f.lo[2], f.lo[3], f.hi[0], f.hi[1], 0, 0}; }
 
+template <int METRIC>   // of the ratio test in the tail (binary frames of 129..256 bits carry the FP6 image too)
 __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
-                                                                     int wgs_per_pair, uint4* __restrict__ rowres, int row_stride) {
+                                                                     int wgs_per_pair, uint4* __restrict__ rowres, int row_stride, double ratio,
+                                                                     unsigned long long* __restrict__ openmask, int mask_stride) {
     constexpr int NSUB = 2, KS = SCREEN_KS;
     constexpr int TILE_V4 = SCREEN_TILE_BYTES / 16;
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
@@ -1127,8 +1136,11 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     const int e_b = T > 0 ? ((gint_t)(Bm2 + 64 * (size_t)B.ntiles))[0] : 0;
     uint4* rr = rowres + (size_t)p * row_stride + ROWS_WAVE * wb;
     const int lane_t = (int)((lds16 - lds_addr(sBb)) >> 4), cl_t = lane_t & 31, h_t = lane_t >> 5;   // (the lane, from what the sweep kept)
+    constexpr unsigned PAD_V = 2u * PADH;
+    unsigned long long open_rows = 0;   // bit 32 s + cl: that row of the wave-block goes to the exact pass
 #pragma unroll
     for (int s = 0; s < NSUB; ++s) {
+        bool open = false;
         const int j = ROWS_WAVE * wb + 32 * s + cl_t;
         const float ma = Am2[j];
         float v1 = BIGF, v2 = BIGF;
@@ -1150,8 +1162,12 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
             const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
             const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
             rr[32 * s + cl_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
+            // match_rowpick_kernel's predicate on the two words just stored (a padding row carries 0xffffffff in the first)
+            open = NSUB * wb + s < A_tiles && w1 < PAD_V && (w2 >= PAD_V || ratio_pass<METRIC>((int)(w1 + pa) - 2, (int)(w2 + pa) - 2, ratio));
         }
+        open_rows |= (__ballot(open) & 0xffffffffull) << (32 * s);
     }
+    if (openmask && lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1318,6 +1334,58 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     }
     __syncthreads();
     for (int g = tid; g < groups; g += FIN_THREADS) items[s_item0 + g] = make_int2(p, g);
+}
+
+// Behind the SCREEN form of the sweep (match_screen_kernel): the same list, state, items and tally from the masks the sweep's tail
+// wrote (openmask[p][wb]: one bit per row of wave-block wb, match_rowpick_kernel's predicate) instead of a pass over rowres. One wave
+// per pair reads the ceil(A_tiles / 2) words that exist; the set bits of a word go to the list behind those of the words before it,
+// each at the popcount of the bits below it: ascending stored rows, as match_rowpick_kernel leaves them.
+// A workgroup is sixteen pairs and adds to the item counter and to the tally ONCE: one add per pair to the same three addresses is what
+// a launch of ~10 000 pairs spent its 0.25 ms on, here as in match_rowpick_kernel (profiles/screen_exact_behind_sweep.txt).
+constexpr int LIST_WAVES = 16;
+__global__ __launch_bounds__(64 * LIST_WAVES) void match_openlist_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
+                                                                         const unsigned long long* __restrict__ openmask, int mask_stride, int row_stride,
+                                                                         int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items,
+                                                                         int* __restrict__ n_items, unsigned long long* __restrict__ tally) {
+    __shared__ int s_groups[LIST_WAVES], s_open[LIST_WAVES], s_rows[LIST_WAVES];
+    __shared__ int s_item0;
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int p = blockIdx.x * LIST_WAVES + wave;
+    int base = 0, rows = 0;
+    if (p < npairs) {   // wave-uniform
+        const FrameDev A = frames[pairs[p].x];
+        rows = A.n;
+        const int nwords = (A.meta[1] + 1) / 2;
+        const unsigned long long* om = openmask + (size_t)p * mask_stride;
+        int* cl = candlist + (size_t)p * row_stride;
+        for (int w0 = 0; w0 < nwords; w0 += 64) {
+            const unsigned long long mine = w0 + lane < nwords ? om[w0 + lane] : 0ull;
+            const int nw = min(64, nwords - w0);
+            for (int k = 0; k < nw; ++k) {   // word w0 + k, the same in every lane
+                const unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), k) << 32) |
+                                             (unsigned)__builtin_amdgcn_readlane((int)mine, k);
+                if ((m >> lane) & 1) cl[base + __popcll(m & ((1ull << lane) - 1))] = 64 * (w0 + k) + lane;
+                base += __popcll(m);
+            }
+        }
+        if (lane == 0) state[p] = make_int4(base, 0, 0, 0);
+    }
+    const int groups = (base + VER_CANDS - 1) / VER_CANDS;
+    if (lane == 0) s_groups[wave] = groups, s_open[wave] = base, s_rows[wave] = rows;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int g = 0;
+        unsigned long long r = 0, o = 0;
+        for (int k = 0; k < LIST_WAVES; ++k) g += s_groups[k], r += (unsigned long long)s_rows[k], o += (unsigned long long)s_open[k];
+        s_item0 = g ? atomicAdd(n_items, g) : 0;
+        atomicAdd(&tally[0], r);   // {real query rows, rows left open} of the call
+        atomicAdd(&tally[1], o);
+    }
+    __syncthreads();
+    int item0 = s_item0;
+    for (int k = 0; k < wave; ++k) item0 += s_groups[k];
+    for (int g = lane; g < groups; g += 64) items[item0 + g] = make_int2(p, g);
 }
 
 // The rows kernel of the operand-swapped sweep (match_sweep_kernel): rowres carries the TILE of a row's minimum, not its column.
@@ -1863,7 +1931,7 @@ static unsigned long long* colprune_totals(eacham_ctx* ctx) { return ctx->flag_d
 static unsigned long long* screen_tally(eacham_ctx* ctx) { return ctx->flag_dev->screen; }
 // every resident frame with rows carries the FP6 image (all frames share one dim class, so this is ks_common == 8)
 static bool frames_have_screen(const eacham_ctx* ctx) {
-    if (ctx->kind_common == FRAME_F32 || ctx->ks_common != 8) return false;
+    if (ctx->kind_common == FRAME_F32 || ctx->ks_common != SCREEN_EXACT_KS) return false;
     for (const auto& f : ctx->frames)
         if (f.n > 0 && !f.screen) return false;
     return true;
@@ -1880,6 +1948,8 @@ struct MatchPlan {
     size_t off_rowres, off_colpart, off_matches, slot_bytes, total;
     // the candidate-only column pass: rowcand | candlist | colres | state | items | n_items
     size_t off_rowcand, off_candlist, off_colres, off_state, off_items, off_nitems, off_bytile, off_aitems, off_openlist;
+    int mask_stride;   // 64-bit words per pair of the screen sweep's open-row masks: one per wave-block
+    size_t off_openmask;
 };
 
 static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
@@ -1925,7 +1995,9 @@ static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     pl.off_bytile = align(pl.off_nitems + 256);
     pl.off_aitems = align(pl.off_bytile + cb * pl.row_stride * sizeof(int));
     pl.off_openlist = align(pl.off_aitems + cb * 2 * max_tiles * sizeof(int4));
-    pl.slot_bytes = align(pl.off_openlist + cb * pl.row_stride * sizeof(int));
+    pl.mask_stride = (pl.row_stride + 63) / 64;
+    pl.off_openmask = align(pl.off_openlist + cb * pl.row_stride * sizeof(int));
+    pl.slot_bytes = align(pl.off_openmask + cb * pl.mask_stride * sizeof(unsigned long long));   // (1/128 of rowres: not counted in per_pair, the launches stay as they were cut)
     pl.total = pl.slot_bytes * pl.slots;
     return pl;
 }
@@ -1982,11 +2054,11 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st1));        // inputs queued on the context stream
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_join, 0));
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(colprune_totals(ctx), 0, 2 * sizeof(unsigned long long), st2));
-    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 2 * sizeof(unsigned long long), st2));
     // The row sweep of the lean form. EACHAM_MATCH_SWEEP_FORM forces the exact (1) or the bound form (2) at every dimension; screen (3)
     // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
     const int form = ctx->match_sweep_form;
     const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 2 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job's last batch is cut short (an eighth of a full one),
     // so the exposed tail is that of ~1 500 pairs instead of ~10 000 (0.8 ms of a 21 ms S200 step).
@@ -2005,12 +2077,17 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
         // matrix cores instead (match_screen_kernel, half the matrix cycles), with the same exact pass behind
         const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
         uint4* rowres = (uint4*)(ws + pl.off_rowres);
+        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows
+        // persistent workgroups over an item list (its length is only known on the device): one round of the chip
+        const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
+        if (screen_sweep) EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_pre, 0, 8 * sizeof(int), st1));   // ahead of the sweep: nothing between it and its exact pass
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
             with_ks(ctx->ks_common, [&](auto ks) {
                 constexpr int KS = decltype(ks)::value;
                 if (screen_sweep)
-                    match_screen_kernel<<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
+                    match_screen_kernel<METRIC><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride, ratio,
+                                                                                          (unsigned long long*)(ws + pl.off_openmask), pl.mask_stride);
                 else if (full_cols)
                     match_tile_kernel<KS><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, st1>>>(
                         ctx->frame_table_dev, pb, pl.wgs_per_pair, pl.col_chunks, rowres, (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
@@ -2019,6 +2096,22 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                 else
                     match_sweep_kernel<KS, false><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
             });
+        }
+        if (screen_sweep) {
+            // The exact pass over the rows the screen left open runs HERE, on the sweep's stream and ahead of ev_tile. Beside the next
+            // sweep it got in only as sweep workgroups retired (164 VGPRs x 3 waves fill a SIMD: 5.8 ms where it takes 1.0 ms alone) and
+            // held the slot the sweep after next waits for; behind its own sweep the next sweep starts behind it and the step is 4 %
+            // shorter (profiles/screen_exact_behind_sweep.txt). The slot-free wait above covers candlist, state and items of this slot;
+            // the HBM-bound tail stays on the second stream.
+            ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st1);
+            int* candlist = (int*)(ws + pl.off_candlist);
+            int4* state = (int4*)(ws + pl.off_state);
+            int2* items = (int2*)(ws + pl.off_items);
+            match_openlist_kernel<<<(nb + LIST_WAVES - 1) / LIST_WAVES, 64 * LIST_WAVES, 0, st1>>>(
+                ctx->frame_table_dev, pb, nb, (const unsigned long long*)(ws + pl.off_openmask), pl.mask_stride, pl.row_stride, candlist, state, items, n_pre,
+                screen_tally(ctx));
+            match_colverify_kernel<SCREEN_EXACT_KS, true><<<vgrid, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
+                                                                                         pl.row_stride, 0, nullptr, rowres);
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
@@ -2036,20 +2129,16 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                 int4* state = (int4*)(ws + pl.off_state);
                 int2* items = (int2*)(ws + pl.off_items);
                 int* n_items = (int*)(ws + pl.off_nitems);
-                int* n_pre = n_items + 8;
                 int* n_aitems = n_items + 16;
                 int* bytile = (int*)(ws + pl.off_bytile);
                 int4* aitems = (int4*)(ws + pl.off_aitems);
                 int* openlist = (int*)(ws + pl.off_openlist);
-                // persistent workgroups over an item list (its length is only known on the device): one round of the chip
-                const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
                 const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
                 with_ks(ctx->ks_common, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value;
-                    if (bound_sweep || screen_sweep) {   // the rows the bound / screen form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it
-                        match_rowpick_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre,
-                                                                          screen_sweep ? screen_tally(ctx) : nullptr);
+                    if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it (the screen form's ran behind its sweep)
+                        match_rowpick_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre);
                         match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
                                                                                         pl.row_stride, 0, nullptr, rowres);
                     }
@@ -2355,7 +2444,7 @@ int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1
         rc = io.upload(d);
         if (rc) return rc;
         uint4* rowres = (uint4*)((char*)ctx->ws + pl.off_rowres);
-        match_screen_kernel<<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride);
+        match_screen_kernel<METRIC_L2><<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride, 0.0, nullptr, 0);
         EACHAM_HIP_TRY(ctx, hipGetLastError());
         rc = io.finish();
         if (rc) return rc;
