@@ -118,7 +118,10 @@ int oracle_triangulate_track(const double* transforms, const uint32_t* frame, co
     if (m < 3) {
         const double *T0 = transforms + 16 * (size_t)frame[0], *T1 = transforms + 16 * (size_t)frame[1];
         oracle_triangulate_point(T0, T1, uv, uv + 2, K, point);
-        if (oracle_triangulation_angle(T0, T1, point) < (double)min_angle) return 0;
+        /* `angle < minTriAngle` at :105, stated so that a NaN angle (a pair without baseline: the null vector is not
+         * defined and the point may be 0/0) is rejected as the >= of the m >= 3 loop (:142) and the kernels reject it:
+         * such a pair is never accepted, whatever its garbage point's z says. */
+        if (!(oracle_triangulation_angle(T0, T1, point) >= (double)min_angle)) return 0;
         for (int i = 0; i < m; ++i) mask[i] = (uint8_t)is_inlier(transforms + 16 * (size_t)frame[i], uv + 2 * i, K, point, max_err);
         ransac_ok = point[2] > 0.0;
         mask_len = m;

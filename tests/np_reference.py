@@ -130,7 +130,7 @@ def tri_ransac(Ts, uvs, K4, max_err, min_angle):
         return False, np.zeros(3), []
     if m < 3:
         X = tri_point(Ts[0], Ts[1], uvs[0], uvs[1], K4)
-        if tri_angle(Ts[0], Ts[1], X) < np.float32(min_angle):
+        if not tri_angle(Ts[0], Ts[1], X) >= np.float32(min_angle):   # (`<` at :105; a NaN angle, no baseline, is rejected as at :142)
             return False, X, []
         mask = [tri_inlier(Ts[i], uvs[i], K4, X, max_err) for i in range(m)]
         return bool(X[2] > 0), X, mask
