@@ -74,6 +74,8 @@ def lib() -> C.CDLL:
     if hasattr(L, "eacham_match_debug_screen"):
         L.eacham_match_debug_screen.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
         L.eacham_match_debug_screen_pair.argtypes = [vp, i32, i32, vp, vp, vp, i32]
+    if hasattr(L, "eacham_match_debug_screen_items"):   # (absent from an older build selected with EACHAM_HIP_LIB)
+        L.eacham_match_debug_screen_items.argtypes = [vp, C.POINTER(i64)]
     f32 = C.c_float
     # (an older build selected with EACHAM_HIP_LIB for a before/after run lacks these three; calling them on it raises AttributeError)
     if hasattr(L, "eacham_match_pair_dot"):

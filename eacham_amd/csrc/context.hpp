@@ -40,8 +40,9 @@ struct FlagBlock {
     unsigned long long colprune[2];   // {settled, verified} candidate columns of the last matching call (eacham_match_debug_colprune)
     int pad1[4];
     unsigned long long dot16[6];      // the tally of the screened dot-product form
-    unsigned long long screen[2];     // {real query rows, rows left open} of the last call's screen sweeps (eacham_match_debug_screen)
-    int pad2[8];
+    unsigned long long screen[3];     // {real query rows, rows left open} of the last call's screen sweeps (eacham_match_debug_screen),
+                                      // {items the exact pass took them in} (eacham_match_debug_screen_items)
+    int pad2[6];
 };
 static_assert(offsetof(FlagBlock, bad_pair) == 1 * sizeof(int) && offsetof(FlagBlock, standin_meta) == 8 * sizeof(int) &&
                   offsetof(FlagBlock, standin_rows) == 16 * sizeof(int) && offsetof(FlagBlock, colprune) == 32 * sizeof(int) &&

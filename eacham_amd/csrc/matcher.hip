@@ -606,9 +606,26 @@ __device__ __forceinline__ void top2_merge(int& m1, int& m2, int s1, int s2) {
 // few whose runner-up shared the minimum's subset — are candidates: match_rowpick_kernel lists them and match_colverify_kernel<KS, true>
 // computes their exact {v1, tile, v2} against the whole train frame (the candidate-only pass of the columns with the frames' roles
 // swapped), overwriting their rowres entries before match_rows2_kernel reads them. out: rowres[p][j] = {v1, 0, u, 0}.
-template <int KS, bool BOUND = false>
+//
+// GATHER (KS = 8, exact): the exact pass behind the screen sweep. The workgroup is `unit` = an item of match_openscan_kernel, {first
+// candidate, count <= 256} into the launch's packed list `cands` ({pair index within the launch, stored query row}), all onto one
+// train frame (the first candidate's pair names it): wave w takes candidates 64 w .. 64 w + 63, a lane gathers ITS row's fragments
+// from the candidate's own query frame (the addressing of match_colverify_kernel's gather), and the tail writes {v1, t1, v2, 0} to
+// rowres[pair][row] from the h == 0 lanes of real candidates. A wave without candidates still stages; a lane past `count` computes
+// on the item's first candidate and writes nothing. Everything between prologue and tail is the sweep as it stands.
+template <bool GATHER>
+struct GatherList {};   // (no argument without the gather)
+template <>
+struct GatherList<true> {
+    const uint2* cands;
+    const int2* items;
+    const int* n_items;
+};
+constexpr int GATHER_WIDTH = 256;   // candidates per item: 64 per wave
+template <int KS, bool BOUND = false, bool GATHER = false>
 __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
-                                                                   int wgs_per_pair, uint4* __restrict__ rowres, int row_stride) {
+                                                                   int wgs_per_pair, uint4* __restrict__ rowres, int row_stride,
+                                                                   GatherList<GATHER> gl = {}) {
     constexpr int NSUB = 2;
     constexpr int TILE_V4 = KS * 64;
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
@@ -619,24 +636,40 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cl = lane & 31, h = lane >> 5;
-    const int rb = blockIdx.x % wgs_per_pair;
-    const int p = blockIdx.x / wgs_per_pair;
+    int2 item = make_int2(0, 0);
+    const uint2* pk = nullptr;            // GATHER: the item's candidates, item.y of them
+    if constexpr (GATHER) {
+        if ((int)blockIdx.x >= *gl.n_items) return;   // workgroup-uniform: the grid is an upper bound of the list
+        item = gl.items[blockIdx.x];
+        pk = gl.cands + item.x;
+    }
+    const int rb = GATHER ? 0 : blockIdx.x % wgs_per_pair;
+    const int p = GATHER ? (int)pk[0].x : blockIdx.x / wgs_per_pair;
     const int2 pr = pairs[p];
     const FrameDev A = frames[pr.x], B = frames[pr.y];
     const int A_tiles = ((gint_t)A.meta)[1];
     const int B_even = ((gint_t)B.meta)[0], T = ((gint_t)B.meta)[1];
-    if (rb * (ROWS_WG / 32) >= A_tiles) return;  // workgroup-uniform
+    if (!GATHER && rb * (ROWS_WG / 32) >= A_tiles) return;  // workgroup-uniform
     const int wb = rb * WAVES + wave;
-    const bool active = NSUB * wb < A_tiles;
+    const bool active = GATHER ? ROWS_WAVE * wave < item.y : NSUB * wb < A_tiles;
     const gfrag_t Afrag = (gfrag_t)A.frag, Bfrag = (gfrag_t)B.frag;
     const gint_t Aca = (gint_t)A.norm, Bhb = (gint_t)B.normb;
     const int wbc = active ? wb : 0;
 
     v4i a[NSUB][KS];   // this wave's 64 query rows, complemented: the B operand (a lane = a query row of the sub-tile)
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s)
+    for (int s = 0; s < NSUB; ++s) {
+        if constexpr (GATHER) {
+            const int i = ROWS_WAVE * wave + 32 * s + cl;
+            const uint2 c = pk[i < item.y ? i : 0];
+            const gfrag_t Qfrag = (gfrag_t)frames[pairs[c.x].x].frag;   // the candidate's own query frame
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) a[s][ks] = ~Afrag[((size_t)(NSUB * wbc + s) * KS + ks) * 64 + lane];
+            for (int ks = 0; ks < KS; ++ks) a[s][ks] = ~Qfrag[((size_t)(c.y >> 5) * KS + ks) * 64 + 32 * h + (c.y & 31)];
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) a[s][ks] = ~Afrag[((size_t)(NSUB * wbc + s) * KS + ks) * 64 + lane];
+        }
+    }
     // running top-2 values and the tile of the minimum, per sub-tile; the even class is set aside at the parity boundary
     // (set aside in LDS, each lane its own words: six registers less through the sweep)
     constexpr int NG = 4;                    // BOUND: running minima per sub-tile (eight: 14 registers spilled at 256-D)
@@ -866,7 +899,9 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
     for (int s = 0; s < NSUB; ++s) {
         // lanes l and l + 32 hold the same query row against complementary train rows of every tile: join them (equal minima:
         // the earlier tile), then the two parity classes as v = 2 (m + ca) + pb (never equal across classes)
-        const int ca = Aca[ROWS_WAVE * wb + 32 * s + cl];
+        const int gi = ROWS_WAVE * wave + 32 * s + cl;                 // GATHER: this lane's candidate
+        const uint2 gc = GATHER ? pk[gi < item.y ? gi : 0] : make_uint2(0u, 0u);
+        const int ca = GATHER ? ((gint_t)frames[pairs[gc.x].x].norm)[gc.y] : Aca[ROWS_WAVE * wb + 32 * s + cl];
         int cls1[2] = {e1[s], x1[s]}, cls2[2] = {e2[s], x2[s]}, clst[2] = {et[s], xt[s]};
         unsigned v1 = 0xffffffffu, v2 = 0xffffffffu, t1 = 0;
 #pragma unroll
@@ -882,7 +917,11 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
             v2 = umin(umin(umax(v1, w1), v2), w2);
             v1 = umin(v1, w1);
         }
-        if (h == 0) rr[32 * s + cl] = make_uint4(v1, t1, v2, 0);
+        if constexpr (GATHER) {
+            if (h == 0 && gi < item.y) rowres[(size_t)gc.x * row_stride + gc.y] = make_uint4(v1, t1, v2, 0);
+        } else {
+            if (h == 0) rr[32 * s + cl] = make_uint4(v1, t1, v2, 0);
+        }
     }
 }
 
@@ -899,13 +938,13 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // accumulators, lane half). Their smallest is n1, their second smallest u bounds the runner-up from above, and the tail turns them
 // into L1 <= the true minimum and U2 >= the true runner-up (screen::lower_d2 / upper_d2 with the row's s and the train frame's E).
 // out: rowres[p][j] = {L1 - pa + 2, 0, U2 - pa + 2, n1}: the bound form's slot and encoding ((e.x + pa) - 2 decodes to L1), so
-// match_rowpick_kernel lists the rows that do not fail the ratio test on (L1, U2), match_colverify_kernel<8, true> overwrites them
-// with exact {v1, tile, v2}, and match_rows2_kernel fails the others on the same two numbers (L1 is a valid lower bound for its L(p)).
+// the rows that do not fail the ratio test on (L1, U2) are listed (match_rowpick_kernel's predicate), the gathered exact sweep
+// (match_sweep_kernel<8, false, true>) overwrites them with exact {v1, tile, v2}, and match_rows2_kernel fails the others on the same two numbers (L1 is a valid lower bound for its L(p)).
 // A row without a real minimum, or whose minima fill one subset only, carries the bound form's padding values. The fourth word
 // (n1, ~0 without one) is read by eacham_match_debug_screen_pair only.
 // openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
-// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane. match_openlist_kernel
-// turns the words of a pair (256 B where its rowres is 32 KB) into the candidate list.
+// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane. match_opencount_kernel /
+// match_openscan_kernel / match_openfill_kernel turn the words of a launch (256 B per pair where its rowres is 32 KB) into one packed candidate list.
 // LDS-DMA ring (three slots of 6 KiB), just-in-time fragment ring, double-buffered accumulators and the six-tiles-per-trip loop are
 // match_sweep_kernel's; a fragment is 24 bytes, two LDS reads.
 // ------------------------------------------------------------------------------------------------
@@ -1336,56 +1375,160 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
     for (int g = tid; g < groups; g += FIN_THREADS) items[s_item0 + g] = make_int2(p, g);
 }
 
-// Behind the SCREEN form of the sweep (match_screen_kernel): the same list, state, items and tally from the masks the sweep's tail
-// wrote (openmask[p][wb]: one bit per row of wave-block wb, match_rowpick_kernel's predicate) instead of a pass over rowres. One wave
-// per pair reads the ceil(A_tiles / 2) words that exist; the set bits of a word go to the list behind those of the words before it,
-// each at the popcount of the bits below it: ascending stored rows, as match_rowpick_kernel leaves them.
-// A workgroup is sixteen pairs and adds to the item counter and to the tally ONCE: one add per pair to the same three addresses is what
-// a launch of ~10 000 pairs spent its 0.25 ms on, here as in match_rowpick_kernel (profiles/screen_exact_behind_sweep.txt).
+// Behind the SCREEN form of the sweep (match_screen_kernel): the rows its tail left open (openmask[p][wb]: one bit per row of
+// wave-block wb, match_rowpick_kernel's predicate) become ONE packed candidate list per launch, cut into items per train-frame run.
+// At the headline nine pairs in ten have an open row but the typical pair has two or three (the bound's slack), and an item streams
+// the whole train frame whatever it holds: per-pair items of 64 ran about half empty (38 103 items for 1.39 M open rows of an S200
+// step). Only the streamed frame has to be common to an item — the exact pass gathers its query rows per lane — so the candidates of
+// consecutive pairs onto one train frame share items (shard.order_pairs sorts a job by train frame): 5 537 items of 256.
+//   segment    a maximal run of consecutive pairs of the launch with one train frame (pairs[p].y); any pair order is legal and
+//              only gives shorter segments
+//   cands[i]   {pair index within the launch, stored query row}: pair order, ascending stored rows inside a pair — so a segment's
+//              candidates are contiguous. No output depends on the order inside a segment (a candidate is a lane of the exact pass)
+//   items[w]   {first candidate, count <= width}, all of one segment (width: GATHER_WIDTH = 256, a workgroup of the gathered sweep); a pair may straddle two items, a segment's last item may be
+//              short, a launch with no open row has none
+// Three kernels, three times per step in the exposed chain:
+//   match_opencount_kernel  a wave per pair: the popcount of its mask words -> state[p].x; a workgroup of sixteen pairs adds to the
+//                           tally ONCE (one add per pair to the same addresses is what a launch of ~10 000 pairs once spent 0.25 ms on)
+//   match_openscan_kernel   ONE workgroup over the <= batch pairs, 1024 at a time: exclusive sum of the counts (state[p].y = the pair's
+//                           first candidate), a running maximum over the segment heads' offsets (the segment's first candidate), a sum
+//                           of ceil(segment total / width) placed at each segment's last pair (the segment's first item); the items
+//                           of the chunk are then written by all threads, each finding its segment by bisection. No atomic but one
+//                           add to the tally's third word
+//   match_openfill_kernel   a wave per pair again: the set bits of a word go behind those of the words before it, each at the
+//                           popcount of the bits below it
 constexpr int LIST_WAVES = 16;
-__global__ __launch_bounds__(64 * LIST_WAVES) void match_openlist_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
-                                                                         const unsigned long long* __restrict__ openmask, int mask_stride, int row_stride,
-                                                                         int* __restrict__ candlist, int4* __restrict__ state, int2* __restrict__ items,
-                                                                         int* __restrict__ n_items, unsigned long long* __restrict__ tally) {
-    __shared__ int s_groups[LIST_WAVES], s_open[LIST_WAVES], s_rows[LIST_WAVES];
-    __shared__ int s_item0;
+constexpr int OSCAN_THREADS = 1024;
+__global__ __launch_bounds__(64 * LIST_WAVES) void match_opencount_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
+                                                                          const unsigned long long* __restrict__ openmask, int mask_stride,
+                                                                          int4* __restrict__ state, unsigned long long* __restrict__ tally) {
+    __shared__ int s_open[LIST_WAVES], s_rows[LIST_WAVES];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int p = blockIdx.x * LIST_WAVES + wave;
-    int base = 0, rows = 0;
+    int open = 0, rows = 0;
     if (p < npairs) {   // wave-uniform
         const FrameDev A = frames[pairs[p].x];
         rows = A.n;
         const int nwords = (A.meta[1] + 1) / 2;
         const unsigned long long* om = openmask + (size_t)p * mask_stride;
-        int* cl = candlist + (size_t)p * row_stride;
-        for (int w0 = 0; w0 < nwords; w0 += 64) {
-            const unsigned long long mine = w0 + lane < nwords ? om[w0 + lane] : 0ull;
-            const int nw = min(64, nwords - w0);
-            for (int k = 0; k < nw; ++k) {   // word w0 + k, the same in every lane
-                const unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), k) << 32) |
-                                             (unsigned)__builtin_amdgcn_readlane((int)mine, k);
-                if ((m >> lane) & 1) cl[base + __popcll(m & ((1ull << lane) - 1))] = 64 * (w0 + k) + lane;
-                base += __popcll(m);
-            }
-        }
-        if (lane == 0) state[p] = make_int4(base, 0, 0, 0);
+        for (int w = lane; w < nwords; w += 64) open += __popcll(om[w]);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) open += __shfl_xor(open, d);
+        if (lane == 0) ((int*)&state[p])[0] = open;
     }
-    const int groups = (base + VER_CANDS - 1) / VER_CANDS;
-    if (lane == 0) s_groups[wave] = groups, s_open[wave] = base, s_rows[wave] = rows;
+    if (lane == 0) s_open[wave] = open, s_rows[wave] = rows;
     __syncthreads();
     if (threadIdx.x == 0) {
-        int g = 0;
         unsigned long long r = 0, o = 0;
-        for (int k = 0; k < LIST_WAVES; ++k) g += s_groups[k], r += (unsigned long long)s_rows[k], o += (unsigned long long)s_open[k];
-        s_item0 = g ? atomicAdd(n_items, g) : 0;
+        for (int k = 0; k < LIST_WAVES; ++k) r += (unsigned long long)s_rows[k], o += (unsigned long long)s_open[k];
         atomicAdd(&tally[0], r);   // {real query rows, rows left open} of the call
         atomicAdd(&tally[1], o);
     }
+}
+
+// inclusive scan over the OSCAN_THREADS threads of the workgroup (sum, or maximum of values >= -1); *total = the last thread's
+template <bool MAX>
+__device__ __forceinline__ int oscan_inclusive(int v, int* s_w /* [OSCAN_THREADS / 64] */, int* total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int u = __shfl_up(v, d);
+        if (lane >= d) v = MAX ? max(v, u) : v + u;
+    }
+    if (lane == 63) s_w[wave] = v;
     __syncthreads();
-    int item0 = s_item0;
-    for (int k = 0; k < wave; ++k) item0 += s_groups[k];
-    for (int g = lane; g < groups; g += 64) items[item0 + g] = make_int2(p, g);
+    int before = MAX ? -1 : 0, all = MAX ? -1 : 0;
+    for (int k = 0; k < OSCAN_THREADS / 64; ++k) {
+        const int e = s_w[k];
+        if (k < wave) before = MAX ? max(before, e) : before + e;
+        all = MAX ? max(all, e) : all + e;
+    }
+    __syncthreads();   // (the next call overwrites s_w)
+    *total = all;
+    return MAX ? max(v, before) : v + before;
+}
+
+__global__ __launch_bounds__(OSCAN_THREADS) void match_openscan_kernel(const int2* __restrict__ pairs, int npairs, int width, int4* __restrict__ state,
+                                                                       int2* __restrict__ items, int* __restrict__ n_items,
+                                                                       unsigned long long* __restrict__ tally) {
+    __shared__ int s_w[OSCAN_THREADS / 64];
+    __shared__ int s_item0[OSCAN_THREADS], s_first[OSCAN_THREADS], s_total[OSCAN_THREADS];
+    const int tid = threadIdx.x;
+    int cand0 = 0, seg0 = 0, item0 = 0;   // carried from chunk to chunk: candidates so far, the open segment's first candidate, items so far
+    // a chunk's words are fetched while the chunk before it is scanned (the barriers would otherwise expose every fetch)
+    int c_nxt = 0, y_nxt = 0, yp_nxt = 0, yn_nxt = 0;
+    auto fetch = [&](int p0) {
+        const int p = p0 + tid;
+        if (p < npairs) {
+            c_nxt = ((const int*)&state[p])[0];
+            y_nxt = pairs[p].y;
+            yp_nxt = p > 0 ? pairs[p - 1].y : 0;
+            yn_nxt = p + 1 < npairs ? pairs[p + 1].y : 0;
+        }
+    };
+    fetch(0);
+    for (int p0 = 0; p0 < npairs; p0 += OSCAN_THREADS) {
+        const int p = p0 + tid;
+        const bool live = p < npairs;
+        const int c = live ? c_nxt : 0;
+        const bool head = live && (p == 0 || yp_nxt != y_nxt);
+        const bool last = live && (p + 1 == npairs || yn_nxt != y_nxt);
+        fetch(p0 + OSCAN_THREADS);
+        int chunk_cands, chunk_items, unused;
+        const int off = cand0 + oscan_inclusive<false>(c, s_w, &chunk_cands) - c;      // the pair's first candidate
+        const int first = max(seg0, oscan_inclusive<true>(head ? off : -1, s_w, &unused));   // its segment's (offsets never decrease)
+        const int total = last ? off + c - first : 0;                                  // at a segment's last pair: the segment's candidates
+        const int ni = (total + width - 1) / width;
+        const int it0 = item0 + oscan_inclusive<false>(ni, s_w, &chunk_items) - ni;     // ... and its first item
+        if (live) state[p] = make_int4(c, off, 0, 0);
+        s_item0[tid] = it0, s_first[tid] = first, s_total[tid] = total;
+        __syncthreads();
+        // item w of the chunk belongs to the last thread t with s_item0[t] <= w: threads without items repeat their successor's value
+        for (int w = item0 + tid; w < item0 + chunk_items; w += OSCAN_THREADS) {
+            int t = 0;   // (s_item0[0] = item0 <= w)
+            for (int hi = OSCAN_THREADS; hi - t > 1;) {
+                const int mid = (t + hi) >> 1;
+                if (s_item0[mid] <= w) t = mid;
+                else hi = mid;
+            }
+            const int k = w - s_item0[t];
+            items[w] = make_int2(s_first[t] + k * width, min(width, s_total[t] - k * width));
+        }
+        seg0 = s_first[OSCAN_THREADS - 1];   // (of a thread past the list: the last segment's, never used again)
+        cand0 += chunk_cands;
+        item0 += chunk_items;
+        __syncthreads();
+    }
+    if (tid == 0) {
+        *n_items = item0;
+        atomicAdd(&tally[2], (unsigned long long)item0);   // {items of the exact pass} of the call
+    }
+}
+
+__global__ __launch_bounds__(64 * LIST_WAVES) void match_openfill_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
+                                                                         const unsigned long long* __restrict__ openmask, int mask_stride,
+                                                                         const int4* __restrict__ state, uint2* __restrict__ cands) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int p = blockIdx.x * LIST_WAVES + wave;
+    if (p >= npairs) return;   // wave-uniform; no workgroup barrier below
+    const int4 st = state[p];
+    if (st.x == 0) return;
+    const int nwords = (frames[pairs[p].x].meta[1] + 1) / 2;
+    const unsigned long long* om = openmask + (size_t)p * mask_stride;
+    uint2* cl = cands + st.y;
+    int base = 0;
+    for (int w0 = 0; w0 < nwords; w0 += 64) {
+        const unsigned long long mine = w0 + lane < nwords ? om[w0 + lane] : 0ull;
+        const int nw = min(64, nwords - w0);
+        for (int k = 0; k < nw; ++k) {   // word w0 + k, the same in every lane
+            const unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), k) << 32) |
+                                         (unsigned)__builtin_amdgcn_readlane((int)mine, k);
+            if ((m >> lane) & 1) cl[base + __popcll(m & ((1ull << lane) - 1))] = make_uint2((unsigned)p, (unsigned)(64 * (w0 + k) + lane));
+            base += __popcll(m);
+        }
+    }
 }
 
 // The rows kernel of the operand-swapped sweep (match_sweep_kernel): rowres carries the TILE of a row's minimum, not its column.
@@ -1927,7 +2070,7 @@ static int check_integer_flag(eacham_ctx* ctx) {
 
 // {settled, verified}: the candidate columns of the last matching call that match_argmin_kernel settled / that went to match_colverify_kernel
 static unsigned long long* colprune_totals(eacham_ctx* ctx) { return ctx->flag_dev->colprune; }
-// {real query rows, rows left open}: what the screen sweeps of the last matching call met / handed to the exact pass
+// {real query rows, rows left open, items}: what the screen sweeps of the last matching call met / handed to the exact pass / in how many items
 static unsigned long long* screen_tally(eacham_ctx* ctx) { return ctx->flag_dev->screen; }
 // every resident frame with rows carries the FP6 image (all frames share one dim class, so this is ks_common == 8)
 static bool frames_have_screen(const eacham_ctx* ctx) {
@@ -2058,7 +2201,7 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
     const int form = ctx->match_sweep_form;
     const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
-    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 2 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 3 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job's last batch is cut short (an eighth of a full one),
     // so the exposed tail is that of ~1 500 pairs instead of ~10 000 (0.8 ms of a 21 ms S200 step).
@@ -2077,10 +2220,9 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
         // matrix cores instead (match_screen_kernel, half the matrix cycles), with the same exact pass behind
         const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
         uint4* rowres = (uint4*)(ws + pl.off_rowres);
-        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows
+        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows (screen form: match_openscan_kernel writes it)
         // persistent workgroups over an item list (its length is only known on the device): one round of the chip
         const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
-        if (screen_sweep) EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_pre, 0, 8 * sizeof(int), st1));   // ahead of the sweep: nothing between it and its exact pass
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
             with_ks(ctx->ks_common, [&](auto ks) {
@@ -2101,17 +2243,26 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
             // The exact pass over the rows the screen left open runs HERE, on the sweep's stream and ahead of ev_tile. Beside the next
             // sweep it got in only as sweep workgroups retired (164 VGPRs x 3 waves fill a SIMD: 5.8 ms where it takes 1.0 ms alone) and
             // held the slot the sweep after next waits for; behind its own sweep the next sweep starts behind it and the step is 4 %
-            // shorter (profiles/screen_exact_behind_sweep.txt). The slot-free wait above covers candlist, state and items of this slot;
+            // shorter (profiles/screen_exact_behind_sweep.txt). The open rows of the whole launch go into one packed list, cut into items
+            // of 256 per run of pairs onto one train frame (the comment above match_opencount_kernel), and the exact pass is the exact
+            // sweep itself with gathered query rows, a workgroup per item: the train tile staged once in LDS for four waves, where
+            // match_colverify_kernel<8, true> fetched it per wave from L2 (profiles/open_rows_packed.txt: 1.70 -> 0.69 ms per step).
+            // The list lives in the slot's rowcand area ({pair, row} is a uint2, one per stored row per pair at the most), which
+            // match_rows2_kernel first writes on the second stream behind ev_tile; {first, count} items: at most row_stride / 64 + 1
+            // per pair, the items area holds row_stride / 32. The slot-free wait above covers rowcand, state and items of this slot;
             // the HBM-bound tail stays on the second stream.
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st1);
-            int* candlist = (int*)(ws + pl.off_candlist);
+            uint2* cands = (uint2*)(ws + pl.off_rowcand);
             int4* state = (int4*)(ws + pl.off_state);
             int2* items = (int2*)(ws + pl.off_items);
-            match_openlist_kernel<<<(nb + LIST_WAVES - 1) / LIST_WAVES, 64 * LIST_WAVES, 0, st1>>>(
-                ctx->frame_table_dev, pb, nb, (const unsigned long long*)(ws + pl.off_openmask), pl.mask_stride, pl.row_stride, candlist, state, items, n_pre,
-                screen_tally(ctx));
-            match_colverify_kernel<SCREEN_EXACT_KS, true><<<vgrid, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
-                                                                                         pl.row_stride, 0, nullptr, rowres);
+            const unsigned long long* openmask = (const unsigned long long*)(ws + pl.off_openmask);
+            const int lgrid = (nb + LIST_WAVES - 1) / LIST_WAVES;
+            match_opencount_kernel<<<lgrid, 64 * LIST_WAVES, 0, st1>>>(ctx->frame_table_dev, pb, nb, openmask, pl.mask_stride, state, screen_tally(ctx));
+            match_openscan_kernel<<<1, OSCAN_THREADS, 0, st1>>>(pb, nb, GATHER_WIDTH, state, items, n_pre, screen_tally(ctx));   // writes *n_pre
+            match_openfill_kernel<<<lgrid, 64 * LIST_WAVES, 0, st1>>>(ctx->frame_table_dev, pb, nb, openmask, pl.mask_stride, state, cands);
+            const int ggrid = nb * ((pl.row_stride + GATHER_WIDTH - 1) / GATHER_WIDTH + 1);   // an upper bound of the items: workgroups past the list leave at once
+            match_sweep_kernel<SCREEN_EXACT_KS, false, true><<<ggrid, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, 0, rowres, pl.row_stride,
+                                                                                           GatherList<true>{cands, items, n_pre});
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
@@ -2418,6 +2569,18 @@ int eacham_match_debug_screen(eacham_ctx* ctx, int64_t* rows, int64_t* open) {
     EACHAM_HIP_TRY(ctx, hipMemcpy(tot, screen_tally(ctx), sizeof(tot), hipMemcpyDeviceToHost));
     *rows = (int64_t)tot[0];
     *open = (int64_t)tot[1];
+    return EACHAM_OK;
+}
+
+int eacham_match_debug_screen_items(eacham_ctx* ctx, int64_t* items) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    (void)hipSetDevice(ctx->device);
+    if (!items) return ctx->fail(EACHAM_ERR_INVALID, "null output");
+    unsigned long long n = 0;
+    EACHAM_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    EACHAM_HIP_TRY(ctx, hipMemcpy(&n, screen_tally(ctx) + 2, sizeof(n), hipMemcpyDeviceToHost));
+    *items = (int64_t)n;
     return EACHAM_OK;
 }
 

@@ -159,6 +159,13 @@ class HipContext:
         self._check(self._L.eacham_match_debug_screen(self._h, C.byref(r), C.byref(o)))
         return r.value, o.value
 
+    def match_screen_items(self) -> int:
+        """Work items the exact pass of the last matching call took those open rows in, over all its launches
+        (eacham_match_debug_screen_items): up to 256 open rows of consecutive pairs that share their train frame per item."""
+        n = C.c_int64(0)
+        self._check(self._L.eacham_match_debug_screen_items(self._h, C.byref(n)))
+        return n.value
+
     def match_screen_pair(self, f1: int, f2: int):
         """(n1, L1, U2) per row of f1, as the screen sweep writes them for the ordered pair (f1, f2) before the exact pass
         (eacham_match_debug_screen_pair): the smallest squared code difference, a lower bound of the row's smallest squared

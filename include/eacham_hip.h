@@ -152,6 +152,11 @@ int eacham_match_debug_colprune(eacham_ctx* ctx, int64_t* settled, int64_t* veri
  * went to the exact pass. Both 0 when the call ran another form. Waits for the context's stream. */
 int eacham_match_debug_screen(eacham_ctx* ctx, int64_t* rows, int64_t* open);
 
+/* Debug getter (tests, A/B runs), beside eacham_match_debug_screen: *items = work items of the exact pass over those open rows in the
+ * LAST matching call, summed over its launches. An item holds up to 256 open rows of consecutive pairs of one launch that share their
+ * train frame. 0 when the call ran another form. Waits for the context's stream. */
+int eacham_match_debug_screen_items(eacham_ctx* ctx, int64_t* items);
+
 /* Debug entry (tests): the screen sweep alone on the ordered pair (f1, f2), before any exact pass. Per row q of f1 (cap >= its rows):
  * n1[q] = the smallest |M_q - M_t|^2 over the rows t of f2 on the FP6 grid (~0 without a real row), l1[q] <= the row's true
  * smallest squared distance, u2[q] >= its true second smallest (-1 where the sweep wrote a padding value: no row, or the minima
