@@ -169,6 +169,7 @@ constexpr float SCREEN_PAD = 8388608.0f;     // 2^23: exact in f32, above any n 
 constexpr int SCREEN_KS = 4;                 // K = 64 steps of a 256-D row
 constexpr int SCREEN_EXACT_KS = 8;           // int8 K = 32 steps of the same row: the exact pass behind the screen (frames_have_screen)
 constexpr int SCREEN_STEP_BYTES = 1536, SCREEN_TILE_BYTES = SCREEN_KS * SCREEN_STEP_BYTES;
+constexpr int SCREEN_CALL_TILES = 2;         // train tiles between two barriers of the screen sweep: 16 MFMAs per wave, the int8 sweep's ratio
 __global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, int npad, const int* __restrict__ orig,
                                        char* __restrict__ image, int* __restrict__ msq, int* __restrict__ sr) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -945,8 +946,10 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
 // predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane. match_opencount_kernel /
 // match_openscan_kernel / match_openfill_kernel turn the words of a launch (256 B per pair where its rowres is 32 KB) into one packed candidate list.
-// LDS-DMA ring (three slots of 6 KiB), just-in-time fragment ring, double-buffered accumulators and the six-tiles-per-trip loop are
-// match_sweep_kernel's; a fragment is 24 bytes, two LDS reads.
+// LDS-DMA ring, just-in-time fragment ring and double-buffered accumulators are match_sweep_kernel's; a fragment is 24 bytes, two
+// LDS reads. The call structure is its own: 8 MFMAs per tile are half the int8 sweep's, so a call covers TWO train tiles between
+// two barriers (six ring slots of 6 KiB, three calls per trip), the four waves stage three pieces each spread over the call, and
+// every wait inside a call is a counted one (see the call below; profiles/screen_two_tiles.txt).
 // ------------------------------------------------------------------------------------------------
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v6i __attribute__((ext_vector_type(6)));
@@ -976,8 +979,10 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
     constexpr float BIGF = 3.0e38f;
     constexpr int SCALE = (int)0x82828282u;   // E8M0 2^3 in every byte, both operands: e2m3 numbers become the integers M, products -M_a M_b
-    __shared__ v4i sB[3][TILE_V4];
-    __shared__ __attribute__((aligned(16))) float sHb[3][32];  // |M_b|^2 / 2 of the tile in the same ring slot: the C-init of its chains
+    constexpr int NT = SCREEN_CALL_TILES, RING = 3 * NT;   // tile v of the train frame lives in ring slot v % RING
+    static_assert(NT == 2 && KS == 4 && NT * 32 == 64, "the waits of a call are counted for two tiles of four steps; wave 0 carries the constants of a call");
+    __shared__ v4i sB[RING][TILE_V4];
+    __shared__ __attribute__((aligned(16))) float sHb[RING][32];  // |M_b|^2 / 2 of the tile in the same ring slot: the C-init of its chains
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1018,26 +1023,35 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
 
     static_assert(TILE_V4 % 64 == 0, "a tile is a whole number of 1 KiB pieces");
     constexpr int PIECES = TILE_V4 / 64;
-    constexpr int PPW = (PIECES + WAVES - 1) / WAVES;
+    static_assert((NT * PIECES) % WAVES == 0, "every wave stages the same number of pieces per call");
+    constexpr int PPW = NT * PIECES / WAVES;   // 3: piece i of a wave is piece wave + WAVES i of the call's NT tiles, the earlier tile first
+    const int TM = T - 1;
     // (the lane offsets of the staging and of the constants' load are kept opaque: added to the frame's base ahead of the loop they
-    // would be held as two 64-bit per-lane addresses through the sweep)
-    unsigned stage_off = (unsigned)(wave * PPW * 64 + lane) * 16u, hb_off = (unsigned)tid * 4u;
-    auto stage_tile = [&](int tile, int slot) {
-        const gbytes_t base = Bimg + (size_t)tile * SCREEN_TILE_BYTES;
+    // would be held as 64-bit per-lane addresses through the sweep)
+    unsigned stage_off = (unsigned)lane * 16u, hb_off = (unsigned)(lane & 31) * 4u;
+    // one 1 KiB piece of train tile `tile` (clamped: tile T - 1 again past the end) into ring slot `slot`; all three are wave-uniform
+    auto stage_piece = [&](int tile, int slot, int piece) {
+        const gbytes_t base = Bimg + (size_t)min(tile, TM) * SCREEN_TILE_BYTES + piece * 1024;
         asm volatile("" : "+v"(stage_off));
-#pragma unroll
-        for (int i = 0; i < PPW; ++i) {
-            const int piece = wave * PPW + i;
-            if (piece < PIECES)
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + stage_off + i * 1024),
-                                                 (__attribute__((address_space(3))) void*)(&sB[slot][piece * 64]), 16, 0, 0);
-        }
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(base + stage_off),
+                                         (__attribute__((address_space(3))) void*)(&sB[slot][piece * 64]), 16, 0, 0);
     };
+    // the constants of tile `tile` + (lane / 32), clamped, one per lane of wave 0: loaded a call before they are stored to the ring
+    auto load_hb = [&](int tile) {
+        asm volatile("" : "+v"(hb_off));
+        const gbytes_t row = reinterpret_cast<gbytes_t>(Bm2) + (size_t)128 * min(tile + (lane >> 5), TM);
+        return *reinterpret_cast<gfloat_t>(row + hb_off);
+    };
+    float hb_new = 0.0f;
     if (T > 0) {
-        stage_tile(0, 0);
-        stage_tile(min(1, T - 1), 1);
-        stage_tile(min(2, T - 1), 2);
-        if (tid < 96) sHb[tid >> 5][tid & 31] = Bm2[32 * min(tid >> 5, T - 1) + (tid & 31)];
+        // tiles 0 .. 2 NT: the first call stages the next two into the slot of tile 0 and the one still empty
+#pragma unroll
+        for (int i = 0; i < ((2 * NT + 1) * PIECES + WAVES - 1) / WAVES; ++i) {
+            const int idx = wave + WAVES * i;
+            if (idx < (2 * NT + 1) * PIECES) stage_piece(idx / PIECES, idx / PIECES, idx % PIECES);
+        }
+        if (tid < 32 * (NT + 2)) sHb[tid >> 5][tid & 31] = Bm2[32 * min(tid >> 5, TM) + (tid & 31)];
+        if (wave == 0) hb_new = load_hb(NT + 2);   // stored at the head of the first call
     }
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
@@ -1077,6 +1091,29 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     };
 #pragma unroll
     for (int i = 0; i < 3; ++i) bq[i].lo = v4i{0, 0, 0, 0}, bq[i].hi = v2i{0, 0};
+    // this lane's bytes in the two planes of slot 0, step 0: slot and step are immediate offsets of the reads
+    unsigned lds16 = lds_addr(sBb) + 16u * lane, lds8 = lds_addr(sBb) + 8u * lane;
+    asm volatile("" : "+v"(lds16), "+v"(lds8));
+    // Inside the sweep every LDS operation is one the compiler does not track, so that every wait is a counted one placed here: the
+    // fragments, the C-init of the chains after next (ci: read into the registers of the accumulators just consumed, joined into the
+    // accumulator at the wait of the half that issues its chains) and wave 0's store of the constants.
+    unsigned hb_rd = lds_addr(&sHb[0][4 * h]), hb_wr = lds_addr(&sHb[0][0]) + 4u * lane;
+    asm volatile("" : "+v"(hb_rd), "+v"(hb_wr));
+    v4f ci[NSUB][4];
+#pragma unroll
+    for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ci[s][g] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    auto cinit_issue = [&](int s, int slot) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) lds_read_frag(ci[s][g], hb_rd, 128 * slot + 32 * g);
+    };
+    // lgkmcnt(0) on everything the sweep may have in flight (ahead of the first call, and behind the last)
+    auto drain_lds = [&]() {
+        asm volatile("s_waitcnt lgkmcnt(0)"
+                     : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi), "+v"(ci[0][0]), "+v"(ci[0][1]),
+                       "+v"(ci[0][2]), "+v"(ci[0][3]), "+v"(ci[1][0]), "+v"(ci[1][1]), "+v"(ci[1][2]), "+v"(ci[1][3]));
+    };
     if (T > 0 && active) {
         const v16f c0 = cinit_of(0);
 #pragma unroll
@@ -1085,88 +1122,127 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
 #pragma unroll
             for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
         }
-        bq[0] = read_plain(1, 0);   // the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never read)
-        bq[1] = read_plain(1, 1);
+        // the constants and the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never consumed)
 #pragma unroll
-        for (int s = 0; s < NSUB; ++s) accB[s] = cinit_of(1);
+        for (int s = 0; s < NSUB; ++s) cinit_issue(s, 1);
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            lds_read_frag(bq[ks].lo, lds16, SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES);
+            lds_read_frag64(bq[ks].hi, lds8, SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 1024);
+        }
+        drain_lds();
     }
     __syncthreads();   // slot 0 is staged into again by the first call below
-    // this lane's bytes in the two planes of slot 0, step 0: slot and step are immediate offsets of the reads
-    unsigned lds16 = lds_addr(sBb) + 16u * lane, lds8 = lds_addr(sBb) + 8u * lane;
-    asm volatile("" : "+v"(lds16), "+v"(lds8));
-    // keys of tile t handled by step ks of tile t + 1's MFMAs: all 32 within the first KS - 1 steps, so that the accumulators are
-    // free for tile t + 2's constants a step before the call's drain
+    // keys of a tile handled by step ks of the next tile's MFMAs: all 32 within the first KS - 1 steps, so that the accumulators are
+    // free for the constants of the tile after next a step before the half ends
     auto key_lo = [](int ks) constexpr { return ks >= KS - 1 ? 32 : (32 * ks + KS - 2) / (KS - 1); };
     // accumulators 4 g .. 4 g + 3 of sub-tile idx / 16 -> the running minimum of that group and tile parity, two at a time
     auto consume = [&](const v16f(&cur)[NSUB], float(&m)[NSUB][4], const int idx) {
         const int ph = idx / 16, eg = idx % 16;
         if (eg & 1) m[ph][eg >> 2] = fmin3(m[ph][eg >> 2], cur[ph][eg - 1], cur[ph][eg]);
     };
-    // One call: epilogue of tile t (held in `cur`), MFMAs of tile t + 1 into `nxt`, tile t + 3 staged into tile t's ring slot, the
-    // first fragments and the constants of tile t + 2 fetched at the end and drained before the call's barrier (match_sweep_kernel).
-    auto tile = [&](auto PHc, auto SLc, auto PARc, const int t) {
-        constexpr int PH = decltype(PHc)::value, SL = decltype(SLc)::value, PAR = decltype(PARc)::value;
-        constexpr int slot_nxt = (SL + 1) % 3, slot_nn = (SL + 2) % 3;
-        v16f(&cur)[NSUB] = PAR ? accB : accA;
-        v16f(&nxt)[NSUB] = PAR ? accA : accB;
-        const int t3 = min(t + 3, T - 1);
-        asm volatile("" : "+v"(hb_off));
-        const float hb_new = (tid < 32) ? *reinterpret_cast<gfloat_t>(reinterpret_cast<gbytes_t>(Bm2 + 32 * t3) + hb_off) : 0.0f;   // lands during this call; stored to the ring before the barrier
-        stage_tile(t3, SL);
-        if (active) {
+    // One call covers NT = 2 train tiles between two barriers (t even, the tile whose chains accA holds; K3 = call mod 3 gives the ring
+    // slots and the phase of the fragment ring, which advances NT KS = 8 steps per call). Half 0: epilogue of tile t from accA under the
+    // chains of tile t + 1 into accB; half 1: epilogue of tile t + 1 from accB under the chains of tile t + 2 into accA — the roles
+    // are back where they started, and xm is indexed by the half. Step i of the eight waits for fragment i, issues fragment i + 2
+    // (the last two are the first of tile t + 3) and, as a set of accumulators is consumed, the C-init of the tile after next into ci.
+    // The LDS queue of a wave is in order and every operation in it is issued here, so every wait is counted: behind the fragment
+    // of step ks of a half were issued
+    //     ks 0   the C-init of the second sub-tile (4), the fragment of step 1 (2): the chains start on that C-init   lgkmcnt(2)
+    //     ks 1   the fragment of step 2 (2)                                                                           lgkmcnt(2)
+    //     ks 2   the fragment of step 3 (2), the C-init of the first sub-tile (4)                                     lgkmcnt(6)
+    //     ks 3   that C-init (4), the fragment of the next step 0 (2), the C-init of the second sub-tile (4)          lgkmcnt(10)
+    // (wave 0's store of the constants at the head of the call is one more operation behind some of them: a wait that asks for more
+    // than it needs). Nothing is drained at the barrier: the two fragments and the C-init in flight read slots that the next call
+    // does not stage into.
+    // Staging: the call stages tiles t + 2 NT + 1 and t + 2 NT + 2 into the slots of tiles t - 1 and t (read for the last time
+    // ahead of the previous barrier), three pieces per wave behind steps 0, 2 and 4, the earlier tile's first. The earlier tile is
+    // read from step 6 of the NEXT call on, the later one a call after that: before the barrier a wave waits for all but the last
+    // piece it issued (vmcnt(1): every wave's last piece belongs to the later tile), so a piece has between half a call and a call
+    // and a half to land. Wave 0 loads the constants of tiles t + 2 NT + 2 / + 3 first (the oldest entry of its counter), stores
+    // them at the head of the next call, and they are read from the call after that on.
+    auto call = [&](auto K3c, const int t) {
+        constexpr int K3 = decltype(K3c)::value;
+        constexpr int BASE = NT * K3;                 // ring slot of tile t
+        constexpr int PH = (K3 * ((NT * KS) % 3)) % 3;
+        auto stage = [&](int i) {
+            const int idx = wave + WAVES * i, later = idx >= PIECES ? 1 : 0;
+            stage_piece(t + 2 * NT + 1 + later, later ? (BASE + 2 * NT + 2) % RING : (BASE + 2 * NT + 1) % RING, idx - PIECES * later);
+        };
+        if (wave == 0) {
+            asm volatile("ds_write_b32 %0, %1 offset:%2" : : "v"(hb_wr), "v"(hb_new), "n"(((BASE + NT + 2) % RING) * 128) : "memory");
+            hb_new = load_hb(t + 2 * NT + 2);
+        }
+        auto half = [&](auto HHc) {
+            constexpr int HH = decltype(HHc)::value;
+            v16f(&cur)[NSUB] = HH ? accB : accA;
+            v16f(&nxt)[NSUB] = HH ? accA : accB;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
-                // the fragment of step ks has landed (the two reads of step ks + 1 may be in flight)
-                asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(bq[(ks + PH) % 3].lo), "+v"(bq[(ks + PH) % 3].hi));
-                const int j = ks + 2;
-                lds_read_frag(bq[(j + PH) % 3].lo, lds16, (j < KS ? slot_nxt : slot_nn) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES);
-                lds_read_frag64(bq[(j + PH) % 3].hi, lds8, (j < KS ? slot_nxt : slot_nn) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES + 1024);
+                const int i = HH * KS + ks, j = i + 2;
+                ScreenFrag& f = bq[(i + PH) % 3];
+                if (ks == 0) {
+                    asm volatile("s_waitcnt lgkmcnt(2)"
+                                 : "+v"(f.lo), "+v"(f.hi), "+v"(ci[0][0]), "+v"(ci[0][1]), "+v"(ci[0][2]), "+v"(ci[0][3]), "+v"(ci[1][0]),
+                                   "+v"(ci[1][1]), "+v"(ci[1][2]), "+v"(ci[1][3]));
 #pragma unroll
-                for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(bq[(ks + PH) % 3], a[s][ks], nxt[s]);
+                    for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) nxt[s][r] = ci[s][r >> 2][r & 3];
+                } else if (ks == 1) {
+                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi));
+                } else if (ks == 2) {
+                    asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.lo), "+v"(f.hi));
+                } else {
+                    asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(f.lo), "+v"(f.hi));
+                }
+                const int off = ((BASE + 1 + j / KS) % RING) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES;
+                lds_read_frag(bq[(j + PH) % 3].lo, lds16, off);
+                lds_read_frag64(bq[(j + PH) % 3].hi, lds8, off + 1024);
+#pragma unroll
+                for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][ks], nxt[s]);
 #pragma unroll
                 for (int idx = key_lo(ks); idx < key_lo(ks + 1); ++idx) {
-                    consume(cur, xm[PAR], idx);
-                    if (idx % 16 == 15) cur[idx / 16] = cinit_of(slot_nn);   // done with these accumulators: tile t + 2's constants, for the next call's chains
+                    consume(cur, xm[HH], idx);
+                    if (idx % 16 == 15) cinit_issue(idx / 16, (BASE + HH + 2) % RING);   // done with these accumulators: the constants of the tile after next
                 }
+                if (i % 2 == 0 && i / 2 < PPW) stage(i / 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi));
+        };
+        if (active) {
+            half(std::integral_constant<int, 0>{});
+            half(std::integral_constant<int, 1>{});
+        } else {
+#pragma unroll
+            for (int i = 0; i < PPW; ++i) stage(i);
         }
-        if (tid < 32) sHb[SL][tid] = hb_new;
-        __syncthreads();
+        asm volatile("s_waitcnt vmcnt(1)" : : : "memory");
+        __builtin_amdgcn_s_barrier();
     };
-    // the last tile has nothing to issue and nothing to stage: its epilogue alone (which accumulators hold it is its parity)
-    auto last = [&](auto PARc) {
-        constexpr int PAR = decltype(PARc)::value;
-        v16f(&cur)[NSUB] = PAR ? accB : accA;
+    // a last tile of even index has nothing to issue and nothing to stage: its epilogue alone, from accA
+    auto last = [&]() {
         if (active) {
 #pragma unroll
-            for (int idx = 0; idx < 32; ++idx) consume(cur, xm[PAR], idx);
+            for (int idx = 0; idx < 32; ++idx) consume(accA, xm[0], idx);
         }
     };
     if (T > 0) {
-        constexpr int ADV = KS % 3;
-        const int TM = T - 1;
-        int t = 0;
-        auto run = [&](auto K6c, int tt) {
-            constexpr int K6 = decltype(K6c)::value;
-            tile(std::integral_constant<int, (K6 * ADV) % 3>{}, std::integral_constant<int, K6 % 3>{}, std::integral_constant<int, K6 % 2>{}, tt);
-        };
-        for (; t + 6 <= TM; t += 6) {
-            run(std::integral_constant<int, 0>{}, t);
-            run(std::integral_constant<int, 1>{}, t + 1);
-            run(std::integral_constant<int, 2>{}, t + 2);
-            run(std::integral_constant<int, 3>{}, t + 3);
-            run(std::integral_constant<int, 4>{}, t + 4);
-            run(std::integral_constant<int, 5>{}, t + 5);
+        // tiles 1 .. TM have their chains inside a call, tiles 0 .. TM - 1 their epilogue: (TM + 1) / 2 calls. With TM odd the last
+        // call's second half consumes tile TM and runs chains on the ring's copy of it, never consumed; with TM even tile TM is left.
+        const int NC = (TM + 1) / 2;
+        int c = 0;
+        for (; c + 3 <= NC; c += 3) {
+            call(std::integral_constant<int, 0>{}, NT * c);
+            call(std::integral_constant<int, 1>{}, NT * (c + 1));
+            call(std::integral_constant<int, 2>{}, NT * (c + 2));
         }
-        if (t < TM) run(std::integral_constant<int, 0>{}, t);
-        if (t + 1 < TM) run(std::integral_constant<int, 1>{}, t + 1);
-        if (t + 2 < TM) run(std::integral_constant<int, 2>{}, t + 2);
-        if (t + 3 < TM) run(std::integral_constant<int, 3>{}, t + 3);
-        if (t + 4 < TM) run(std::integral_constant<int, 4>{}, t + 4);
-        if (TM & 1) last(std::integral_constant<int, 1>{});
-        else last(std::integral_constant<int, 0>{});
+        if (c < NC) call(std::integral_constant<int, 0>{}, NT * c);
+        if (c + 1 < NC) call(std::integral_constant<int, 1>{}, NT * (c + 1));
+        // nothing may land in a register or in this workgroup's LDS once the sweep is over
+        asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
+        drain_lds();
+        if (!(TM & 1)) last();
     }
     if (!active) return;
     // join the partner lane (the same query row against the other half of every tile's train rows) and the tile parities: the two
