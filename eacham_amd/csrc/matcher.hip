@@ -1072,9 +1072,13 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         }
         return c;
     };
+    // (the scale is held in one register through the sweep: set up again inside a call it took the register of wave 0's load of the
+    // constants, and the compiler put a vmcnt(0) in front of it that drained every wave's staging)
+    int scale = SCALE;
+    asm volatile("" : "+v"(scale));
     auto mfma = [&](const ScreenFrag& b, const v6i& q, const v16f& c) {
         const v8i q8 = __builtin_shufflevector(q, q, 0, 1, 2, 3, 4, 5, -1, -1);
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, SCALE, 0, SCALE);
+        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, scale, 0, scale);
     };
     v16f accA[NSUB], accB[NSUB];
 #pragma unroll
@@ -1095,24 +1099,24 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     unsigned lds16 = lds_addr(sBb) + 16u * lane, lds8 = lds_addr(sBb) + 8u * lane;
     asm volatile("" : "+v"(lds16), "+v"(lds8));
     // Inside the sweep every LDS operation is one the compiler does not track, so that every wait is a counted one placed here: the
-    // fragments, the C-init of the chains after next (ci: read into the registers of the accumulators just consumed, joined into the
-    // accumulator at the wait of the half that issues its chains) and wave 0's store of the constants.
+    // fragments, the C-init of the chains after next (ci: read into registers of the accumulators just consumed, handed to the first
+    // MFMAs as their C operand behind the wait of the half that issues its chains) and wave 0's store of the constants.
     unsigned hb_rd = lds_addr(&sHb[0][4 * h]), hb_wr = lds_addr(&sHb[0][0]) + 4u * lane;
     asm volatile("" : "+v"(hb_rd), "+v"(hb_wr));
-    v4f ci[NSUB][4];
+    // A lane's 16 constants depend on the tile and on its half h only, so ONE set serves both query sub-tiles: it is the C operand of
+    // both first chain steps, of which one writes accumulators of its own (D != C) and the other continues in ci's registers.
+    v4f ci[4];
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s)
+    for (int g = 0; g < 4; ++g) ci[g] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    auto cinit_issue = [&](int slot) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) ci[s][g] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
-    auto cinit_issue = [&](int s, int slot) {
-#pragma unroll
-        for (int g = 0; g < 4; ++g) lds_read_frag(ci[s][g], hb_rd, 128 * slot + 32 * g);
+        for (int g = 0; g < 4; ++g) lds_read_frag(ci[g], hb_rd, 128 * slot + 32 * g);
     };
     // lgkmcnt(0) on everything the sweep may have in flight (ahead of the first call, and behind the last)
     auto drain_lds = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi), "+v"(ci[0][0]), "+v"(ci[0][1]),
-                       "+v"(ci[0][2]), "+v"(ci[0][3]), "+v"(ci[1][0]), "+v"(ci[1][1]), "+v"(ci[1][2]), "+v"(ci[1][3]));
+                     : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi), "+v"(ci[0]), "+v"(ci[1]),
+                       "+v"(ci[2]), "+v"(ci[3]));
     };
     if (T > 0 && active) {
         const v16f c0 = cinit_of(0);
@@ -1123,8 +1127,7 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
             for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
         }
         // the constants and the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never consumed)
-#pragma unroll
-        for (int s = 0; s < NSUB; ++s) cinit_issue(s, 1);
+        cinit_issue(1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
             lds_read_frag(bq[ks].lo, lds16, SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES);
@@ -1145,13 +1148,17 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     // slots and the phase of the fragment ring, which advances NT KS = 8 steps per call). Half 0: epilogue of tile t from accA under the
     // chains of tile t + 1 into accB; half 1: epilogue of tile t + 1 from accB under the chains of tile t + 2 into accA — the roles
     // are back where they started, and xm is indexed by the half. Step i of the eight waits for fragment i, issues fragment i + 2
-    // (the last two are the first of tile t + 3) and, as a set of accumulators is consumed, the C-init of the tile after next into ci.
-    // The LDS queue of a wave is in order and every operation in it is issued here, so every wait is counted: behind the fragment
-    // of step ks of a half were issued
-    //     ks 0   the C-init of the second sub-tile (4), the fragment of step 1 (2): the chains start on that C-init   lgkmcnt(2)
-    //     ks 1   the fragment of step 2 (2)                                                                           lgkmcnt(2)
-    //     ks 2   the fragment of step 3 (2), the C-init of the first sub-tile (4)                                     lgkmcnt(6)
-    //     ks 3   that C-init (4), the fragment of the next step 0 (2), the C-init of the second sub-tile (4)          lgkmcnt(10)
+    // (the last two are the first of tile t + 3) and, once per half, the C-init of the tile after next into ci: four ds_read_b128
+    // behind the last key of the tile being consumed, at step 2. One set of constants starts the chains of both query sub-tiles (a
+    // lane's sixteen depend on the tile and its half h alone), and ci's registers went to a chain at step 0 of the half.
+    // The LDS queue of a wave is in order and every operation in it is issued here, so every wait is counted. A half issues
+    //     step 0: F2    step 1: F3    step 2: F4, C    step 3: F5          (F_k: the two reads of the fragment of step k, F4 / F5 the
+    //                                                                       next half's steps 0 / 1; C: the four reads of the C-init)
+    // so that behind the fragment of step ks were issued
+    //     ks 0   the C-init (4, needed too: the chains start on it), the fragment of step 1 (2)   lgkmcnt(2)
+    //     ks 1   the fragment of step 2 (2)                                                        lgkmcnt(2)
+    //     ks 2   the fragment of step 3 (2)                                                        lgkmcnt(2)
+    //     ks 3   the fragment of the next step 0 (2), the C-init (4)                               lgkmcnt(6)
     // (wave 0's store of the constants at the head of the call is one more operation behind some of them: a wait that asks for more
     // than it needs). Nothing is drained at the barrier: the two fragments and the C-init in flight read slots that the next call
     // does not stage into.
@@ -1181,30 +1188,34 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
             for (int ks = 0; ks < KS; ++ks) {
                 const int i = HH * KS + ks, j = i + 2;
                 ScreenFrag& f = bq[(i + PH) % 3];
-                if (ks == 0) {
-                    asm volatile("s_waitcnt lgkmcnt(2)"
-                                 : "+v"(f.lo), "+v"(f.hi), "+v"(ci[0][0]), "+v"(ci[0][1]), "+v"(ci[0][2]), "+v"(ci[0][3]), "+v"(ci[1][0]),
-                                   "+v"(ci[1][1]), "+v"(ci[1][2]), "+v"(ci[1][3]));
-#pragma unroll
-                    for (int s = 0; s < NSUB; ++s)
-#pragma unroll
-                        for (int r = 0; r < 16; ++r) nxt[s][r] = ci[s][r >> 2][r & 3];
-                } else if (ks == 1) {
-                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi));
-                } else if (ks == 2) {
-                    asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.lo), "+v"(f.hi));
-                } else {
-                    asm volatile("s_waitcnt lgkmcnt(10)" : "+v"(f.lo), "+v"(f.hi));
-                }
                 const int off = ((BASE + 1 + j / KS) % RING) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES;
+                if (ks == 0) {
+                    // the fragment of this step and, behind it, the C-init were issued at step 2 of the half before: younger is the fragment of step 1
+                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi), "+v"(ci[0]), "+v"(ci[1]), "+v"(ci[2]), "+v"(ci[3]));
+                } else if (ks < KS - 1) {
+                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi));   // issued two steps ago; younger: the fragment of the next step
+                } else {
+                    // issued at step 1; younger: the fragment of the next step 0 (2) and the C-init (4), both issued at step 2
+                    asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.lo), "+v"(f.hi));
+                }
                 lds_read_frag(bq[(j + PH) % 3].lo, lds16, off);
                 lds_read_frag64(bq[(j + PH) % 3].hi, lds8, off + 1024);
+                if (ks == 0) {
+                    // both chains start on the one set of constants: the first sub-tile's writes registers of its own (D != C), the second
+                    // sub-tile's goes on in those of the constants, dead behind it
+                    v16f c0;
 #pragma unroll
-                for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][ks], nxt[s]);
+                    for (int r = 0; r < 16; ++r) c0[r] = ci[r >> 2][r & 3];
+#pragma unroll
+                    for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][0], c0);
+                } else {
+#pragma unroll
+                    for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][ks], nxt[s]);
+                }
 #pragma unroll
                 for (int idx = key_lo(ks); idx < key_lo(ks + 1); ++idx) {
                     consume(cur, xm[HH], idx);
-                    if (idx % 16 == 15) cinit_issue(idx / 16, (BASE + HH + 2) % RING);   // done with these accumulators: the constants of the tile after next
+                    if (idx == 31) cinit_issue((BASE + HH + 2) % RING);   // both accumulator sets are free: the constants of the tile after next
                 }
                 if (i % 2 == 0 && i / 2 < PPW) stage(i / 2);
                 __builtin_amdgcn_sched_barrier(0);
