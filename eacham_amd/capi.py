@@ -69,6 +69,8 @@ def lib() -> C.CDLL:
     L.eacham_match_pairs_directed.argtypes = [vp, vp, i32, dbl, vp, vp, vp, vp, i64, C.POINTER(i64)]
     L.eacham_match_all_pairs_dev.argtypes = [vp, vp, i32, dbl, i32, i32, vp, vp, vp, i64, vp, vp]
     L.eacham_match_debug_batches.argtypes = [vp, i32, i32, vp, i32, C.POINTER(i32), C.POINTER(i32)]
+    if hasattr(L, "eacham_match_debug_plan"):      # (absent from older builds selected with EACHAM_HIP_LIB)
+        L.eacham_match_debug_plan.argtypes = [vp, i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]
     if hasattr(L, "eacham_match_debug_colprune"):  # (absent from older builds selected with EACHAM_HIP_LIB)
         L.eacham_match_debug_colprune.argtypes = [vp, C.POINTER(i64), C.POINTER(i64)]
     if hasattr(L, "eacham_match_debug_screen"):

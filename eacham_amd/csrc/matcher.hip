@@ -1629,7 +1629,13 @@ __global__ __launch_bounds__(64 * LIST_WAVES) void match_openfill_kernel(const F
 // every column but the best one is at least the runner-up). match_argmin_kernel settles candidate columns with it.
 constexpr int MAX_TILES = MAX_ROWS / 32;
 constexpr int AITEM_SHARED = 1 << 16;   // aitems[..].y: the tile, plus this flag when the pair has more than one item of that tile
-template <int METRIC>
+// OPEN = true (mode 0 behind the SCREEN form of the sweep only): every candidate is a row the screen left open, and state[p].x still
+// holds their number (match_opencount_kernel; match_openscan_kernel kept it). A pair with no more than min_mutual open rows is dead
+// whatever its rows hold (nine pairs in ten of S200), so it gets a dead pair's state — not live, no arg-min item, which is all that
+// match_colpick_kernel and match_finalize2_kernel read of it (count 0) — without one byte of its 32 KB of rowres; its rowcand,
+// candlist and L(p) are left out, nothing reads them for a dead pair. The count is read by every thread and its word is stored
+// back unchanged, so the one store needs no barrier ahead of it.
+template <int METRIC, bool OPEN = false>
 __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand, int* __restrict__ candlist, int* __restrict__ bytile,
@@ -1640,6 +1646,13 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     __shared__ int s_aitem0, s_low;
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
+    if constexpr (OPEN) {
+        const int open = ((const int*)&state[p])[0];
+        if (open <= min_mutual) {   // workgroup-uniform
+            if (tid == 0) state[p] = make_int4(open, 0, 0x7fffffff, 0);
+            return;
+        }
+    }
     const int2 pr = pairs[p];
     const FrameDev A = frames[pr.x], B = frames[pr.y];
     const int A_even = A.meta[0], A_tiles = A.meta[1], B_tiles = B.meta[1];
@@ -2170,6 +2183,8 @@ static bool frames_have_screen(const eacham_ctx* ctx) {
 struct MatchPlan {
     int batch;       // pairs per launch
     int round_pairs; // pairs of one round of 512 workgroups (launches are sized in whole rounds)
+    int tail_pairs;  // the job's short last launch holds this many pairs at the most
+    int full_launches, full_rounds, long_launches;   // the cut of a job through two slots (make_plan, next_batch)
     int wb_stride;   // wave-blocks per frame (max over resident frames)
     int row_stride;  // padded rows per frame (max)
     int wgs_per_pair;
@@ -2209,8 +2224,22 @@ static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     // of its first half runs beside the tile kernel of the second
     if (batch >= npairs && npairs >= 8 * round_pairs) batch = ((npairs + 1) / 2 + round_pairs - 1) / round_pairs * round_pairs;
     pl.batch = std::max(batch, 1);
-    pl.round_pairs = round_pairs;
+    pl.round_pairs = pl.batch % round_pairs == 0 ? round_pairs : 1;   // (a budget below one round: launches are sized in pairs)
     pl.slots = (pl.batch < npairs && !ctx->match_no_overlap) ? 2 : 1;  // (diagnostic switch, read once at eacham_ctx_create)
+    // The cut of the whole job, two slots in use: n full launches and ONE short last launch, the only one whose exact pass and
+    // candidate tail nothing hides. The short launch is planned first — the last tail_pairs of the job at the most (an eighth of
+    // a full launch in whole rounds), less whatever fills the full launches up to whole rounds — and the rest is dealt out over as
+    // few launches as the budget allows, equal to a round. So the last launch is never the budget's remnant: full launches with only the
+    // last one shortened had cut S200 into 9 792 + 9 792 + 316 and cut 2 x batch + 1 pairs into batch + batch + 1 (profiles/launch_cut.txt).
+    pl.tail_pairs = std::max(pl.round_pairs, pl.batch / 8 / pl.round_pairs * pl.round_pairs);
+    pl.full_launches = pl.full_rounds = pl.long_launches = 0;
+    if (pl.slots == 2) {
+        const int rp = pl.round_pairs, last_max = std::min(pl.tail_pairs, pl.batch);   // last launch: (last_max - rp, last_max] pairs
+        const int rounds = (npairs - last_max + rp - 1) / rp;                          // of all full launches; >= 1: npairs > batch
+        pl.full_launches = (int)(((long long)rounds * rp + pl.batch - 1) / pl.batch);
+        pl.full_rounds = rounds / pl.full_launches;
+        pl.long_launches = rounds % pl.full_launches;   // the first so many take one round more (then full_rounds * rp < batch)
+    }
     auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
     pl.off_rowres = 0;
     pl.off_colpart = align(pl.off_rowres + (size_t)pl.batch * pl.col_chunks * pl.row_stride * sizeof(int4));
@@ -2232,14 +2261,12 @@ static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     return pl;
 }
 
-// Pairs of the launch that starts at `first`: full batches, the job's last one cut short (an eighth of a full one) when two
-// workspace slots are in use. One definition for run_match and for eacham_match_debug_batches.
-static int next_batch(const MatchPlan& pl, int first, int npairs) {
-    const int tail_pairs = std::max(pl.round_pairs, pl.batch / 8 / pl.round_pairs * pl.round_pairs);
-    int nb = std::min(pl.batch, npairs - first);
-    if (pl.slots == 2 && first + nb == npairs && nb > 2 * tail_pairs)
-        nb = (nb - tail_pairs + pl.round_pairs - 1) / pl.round_pairs * pl.round_pairs;  // leave the tail for one more, short launch
-    return nb;
+// Pairs of launch b, which starts at `first`: the cut make_plan planned for the npairs it was given when two workspace slots are in
+// use (equal full launches, then the short one), else full batches and what is left. One definition for run_match and for
+// eacham_match_debug_batches.
+static int next_batch(const MatchPlan& pl, int b, int first, int npairs) {
+    if (pl.slots == 2 && b < pl.full_launches) return (pl.full_rounds + (b < pl.long_launches ? 1 : 0)) * pl.round_pairs;
+    return std::min(pl.batch, npairs - first);
 }
 
 // Core driver, CSR over the pairs out. mode 0 = mutual + thresholds, mode 1 = directed lists.
@@ -2290,11 +2317,12 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 3 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
-    // batch's sweep — except the last batch's, which nothing hides: the job's last batch is cut short (an eighth of a full one),
-    // so the exposed tail is that of ~1 500 pairs instead of ~10 000 (0.8 ms of a 21 ms S200 step).
+    // batch's sweep — except the last batch's, which nothing hides: the job is cut into equal full batches and a short last one
+    // (an eighth of a full one at the most; make_plan), so the exposed lists, exact pass and tail are those of ~1 200 pairs instead
+    // of ~10 000. S200 under the 1 GiB budget: 9 344 + 9 344 + 1 212 pairs.
     int b = 0;
     for (int first = 0, nb = 0; first < npairs; first += nb, ++b) {
-        nb = next_batch(pl, first, npairs);
+        nb = next_batch(pl, b, first, npairs);
         const int slot = b % pl.slots;
         char* ws = (char*)ctx->ws + (size_t)slot * pl.slot_bytes;
         const int2* pb = pairs_dev + first;
@@ -2380,8 +2408,13 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                         match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
                                                                                         pl.row_stride, 0, nullptr, rowres);
                     }
-                    match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
-                                                                    rowcand, candlist, bytile, state, aitems, n_aitems);
+                    // (mutual matching behind the screen sweep: a pair its open count already fails leaves before it reads a row; L2 only)
+                    if (METRIC == METRIC_L2 && screen_sweep && mode == 0)
+                        match_rows2_kernel<METRIC_L2, true><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual,
+                                                                                  mode, rowcand, candlist, bytile, state, aitems, n_aitems);
+                    else
+                        match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
+                                                                        rowcand, candlist, bytile, state, aitems, n_aitems);
                     match_argmin_kernel<KS, METRIC><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride,
                                                                    mode == 0 ? colres : nullptr, state, ratio, ctx->match_colprune ? 1 : 0);
                     if (mode == 0) {   // the candidates the arg-min pass could not settle (state[p].w of them): listed, then the column pass
@@ -2625,11 +2658,23 @@ int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int3
     MatchPlan pl = make_plan(ctx, std::max(npairs, 1), full_cols);
     int b = 0;
     for (int first = 0, nb = 0; first < npairs; first += nb, ++b) {
-        nb = next_batch(pl, first, npairs);
+        nb = next_batch(pl, b, first, npairs);
         if (b < cap) starts[b] = first;
     }
     *n_batches = b;
     if (n_slots) *n_slots = pl.slots;
+    return EACHAM_OK;
+}
+
+int eacham_match_debug_plan(eacham_ctx* ctx, int npairs, int with_stats, int* batch, int* round_pairs, int* tail_pairs) {
+    if (!ctx) return EACHAM_ERR_INVALID;
+    std::lock_guard<std::mutex> lock(ctx->mu);
+    if (npairs < 0 || !batch || !round_pairs || !tail_pairs) return ctx->fail(EACHAM_ERR_INVALID, "bad arguments to match_debug_plan");
+    if (ctx->kind_common == FRAME_F32) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "the fp32 path plans its batches on its own");
+    const MatchPlan pl = make_plan(ctx, std::max(npairs, 1), with_stats != 0);
+    *batch = pl.batch;
+    *round_pairs = pl.round_pairs;
+    *tail_pairs = pl.tail_pairs;
     return EACHAM_OK;
 }
 

@@ -145,6 +145,13 @@ class HipContext:
         self._check(self._L.eacham_match_debug_batches(self._h, npairs, int(stats), starts.ctypes.data, len(starts), C.byref(nb), C.byref(ns)))
         return starts[:min(nb.value, len(starts))].copy(), ns.value
 
+    def match_plan(self, npairs: int, stats: bool = False):
+        """(batch, round_pairs, tail_pairs): the most pairs of a launch, the unit launches are sized in and the most pairs of a job's
+        short last launch, for a job of `npairs` pairs of the resident frames (eacham_match_debug_plan)."""
+        b, r, t = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._check(self._L.eacham_match_debug_plan(self._h, npairs, int(stats), C.byref(b), C.byref(r), C.byref(t)))
+        return b.value, r.value, t.value
+
     def match_colprune(self):
         """(settled, verified): candidate columns of the last match_all_pairs call that the arg-min pass settled from the row sweep's
         minima / that went through the column pass (eacham_match_debug_colprune)."""

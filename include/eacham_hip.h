@@ -141,6 +141,11 @@ int eacham_match_all_pairs_dev(eacham_ctx* ctx, const int32_t* pairs_dev, int np
  * oracle samples on both sides of every launch boundary of the job of apps/sfm/main.cpp:84-147. */
 int eacham_match_debug_batches(eacham_ctx* ctx, int npairs, int with_stats, int32_t* starts, int cap, int* n_batches, int* n_slots);
 
+/* Debug getter (tests), beside eacham_match_debug_batches: the numbers that cut is made from. *batch = the most pairs a launch may
+ * hold (the workspace budget), *round_pairs = the unit launches are sized in (pairs of one round of workgroups; 1 where the budget
+ * holds less than a round), *tail_pairs = the most pairs the short last launch of a job through two slots holds. */
+int eacham_match_debug_plan(eacham_ctx* ctx, int npairs, int with_stats, int* batch, int* round_pairs, int* tail_pairs);
+
 /* Debug getter (tests, A/B runs): the candidate columns of the LAST eacham_match_all_pairs[_dev] call on this context (lean form,
  * int8 frames) that were settled from the row sweep's minima without computing a distance (*settled) and that went through the
  * column pass (*verified); live pairs only. EACHAM_MATCH_COLPRUNE=0 at eacham_ctx_create sends every candidate down the column
