@@ -23,8 +23,8 @@ KERNEL_BA_SOLVE = 4
 KERNEL_BA_ERROR = 5
 KERNEL_TRIANGULATE = 6
 KERNEL_SCORE = 7
-SCORE_ESSENTIAL, SCORE_HOMOGRAPHY, SCORE_PNP = 0, 1, 2
-SOLVE_HOMOGRAPHY4, SOLVE_ESSENTIAL5 = 0, 1
+SCORE_ESSENTIAL, SCORE_HOMOGRAPHY, SCORE_PNP, SCORE_FUNDAMENTAL = 0, 1, 2, 3
+SOLVE_HOMOGRAPHY4, SOLVE_ESSENTIAL5, SOLVE_FUNDAMENTAL7 = 0, 1, 2
 TWOVIEW_POSES, TWOVIEW_SOLUTIONS = 0, 1
 SAMPLING_OPENCV, SAMPLING_COUNTER = 0, 1
 

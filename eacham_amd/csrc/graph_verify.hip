@@ -10,8 +10,8 @@
 //   gv_draw_counter     a thread per (pair, sample): counter_sample (include/eacham/CvSampling.hpp), the function draw_samples calls
 //   gv_draw_opencv      a thread per pair — the stream restarts from (uint64)-1 for every pair and every draw depends on the ones
 //                       before it: `iterations` cv_get_subset calls of at most 1000 attempts, for the homography with
-//                       cv_check_subset_homography on the pair's gathered points converted to float, as lmeds_samples does it; a
-//                       pair stops where getSubset gives up
+//                       cv_check_subset_homography and for the fundamental matrix with cv_check_subset_fundamental on the pair's
+//                       gathered points converted to float, as lmeds_samples does it; a pair stops where getSubset gives up
 //                       both write the fixed-stride `samples` (npairs x iterations x m, -1 behind a pair's count) and the counts
 //   prim::exclusive_scan of the counts (npairs + 1 entries, the last 0) -> sample_ptr;  gv_compact -> the packed sample_idx
 //   lmeds_launch        (lmeds_batch.hip) the lb_* kernels, unchanged, on these device arrays; the per-problem results land in caller-pair
@@ -20,10 +20,11 @@
 //                       from, which is what eacham_graph_tracks takes as `keep` (bytes that belong to no pair: zero)
 //
 // READ-BACKS. The number of samples is known on the host — (pairs with n >= m) x iterations — except under the OpenCV stream for the
-// homography, where checkSubset can make getSubset give up: then the total (8 bytes) is read back once through the pinned mirror.
+// homography and the fundamental matrix, where checkSubset can make getSubset give up: then the total (8 bytes) is read back once through the pinned mirror.
 // The scratch is sized by the host-known bound either way; the launches cover exactly sample_ptr[npairs] samples.
 #include "context.hpp"
 #include "devprim.hpp"
+#include "solve_launch.hpp"
 #include "../../include/eacham/CvSampling.hpp"
 
 #include <climits>
@@ -74,7 +75,8 @@ __global__ __launch_bounds__(GV) void gv_draw_counter_kernel(int P, int iteratio
     for (int k = 0; k < M; ++k) samples[g * M + k] = idx[k];
 }
 
-template <int M, bool HOMOGRAPHY>
+// CHECK: the callback's checkSubset — 0 none (essential), 1 the homography's, 2 the fundamental matrix's
+template <int M, int CHECK>
 __global__ __launch_bounds__(GV_PAIR) void gv_draw_opencv_kernel(int P, int iterations, const long long* __restrict__ pair_ptr,
                                                                  const double* __restrict__ a, const double* __restrict__ b,
                                                                  int* __restrict__ samples, int* __restrict__ n_samples,
@@ -91,16 +93,17 @@ __global__ __launch_bounds__(GV_PAIR) void gv_draw_opencv_kernel(int P, int iter
         for (; done < iterations; ++done) {
             int32_t idx[M];
             const bool found = hip::cv_get_subset(rng, (int)n, M, idx, 1000, [&](const int32_t* s) {
-                if constexpr (!HOMOGRAPHY) {
+                if constexpr (CHECK == 0) {
                     return true;
                 } else {
-                    float fa[8], fb[8];
+                    float fa[2 * M], fb[2 * M];
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) {
+                    for (int k = 0; k < M; ++k) {
                         fa[2 * k] = (float)pa[2 * (size_t)s[k]], fa[2 * k + 1] = (float)pa[2 * (size_t)s[k] + 1];
                         fb[2 * k] = (float)pb[2 * (size_t)s[k]], fb[2 * k + 1] = (float)pb[2 * (size_t)s[k] + 1];
                     }
-                    return hip::cv_check_subset_homography(fa, fb, 4);
+                    if constexpr (CHECK == 1) return hip::cv_check_subset_homography(fa, fb, M);
+                    else return hip::cv_check_subset_fundamental(fa, fb, M);
                 }
             });
             if (!found) break;
@@ -178,12 +181,13 @@ extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, i
     eacham_ctx* ctx = g->ctx;
     return verify_entry(ctx, "graph_verify", [&]() -> int {
         if (!g->has_xy) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: the graph has no keypoint coordinates (eacham_graph_set_keypoints)");
-        if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown kind %d", kind);
+        if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
+            return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown kind %d", kind);
         if (sampling != EACHAM_SAMPLING_OPENCV && sampling != EACHAM_SAMPLING_COUNTER)
             return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown sampling %d", sampling);
         if (iterations < 0) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: negative iterations");
-        const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4;
-        const int P = g->npairs, m = homography ? 4 : 5, maxm = homography ? 1 : 10;
+        const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4, fundamental = kind == EACHAM_SOLVE_FUNDAMENTAL7;
+        const int P = g->npairs, m = solve_sample_size(kind), maxm = solve_max_models(kind);
         if (P == 0) return EACHAM_OK;
         long long n_ok = 0, max_n = 0;   // pairs with a minimal sample's worth of matches; the largest of them
         for (int p = 0; p < P; ++p)
@@ -193,7 +197,7 @@ extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, i
             return ctx->fail(EACHAM_ERR_CAPACITY, "graph_verify: %lld points / %d pairs x %d samples in one call", NP, P, iterations);
         EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if (retain && !g->keep_mask) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->keep_mask, std::max<size_t>((size_t)g->n_src, 16)));
-        const bool need_rows = lmeds_needs_rows(max_n), count_known = !(homography && sampling == EACHAM_SAMPLING_OPENCV);
+        const bool need_rows = lmeds_needs_rows(max_n), count_known = !((homography || fundamental) && sampling == EACHAM_SAMPLING_OPENCV);
         const long long cand_cap = S_cap * maxm;
         const int score_grid = lmeds_score_grid(cand_cap, max_n);
         hipStream_t st = ctx->stream;
@@ -229,15 +233,18 @@ extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, i
                 const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
                 const unsigned long long* d_seeds = seeds ? d(h_seeds) : nullptr;
                 if (homography) gv_draw_counter_kernel<4><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+                else if (fundamental) gv_draw_counter_kernel<7><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
                 else gv_draw_counter_kernel<5><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
             } else {
                 const unsigned grid = gv_blocks(P, GV_PAIR);
-                if (homography) gv_draw_opencv_kernel<4, true><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-                else gv_draw_opencv_kernel<5, false><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+                if (homography) gv_draw_opencv_kernel<4, 1><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+                else if (fundamental) gv_draw_opencv_kernel<7, 2><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+                else gv_draw_opencv_kernel<5, 0><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
             }
             prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
             if (slots > 0) {
                 if (homography) gv_compact_kernel<4><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+                else if (fundamental) gv_compact_kernel<7><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
                 else gv_compact_kernel<5><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
             }
         }

@@ -5,7 +5,7 @@
 // winner — runs here for n_problems pairs with no host turn between the stages: the inputs go up once, the results come back
 // once, and the number of launches does not depend on n_problems.
 //
-//   solve_minimal_launch        (solve.hip, through solve_launch.hpp) the list instantiation of solve_h4_kernel / solve_e5_kernel — the
+//   solve_minimal_launch        (solve.hip, through solve_launch.hpp) the list instantiation of solve_h4_kernel / solve_e5_kernel / solve_f7_kernel — the
 //                               kernels eacham_solve_minimal launches, not a copy of them: a wave per sample on the sample's own
 //                               problem, found by a binary search in sample_ptr (and left in sample_problem[] for the stages below);
 //                               a problem with fewer points than a minimal sample has no candidates
@@ -32,8 +32,9 @@
 namespace eacham {
 namespace {
 
-// KIND 0 = essential (Sampson distance, fp64), 1 = homography (transfer error, fp32): score_one's kinds.
-// first[s] = candidates before sample s (the exclusive scan of n_models), *total = all of them; max_models = 10 / 1.
+// KIND 0 = essential (Sampson distance, fp64), 1 = homography (transfer error, fp32), 3 = fundamental (the larger epipolar-line
+// distance, fp64, K ignored): score_one's kinds.
+// first[s] = candidates before sample s (the exclusive scan of n_models), *total = all of them; max_models = 10 / 1 / 3.
 template <int KIND>
 __global__ __launch_bounds__(SC_BLOCK) void lb_score_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ a,
                                                             const double* __restrict__ b, const double* __restrict__ Kdev, int normalise,
@@ -53,7 +54,7 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_score_kernel(const long long* __r
     for (int c = blockIdx.x; c < ncand; c += gridDim.x) {   // (c, and every barrier below, is uniform over the workgroup)
         const int s = prim::segment_of(first, n_samples, c);
         const long long base = point_ptr[sample_problem[s]];
-        const int n = (int)(point_ptr[sample_problem[s] + 1] - base);   // >= 4: the sample was solved
+        const int n = (int)(point_ptr[sample_problem[s] + 1] - base);   // >= m: the sample was solved
         const double* pm = models + 9 * ((size_t)s * max_models + (c - first[s]));
         const double* pa = a + 2 * base;
         const double* pb = b + 2 * base;
@@ -103,7 +104,7 @@ __global__ __launch_bounds__(SC_BLOCK) void lb_select_kernel(const long long* __
                                                              float* __restrict__ out_thresholds, int* __restrict__ out_inliers,
                                                              unsigned char* __restrict__ out_masks, int* __restrict__ out_winner,
                                                              int* __restrict__ out_ncand) {
-    constexpr int m = KIND == 0 ? 5 : 4;
+    constexpr int m = KIND == 0 ? 5 : (KIND == 3 ? 7 : 4);
     __shared__ Best wbest[SC_BLOCK / 64];
     __shared__ int wsum[SC_BLOCK / 64];
     const int p = blockIdx.x;
@@ -183,7 +184,7 @@ int lmeds_score_grid(long long cand_cap, long long max_n) {
 }
 
 int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L) {
-    const int P = L.P, maxm = L.kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
+    const int P = L.P, maxm = solve_max_models(L.kind);
     const long long S = L.S, max_n = L.max_n;
     const bool need_rows = lmeds_needs_rows(max_n);
     const double* d_K = L.has_K ? L.K : nullptr;
@@ -209,6 +210,7 @@ int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L) {
                                                        L.masks, L.winner, L.n_candidates);                                                         \
     } while (0)
     if (L.kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_LB_LAUNCH(0);
+    else if (L.kind == EACHAM_SOLVE_FUNDAMENTAL7) EACHAM_LB_LAUNCH(3);
     else EACHAM_LB_LAUNCH(1);
 #undef EACHAM_LB_LAUNCH
     EACHAM_HIP_TRY(ctx, hipGetLastError());
@@ -224,11 +226,12 @@ extern "C" int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, con
                                   float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates) {
     if (!ctx) return EACHAM_ERR_INVALID;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: unknown kind %d", kind);
+    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
+        return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: unknown kind %d", kind);
     if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: negative number of problems");
     if (n_problems == 0) return EACHAM_OK;
     if (!point_ptr || !sample_ptr) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: null offset table");
-    const int P = n_problems, m = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 4 : 5, maxm = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
+    const int P = n_problems, m = solve_sample_size(kind), maxm = solve_max_models(kind);
     if (point_ptr[0] != 0 || sample_ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "lmeds_batch: an offset table does not start at 0");
     for (int p = 0; p < P; ++p)
         if (point_ptr[p + 1] < point_ptr[p] || sample_ptr[p + 1] < sample_ptr[p])

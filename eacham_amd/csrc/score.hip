@@ -79,7 +79,7 @@ extern "C" int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, 
                                        int32_t* inlier_counts, float* medians) {
     if (!ctx) return EACHAM_ERR_INVALID;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (kind < EACHAM_SCORE_ESSENTIAL || kind > EACHAM_SCORE_PNP || n_points < 0 || n_models < 0)
+    if (kind < EACHAM_SCORE_ESSENTIAL || kind > EACHAM_SCORE_FUNDAMENTAL || n_points < 0 || n_models < 0)
         return ctx->fail(EACHAM_ERR_INVALID, "score: bad kind or negative size");
     if (n_models == 0) return EACHAM_OK;
     if (!models || (n_points > 0 && (!a || !b)) || (kind == EACHAM_SCORE_PNP && !K))
@@ -114,7 +114,8 @@ extern "C" int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, 
     } while (0)
         if (kind == EACHAM_SCORE_ESSENTIAL) EACHAM_SCORE_LAUNCH(0);
         else if (kind == EACHAM_SCORE_HOMOGRAPHY) EACHAM_SCORE_LAUNCH(1);
-        else EACHAM_SCORE_LAUNCH(2);
+        else if (kind == EACHAM_SCORE_PNP) EACHAM_SCORE_LAUNCH(2);
+        else EACHAM_SCORE_LAUNCH(3);
 #undef EACHAM_SCORE_LAUNCH
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());

@@ -44,6 +44,22 @@ __device__ __forceinline__ float score_one(const double* __restrict__ a, const d
         const float dx = fadd(fmul(fadd(fadd(fmul(H0, x), fmul(H1, y)), H2), ww), -mx);
         const float dy = fadd(fmul(fadd(fadd(fmul(H3, x), fmul(H4, y)), H5), ww), -my);
         return fadd(fmul(dx, dx), fmul(dy, dy));
+    } else if (KIND == 3) {
+        // FMEstimatorCallback::computeError on pixels (K is ignored, nothing is normalised), x1 = (a, 1), x2 = (b, 1):
+        //   l2 = F x1:   l2[r] = (F[3r] a0 + F[3r+1] a1) + F[3r+2]          l1 = F^T x2:   l1[r] = (F[r] b0 + F[3+r] b1) + F[6+r]
+        //   d = (b0 l2[0] + b1 l2[1]) + l2[2],   d2 = d d
+        //   err = (float)max(d2 / (l1[0]^2 + l1[1]^2), d2 / (l2[0]^2 + l2[1]^2))      every operation rounded on its own, no FMA
+        double l2[3], l1[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+            l2[r] = dadd(dadd(dmul(M[3 * r], a[0]), dmul(M[3 * r + 1], a[1])), M[3 * r + 2]);
+            l1[r] = dadd(dadd(dmul(M[r], b[0]), dmul(M[3 + r], b[1])), M[6 + r]);
+        }
+        const double d = dadd(dadd(dmul(b[0], l2[0]), dmul(b[1], l2[1])), l2[2]);
+        const double d2 = dmul(d, d);
+        const double e1 = __ddiv_rn(d2, dadd(dmul(l1[0], l1[0]), dmul(l1[1], l1[1])));
+        const double e2 = __ddiv_rn(d2, dadd(dmul(l2[0], l2[0]), dmul(l2[1], l2[1])));
+        return (float)(e1 < e2 ? e2 : e1);   // std::max(e1, e2): e1 unless e2 is greater
     } else {
         const double X = dadd(dadd(dadd(dmul(M[0], a[0]), dmul(M[1], a[1])), dmul(M[2], a[2])), M[9]);
         const double Y = dadd(dadd(dadd(dmul(M[3], a[0]), dmul(M[4], a[1])), dmul(M[5], a[2])), M[10]);

@@ -8,6 +8,13 @@
 //       -> EACHAM_SOLVE_ESSENTIAL5: EMEstimatorCallback::runKernel (five-point.cpp), Nister's five-point algorithm: null space of
 //          the 5 x 9 epipolar system (Householder), the ten cubic constraints as a 10 x 20 matrix, Gauss-Jordan, det B(z) = a
 //          degree-10 polynomial, its real roots (Durand-Kerner + Newton polish), up to ten unit-norm E per sample
+//   cv::findFundamentalMat(pts1, pts2, cv::FM_LMEDS, 3.0, 0.99, 1000, mask)          (not a call of the reference: the estimator for
+//                                                                                     image sets whose K is unknown or guessed)
+//       -> EACHAM_SOLVE_FUNDAMENTAL7: run7Point (fundam.cpp) restated with two deliberate deviations — (1) Hartley normalisation of
+//          each image's seven points (centroid, mean distance sqrt(2)) because the null space comes from the 9 x 9 Jacobi eigen-solver
+//          on A^T A, not from an SVD of the 7 x 9 system on raw pixels; (2) unit Frobenius norm, not F[8] = 1. The cubic
+//          det(z f1 + f2), its real roots by the five-point solver's Durand-Kerner recipe for degree <= 3, up to three F per sample
+//          (solve_dev.hpp: fundamental7_wave)
 //   cv::solvePnPRansac(pts3d, pts2d, K, dist, rvec, t, false, 10000, 4.0f, 0.999f, inliers, cv::SOLVEPNP_EPNP)   :227-228
 //       -> eacham_solve_pnp: EPnP on every 5-point sample (the RANSAC kernel) and on the inlier set (the final refit): four control
 //          points, M^T M of the projection system, its four smallest eigenvectors (Jacobi 12 x 12), the 6 x 10 distance system, three
@@ -204,6 +211,37 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_e5_kernel(SolveSeg seg
     if (lane == 0) n_models[s] = n;
 }
 
+// The seven-point solver (fundamental7_wave, solve_dev.hpp): the shape of solve_h4_kernel, up to 3 models of 9 doubles per sample,
+// the slots behind n_models zero. K is not an argument: a fundamental matrix lives in pixels.
+template <bool LIST>
+__global__ __launch_bounds__(64 * SOLVE_WAVES) void solve_f7_kernel(SolveSeg seg, const double* __restrict__ a, const double* __restrict__ b, int n_samples,
+                                                                   const int* __restrict__ idx, double* __restrict__ models, int* __restrict__ n_models) {
+    __shared__ double AtA[SOLVE_WAVES][81], V[SOLVE_WAVES][81];
+    __shared__ JacRound R[SOLVE_WAVES];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.x * SOLVE_WAVES + wave;
+    if (s >= n_samples) return;
+    if constexpr (LIST) {
+        long long base;
+        if (!sample_segment(seg, s, 7, base)) {   // no candidates
+            if (lane == 0) n_models[s] = 0;
+            return;
+        }
+        a += 2 * base, b += 2 * base;
+    }
+    double pa[14], pb[14], out[27];
+    gather_sample<7>(idx + (size_t)s * 7, a, b, pa, pb);
+    const int n = fundamental7_wave(pa, pb, out, AtA[wave], V[wave], R[wave]);
+    if (lane < 27) {   // (identical values in every lane: entry `lane` by selection)
+        double v = 0.0;
+#pragma unroll
+        for (int k = 0; k < 27; ++k)
+            if (k == lane) v = out[k];
+        models[27 * (size_t)s + lane] = v;
+    }
+    if (lane == 0) n_models[s] = n;
+}
+
 }  // namespace
 
 void solve_minimal_launch(hipStream_t st, const MinimalLaunch& L) {
@@ -211,6 +249,8 @@ void solve_minimal_launch(hipStream_t st, const MinimalLaunch& L) {
     const bool list = L.seg.point_ptr != nullptr;
     if (L.kind == EACHAM_SOLVE_HOMOGRAPHY4)
         (list ? solve_h4_kernel<true> : solve_h4_kernel<false>)<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.seg, L.a, L.b, L.n_samples, L.sample_idx, L.models, L.n_models);
+    else if (L.kind == EACHAM_SOLVE_FUNDAMENTAL7)
+        (list ? solve_f7_kernel<true> : solve_f7_kernel<false>)<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.seg, L.a, L.b, L.n_samples, L.sample_idx, L.models, L.n_models);
     else
         (list ? solve_e5_kernel<true> : solve_e5_kernel<false>)<<<grid, 64 * SOLVE_WAVES, 0, st>>>(L.seg, L.a, L.b, L.K, L.has_K ? 1 : 0, L.n_samples, L.sample_idx,
                                                                                                  L.models, L.n_models);
@@ -233,11 +273,12 @@ extern "C" int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, con
                                     int n_samples, const int32_t* sample_idx, double* models, int32_t* n_models) {
     if (!ctx) return EACHAM_ERR_INVALID;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5) return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: unknown kind %d", kind);
+    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
+        return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: unknown kind %d", kind);
     if (n_points < 0 || n_samples < 0 || (n_samples > 0 && (!a || !b || !sample_idx || !models || !n_models)))
         return ctx->fail(EACHAM_ERR_INVALID, "solve_minimal: null argument or negative size");
     if (n_samples == 0) return EACHAM_OK;
-    const int m = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 4 : 5, maxm = kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : 10;
+    const int m = solve_sample_size(kind), maxm = solve_max_models(kind);
     if (int rc = check_sample_idx(ctx, "solve_minimal", -1, sample_idx, (long long)n_samples * m, n_points)) return rc;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;

@@ -1,5 +1,5 @@
 // solve_dev.hpp — the device functions of the minimal solvers that more than one translation unit runs: the homography
-// (4 points) and five-point (essential matrix) solvers by one wave per sample, EPnP's two halves, and the small dense algebra
+// (4 points), five-point (essential matrix) and seven-point (fundamental matrix) solvers by one wave per sample, EPnP's two halves, and the small dense algebra
 // under them. solve.hip holds the solver kernels of every entry point (one template per stage, a one-problem and a list
 // instantiation: solve_launch.hpp); pnp_batch.hip includes this file for the refit body (pnp_refit_body) and the rule among
 // EPnP's three starts (pnp_first_smallest). Every includer is compiled with -ffp-contract=off (csrc/Makefile).
@@ -757,6 +757,277 @@ __device__ static int homography4_wave(const double* a, const double* b, double*
 #pragma unroll
     for (int k = 0; k < 9; ++k) H[k] *= s;
     return 1;
+}
+
+/* ---- seven-point (fundamental matrix), one WAVE per sample ------------------------------------------------------------------
+ * OpenCV 4.5.5's run7Point (fundam.cpp) restated, with two deliberate deviations:
+ *   1. HARTLEY NORMALISATION. Each image's seven points are translated to their centroid (p0 + (sum of (pi - p0)) / 7) and scaled so
+ *      that their mean distance from it is sqrt(2) (sums in index order, every operation rounded on its own), the models are denormalised as
+ *      T2^T F^ T1. OpenCV solves on raw pixels with a one-sided Jacobi SVD of the 7 x 9 system; here the null space comes from
+ *      the 9 x 9 eigen-solver on A^T A (jacobi_wave<9>, what homography4_wave uses), which squares the condition number: on raw
+ *      pixels that form is useless (held-out epipolar errors above 1e4 px^2 on exact data), normalised it is better than
+ *      OpenCV's own (1e-11 against 8e-5 px^2).
+ *   2. SCALING. A model leaves with unit Frobenius norm, as ESSENTIAL5 emits its models, not with F[8] = 1 (which OpenCV gives
+ *      up on when F[8] ~ 0).
+ * Steps: the normalisations; A^T A shared (an upper-triangle entry per lane, the seven points added in order; row of a
+ * correspondence = x2 x1, x2 y1, x2, y2 x1, y2 y1, y2, x1, y1, 1); jacobi_wave<9>; f2 = the eigenvector of the smallest eigenvalue,
+ * f1 = that of the second smallest (first of equals by strict <), minus f2; the cubic det(z f1 + f2) by run7Point's four c[]
+ * expressions in the order written below; its real roots by real_roots3; per root F^ = f1 z + f2, denormalised, / its norm.
+ * Everything after the eigen-solver runs on identical values in every lane.
+ * A DEGENERATE sample is no error: 0 models when a normalisation scale is not finite (all points of an image coincide, or a
+ * coordinate is not finite), when the cubic is all zero, or when no real root is left; a root whose model has no finite positive
+ * norm is squeezed out.
+ *
+ * real_roots3: the Durand-Kerner recipe of essential5_wave / real_roots10 (solve_oracle.c) for degree <= 3, run sequentially:
+ * degree drop at 1e-14 cmax, monic, the start values r0 (0.4 + 0.9 i)^k with r0 = |m0|^(1/deg) by 80 Newton steps clamped to
+ * [0.5, bound], at most 200 simultaneous sweeps stopped at a largest correction of 1e-11 bound, a root is real iff
+ * |zi| <= 1e-7 (1 + |zr|), four Newton steps on the real polynomial, real roots ascending (equals in iterate order).
+ * Only + - * / sqrt, fabs, fmax, fmin: the CPU restatement (tests/cpp/fundamental_reference.c) gives the same bits. */
+__device__ __forceinline__ int real_roots3(double c0, double c1, double c2, double c3 /* c0 + c1 z + c2 z^2 + c3 z^3 */, double* roots /* 3 */) {
+    // (the coefficients by value and the leading one picked in the branches: as an array indexed by the degree they went to scratch)
+    double cmax = 0.0;
+    cmax = fmax(cmax, fabs(c0));
+    cmax = fmax(cmax, fabs(c1));
+    cmax = fmax(cmax, fabs(c2));
+    cmax = fmax(cmax, fabs(c3));
+    if (!(cmax > 0.0)) return 0;
+    int deg = 3;
+    double lead = c3;
+    if (fabs(c3) <= 1e-14 * cmax) {
+        deg = 2, lead = c2;
+        if (fabs(c2) <= 1e-14 * cmax) {
+            deg = 1, lead = c1;
+            if (fabs(c1) <= 1e-14 * cmax) deg = 0;
+        }
+    }
+    if (deg == 0) return 0;
+    const double c[3] = {c0, c1, c2};
+    double m[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) m[k] = k < deg ? c[k] / lead : 0.0;
+    double bound = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if (k < deg) bound = fmax(bound, fabs(m[k]));
+    bound += 1.0;
+    double zr[3] = {0, 0, 0}, zi[3] = {0, 0, 0};
+    {
+        double r0 = 1.0;
+        const double a0 = fabs(m[0]);
+        if (a0 > 0.0) {
+            double y = a0 > 1.0 ? a0 : 1.0;
+            for (int it = 0; it < 80; ++it) {
+                double yp = 1.0;
+                for (int j = 0; j < deg - 1; ++j) yp *= y;
+                y = ((deg - 1) * y + a0 / yp) / deg;
+            }
+            r0 = y;
+        }
+        r0 = fmin(fmax(r0, 0.5), bound);
+        double cr = 1.0, ci = 0.0;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (k < deg) zr[k] = r0 * cr, zi[k] = r0 * ci;
+            const double tr = cr * 0.4 - ci * 0.9, ti = cr * 0.9 + ci * 0.4;
+            cr = tr, ci = ti;
+        }
+    }
+    for (int it = 0; it < 200; ++it) {
+        double change = 0.0, nzr[3], nzi[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            nzr[k] = zr[k], nzi[k] = zi[k];
+            double pr = 1.0, pi = 0.0;  /* Horner on the monic polynomial */
+#pragma unroll
+            for (int j = 2; j >= 0; --j)
+                if (j < deg) {
+                    const double tr = pr * zr[k] - pi * zi[k] + m[j], ti = pr * zi[k] + pi * zr[k];
+                    pr = tr, pi = ti;
+                }
+            double dr = 1.0, di = 0.0;
+#pragma unroll
+            for (int j = 0; j < 3; ++j)
+                if (j < deg && j != k) {
+                    const double ar = zr[k] - zr[j], ai = zi[k] - zi[j];
+                    const double tr = dr * ar - di * ai, ti = dr * ai + di * ar;
+                    dr = tr, di = ti;
+                }
+            const double den = dr * dr + di * di;
+            if (k < deg && den > 0.0) {
+                const double qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
+                nzr[k] = zr[k] - qr;
+                nzi[k] = zi[k] - qi;
+                change = fmax(change, fabs(qr) + fabs(qi));
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) zr[k] = nzr[k], zi[k] = nzi[k];
+        if (change <= 1e-11 * bound) break;
+    }
+    double z[3] = {0, 0, 0};
+    bool real[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        real[k] = k < deg && !(fabs(zi[k]) > 1e-7 * (1.0 + fabs(zr[k])));
+        double v = zr[k];
+        bool going = real[k];
+#pragma unroll
+        for (int it = 0; it < 4; ++it) {  /* Newton polish on the real polynomial: stops for good at a zero derivative */
+            double p = lead, d = 0.0;
+#pragma unroll
+            for (int j = 2; j >= 0; --j)
+                if (j < deg) {
+                    d = d * v + p;
+                    p = p * v + c[j];
+                }
+            going = going && fabs(d) > 0.0;
+            if (going) v -= p / d;
+        }
+        z[k] = real[k] ? v : 0.0;
+    }
+    /* ascending, equals in iterate order: root k goes to the slot of its rank */
+    int n = 0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) n += real[k];
+#pragma unroll
+    for (int s = 0; s < 3; ++s) roots[s] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        int rank = 0;
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (j != k && real[j] && (z[j] < z[k] || (z[j] == z[k] && j < k))) ++rank;
+#pragma unroll
+        for (int s = 0; s < 3; ++s)
+            if (real[k] && rank == s) roots[s] = z[k];
+    }
+    return n;
+}
+
+// centroid and scale of a sample's seven points in one image; false: the scale is not finite
+__device__ __forceinline__ bool f7_normalisation(const double* p, double& cx, double& cy, double& s) {
+    // the centroid as p0 + (sum of (pi - p0)) / 7: seven coincident points give differences, distances and a mean distance of exactly 0
+    // (as (sum of pi) / 7 the centroid of seven equal points can miss them by an ulp, and the scale comes out finite and huge)
+    double sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) sx += p[2 * i] - p[0], sy += p[2 * i + 1] - p[1];
+    cx = p[0] + sx / 7.0, cy = p[1] + sy / 7.0;
+    double d = 0.0;
+#pragma unroll
+    for (int i = 0; i < 7; ++i) {
+        const double dx = p[2 * i] - cx, dy = p[2 * i + 1] - cy;
+        d += sqrt(dx * dx + dy * dy);
+    }
+    d = d / 7.0;
+    s = 1.4142135623730951 / d;
+    return s <= 1.7976931348623157e308;   // (false for a NaN as well)
+}
+
+/* a, b: this sample's 7 x 2 points of image 1 / image 2. Returns the number of models (0..3); F (27, the slots behind the count
+ * zero) valid in every lane. */
+__device__ static int fundamental7_wave(const double* a, const double* b, double* F, double* AtA /* 81 */, double* V /* 81 */, JacRound& R) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int k = 0; k < 27; ++k) F[k] = 0.0;
+    double c1x, c1y, s1, c2x, c2y, s2;
+    const bool ok1 = f7_normalisation(a, c1x, c1y, s1), ok2 = f7_normalisation(b, c2x, c2y, s2);
+    if (!ok1 || !ok2) return 0;   // (wave-uniform)
+    for (int e = lane; e < 81; e += 64) {
+        const int j = e / 9, k = e % 9;
+        if (k < j) continue;
+        double acc = 0.0;
+#pragma unroll
+        for (int i = 0; i < 7; ++i) {
+            const double x1 = (a[2 * i] - c1x) * s1, y1 = (a[2 * i + 1] - c1y) * s1;
+            const double x2 = (b[2 * i] - c2x) * s2, y2 = (b[2 * i + 1] - c2y) * s2;
+            const double row[9] = {x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, 1.0};
+            double rj = 0, rk = 0;
+#pragma unroll
+            for (int q = 0; q < 9; ++q) {
+                if (q == j) rj = row[q];
+                if (q == k) rk = row[q];
+            }
+            acc += rj * rk;
+        }
+        AtA[j * 9 + k] = acc;
+        AtA[k * 9 + j] = acc;
+    }
+    wave_sync_lds();
+    double w[9];
+    jacobi_wave<9>(AtA, V, w, R);
+    int lo = 0, lo2 = -1;
+#pragma unroll
+    for (int i = 1; i < 9; ++i) {
+        double wb = 0;
+#pragma unroll
+        for (int q = 0; q < 9; ++q)
+            if (q == lo) wb = w[q];
+        if (w[i] < wb) lo = i;
+    }
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        if (i == lo) continue;
+        double wb = 0;
+#pragma unroll
+        for (int q = 0; q < 9; ++q)
+            if (q == lo2) wb = w[q];
+        if (lo2 < 0 || w[i] < wb) lo2 = i;
+    }
+    double f1[9], f2[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) {
+        f2[k] = V[k * 9 + lo];
+        f1[k] = V[k * 9 + lo2] - f2[k];
+    }
+    /* det(z f1 + f2) = c[0] z^3 + c[1] z^2 + c[2] z + c[3], run7Point's expressions */
+    double c[4], t0, t1, t2;
+    t0 = f2[4] * f2[8] - f2[5] * f2[7];
+    t1 = f2[3] * f2[8] - f2[5] * f2[6];
+    t2 = f2[3] * f2[7] - f2[4] * f2[6];
+    c[3] = f2[0] * t0 - f2[1] * t1 + f2[2] * t2;
+    c[2] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2 - f1[3] * (f2[1] * f2[8] - f2[2] * f2[7]) + f1[4] * (f2[0] * f2[8] - f2[2] * f2[6]) -
+           f1[5] * (f2[0] * f2[7] - f2[1] * f2[6]) + f1[6] * (f2[1] * f2[5] - f2[2] * f2[4]) - f1[7] * (f2[0] * f2[5] - f2[2] * f2[3]) +
+           f1[8] * (f2[0] * f2[4] - f2[1] * f2[3]);
+    t0 = f1[4] * f1[8] - f1[5] * f1[7];
+    t1 = f1[3] * f1[8] - f1[5] * f1[6];
+    t2 = f1[3] * f1[7] - f1[4] * f1[6];
+    c[1] = f2[0] * t0 - f2[1] * t1 + f2[2] * t2 - f2[3] * (f1[1] * f1[8] - f1[2] * f1[7]) + f2[4] * (f1[0] * f1[8] - f1[2] * f1[6]) -
+           f2[5] * (f1[0] * f1[7] - f1[1] * f1[6]) + f2[6] * (f1[1] * f1[5] - f1[2] * f1[4]) - f2[7] * (f1[0] * f1[5] - f1[2] * f1[3]) +
+           f2[8] * (f1[0] * f1[4] - f1[1] * f1[3]);
+    c[0] = f1[0] * t0 - f1[1] * t1 + f1[2] * t2;
+    double roots[3];
+    const int nr = real_roots3(c[3], c[2], c[1], c[0], roots);
+    /* T2^T = [s2 0 0; 0 s2 0; -c2x s2, -c2y s2, 1], T1 = [s1 0 -c1x s1; 0 s1 -c1y s1; 0 0 1] */
+    const double t2t[9] = {s2, 0, 0, 0, s2, 0, -c2x * s2, -c2y * s2, 1};
+    const double t1m[9] = {s1, 0, -c1x * s1, 0, s1, -c1y * s1, 0, 0, 1};
+    int n = 0;
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        double Fh[9], T[9], G[9];
+#pragma unroll
+        for (int k = 0; k < 9; ++k) Fh[k] = f1[k] * roots[r] + f2[k];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) T[3 * i + j] = t2t[3 * i] * Fh[j] + t2t[3 * i + 1] * Fh[3 + j] + t2t[3 * i + 2] * Fh[6 + j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) G[3 * i + j] = T[3 * i] * t1m[j] + T[3 * i + 1] * t1m[3 + j] + T[3 * i + 2] * t1m[6 + j];
+        double nrm = 0.0;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) nrm += G[k] * G[k];
+        nrm = sqrt(nrm);
+        const bool emit = r < nr && nrm > 0.0 && nrm < 1e300;
+#pragma unroll
+        for (int k = 0; k < 9; ++k) {   // slot n (0 <= n <= r) by selection: no run-time index into F
+#pragma unroll
+            for (int s = 0; s < 3; ++s)
+                if (s <= r && emit && s == n) F[9 * s + k] = G[k] / nrm;
+        }
+        n += emit;
+    }
+    return n;
 }
 
 /* ---- EPnP ------------------------------------------------------------------------------------------------------ */

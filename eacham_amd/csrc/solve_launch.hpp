@@ -16,7 +16,11 @@ struct SolveSeg {
     int* sample_problem;
 };
 
-// Every minimal sample -> its model(s): models [n_samples][1 or 10][9], n_models [n_samples] (kind: EACHAM_SOLVE_*).
+// A minimal sample's points and the models it can give, per kind (EACHAM_SOLVE_*): homography 4 / 1, essential 5 / 10, fundamental 7 / 3.
+inline int solve_sample_size(int kind) { return kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 4 : (kind == EACHAM_SOLVE_FUNDAMENTAL7 ? 7 : 5); }
+inline int solve_max_models(int kind) { return kind == EACHAM_SOLVE_HOMOGRAPHY4 ? 1 : (kind == EACHAM_SOLVE_FUNDAMENTAL7 ? 3 : 10); }
+
+// Every minimal sample -> its model(s): models [n_samples][1, 10 or 3][9], n_models [n_samples] (kind: EACHAM_SOLVE_*).
 struct MinimalLaunch {
     int kind;
     SolveSeg seg;

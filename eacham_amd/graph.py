@@ -68,10 +68,10 @@ class GraphVerify(NamedTuple):
 def lmeds_iterations(kind: str, max_iters: int | None = None, confidence: float | None = None) -> int:
     """The samples LMeDSPointSetRegistrator::run asks for, as twoview_detail::lmeds computes them: RANSACUpdateNumIters at an
     assumed outlier ratio of 0.45, at least 3, at most max_iters. Defaults: the reference's calls (essential 1000 / 0.99 -> 89,
-    homography 100 / 0.999 -> 72)."""
+    homography 100 / 0.999 -> 72) and cv::findFundamentalMat's own (fundamental 1000 / 0.99 -> 300)."""
     import math
-    essential = kind.startswith("essential")
-    m = 5 if essential else 4
+    essential = kind.startswith("essential") or kind.startswith("fundamental")   # (cv::findFundamentalMat's defaults are 1000 / 0.99 too)
+    m = 7 if kind.startswith("fundamental") else (5 if essential else 4)
     max_iters = (1000 if essential else 100) if max_iters is None else int(max_iters)
     p = min(max((0.99 if essential else 0.999) if confidence is None else float(confidence), 0.0), 1.0)
     tiny = np.finfo(np.float64).tiny
@@ -119,14 +119,14 @@ class ResidentGraph:
 
     def verify(self, kind: str, K=None, sampling: str = "opencv", iterations: int | None = None, seeds=None, retain: bool = False,
                want_samples: bool = False) -> GraphVerify:
-        """eacham_graph_verify: LMedS ("essential" with K = fx fy cx cy or None for normalised points, or "homography") for every
-        pair of the graph, gathered, sampled and solved on the device. iterations defaults to lmeds_iterations(kind); seeds: one
+        """eacham_graph_verify: LMedS ("essential" with K = fx fy cx cy or None for normalised points, "homography", or
+        "fundamental": pixels, K ignored) for every pair of the graph, gathered, sampled and solved on the device. iterations defaults to lmeds_iterations(kind); seeds: one
         per pair for sampling="counter" (None: 12345). retain=True keeps the mask on the device for tracks_verified()."""
         from . import capi
-        homography = kind.startswith("homography")
-        if not homography and not kind.startswith("essential"):
+        homography, fundamental = kind.startswith("homography"), kind.startswith("fundamental")
+        if not homography and not fundamental and not kind.startswith("essential"):
             raise ValueError(f"unknown kind {kind!r}")
-        k, m = (capi.SOLVE_HOMOGRAPHY4, 4) if homography else (capi.SOLVE_ESSENTIAL5, 5)
+        k, m = (capi.SOLVE_HOMOGRAPHY4, 4) if homography else ((capi.SOLVE_FUNDAMENTAL7, 7) if fundamental else (capi.SOLVE_ESSENTIAL5, 5))
         its = lmeds_iterations(kind) if iterations is None else int(iterations)
         return self._verify_raw(k, m, K, SAMPLINGS[sampling], its, seeds, retain, want_samples)
 

@@ -12,7 +12,8 @@ import numpy as np
 from . import capi
 from .score import SOLVERS
 
-KINDS = {"homography": "homography4", "essential": "essential5", "homography4": "homography4", "essential5": "essential5"}
+KINDS = {"homography": "homography4", "essential": "essential5", "fundamental": "fundamental7",
+         "homography4": "homography4", "essential5": "essential5", "fundamental7": "fundamental7"}
 
 
 class LmedsBatch(NamedTuple):
@@ -78,7 +79,8 @@ def _call(ctx, k, point_ptr, a, b, sample_ptr, sample_idx, K):
 
 
 def lmeds_batch(ctx, kind: str, uv1, uv2, samples, K=None) -> LmedsBatch:
-    """kind "essential" (5-point samples, K = fx fy cx cy or None for normalised points) or "homography" (4-point samples).
+    """kind "essential" (5-point samples, K = fx fy cx cy or None for normalised points), "homography" (4-point samples) or
+    "fundamental" (7-point samples on pixels, K ignored).
     uv1[p], uv2[p]: the n_p x 2 matches of pair p; samples[p]: its s_p x m minimal samples (indices into its own matches)."""
     k, _, _ = SOLVERS[KINDS[kind]]
     point_ptr, a, b, sample_ptr, idx = pack(kind, uv1, uv2, samples)

@@ -352,7 +352,8 @@ class HipContext:
 
     # ---- profiling -------------------------------------------------------------------------
     def lmeds_batch(self, kind: str, uv1, uv2, samples, K=None):
-        """eacham_lmeds_batch: LMedS two-view estimation of a list of pairs in one call (eacham_amd/lmeds.py)."""
+        """eacham_lmeds_batch: LMedS two-view estimation of a list of pairs in one call (eacham_amd/lmeds.py); kind "essential",
+        "homography" or "fundamental" (7-point samples on pixels, K ignored)."""
         from . import lmeds
         return lmeds.lmeds_batch(self, kind, uv1, uv2, samples, K)
 

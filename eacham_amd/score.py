@@ -1,5 +1,5 @@
 """Host-side mirror of eacham_score_hypotheses (include/eacham_hip.h): batch scoring of essential-matrix,
-homography and PnP pose candidates — the data-parallel part of the robust estimators RecoverPoseTwoView and
+homography, fundamental-matrix and PnP pose candidates — the data-parallel part of the robust estimators RecoverPoseTwoView and
 RecoverPosePnP call (modules/sfm/reconstruction/ReconstructionManager.cpp:57-61, :75, :227-228). Test / bench driver."""
 from __future__ import annotations
 
@@ -9,7 +9,7 @@ import numpy as np
 
 from . import capi
 
-KINDS = {"essential": capi.SCORE_ESSENTIAL, "homography": capi.SCORE_HOMOGRAPHY, "pnp": capi.SCORE_PNP}
+KINDS = {"essential": capi.SCORE_ESSENTIAL, "homography": capi.SCORE_HOMOGRAPHY, "pnp": capi.SCORE_PNP, "fundamental": capi.SCORE_FUNDAMENTAL}
 
 
 def marshal(kind: str, a, b, models, K):
@@ -38,12 +38,13 @@ def score_hypotheses(ctx, kind: str, a, b, models, K=None, threshold: float = 16
     return err, counts, med
 
 
-SOLVERS = {"homography4": (capi.SOLVE_HOMOGRAPHY4, 4, 1), "essential5": (capi.SOLVE_ESSENTIAL5, 5, 10)}
+SOLVERS = {"homography4": (capi.SOLVE_HOMOGRAPHY4, 4, 1), "essential5": (capi.SOLVE_ESSENTIAL5, 5, 10), "fundamental7": (capi.SOLVE_FUNDAMENTAL7, 7, 3)}
 
 
 def solve_minimal(ctx, kind: str, a, b, samples, K=None):
-    """eacham_solve_minimal: every minimal sample (rows of `samples`: 4 / 5 point indices) -> its model(s).
-    Returns (models [n_samples, max_models, 9] float64, n_models [n_samples] int32); max_models = 1 / 10."""
+    """eacham_solve_minimal: every minimal sample (rows of `samples`: 4 / 5 / 7 point indices) -> its model(s).
+    Returns (models [n_samples, max_models, 9] float64, n_models [n_samples] int32); max_models = 1 / 10 / 3. "fundamental7" works on
+    pixels and does not read K."""
     k, m, maxm = SOLVERS[kind]
     a = np.ascontiguousarray(a, dtype=np.float64).reshape(-1, 2)
     b = np.ascontiguousarray(b, dtype=np.float64).reshape(-1, 2)

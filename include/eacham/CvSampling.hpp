@@ -8,9 +8,10 @@
 //                                                    next() = (unsigned)state;   uniform(a, b) = a + next() % (b - a)
 //   * getSubset draws modelPoints indices one by one with rng.uniform(0, count), drawing again while the index repeats one
 //     already in the subset; the finished subset goes through the callback's checkSubset and is drawn afresh when that
-//     refuses it (at most 1000 attempts under LMedS, 10 000 under RANSAC). Only HomographyEstimatorCallback has a
-//     checkSubset (fundam.cpp): the last point must not be collinear with any two earlier ones, in either image, and the four
-//     correspondences must keep their orientation (the sign test of Marquez-Neila et al.).
+//     refuses it (at most 1000 attempts under LMedS, 10 000 under RANSAC). Of the reference's calls only
+//     HomographyEstimatorCallback has a checkSubset (fundam.cpp): the last point must not be collinear with any two earlier
+//     ones, in either image, and the four correspondences must keep their orientation (the sign test of Marquez-Neila et al.).
+//     FMEstimatorCallback (cv::findFundamentalMat, the library's uncalibrated kind) has the collinearity half alone.
 // OpenCV is not in this image and none of it could be run here: everything above is written FROM MEMORY of the 4.5.5 sources
 // and is unverified ("parity unpinned", like the rest of the estimators). What it buys is that the documented deviation
 // "the samples come from the library's own counter-based generator" is gone by default: with OpenCV at hand, E / H / the PnP
@@ -24,7 +25,7 @@
 #include <vector>
 
 // The streams below are stated ONCE for the host and for the kernels that draw on the device (eacham_amd/csrc/graph_verify.hip):
-// EACHAM_HD marks what both compile; the unroll hint lets the 4 - 5 indices of a subset stay in registers there.
+// EACHAM_HD marks what both compile; the unroll hint lets the 4 - 7 indices of a subset stay in registers there.
 #if defined(__HIPCC__)
 #define EACHAM_HD __host__ __device__
 #define EACHAM_UNROLL _Pragma("unroll")
@@ -90,6 +91,13 @@ EACHAM_HD inline bool cv_check_subset_homography(const float* src, const float* 
         if (negative != 0 && negative != 4) return false;
     }
     return true;
+}
+
+// FMEstimatorCallback::checkSubset (fundam.cpp) for a subset of `count` correspondences: the last point must not be collinear with
+// any two earlier ones, in either image. No orientation test.
+EACHAM_HD inline bool cv_check_subset_fundamental(const float* src, const float* dst, int count) {
+    using namespace cvsampling_detail;
+    return !have_collinear_points(src, count) && !have_collinear_points(dst, count);
 }
 
 // One getSubset call: m distinct indices out of n into idx[0..m). `check(idx)` is the callback's checkSubset (may be empty).

@@ -89,6 +89,14 @@ inline std::vector<RobustModel> VerifyEssential(ResidentMatchGraph& rg, const do
     return graphverify_detail::verify(rg, EACHAM_SOLVE_ESSENTIAL5, 5, K4, maxIters, prob, seeds, sampling, retain, traces);
 }
 
+// FindFundamentalMatBatch for every pair of the resident graph — the verification that reads no intrinsics: result[p] (and traces[p])
+// equal FindFundamentalMatBatch(ctx, uv1, uv2, [seeds,] maxIters, prob, sampling, traces)[p] on the host-gathered points, field for
+// field. There is no refit. retain and seeds as for VerifyEssential.
+inline std::vector<RobustModel> VerifyFundamental(ResidentMatchGraph& rg, int maxIters = 1000, double prob = 0.99, Sampling sampling = Sampling::OpenCV,
+                                                  std::vector<LmedsTrace>* traces = nullptr, bool retain = true, const std::vector<uint64_t>& seeds = {}) {
+    return graphverify_detail::verify(rg, EACHAM_SOLVE_FUNDAMENTAL7, 7, nullptr, maxIters, prob, seeds, sampling, retain, traces);
+}
+
 // FindHomographyBatch for every pair of the resident graph. The refit of cv::findHomography on the winner's inliers stays a host
 // step on the returned mask (RefitHomography), so the matches and pixels it reads are given again: `pairs` and `g` as the graph was
 // made from them, keypoints[f] = x0 y0 x1 y1 ... Only pairs with a model and more than 4 matches are gathered for it.

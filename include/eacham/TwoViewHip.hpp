@@ -5,12 +5,14 @@
 //   cv::findHomography(pts1, pts2, cv::LMEDS, 4.0, mask2, 100, 0.999)               :75      -> FindHomography
 //   cv::decomposeHomographyMat(H, K, Rs, ts, normals)                               :92      -> DecomposeHomographyMat
 //   cv::recoverPose(E, pts1, pts2, K, R, t, 50.0f, mask)                            :150     -> RecoverPose
+// and, for image sets whose intrinsics are unknown or guessed (the reference guesses fx = 1.2 x width), the estimator that does not
+// read K:  cv::findFundamentalMat(pts1, pts2, cv::FM_LMEDS, 3.0, 0.99, 1000, mask)                    -> FindFundamentalMat
 //
 // The robust estimators are the pair (eacham_solve_minimal: every minimal sample -> its models, one launch) +
 // (eacham_score_hypotheses: every model against every correspondence, one launch) with the LMedS rule of
 // LMeDSPointSetRegistrator::run in between: smallest median wins, sigma = 2.5 * 1.4826 * (1 + 5 / (n - m)) * sqrt(median),
 // inliers = err <= sigma^2 (ptsetreg.cpp). The SAMPLES: by default OpenCV's own stream (Sampling::OpenCV, CvSampling.hpp: cv::RNG
-// seeded (uint64)-1 per call, getSubset, the homography's checkSubset — restated from memory of the 4.5.5 sources, unverified
+// seeded (uint64)-1 per call, getSubset, the homography's and the fundamental matrix's checkSubset — restated from memory of the 4.5.5 sources, unverified
 // here like the rest: parity unpinned); Sampling::Counter is the library's counter-based generator seeded by the caller (the
 // rounds 1-3 form). The tests hold the result against ground truth under both. Neither estimator is followed by OpenCV's final
 // Levenberg-Marquardt polish on the inliers except findHomography's (RefitHomography below; findEssentialMat has none).
@@ -149,41 +151,54 @@ inline int ransac_update_num_iters(double p, double ep, int m, int maxIters) {
 // registrator's own stream — RNG rng((uint64)-1), getSubset with at most 1000 attempts per subset, the homography's
 // checkSubset (CvSampling.hpp) — and may return fewer subsets when getSubset gives up (run() then stops iterating);
 // Sampling::Counter is the library's counter-based generator seeded by the caller.
-inline std::vector<int32_t> lmeds_samples(int n, int m, int iterations, bool homography, const std::vector<double>& uv1,
+// The checkSubset of the estimator's callback: none (EMEstimatorCallback), the homography's (m = 4), the fundamental matrix's (m = 7).
+enum class SubsetCheck { None, Homography, Fundamental };
+inline SubsetCheck subset_check_of(int solve_kind) {
+    return solve_kind == EACHAM_SOLVE_HOMOGRAPHY4 ? SubsetCheck::Homography
+                                                  : (solve_kind == EACHAM_SOLVE_FUNDAMENTAL7 ? SubsetCheck::Fundamental : SubsetCheck::None);
+}
+inline std::vector<int32_t> lmeds_samples(int n, int m, int iterations, SubsetCheck check, const std::vector<double>& uv1,
                                           const std::vector<double>& uv2, uint64_t seed, Sampling sampling) {
     if (sampling == Sampling::Counter) return draw_samples(n, m, iterations, seed);
+    const int pts = check == SubsetCheck::Fundamental ? 7 : 4;   // the points the check reads
+    if (check != SubsetCheck::None && m < pts) throw std::invalid_argument("lmeds_samples: the check reads more points than a subset has");
     std::vector<int32_t> idx;
     idx.reserve((size_t)iterations * m);
     CvRNG rng(0xffffffffffffffffull);
     std::vector<int32_t> sub(m);
     for (int it = 0; it < iterations; ++it) {
         const bool found = cv_get_subset(rng, n, m, sub.data(), 1000, [&](const int32_t* s) {
-            if (!homography) return true;
-            float a[8], b[8];
-            for (int k = 0; k < 4; ++k) {
+            if (check == SubsetCheck::None) return true;
+            float a[14], b[14];
+            for (int k = 0; k < pts; ++k) {
                 a[2 * k] = (float)uv1[2 * (size_t)s[k]], a[2 * k + 1] = (float)uv1[2 * (size_t)s[k] + 1];
                 b[2 * k] = (float)uv2[2 * (size_t)s[k]], b[2 * k + 1] = (float)uv2[2 * (size_t)s[k] + 1];
             }
-            return cv_check_subset_homography(a, b, 4);
+            return check == SubsetCheck::Homography ? cv_check_subset_homography(a, b, 4) : cv_check_subset_fundamental(a, b, 7);
         });
         if (!found) break;
         idx.insert(idx.end(), sub.begin(), sub.end());
     }
     return idx;
 }
+// ... as it was before the fundamental kind: the homography's check or none
+inline std::vector<int32_t> lmeds_samples(int n, int m, int iterations, bool homography, const std::vector<double>& uv1,
+                                          const std::vector<double>& uv2, uint64_t seed, Sampling sampling) {
+    return lmeds_samples(n, m, iterations, homography ? SubsetCheck::Homography : SubsetCheck::None, uv1, uv2, seed, sampling);
+}
 
 inline RobustModel lmeds(Context& ctx, int solve_kind, int score_kind, int m, const std::vector<double>& uv1, const std::vector<double>& uv2,
                          const double* K4, int maxIters, double confidence, uint64_t seed, Sampling sampling, LmedsTrace* trace = nullptr,
                          const std::vector<int32_t>* given = nullptr) {   // given: the samples to use, in place of drawing them
     RobustModel out;
-    const int n = (int)(uv1.size() / 2), maxm = solve_kind == EACHAM_SOLVE_ESSENTIAL5 ? 10 : 1;
+    const int n = (int)(uv1.size() / 2), maxm = solve_kind == EACHAM_SOLVE_ESSENTIAL5 ? 10 : (solve_kind == EACHAM_SOLVE_FUNDAMENTAL7 ? 3 : 1);
     if (n < m || uv2.size() != uv1.size() || maxIters <= 0) return out;
     int iterations = std::min(maxIters, std::max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3));
     std::vector<int32_t> idx;
     if (given)
         idx.assign(given->begin(), given->begin() + (size_t)m * std::min<size_t>(iterations, given->size() / m));
     else
-        idx = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1, uv2, seed, sampling);
+        idx = lmeds_samples(n, m, iterations, subset_check_of(solve_kind), uv1, uv2, seed, sampling);
     iterations = (int)(idx.size() / m);
     out.iterations = iterations;
     if (trace) trace->samples = idx;
@@ -239,6 +254,24 @@ inline RobustModel FindEssentialMat(Context& ctx, const std::vector<double>& uv1
                                     LmedsTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
     return twoview_detail::lmeds(ctx, EACHAM_SOLVE_ESSENTIAL5, EACHAM_SCORE_ESSENTIAL, 5, uv1, uv2, K4, maxIters, prob, seed, sampling, trace, samples);
 }
+// cv::findFundamentalMat(pts1, pts2, FM_LMEDS, 3.0, confidence, maxIters, mask) for image pairs without (trusted) intrinsics: pixels
+// in, no K. The seven-point solver (EACHAM_SOLVE_FUNDAMENTAL7: Hartley-normalised, unit Frobenius norm — eacham_hip.h states the
+// two deviations from run7Point) under the LMedS rule, scored by the larger epipolar-line distance (EACHAM_SCORE_FUNDAMENTAL).
+// The model is the winner as solved: cv::findFundamentalMat has no refit either. 1000 asked for with confidence 0.99 and 7-point
+// samples are 300 iterations.
+inline RobustModel FindFundamentalMat(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, int maxIters = 1000,
+                                      double confidence = 0.99, uint64_t seed = 12345, Sampling sampling = Sampling::OpenCV,
+                                      LmedsTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
+    return twoview_detail::lmeds(ctx, EACHAM_SOLVE_FUNDAMENTAL7, EACHAM_SCORE_FUNDAMENTAL, 7, uv1, uv2, nullptr, maxIters, confidence, seed, sampling, trace,
+                                 samples);
+}
+// E = K^T F K for K = [fx 0 cx; 0 fy cy; 0 0 1] (K4 = fx fy cx cy, the same camera for both images): a verified uncalibrated edge
+// goes on into RecoverPose / RecoverPoseBatch once intrinsics are known. The scale is F's.
+inline Mat3 EssentialFromFundamental(const Mat3& F, const double* K4) {
+    const Mat3 K{K4[0], 0, K4[2], 0, K4[1], K4[3], 0, 0, 1};
+    return twoview_detail::mul(twoview_detail::mul(twoview_detail::transpose(K), F), K);
+}
+
 // What cv::findHomography does with the inliers of the robust stage (fundam.cpp, "if (result && npoints > 4 ...)"): the
 // normalised DLT over ALL inliers (HomographyEstimatorCallback::runKernel with count = inliers), then at most 10
 // Levenberg-Marquardt iterations on the 8 free entries (H[8] = 1) of the forward transfer error. Host arithmetic: a 9 x 9
@@ -399,7 +432,7 @@ inline std::vector<RobustModel> lmeds_batch(Context& ctx, int solve_kind, int m,
         const int n = (int)(uv1[p].size() / 2);
         if (n >= m && uv2[p].size() == uv1[p].size() && maxIters > 0) {   // (otherwise lmeds() returns at once: an empty problem here)
             const int iterations = std::min(maxIters, std::max(ransac_update_num_iters(confidence, 0.45, m, maxIters), 3));
-            const std::vector<int32_t> s = lmeds_samples(n, m, iterations, solve_kind == EACHAM_SOLVE_HOMOGRAPHY4, uv1[p], uv2[p], seeds[p], sampling);
+            const std::vector<int32_t> s = lmeds_samples(n, m, iterations, subset_check_of(solve_kind), uv1[p], uv2[p], seeds[p], sampling);
             out[p].iterations = (int)(s.size() / m);
             if (traces) (*traces)[p].samples = s;
             a.insert(a.end(), uv1[p].begin(), uv1[p].begin() + 2 * (size_t)n);
@@ -459,6 +492,20 @@ inline std::vector<RobustModel> FindEssentialMatBatch(Context& ctx, const std::v
                                                       const std::vector<uint64_t>& seeds, int maxIters = 1000, double prob = 0.99,
                                                       Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
     return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_ESSENTIAL5, 5, uv1, uv2, K4, maxIters, prob, seeds, sampling, traces);
+}
+// FindFundamentalMat for every pair of a list through one eacham_lmeds_batch call: result[p] equals FindFundamentalMat(ctx, uv1[p],
+// uv2[p], maxIters, confidence, 12345, sampling) field for field.
+inline std::vector<RobustModel> FindFundamentalMatBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                        const std::vector<std::vector<double>>& uv2, int maxIters = 1000, double confidence = 0.99,
+                                                        Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
+    return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_FUNDAMENTAL7, 7, uv1, uv2, nullptr, maxIters, confidence, 12345, sampling, traces);
+}
+// ... with a seed per pair: result[p] equals FindFundamentalMat(ctx, uv1[p], uv2[p], maxIters, confidence, seeds[p], sampling).
+inline std::vector<RobustModel> FindFundamentalMatBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                        const std::vector<std::vector<double>>& uv2, const std::vector<uint64_t>& seeds,
+                                                        int maxIters = 1000, double confidence = 0.99, Sampling sampling = Sampling::OpenCV,
+                                                        std::vector<LmedsTrace>* traces = nullptr) {
+    return twoview_detail::lmeds_batch(ctx, EACHAM_SOLVE_FUNDAMENTAL7, 7, uv1, uv2, nullptr, maxIters, confidence, seeds, sampling, traces);
 }
 // FindHomography for every pair of a list: one eacham_lmeds_batch call, then the host refit of FindHomography per pair.
 // result[p] equals FindHomography(ctx, uv1[p], uv2[p], maxIters, seeds[p], confidence, sampling).

@@ -492,6 +492,13 @@ int eacham_two_view_points(eacham_ctx* ctx, int n_matches, const double* uv1, co
 #define EACHAM_SCORE_ESSENTIAL 0
 #define EACHAM_SCORE_HOMOGRAPHY 1
 #define EACHAM_SCORE_PNP 2
+/*   kind FUNDAMENTAL a, b = n x 2 PIXELS of view 1 / view 2; models = n_models x 9 row-major F (x2' F x1 = 0). K is ignored (NULL or
+ *                    not) and nothing is normalised. FMEstimatorCallback::computeError, the larger of the two squared distances
+ *                    from a point to its epipolar line, fp64 with every operation rounded on its own, cast to float once:
+ *                      l2[r] = (F[3r] a0 + F[3r+1] a1) + F[3r+2],  l1[r] = (F[r] b0 + F[3+r] b1) + F[6+r],
+ *                      d = (b0 l2[0] + b1 l2[1]) + l2[2],  d2 = d d,
+ *                      err = (float)std::max(d2 / (l1[0] l1[0] + l1[1] l1[1]), d2 / (l2[0] l2[0] + l2[1] l2[1])). */
+#define EACHAM_SCORE_FUNDAMENTAL 3
 int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, const double* a, const double* b, int n_models,
                             const double* models, const double* K, float threshold, float* errors,
                             int32_t* inlier_counts, float* medians);
@@ -511,6 +518,21 @@ int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, const doubl
  * Pair it with eacham_score_hypotheses (all models against all correspondences) for the RANSAC / LMedS choice. */
 #define EACHAM_SOLVE_HOMOGRAPHY4 0
 #define EACHAM_SOLVE_ESSENTIAL5 1
+/*   kind FUNDAMENTAL7 a, b = n_points x 2 pixels of view 1 / view 2; 7 indices per sample; up to 3 models of 9 doubles (row-major F,
+ *                     x2' F x1 = 0, unit Frobenius norm), models = n_samples x 3 x 9, the slots beyond n_models[s] zero. K is not
+ *                     read. OpenCV 4.5.5's run7Point restated with two deliberate deviations (parity with OpenCV is unpinned here
+ *                     as everywhere):
+ *                       1. Hartley normalisation: each image's 7 points are moved to their centroid (p0 + sum(pi - p0) / 7) and scaled to a mean distance
+ *                          of sqrt(2) from it (fp64, sums in index order), the models are denormalised as T2' F^ T1. OpenCV solves
+ *                          on raw pixels with an SVD of the 7 x 9 system; here the null space comes from the 9 x 9 Jacobi
+ *                          eigen-solver on A'A (the homography's), which squares the condition number and needs the normalisation.
+ *                       2. A model has unit Frobenius norm after denormalisation (as ESSENTIAL5's), not F[8] = 1.
+ *                     Null space: f2 = eigenvector of the smallest eigenvalue, f1 = that of the second smallest, minus f2; the
+ *                     cubic det(z f1 + f2) by run7Point's c[] expressions; its roots by ESSENTIAL5's Durand-Kerner recipe (degree
+ *                     drop at 1e-14 cmax, a root is real iff |zi| <= 1e-7 (1 + |zr|), four Newton steps, real roots ascending).
+ *                     A degenerate sample is no error: n_models = 0 and zero models when a normalisation scale is not finite (all
+ *                     points of one image coincide), the cubic is all zero or no real root is left. */
+#define EACHAM_SOLVE_FUNDAMENTAL7 2
 int eacham_solve_minimal(eacham_ctx* ctx, int kind, int n_points, const double* a, const double* b, const double* K,
                          int n_samples, const int32_t* sample_idx, double* models, int32_t* n_models);
 
@@ -534,8 +556,9 @@ int eacham_solve_pnp(eacham_ctx* ctx, int n_points, const double* object_points,
  * n_problems. Problem p owns the points point_ptr[p] .. point_ptr[p+1] of a / b (rows of 2 doubles) and the samples
  * sample_ptr[p] .. sample_ptr[p+1] of sample_idx (4 / 5 indices per sample, LOCAL to the problem's points; drawing them
  * stays with the caller, as for eacham_solve_minimal). Both offset tables have n_problems + 1 entries, start at 0 and
- * do not decrease. kind = EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5; K = fx fy cx cy shared by all problems
- * (NULL as in eacham_solve_minimal). Per problem, with n points and m = 4 / 5:
+ * do not decrease. kind = EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5 | EACHAM_SOLVE_FUNDAMENTAL7 (7 indices per sample,
+ * up to 3 candidates per sample, scored with EACHAM_SCORE_FUNDAMENTAL, K ignored); K = fx fy cx cy shared by all problems
+ * (NULL as in eacham_solve_minimal). Per problem, with n points and m = 4 / 5 / 7:
  *   every sample is solved and the candidates are flattened in sample order, then root order; every candidate's median
  *   error over the problem's own points is taken; the winner is the FIRST candidate with the smallest non-NaN median
  *   (TIES: equal medians keep the earlier candidate); sigma = max(2.5 * 1.4826 * (1 + 5 / max(n - m, 1)) *
@@ -713,10 +736,11 @@ int eacham_graph_tracks(eacham_graph* graph, const uint8_t* keep, int min_len, i
 int eacham_graph_set_keypoints(eacham_graph* graph, const double* xy);
 /* eacham_graph_verify: PROBLEM p is caller pair p of eacham_graph_create (every per-pair output has npairs entries), its points
  * the pair's matches in the caller's order: a[i] = xy[kp_offsets[f1] + q[i]], b[i] = xy[kp_offsets[f2] + t[i]].
- *   kind         EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5; K as in eacham_lmeds_batch (4 doubles on the host, NULL =
- *                already normalised; read by the essential kind only)
+ *   kind         EACHAM_SOLVE_HOMOGRAPHY4 | EACHAM_SOLVE_ESSENTIAL5 | EACHAM_SOLVE_FUNDAMENTAL7; K as in eacham_lmeds_batch (4 doubles
+ *                on the host, NULL = already normalised; read by the essential kind only)
  *   sampling     EACHAM_SAMPLING_OPENCV: per pair cv::RNG((uint64)-1), getSubset with at most 1000 attempts per subset and, for
- *                the homography, checkSubset on the pair's points as floats; a pair stops where getSubset gives up.
+ *                the homography and the fundamental matrix, their checkSubset on the pair's points as floats
+ *                (cv_check_subset_homography / cv_check_subset_fundamental); a pair stops where getSubset gives up.
  *                EACHAM_SAMPLING_COUNTER: the counter-based stream, seeded per pair by seeds[p] (seeds == NULL: 12345 for every
  *                pair; the OpenCV stream does not read seeds). Both are the functions of include/eacham/CvSampling.hpp that the
  *                host's lmeds_samples / draw_samples call, compiled for the device.
