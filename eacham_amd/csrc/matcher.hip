@@ -608,17 +608,20 @@ __device__ __forceinline__ void top2_merge(int& m1, int& m2, int s1, int s2) {
 // computes their exact {v1, tile, v2} against the whole train frame (the candidate-only pass of the columns with the frames' roles
 // swapped), overwriting their rowres entries before match_rows2_kernel reads them. out: rowres[p][j] = {v1, 0, u, 0}.
 //
-// GATHER (KS = 8, exact): the exact pass behind the screen sweep. The workgroup is `unit` = an item of match_openscan_kernel, {first
-// candidate, count <= 256} into the launch's packed list `cands` ({pair index within the launch, stored query row}), all onto one
-// train frame (the first candidate's pair names it): wave w takes candidates 64 w .. 64 w + 63, a lane gathers ITS row's fragments
-// from the candidate's own query frame (the addressing of match_colverify_kernel's gather), and the tail writes {v1, t1, v2, 0} to
-// rowres[pair][row] from the h == 0 lanes of real candidates. A wave without candidates still stages; a lane past `count` computes
-// on the item's first candidate and writes nothing. Everything between prologue and tail is the sweep as it stands.
+// GATHER (KS = 8, exact): the exact pass behind the screen sweep. The workgroup is an item of the list the screen sweep's tail wrote
+// (the comment above match_openprep_kernel): {segment head h, k} = candidates 256 k .. of the segment's region cands[h row_stride ..]
+// ({pair index within the launch, stored query row}), min(256, segcount[h] - 256 k) of them and all onto one train frame (the
+// first candidate's pair names it): wave w takes candidates 64 w .. 64 w + 63, a lane gathers ITS row's fragments from the
+// candidate's own query frame (the addressing of match_colverify_kernel's gather), and the tail writes {v1, t1, v2, 0} to
+// rowres[pair][row] from the h == 0 lanes of real candidates. A wave without candidates still stages; a lane past the count computes
+// on the item's first candidate and writes nothing. Everything between prologue and tail is the sweep as it stands. The items are
+// dense in [0, *n_items), in the order they were created; the workgroup is item blockIdx.x of a grid that bounds the list from above.
 template <bool GATHER>
 struct GatherList {};   // (no argument without the gather)
 template <>
 struct GatherList<true> {
     const uint2* cands;
+    const int* segcount;
     const int2* items;
     const int* n_items;
 };
@@ -641,8 +644,9 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
     const uint2* pk = nullptr;            // GATHER: the item's candidates, item.y of them
     if constexpr (GATHER) {
         if ((int)blockIdx.x >= *gl.n_items) return;   // workgroup-uniform: the grid is an upper bound of the list
-        item = gl.items[blockIdx.x];
-        pk = gl.cands + item.x;
+        item = gl.items[blockIdx.x];      // {segment head, k}: the sweep that counted the segment has ended, its count is final
+        pk = gl.cands + (size_t)item.x * row_stride + GATHER_WIDTH * item.y;
+        item.y = min(GATHER_WIDTH, gl.segcount[item.x] - GATHER_WIDTH * item.y);
     }
     const int rb = GATHER ? 0 : blockIdx.x % wgs_per_pair;
     const int p = GATHER ? (int)pk[0].x : blockIdx.x / wgs_per_pair;
@@ -944,8 +948,10 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // A row without a real minimum, or whose minima fill one subset only, carries the bound form's padding values. The fourth word
 // (n1, ~0 without one) is read by eacham_match_debug_screen_pair only.
 // openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
-// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane. match_opencount_kernel /
-// match_openscan_kernel / match_openfill_kernel turn the words of a launch (256 B per pair where its rowres is 32 KB) into one packed candidate list.
+// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane (256 B per pair
+// where its rowres is 32 KB: match_rows2_kernel<.., true> counts a pair's open rows from them). With the same word the tail
+// reserves room in the candidate list of the pair's segment — one returning add per wave with an open row — and writes its
+// candidates and, where its range holds a multiple of 256, the item that starts there (OpenList, match_openprep_kernel).
 // LDS-DMA ring, just-in-time fragment ring and double-buffered accumulators are match_sweep_kernel's; a fragment is 24 bytes, two
 // LDS reads. The call structure is its own: 8 MFMAs per tile are half the int8 sweep's, so a call covers TWO train tiles between
 // two barriers (six ring slots of 6 KiB, three calls per trip), the four waves stage three pieces each spread over the call, and
@@ -967,13 +973,22 @@ __device__ __forceinline__ float fmin3(float a, float b, float c) {
 // the ratio test of the finalize kernels (defined with them below): the screen kernel's tail lists its open rows with it
 template <int METRIC>
 __device__ __forceinline__ bool ratio_pass(int d2_best, int d2_second, double ratio);
+// the candidate list of a launch as the tail writes it (the comment above match_openprep_kernel); unused where openmask is null
+struct OpenList {
+    const int* seghead;   // [pair of the launch] its segment's head, a pair index within the launch
+    int* segcount;        // [pair of the launch] at a head: candidates of the segment so far
+    uint2* cands;         // segment of head h: cands[h * row_stride ..]
+    int2* items;          // {head, k}: candidates 256 k .. of that segment
+    int* n_items;         // of the launch
+};
 struct ScreenFrag { v4i lo; v2i hi; };   // a lane's 32 codes of one K = 64 step
 __device__ __forceinline__ v8i screen_operand(const ScreenFrag& f) { return v8i{f.lo[0], f.lo[1], f.lo[2], f.lo[3], f.hi[0], f.hi[1], 0, 0}; }
 
 template <int METRIC>   // of the ratio test in the tail (binary frames of 129..256 bits carry the FP6 image too)
 __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
                                                                      int wgs_per_pair, uint4* __restrict__ rowres, int row_stride, double ratio,
-                                                                     unsigned long long* __restrict__ openmask, int mask_stride) {
+                                                                     unsigned long long* __restrict__ openmask, int mask_stride,
+                                                                     OpenList ol) {
     constexpr int NSUB = 2, KS = SCREEN_KS;
     constexpr int TILE_V4 = SCREEN_TILE_BYTES / 16;
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
@@ -1293,7 +1308,19 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         }
         open_rows |= (__ballot(open) & 0xffffffffull) << (32 * s);
     }
-    if (openmask && lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
+    if (!openmask) return;   // (the debug entry: no list)
+    if (lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
+    // the wave's open rows go into its segment's region of the candidate list (the comment above match_openprep_kernel)
+    const int c = __popcll(open_rows);
+    if (c == 0) return;      // wave-uniform: open_rows is a ballot
+    const int head = ol.seghead[p];
+    int pos = 0;
+    if (lane_t == 0) pos = atomicAdd(&ol.segcount[head], c);
+    pos = __shfl(pos, 0);
+    if ((open_rows >> lane_t) & 1)
+        ol.cands[(size_t)head * row_stride + pos + __popcll(open_rows & ((1ull << lane_t) - 1))] = make_uint2((unsigned)p, (unsigned)(ROWS_WAVE * wb + lane_t));
+    const int k = (pos + GATHER_WIDTH - 1) / GATHER_WIDTH;   // c <= 64: at most one multiple of the width in [pos, pos + c)
+    if (lane_t == 0 && GATHER_WIDTH * k < pos + c) ol.items[atomicAdd(ol.n_items, 1)] = make_int2(head, k);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1463,158 +1490,106 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
 }
 
 // Behind the SCREEN form of the sweep (match_screen_kernel): the rows its tail left open (openmask[p][wb]: one bit per row of
-// wave-block wb, match_rowpick_kernel's predicate) become ONE packed candidate list per launch, cut into items per train-frame run.
+// wave-block wb, match_rowpick_kernel's predicate) become ONE candidate list per launch, cut into items per train-frame run.
 // At the headline nine pairs in ten have an open row but the typical pair has two or three (the bound's slack), and an item streams
 // the whole train frame whatever it holds: per-pair items of 64 ran about half empty (38 103 items for 1.39 M open rows of an S200
 // step). Only the streamed frame has to be common to an item — the exact pass gathers its query rows per lane — so the candidates of
 // consecutive pairs onto one train frame share items (shard.order_pairs sorts a job by train frame): 5 537 items of 256.
 //   segment    a maximal run of consecutive pairs of the launch with one train frame (pairs[p].y); any pair order is legal and
-//              only gives shorter segments
-//   cands[i]   {pair index within the launch, stored query row}: pair order, ascending stored rows inside a pair — so a segment's
-//              candidates are contiguous. No output depends on the order inside a segment (a candidate is a lane of the exact pass)
-//   items[w]   {first candidate, count <= width}, all of one segment (width: GATHER_WIDTH = 256, a workgroup of the gathered sweep); a pair may straddle two items, a segment's last item may be
-//              short, a launch with no open row has none
-// Three kernels, three times per step in the exposed chain:
-//   match_opencount_kernel  a wave per pair: the popcount of its mask words -> state[p].x; a workgroup of sixteen pairs adds to the
-//                           tally ONCE (one add per pair to the same addresses is what a launch of ~10 000 pairs once spent 0.25 ms on)
-//   match_openscan_kernel   ONE workgroup over the <= batch pairs, 1024 at a time: exclusive sum of the counts (state[p].y = the pair's
-//                           first candidate), a running maximum over the segment heads' offsets (the segment's first candidate), a sum
-//                           of ceil(segment total / width) placed at each segment's last pair (the segment's first item); the items
-//                           of the chunk are then written by all threads, each finding its segment by bisection. No atomic but one
-//                           add to the tally's third word
-//   match_openfill_kernel   a wave per pair again: the set bits of a word go behind those of the words before it, each at the
-//                           popcount of the bits below it
-constexpr int LIST_WAVES = 16;
-constexpr int OSCAN_THREADS = 1024;
-__global__ __launch_bounds__(64 * LIST_WAVES) void match_opencount_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
-                                                                          const unsigned long long* __restrict__ openmask, int mask_stride,
-                                                                          int4* __restrict__ state, unsigned long long* __restrict__ tally) {
-    __shared__ int s_open[LIST_WAVES], s_rows[LIST_WAVES];
+//              only gives shorter segments. Its head is its first pair
+//   cands      {pair index within the launch, stored query row}. The segment of head h owns cands[h * row_stride ..] of the
+//              slot's rowcand area: room for row_stride candidates per pair of the segment, never less than its open rows, so no
+//              prefix sum places it. Inside the region the candidates stand in the order the sweep's waves reserved their room
+//              (one returning add of the wave's open rows to segcount[h]): no output depends on it, a candidate is a lane of the
+//              exact pass
+//   items      {h, k}: candidates 256 k .. 256 k + 255 of the segment of head h, as far as segcount[h] goes (width GATHER_WIDTH =
+//              256, a workgroup of the gathered sweep). The wave whose reservation holds candidate 256 k creates the item (one
+//              add to the launch's counter), so a segment of n open rows has ceil(n / 256) items and a launch with no open row
+//              none; their order in the list is that of the adds
+// seghead, segcount and the item counters are arrays of the CALL, outside the workspace slots: match_openprep_kernel sets them up
+// for every launch ahead of the first sweep (the launches are a function of the pair's index: LaunchCut), and nothing of the list
+// runs between a sweep and its exact pass. The debug tallies: the real query rows here (they depend on the pairs only), open rows
+// and items by match_opentally_kernel on the second stream behind the exact pass — one add per workgroup, never one per pair.
+struct LaunchCut {   // the launches of a job (next_batch) as a function of the pair: [0, n1) in launches of len1, [n1, n2) of len2, then len3
+    int n1, len1, n2, len2, len3;
+};
+__host__ __device__ inline int launch_of(const LaunchCut& c, int i, int* start) {
+    if (i < c.n1) { const int b = i / c.len1; *start = b * c.len1; return b; }
+    if (i < c.n2) { const int b = (i - c.n1) / c.len2; *start = c.n1 + b * c.len2; return c.n1 / c.len1 + b; }
+    const int b = (i - c.n2) / c.len3;
+    *start = c.n2 + b * c.len3;
+    return c.n1 / c.len1 + (c.n2 - c.n1) / c.len2 + b;
+}
+constexpr int PREP_THREADS = 256;
+__global__ __launch_bounds__(PREP_THREADS) void match_openprep_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
+                                                                      LaunchCut cut, int* __restrict__ seghead, int* __restrict__ segcount,
+                                                                      int* __restrict__ launch_items, unsigned long long* __restrict__ tally) {
+    __shared__ unsigned long long s_rows[PREP_THREADS / 64];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int p = blockIdx.x * LIST_WAVES + wave;
-    int open = 0, rows = 0;
-    if (p < npairs) {   // wave-uniform
-        const FrameDev A = frames[pairs[p].x];
-        rows = A.n;
-        const int nwords = (A.meta[1] + 1) / 2;
-        const unsigned long long* om = openmask + (size_t)p * mask_stride;
-        for (int w = lane; w < nwords; w += 64) open += __popcll(om[w]);
-#pragma unroll
-        for (int d = 32; d >= 1; d >>= 1) open += __shfl_xor(open, d);
-        if (lane == 0) ((int*)&state[p])[0] = open;
+    const int i = blockIdx.x * PREP_THREADS + threadIdx.x;
+    const bool live = i < npairs;
+    int start = 0, y = 0, v = -1;   // v: the last segment head at or before pair i, as far as this wave sees
+    unsigned long long rows = 0;
+    if (live) {
+        const int2 pr = pairs[i];
+        const int b = launch_of(cut, i, &start);
+        y = pr.y;
+        rows = (unsigned long long)frames[pr.x].n;
+        if (i == start || pairs[i - 1].y != y) v = i;
+        segcount[i] = 0;
+        if (i == start) launch_items[b] = 0;
     }
-    if (lane == 0) s_open[wave] = open, s_rows[wave] = rows;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long r = 0, o = 0;
-        for (int k = 0; k < LIST_WAVES; ++k) r += (unsigned long long)s_rows[k], o += (unsigned long long)s_open[k];
-        atomicAdd(&tally[0], r);   // {real query rows, rows left open} of the call
-        atomicAdd(&tally[1], o);
-    }
-}
-
-// inclusive scan over the OSCAN_THREADS threads of the workgroup (sum, or maximum of values >= -1); *total = the last thread's
-template <bool MAX>
-__device__ __forceinline__ int oscan_inclusive(int v, int* s_w /* [OSCAN_THREADS / 64] */, int* total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int d = 1; d < 64; d <<= 1) {
         const int u = __shfl_up(v, d);
-        if (lane >= d) v = MAX ? max(v, u) : v + u;
+        if (lane >= d) v = max(v, u);
     }
-    if (lane == 63) s_w[wave] = v;
-    __syncthreads();
-    int before = MAX ? -1 : 0, all = MAX ? -1 : 0;
-    for (int k = 0; k < OSCAN_THREADS / 64; ++k) {
-        const int e = s_w[k];
-        if (k < wave) before = MAX ? max(before, e) : before + e;
-        all = MAX ? max(all, e) : all + e;
-    }
-    __syncthreads();   // (the next call overwrites s_w)
-    *total = all;
-    return MAX ? max(v, before) : v + before;
-}
-
-__global__ __launch_bounds__(OSCAN_THREADS) void match_openscan_kernel(const int2* __restrict__ pairs, int npairs, int width, int4* __restrict__ state,
-                                                                       int2* __restrict__ items, int* __restrict__ n_items,
-                                                                       unsigned long long* __restrict__ tally) {
-    __shared__ int s_w[OSCAN_THREADS / 64];
-    __shared__ int s_item0[OSCAN_THREADS], s_first[OSCAN_THREADS], s_total[OSCAN_THREADS];
-    const int tid = threadIdx.x;
-    int cand0 = 0, seg0 = 0, item0 = 0;   // carried from chunk to chunk: candidates so far, the open segment's first candidate, items so far
-    // a chunk's words are fetched while the chunk before it is scanned (the barriers would otherwise expose every fetch)
-    int c_nxt = 0, y_nxt = 0, yp_nxt = 0, yn_nxt = 0;
-    auto fetch = [&](int p0) {
-        const int p = p0 + tid;
-        if (p < npairs) {
-            c_nxt = ((const int*)&state[p])[0];
-            y_nxt = pairs[p].y;
-            yp_nxt = p > 0 ? pairs[p - 1].y : 0;
-            yn_nxt = p + 1 < npairs ? pairs[p + 1].y : 0;
-        }
-    };
-    fetch(0);
-    for (int p0 = 0; p0 < npairs; p0 += OSCAN_THREADS) {
-        const int p = p0 + tid;
-        const bool live = p < npairs;
-        const int c = live ? c_nxt : 0;
-        const bool head = live && (p == 0 || yp_nxt != y_nxt);
-        const bool last = live && (p + 1 == npairs || yn_nxt != y_nxt);
-        fetch(p0 + OSCAN_THREADS);
-        int chunk_cands, chunk_items, unused;
-        const int off = cand0 + oscan_inclusive<false>(c, s_w, &chunk_cands) - c;      // the pair's first candidate
-        const int first = max(seg0, oscan_inclusive<true>(head ? off : -1, s_w, &unused));   // its segment's (offsets never decrease)
-        const int total = last ? off + c - first : 0;                                  // at a segment's last pair: the segment's candidates
-        const int ni = (total + width - 1) / width;
-        const int it0 = item0 + oscan_inclusive<false>(ni, s_w, &chunk_items) - ni;     // ... and its first item
-        if (live) state[p] = make_int4(c, off, 0, 0);
-        s_item0[tid] = it0, s_first[tid] = first, s_total[tid] = total;
-        __syncthreads();
-        // item w of the chunk belongs to the last thread t with s_item0[t] <= w: threads without items repeat their successor's value
-        for (int w = item0 + tid; w < item0 + chunk_items; w += OSCAN_THREADS) {
-            int t = 0;   // (s_item0[0] = item0 <= w)
-            for (int hi = OSCAN_THREADS; hi - t > 1;) {
-                const int mid = (t + hi) >> 1;
-                if (s_item0[mid] <= w) t = mid;
-                else hi = mid;
+    // lanes without a head up to them continue the segment of the wave's first pair (a launch starts a segment, so they are of its
+    // launch): the wave looks for its head 64 pairs at a time, back to the start of the launch
+    const bool need = live && v < 0;
+    if (__ballot(need)) {   // wave-uniform; lane 0 is one of them
+        const int w0 = blockIdx.x * PREP_THREADS + 64 * wave, s0 = __shfl(start, 0), y0 = __shfl(y, 0);
+        int hd = s0;
+        for (int base = w0 - 1; base >= s0; base -= 64) {
+            const int j = base - lane;
+            const unsigned long long m = __ballot(j >= s0 && pairs[j].y != y0);
+            if (m) {   // the nearest pair onto another frame: the segment starts behind it
+                hd = base - (__ffsll((long long)m) - 1) + 1;
+                break;
             }
-            const int k = w - s_item0[t];
-            items[w] = make_int2(s_first[t] + k * width, min(width, s_total[t] - k * width));
         }
-        seg0 = s_first[OSCAN_THREADS - 1];   // (of a thread past the list: the last segment's, never used again)
-        cand0 += chunk_cands;
-        item0 += chunk_items;
-        __syncthreads();
+        if (need) v = hd;
     }
-    if (tid == 0) {
-        *n_items = item0;
-        atomicAdd(&tally[2], (unsigned long long)item0);   // {items of the exact pass} of the call
+    if (live) seghead[i] = v - start;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) rows += __shfl_xor(rows, d);
+    if (lane == 0) s_rows[wave] = rows;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long r = 0;
+        for (int k = 0; k < PREP_THREADS / 64; ++k) r += s_rows[k];
+        atomicAdd(&tally[0], r);   // {real query rows} of the call
     }
 }
 
-__global__ __launch_bounds__(64 * LIST_WAVES) void match_openfill_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
-                                                                         const unsigned long long* __restrict__ openmask, int mask_stride,
-                                                                         const int4* __restrict__ state, uint2* __restrict__ cands) {
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int p = blockIdx.x * LIST_WAVES + wave;
-    if (p >= npairs) return;   // wave-uniform; no workgroup barrier below
-    const int4 st = state[p];
-    if (st.x == 0) return;
-    const int nwords = (frames[pairs[p].x].meta[1] + 1) / 2;
-    const unsigned long long* om = openmask + (size_t)p * mask_stride;
-    uint2* cl = cands + st.y;
-    int base = 0;
-    for (int w0 = 0; w0 < nwords; w0 += 64) {
-        const unsigned long long mine = w0 + lane < nwords ? om[w0 + lane] : 0ull;
-        const int nw = min(64, nwords - w0);
-        for (int k = 0; k < nw; ++k) {   // word w0 + k, the same in every lane
-            const unsigned long long m = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(mine >> 32), k) << 32) |
-                                         (unsigned)__builtin_amdgcn_readlane((int)mine, k);
-            if ((m >> lane) & 1) cl[base + __popcll(m & ((1ull << lane) - 1))] = make_uint2((unsigned)p, (unsigned)(64 * (w0 + k) + lane));
-            base += __popcll(m);
-        }
+// {rows left open, items of the exact pass} of a launch into the call's tally, once the launch's sweep has ended
+constexpr int TALLY_THREADS = 1024;
+__global__ __launch_bounds__(TALLY_THREADS) void match_opentally_kernel(const int* __restrict__ seghead, const int* __restrict__ segcount, int npairs,
+                                                                        const int* __restrict__ n_items, unsigned long long* __restrict__ tally) {
+    __shared__ unsigned long long s_open[TALLY_THREADS / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p = blockIdx.x * TALLY_THREADS + threadIdx.x;
+    unsigned long long open = p < npairs && seghead[p] == p ? (unsigned long long)segcount[p] : 0ull;
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) open += __shfl_xor(open, d);
+    if (lane == 0) s_open[wave] = open;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        unsigned long long o = 0;
+        for (int k = 0; k < TALLY_THREADS / 64; ++k) o += s_open[k];
+        atomicAdd(&tally[1], o);
+        if (blockIdx.x == 0) atomicAdd(&tally[2], (unsigned long long)*n_items);
     }
 }
 
@@ -1629,17 +1604,18 @@ __global__ __launch_bounds__(64 * LIST_WAVES) void match_openfill_kernel(const F
 // every column but the best one is at least the runner-up). match_argmin_kernel settles candidate columns with it.
 constexpr int MAX_TILES = MAX_ROWS / 32;
 constexpr int AITEM_SHARED = 1 << 16;   // aitems[..].y: the tile, plus this flag when the pair has more than one item of that tile
-// OPEN = true (mode 0 behind the SCREEN form of the sweep only): every candidate is a row the screen left open, and state[p].x still
-// holds their number (match_opencount_kernel; match_openscan_kernel kept it). A pair with no more than min_mutual open rows is dead
+// OPEN = true (mode 0 behind the SCREEN form of the sweep only): every candidate is a row the screen left open, and their number is
+// the popcount of the pair's mask words (openmask[p][..], 256 B where its rowres is 32 KB; every wave counts them all, so no
+// barrier). A pair with no more than min_mutual open rows is dead
 // whatever its rows hold (nine pairs in ten of S200), so it gets a dead pair's state — not live, no arg-min item, which is all that
-// match_colpick_kernel and match_finalize2_kernel read of it (count 0) — without one byte of its 32 KB of rowres; its rowcand,
-// candlist and L(p) are left out, nothing reads them for a dead pair. The count is read by every thread and its word is stored
-// back unchanged, so the one store needs no barrier ahead of it.
+// match_colpick_kernel and match_finalize2_kernel read of it (count 0) — without one byte of its rowres; its rowcand,
+// candlist and L(p) are left out, nothing reads them for a dead pair.
 template <int METRIC, bool OPEN = false>
 __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, const uint4* __restrict__ rowres, int row_stride, double ratio,
     int min_dir, int min_mutual, int mode, uint2* __restrict__ rowcand, int* __restrict__ candlist, int* __restrict__ bytile,
-    int4* __restrict__ state, int4* __restrict__ aitems, int* __restrict__ n_aitems) {
+    int4* __restrict__ state, int4* __restrict__ aitems, int* __restrict__ n_aitems,
+    const unsigned long long* __restrict__ openmask = nullptr, int mask_stride = 0) {   // (OPEN only)
     __shared__ int s_wave[FIN_THREADS / 64];
     __shared__ int s_cnt[MAX_TILES], s_pos[MAX_TILES], s_grp[MAX_TILES];
     __shared__ int s_scan[FIN_THREADS], s_scan2[FIN_THREADS];
@@ -1647,8 +1623,12 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rows2_kernel(
     const int tid = threadIdx.x;
     const int p = blockIdx.x;
     if constexpr (OPEN) {
-        const int open = ((const int*)&state[p])[0];
-        if (open <= min_mutual) {   // workgroup-uniform
+        const int nwords = (frames[pairs[p].x].meta[1] + 1) / 2;   // the words the sweep wrote: one per wave-block with a real tile
+        int open = 0;
+        for (int w = tid & 63; w < nwords; w += 64) open += __popcll(openmask[(size_t)p * mask_stride + w]);
+#pragma unroll
+        for (int d = 32; d >= 1; d >>= 1) open += __shfl_xor(open, d);
+        if (open <= min_mutual) {   // workgroup-uniform: every wave has counted all the words
             if (tid == 0) state[p] = make_int4(open, 0, 0x7fffffff, 0);
             return;
         }
@@ -2268,6 +2248,15 @@ static int next_batch(const MatchPlan& pl, int b, int first, int npairs) {
     if (pl.slots == 2 && b < pl.full_launches) return (pl.full_rounds + (b < pl.long_launches ? 1 : 0)) * pl.round_pairs;
     return std::min(pl.batch, npairs - first);
 }
+// ... and the same launches as a function of the pair's index, for match_openprep_kernel (run_match_metric checks one against the other)
+static LaunchCut launch_cut(const MatchPlan& pl) {
+    LaunchCut c{0, 1, 0, 1, pl.batch};
+    if (pl.slots == 2) {
+        c.len1 = (pl.full_rounds + 1) * pl.round_pairs, c.n1 = pl.long_launches * c.len1;
+        c.len2 = pl.full_rounds * pl.round_pairs, c.n2 = c.n1 + (pl.full_launches - pl.long_launches) * c.len2;
+    }
+    return c;
+}
 
 // Core driver, CSR over the pairs out. mode 0 = mutual + thresholds, mode 1 = directed lists.
 template <int METRIC>
@@ -2297,8 +2286,30 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     // (|m12|, |m21|) or use other thresholds get every column's top-2 from the sweep itself, as before.
     const bool full_cols = mode == 0 && (stats_dev != nullptr || (long long)min_mutual < (long long)min_dir - 1);
     MatchPlan pl = make_plan(ctx, npairs, full_cols);
-    rc = ensure_workspace(ctx, pl.total);
+    // The row sweep of the lean form. EACHAM_MATCH_SWEEP_FORM forces the exact (1) or the bound form (2) at every dimension; screen (3)
+    // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
+    const int form = ctx->match_sweep_form;
+    const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
+    // behind the slots, under the screen sweep: the arrays of the call that its candidate list needs (seghead | segcount | one item
+    // counter per launch)
+    const LaunchCut cut = launch_cut(pl);
+    const size_t call_pairs = ((size_t)npairs + 63) & ~(size_t)63;
+    size_t call_ints = 0;
+    if (screen_sweep) {
+        int launches = 0;
+        for (int first = 0; first < npairs; ++launches) {
+            int start = 0;
+            if (launch_of(cut, first, &start) != launches || start != first)
+                return ctx->fail(EACHAM_ERR_INVALID, "internal: launch %d at pair %d is not where the cut has it", launches, first);
+            first += next_batch(pl, launches, first, npairs);
+        }
+        call_ints = 2 * call_pairs + (size_t)launches;
+    }
+    rc = ensure_workspace(ctx, pl.total + call_ints * sizeof(int));
     if (rc) return rc;
+    int* const seghead = (int*)((char*)ctx->ws + pl.total);
+    int* const segcount = seghead + call_pairs;
+    int* const launch_items = segcount + call_pairs;
     const size_t fin_smem = (size_t)(full_cols ? 2 : 1) * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024) {
         if (full_cols) EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_kernel<METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
@@ -2311,11 +2322,10 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st1));        // inputs queued on the context stream
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_join, 0));
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(colprune_totals(ctx), 0, 2 * sizeof(unsigned long long), st2));
-    // The row sweep of the lean form. EACHAM_MATCH_SWEEP_FORM forces the exact (1) or the bound form (2) at every dimension; screen (3)
-    // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
-    const int form = ctx->match_sweep_form;
-    const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
-    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 3 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 3 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it first
+    if (screen_sweep)   // segment heads, zeroed counters and the rows of the tally for every launch of the call: nothing of the list sits between two sweeps
+        match_openprep_kernel<<<(npairs + PREP_THREADS - 1) / PREP_THREADS, PREP_THREADS, 0, st1>>>(ctx->frame_table_dev, pairs_dev, npairs, cut, seghead, segcount,
+                                                                                                    launch_items, screen_tally(ctx));
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job is cut into equal full batches and a short last one
     // (an eighth of a full one at the most; make_plan), so the exposed lists, exact pass and tail are those of ~1 200 pairs instead
@@ -2335,7 +2345,7 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
         // matrix cores instead (match_screen_kernel, half the matrix cycles), with the same exact pass behind
         const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
         uint4* rowres = (uint4*)(ws + pl.off_rowres);
-        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows (screen form: match_openscan_kernel writes it)
+        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows of the bound form
         // persistent workgroups over an item list (its length is only known on the device): one round of the chip
         const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
         {
@@ -2344,7 +2354,9 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                 constexpr int KS = decltype(ks)::value;
                 if (screen_sweep)
                     match_screen_kernel<METRIC><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride, ratio,
-                                                                                          (unsigned long long*)(ws + pl.off_openmask), pl.mask_stride);
+                                                                                          (unsigned long long*)(ws + pl.off_openmask), pl.mask_stride,
+                                                                                          OpenList{seghead + first, segcount + first, (uint2*)(ws + pl.off_rowcand),
+                                                                                                   (int2*)(ws + pl.off_items), launch_items + b});
                 else if (full_cols)
                     match_tile_kernel<KS><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, st1>>>(
                         ctx->frame_table_dev, pb, pl.wgs_per_pair, pl.col_chunks, rowres, (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
@@ -2358,26 +2370,21 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
             // The exact pass over the rows the screen left open runs HERE, on the sweep's stream and ahead of ev_tile. Beside the next
             // sweep it got in only as sweep workgroups retired (164 VGPRs x 3 waves fill a SIMD: 5.8 ms where it takes 1.0 ms alone) and
             // held the slot the sweep after next waits for; behind its own sweep the next sweep starts behind it and the step is 4 %
-            // shorter (profiles/screen_exact_behind_sweep.txt). The open rows of the whole launch go into one packed list, cut into items
-            // of 256 per run of pairs onto one train frame (the comment above match_opencount_kernel), and the exact pass is the exact
-            // sweep itself with gathered query rows, a workgroup per item: the train tile staged once in LDS for four waves, where
-            // match_colverify_kernel<8, true> fetched it per wave from L2 (profiles/open_rows_packed.txt: 1.70 -> 0.69 ms per step).
+            // shorter (profiles/screen_exact_behind_sweep.txt). The sweep's tail has written the open rows of the whole launch as one
+            // candidate list, cut into items of 256 per run of pairs onto one train frame (the comment above match_openprep_kernel), so
+            // the exact pass follows the sweep directly: the exact sweep itself with gathered query rows, the train tile staged once in
+            // LDS for four waves, where match_colverify_kernel<8, true> fetched it per wave from L2 (profiles/open_rows_packed.txt).
             // The list lives in the slot's rowcand area ({pair, row} is a uint2, one per stored row per pair at the most), which
-            // match_rows2_kernel first writes on the second stream behind ev_tile; {first, count} items: at most row_stride / 64 + 1
-            // per pair, the items area holds row_stride / 32. The slot-free wait above covers rowcand, state and items of this slot;
+            // match_rows2_kernel first writes on the second stream behind ev_tile; {head, k} items: at most row_stride / 256 + 1
+            // per pair, the items area holds row_stride / 32. The slot-free wait above covers rowcand and items of this slot;
             // the HBM-bound tail stays on the second stream.
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st1);
-            uint2* cands = (uint2*)(ws + pl.off_rowcand);
-            int4* state = (int4*)(ws + pl.off_state);
-            int2* items = (int2*)(ws + pl.off_items);
-            const unsigned long long* openmask = (const unsigned long long*)(ws + pl.off_openmask);
-            const int lgrid = (nb + LIST_WAVES - 1) / LIST_WAVES;
-            match_opencount_kernel<<<lgrid, 64 * LIST_WAVES, 0, st1>>>(ctx->frame_table_dev, pb, nb, openmask, pl.mask_stride, state, screen_tally(ctx));
-            match_openscan_kernel<<<1, OSCAN_THREADS, 0, st1>>>(pb, nb, GATHER_WIDTH, state, items, n_pre, screen_tally(ctx));   // writes *n_pre
-            match_openfill_kernel<<<lgrid, 64 * LIST_WAVES, 0, st1>>>(ctx->frame_table_dev, pb, nb, openmask, pl.mask_stride, state, cands);
-            const int ggrid = nb * ((pl.row_stride + GATHER_WIDTH - 1) / GATHER_WIDTH + 1);   // an upper bound of the items: workgroups past the list leave at once
-            match_sweep_kernel<SCREEN_EXACT_KS, false, true><<<ggrid, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, 0, rowres, pl.row_stride,
-                                                                                           GatherList<true>{cands, items, n_pre});
+            // a workgroup per item, the grid an upper bound of the dense list: workgroups past it leave at once. (Persistent workgroups
+            // over the list, one round of the chip, were slower at two and at three waves per SIMD: profiles/open_rows_reserved.txt)
+            const int ggrid = nb * ((pl.row_stride + GATHER_WIDTH - 1) / GATHER_WIDTH + 1);
+            match_sweep_kernel<SCREEN_EXACT_KS, false, true><<<ggrid, WG_THREADS, 0, st1>>>(
+                ctx->frame_table_dev, pb, 0, rowres, pl.row_stride,
+                GatherList<true>{(const uint2*)(ws + pl.off_rowcand), segcount + first, (const int2*)(ws + pl.off_items), launch_items + b});
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
@@ -2401,6 +2408,9 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                 int* openlist = (int*)(ws + pl.off_openlist);
                 const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
+                if (screen_sweep)   // the launch's open rows and items into the debug tally: off the sweeps' chain
+                    match_opentally_kernel<<<(nb + TALLY_THREADS - 1) / TALLY_THREADS, TALLY_THREADS, 0, st2>>>(seghead + first, segcount + first, nb, launch_items + b,
+                                                                                                           screen_tally(ctx));
                 with_ks(ctx->ks_common, [&](auto ks) {
                     constexpr int KS = decltype(ks)::value;
                     if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it (the screen form's ran behind its sweep)
@@ -2411,7 +2421,8 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
                     // (mutual matching behind the screen sweep: a pair its open count already fails leaves before it reads a row; L2 only)
                     if (METRIC == METRIC_L2 && screen_sweep && mode == 0)
                         match_rows2_kernel<METRIC_L2, true><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual,
-                                                                                  mode, rowcand, candlist, bytile, state, aitems, n_aitems);
+                                                                                  mode, rowcand, candlist, bytile, state, aitems, n_aitems,
+                                                                                  (const unsigned long long*)(ws + pl.off_openmask), pl.mask_stride);
                     else
                         match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
                                                                         rowcand, candlist, bytile, state, aitems, n_aitems);
@@ -2739,7 +2750,8 @@ int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1
         rc = io.upload(d);
         if (rc) return rc;
         uint4* rowres = (uint4*)((char*)ctx->ws + pl.off_rowres);
-        match_screen_kernel<METRIC_L2><<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride, 0.0, nullptr, 0);
+        match_screen_kernel<METRIC_L2><<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride, 0.0, nullptr, 0,
+                                                                                        OpenList{});
         EACHAM_HIP_TRY(ctx, hipGetLastError());
         rc = io.finish();
         if (rc) return rc;
