@@ -28,6 +28,7 @@
 #include "ba_plan.hpp"
 #include "ba_groups.hpp"
 #include "devprim.hpp"
+#include "ws_carve.hpp"
 
 #include <cstdlib>
 
@@ -3540,18 +3541,6 @@ __global__ __launch_bounds__(TPB) void prep_block_fill(int nc, int nblk, const i
     blocks[at.b] = make_int4(c, c2, at.c, k);
     for (int i = 0; i < k; ++i) chunks[at.c + i] = make_int4(at.b, at.a + PAIR_CHUNK * i, min(PAIR_CHUNK, cnt - PAIR_CHUNK * i), i);
 }
-
-struct Bump {  // carves 256-byte aligned arrays out of a scratch buffer (base == nullptr: sizes only)
-    char* base;
-    size_t off = 0;
-    explicit Bump(void* b) : base((char*)b) {}
-    template <class T>
-    T* take(size_t n) {
-        T* p = base ? (T*)(base + off) : nullptr;
-        off += (std::max<size_t>(n, 1) * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
-};
 
 // ---- device form of the landmark-major structure (ba_groups.hpp holds the definition; these kernels reproduce build_groups
 // bit for bit: tests/test_ba_prepare_gpu.py compares every array) -------------------------------------------------------------

@@ -388,12 +388,10 @@ int upload_frame_f32(eacham_ctx* ctx, int frame_id, const float* src_dev, int n,
 int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
                   int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
                   int4* stats_dev);
-// How the float path cuts a job into launches and lays one launch's arrays into the workspace (both of its forms, L2 and dot product)
-struct MatchPlanF32 {
-    int row_stride, wb_stride, wgs_per_pair;  // padded rows per frame (max over the resident frames), its 32-row tiles, workgroups per pair
-    int batch;                                // pairs per launch
-    size_t off_rowres, off_colpart, off_matches, total;
-};
+// How the float path cuts a job into launches and lays one launch's arrays into the workspace (both of its forms, L2 and dot
+// product): match_plan.hpp, here for the resident frames
+struct MatchPlanF32;
+struct F32Arrays;
 MatchPlanF32 plan_match_f32(const eacham_ctx* ctx, int npairs);
 // matcher_dot.hip
 int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_score, int min_dir, int min_mutual, int mode,
@@ -401,7 +399,7 @@ int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_
                   long long* total_dev, int4* stats_dev);
 // the launches of run_match_dot, shared with the screened form: the fp32 tile kernel over nb pairs, and finalize + scan + compaction
 void launch_match_tile_dot(eacham_ctx* ctx, const int2* pb, int nb, const MatchPlanF32& pl, int2* rr, int2* cp);
-int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const int2* pb, int nb, int first, bool is_last, int2* rr, int2* cp,
+int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const F32Arrays& a, const int2* pb, int nb, int first, bool is_last,
                           float min_score, int min_dir, int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
                           uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev);
 // matcher_dot16.hip

@@ -26,6 +26,7 @@
 // 1, which no ratio <= 1 accepts), so no row index is carried through the column reduction.
 // A running top-2 costs two VALU ops:  m2 = med3(m1, m2, key); m1 = min(m1, key).
 #include "context.hpp"
+#include "match_plan.hpp"
 #include "match_screen.hpp"
 #include "match_tail.hpp"
 
@@ -56,6 +57,7 @@ constexpr int MATCH_NSUB = 2;                        // 32-row MFMA sub-tiles pe
 constexpr int ROWS_PER_WAVE = 32 * MATCH_NSUB;
 constexpr int ROWS_PER_WG = WAVES * ROWS_PER_WAVE;
 constexpr int GROUP_TILES = MATCH_NSUB;              // tiles in use are padded to whole wave-blocks
+static_assert(PLAN_WG_TILES == ROWS_PER_WG / 32 && PLAN_CHUNK_TILES == CHUNK_TILES, "match_plan.hpp plans for these kernels");
 
 // ------------------------------------------------------------------------------------------------
 // upload: fp32 row-major -> fragment-major int8 + squared norms
@@ -1507,19 +1509,9 @@ __global__ __launch_bounds__(FIN_THREADS) void match_rowpick_kernel(
 //              add to the launch's counter), so a segment of n open rows has ceil(n / 256) items and a launch with no open row
 //              none; their order in the list is that of the adds
 // seghead, segcount and the item counters are arrays of the CALL, outside the workspace slots: match_openprep_kernel sets them up
-// for every launch ahead of the first sweep (the launches are a function of the pair's index: LaunchCut), and nothing of the list
+// for every launch ahead of the first sweep (the launches are a function of the pair's index: LaunchCut, match_plan.hpp), and nothing of the list
 // runs between a sweep and its exact pass. The debug tallies: the real query rows here (they depend on the pairs only), open rows
 // and items by match_opentally_kernel on the second stream behind the exact pass — one add per workgroup, never one per pair.
-struct LaunchCut {   // the launches of a job (next_batch) as a function of the pair: [0, n1) in launches of len1, [n1, n2) of len2, then len3
-    int n1, len1, n2, len2, len3;
-};
-__host__ __device__ inline int launch_of(const LaunchCut& c, int i, int* start) {
-    if (i < c.n1) { const int b = i / c.len1; *start = b * c.len1; return b; }
-    if (i < c.n2) { const int b = (i - c.n1) / c.len2; *start = c.n1 + b * c.len2; return c.n1 / c.len1 + b; }
-    const int b = (i - c.n2) / c.len3;
-    *start = c.n2 + b * c.len3;
-    return c.n1 / c.len1 + (c.n2 - c.n1) / c.len2 + b;
-}
 constexpr int PREP_THREADS = 256;
 __global__ __launch_bounds__(PREP_THREADS) void match_openprep_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs, int npairs,
                                                                       LaunchCut cut, int* __restrict__ seghead, int* __restrict__ segcount,
@@ -2160,102 +2152,119 @@ static bool frames_have_screen(const eacham_ctx* ctx) {
     return true;
 }
 
-struct MatchPlan {
-    int batch;       // pairs per launch
-    int round_pairs; // pairs of one round of 512 workgroups (launches are sized in whole rounds)
-    int tail_pairs;  // the job's short last launch holds this many pairs at the most
-    int full_launches, full_rounds, long_launches;   // the cut of a job through two slots (make_plan, next_batch)
-    int wb_stride;   // wave-blocks per frame (max over resident frames)
-    int row_stride;  // padded rows per frame (max)
-    int wgs_per_pair;
-    int col_chunks;  // sweeps of <= 4096 train rows per pair
-    int slots;       // workspace copies: batch i+1's tile kernel overlaps batch i's finalize
-    size_t off_rowres, off_colpart, off_matches, slot_bytes, total;
-    // the candidate-only column pass: rowcand | candlist | colres | state | items | n_items
-    size_t off_rowcand, off_candlist, off_colres, off_state, off_items, off_nitems, off_bytile, off_aitems, off_openlist;
-    int mask_stride;   // 64-bit words per pair of the screen sweep's open-row masks: one per wave-block
-    size_t off_openmask;
-};
-
+// The plan of a job (match_plan.hpp) for the resident frames
 static MatchPlan make_plan(const eacham_ctx* ctx, int npairs, bool full_cols) {
     int max_tiles = std::max(4, GROUP_TILES);
     for (const auto& f : ctx->frames)
         if (f.n >= 0) max_tiles = std::max(max_tiles, f.tiles_used);
-    MatchPlan pl;
-    pl.row_stride = max_tiles * 32;
-    pl.wb_stride = (max_tiles + (ROWS_PER_WG / 32) - 1) / (ROWS_PER_WG / 32) + 1;  // column-partial slots per pair: one per workgroup + 1
-    pl.wgs_per_pair = (max_tiles + (ROWS_PER_WG / 32) - 1) / (ROWS_PER_WG / 32);
-    pl.col_chunks = (max_tiles + CHUNK_TILES - 1) / CHUNK_TILES;
-    // per pair: row results + match list, and EITHER the column partials of the full sweep OR the arrays of the candidate pass
-    const size_t colpart_pp = full_cols ? (size_t)pl.wb_stride * pl.row_stride * sizeof(int2) : 0;
-    const size_t cand_pp = full_cols ? 0 : (size_t)pl.row_stride * (sizeof(uint2) + 3 * sizeof(int) + sizeof(uint2)) + sizeof(int4) +
-                                               (size_t)max_tiles * (sizeof(int2) + 2 * sizeof(int4));
-    size_t per_pair = (size_t)pl.col_chunks * pl.row_stride * sizeof(int4) + (size_t)pl.row_stride * sizeof(uint2) + colpart_pp + cand_pp;
-    // bound a slot near 1 GiB so the column partials of one batch stay cache-friendly
-    size_t budget = (size_t)ctx->match_budget_mb << 20;
-    int batch = (int)std::min<size_t>(std::max<size_t>(budget / per_pair, 1), (size_t)npairs);
-    // whole rounds of workgroups (2 per CU x 256 CUs) keep the tail of a launch short
-    const int wgs = pl.wgs_per_pair * pl.col_chunks;
-    int round_pairs = 512;
-    for (int g = 512; g >= 1; g >>= 1)
-        if (wgs % g == 0) { round_pairs = 512 / g; break; }
-    if (batch < npairs && batch > round_pairs) batch -= batch % round_pairs;
-    // a job that fits one launch (a shard of a multi-GPU run) is still cut in two, so that the finalize
-    // of its first half runs beside the tile kernel of the second
-    if (batch >= npairs && npairs >= 8 * round_pairs) batch = ((npairs + 1) / 2 + round_pairs - 1) / round_pairs * round_pairs;
-    pl.batch = std::max(batch, 1);
-    pl.round_pairs = pl.batch % round_pairs == 0 ? round_pairs : 1;   // (a budget below one round: launches are sized in pairs)
-    pl.slots = (pl.batch < npairs && !ctx->match_no_overlap) ? 2 : 1;  // (diagnostic switch, read once at eacham_ctx_create)
-    // The cut of the whole job, two slots in use: n full launches and ONE short last launch, the only one whose exact pass and
-    // candidate tail nothing hides. The short launch is planned first — the last tail_pairs of the job at the most (an eighth of
-    // a full launch in whole rounds), less whatever fills the full launches up to whole rounds — and the rest is dealt out over as
-    // few launches as the budget allows, equal to a round. So the last launch is never the budget's remnant: full launches with only the
-    // last one shortened had cut S200 into 9 792 + 9 792 + 316 and cut 2 x batch + 1 pairs into batch + batch + 1 (profiles/launch_cut.txt).
-    pl.tail_pairs = std::max(pl.round_pairs, pl.batch / 8 / pl.round_pairs * pl.round_pairs);
-    pl.full_launches = pl.full_rounds = pl.long_launches = 0;
-    if (pl.slots == 2) {
-        const int rp = pl.round_pairs, last_max = std::min(pl.tail_pairs, pl.batch);   // last launch: (last_max - rp, last_max] pairs
-        const int rounds = (npairs - last_max + rp - 1) / rp;                          // of all full launches; >= 1: npairs > batch
-        pl.full_launches = (int)(((long long)rounds * rp + pl.batch - 1) / pl.batch);
-        pl.full_rounds = rounds / pl.full_launches;
-        pl.long_launches = rounds % pl.full_launches;   // the first so many take one round more (then full_rounds * rp < batch)
-    }
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    pl.off_rowres = 0;
-    pl.off_colpart = align(pl.off_rowres + (size_t)pl.batch * pl.col_chunks * pl.row_stride * sizeof(int4));
-    pl.off_matches = align(pl.off_colpart + (full_cols ? (size_t)pl.batch * pl.wb_stride * pl.row_stride * sizeof(int2) : 0));
-    pl.off_rowcand = align(pl.off_matches + (size_t)pl.batch * pl.row_stride * sizeof(uint2));
-    const size_t cb = full_cols ? 0 : (size_t)pl.batch;  // the candidate arrays exist in the other form only
-    pl.off_candlist = align(pl.off_rowcand + cb * pl.row_stride * sizeof(uint2));
-    pl.off_colres = align(pl.off_candlist + cb * pl.row_stride * sizeof(int));
-    pl.off_state = align(pl.off_colres + cb * pl.row_stride * sizeof(uint2));
-    pl.off_items = align(pl.off_state + cb * sizeof(int4));
-    pl.off_nitems = align(pl.off_items + cb * max_tiles * sizeof(int2));
-    pl.off_bytile = align(pl.off_nitems + 256);
-    pl.off_aitems = align(pl.off_bytile + cb * pl.row_stride * sizeof(int));
-    pl.off_openlist = align(pl.off_aitems + cb * 2 * max_tiles * sizeof(int4));
-    pl.mask_stride = (pl.row_stride + 63) / 64;
-    pl.off_openmask = align(pl.off_openlist + cb * pl.row_stride * sizeof(int));
-    pl.slot_bytes = align(pl.off_openmask + cb * pl.mask_stride * sizeof(unsigned long long));   // (1/128 of rowres: not counted in per_pair, the launches stay as they were cut)
-    pl.total = pl.slot_bytes * pl.slots;
-    return pl;
+    // (match_no_overlap: diagnostic switch, read once at eacham_ctx_create)
+    return make_plan(MatchPlanIn{max_tiles, npairs, (size_t)ctx->match_budget_mb << 20, full_cols, ctx->match_no_overlap});
 }
 
-// Pairs of launch b, which starts at `first`: the cut make_plan planned for the npairs it was given when two workspace slots are in
-// use (equal full launches, then the short one), else full batches and what is left. One definition for run_match and for
-// eacham_match_debug_batches.
-static int next_batch(const MatchPlan& pl, int b, int first, int npairs) {
-    if (pl.slots == 2 && b < pl.full_launches) return (pl.full_rounds + (b < pl.long_launches ? 1 : 0)) * pl.round_pairs;
-    return std::min(pl.batch, npairs - first);
+// A matching call of the int8 kinds as its launches see it, and one launch: pairs [first, first + nb) of the call, its launch b, in
+// workspace slot s. The four sequences a launch consists of follow; run_match_metric orders them on the two streams.
+struct MatchCall {
+    eacham_ctx* ctx;
+    MatchPlan pl;
+    CallArrays call;
+    hipStream_t st1, st2;
+    double ratio;
+    int min_dir, min_mutual, mode;
+    size_t fin_smem;
+    bool screen_sweep, bound_sweep;
+};
+struct MatchLaunch {
+    Slot s;
+    const int2* pb;
+    int nb, first, b;
+    int* cnt;
+};
+
+// The row sweep, on st1. The full-column form sweeps with match_tile_kernel, the lean form with match_sweep_kernel: up to 128-D its
+// BOUND form (the sweep is bound by its epilogue's VALU work there) + an exact pass over the rows it could not finish; above, where
+// the matrix pipe binds, the rows are screened on the FP6 matrix cores (match_screen_kernel), the same exact pass behind
+template <int METRIC>
+static void launch_sweep(const MatchCall& c, const MatchLaunch& l) {
+    const MatchPlan& pl = c.pl;
+    const FrameDev* frames = c.ctx->frame_table_dev;
+    with_ks(c.ctx->ks_common, [&](auto ks) {
+        constexpr int KS = decltype(ks)::value;
+        if (c.screen_sweep)
+            match_screen_kernel<METRIC><<<l.nb * pl.wgs_per_pair, WG_THREADS, 0, c.st1>>>(
+                frames, l.pb, pl.wgs_per_pair, l.s.rowres, pl.row_stride, c.ratio, l.s.openmask, pl.mask_stride,
+                OpenList{c.call.seghead + l.first, c.call.segcount + l.first, l.s.rowcand, l.s.items, c.call.launch_items + l.b});
+        else if (pl.full_cols)
+            match_tile_kernel<KS><<<l.nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, c.st1>>>(
+                frames, l.pb, pl.wgs_per_pair, pl.col_chunks, l.s.rowres, l.s.colpart, pl.wb_stride, pl.row_stride);
+        else if (c.bound_sweep)
+            match_sweep_kernel<KS, true><<<l.nb * pl.wgs_per_pair, WG_THREADS, 0, c.st1>>>(frames, l.pb, pl.wgs_per_pair, l.s.rowres, pl.row_stride);
+        else
+            match_sweep_kernel<KS, false><<<l.nb * pl.wgs_per_pair, WG_THREADS, 0, c.st1>>>(frames, l.pb, pl.wgs_per_pair, l.s.rowres, pl.row_stride);
+    });
 }
-// ... and the same launches as a function of the pair's index, for match_openprep_kernel (run_match_metric checks one against the other)
-static LaunchCut launch_cut(const MatchPlan& pl) {
-    LaunchCut c{0, 1, 0, 1, pl.batch};
-    if (pl.slots == 2) {
-        c.len1 = (pl.full_rounds + 1) * pl.round_pairs, c.n1 = pl.long_launches * c.len1;
-        c.len2 = pl.full_rounds * pl.round_pairs, c.n2 = c.n1 + (pl.full_launches - pl.long_launches) * c.len2;
-    }
-    return c;
+
+// The exact pass over the rows the screen left open, on the sweep's stream directly behind it and ahead of ev_tile (beside the next
+// sweep it got in only as sweep workgroups retired and held the slot the sweep after next waits for: DESIGN.md 3.3,
+// profiles/screen_exact_behind_sweep.txt): the exact sweep itself with gathered query rows, over the candidate list the sweep's tail
+// wrote (the comment above match_openprep_kernel). The list lives in the slot's rowcand area ({pair, row} is a uint2, one per stored
+// row per pair at the most), which match_rows2_kernel first writes on the second stream behind ev_tile; {head, k} items: at most
+// row_stride / 256 + 1 per pair, the items area holds row_stride / 32. The slot-free wait covers rowcand and items of this slot.
+static void launch_open_rows_exact(const MatchCall& c, const MatchLaunch& l) {
+    // a workgroup per item, the grid an upper bound of the dense list: workgroups past it leave at once
+    const int ggrid = l.nb * ((c.pl.row_stride + GATHER_WIDTH - 1) / GATHER_WIDTH + 1);
+    match_sweep_kernel<SCREEN_EXACT_KS, false, true><<<ggrid, WG_THREADS, 0, c.st1>>>(
+        c.ctx->frame_table_dev, l.pb, 0, l.s.rowres, c.pl.row_stride,
+        GatherList<true>{l.s.rowcand, c.call.segcount + l.first, l.s.items, c.call.launch_items + l.b});
+}
+
+// The tail of the full-column form, on st2: every column's top-2 came out of the sweep
+template <int METRIC>
+static void launch_full_cols_tail(const MatchCall& c, const MatchLaunch& l, int4* stats) {
+    match_finalize_kernel<METRIC><<<l.nb, FIN_THREADS, c.fin_smem, c.st2>>>(c.ctx->frame_table_dev, l.pb, l.s.rowres, l.s.colpart, c.pl.col_chunks, c.pl.wb_stride,
+                                                                     c.pl.row_stride, c.ratio, c.min_dir, c.min_mutual, c.mode, l.s.matches, l.cnt, stats);
+}
+
+// The tail of the lean form, on st2: (the bound form's open rows) -> passing rows and their candidate columns -> arg-min over the
+// candidates' tiles -> the columns it could not settle -> matches
+template <int METRIC>
+static int launch_lean_tail(const MatchCall& c, const MatchLaunch& l) {
+    eacham_ctx* ctx = c.ctx;
+    const MatchPlan& pl = c.pl;
+    const Slot& s = l.s;
+    const FrameDev* frames = ctx->frame_table_dev;
+    hipStream_t st2 = c.st2;
+    const int nb = l.nb, mode = c.mode;
+    int *n_items = &s.counters->n_items, *n_pre = &s.counters->n_pre, *n_aitems = &s.counters->n_aitems;
+    // persistent workgroups over an item list (its length is only known on the device): one round of the chip
+    const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
+    const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
+    EACHAM_HIP_TRY(ctx, hipMemsetAsync(s.counters, 0, sizeof(SlotCounters), st2));
+    if (c.screen_sweep)   // the launch's open rows and items into the debug tally: off the sweeps' chain
+        match_opentally_kernel<<<(nb + TALLY_THREADS - 1) / TALLY_THREADS, TALLY_THREADS, 0, st2>>>(c.call.seghead + l.first, c.call.segcount + l.first, nb,
+                                                                                               c.call.launch_items + l.b, screen_tally(ctx));
+    with_ks(ctx->ks_common, [&](auto ks) {
+        constexpr int KS = decltype(ks)::value;
+        if (c.bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it (the screen form's ran behind its sweep)
+            match_rowpick_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(frames, l.pb, s.rowres, pl.row_stride, c.ratio, s.candlist, s.state, s.items, n_pre);
+            match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(frames, l.pb, nullptr, s.candlist, s.state, s.items, n_pre, pl.row_stride, 0, nullptr, s.rowres);
+        }
+        // (mutual matching behind the screen sweep: a pair its open count already fails leaves before it reads a row; L2 only)
+        if (METRIC == METRIC_L2 && c.screen_sweep && mode == 0)
+            match_rows2_kernel<METRIC_L2, true><<<nb, FIN_THREADS, 0, st2>>>(frames, l.pb, s.rowres, pl.row_stride, c.ratio, c.min_dir, c.min_mutual, mode, s.rowcand,
+                                                                      s.candlist, s.bytile, s.state, s.aitems, n_aitems, s.openmask, pl.mask_stride);
+        else
+            match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(frames, l.pb, s.rowres, pl.row_stride, c.ratio, c.min_dir, c.min_mutual, mode, s.rowcand,
+                                                            s.candlist, s.bytile, s.state, s.aitems, n_aitems);
+        match_argmin_kernel<KS, METRIC><<<agrid, 64, 0, st2>>>(frames, l.pb, s.rowcand, s.bytile, s.aitems, n_aitems, pl.row_stride, mode == 0 ? s.colres : nullptr,
+                                                       s.state, c.ratio, ctx->match_colprune ? 1 : 0);
+        if (mode == 0) {   // the candidates the arg-min pass could not settle (state[p].w of them): listed, then the column pass
+            match_colpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(s.candlist, s.colres, s.state, pl.row_stride, s.openlist, s.items, n_items, colprune_totals(ctx));
+            match_colverify_kernel<KS><<<vgrid, WG_THREADS, 0, st2>>>(frames, l.pb, s.rowcand, s.openlist, s.state, s.items, n_items, pl.row_stride, 3, s.colres);
+        }
+    });
+    match_finalize2_kernel<METRIC><<<nb, FIN_THREADS, c.fin_smem, st2>>>(frames, l.pb, s.rowcand, s.colres, s.state, pl.row_stride, c.ratio, c.min_mutual, mode,
+                                                                  s.matches, l.cnt);
+    return EACHAM_OK;
 }
 
 // Core driver, CSR over the pairs out. mode 0 = mutual + thresholds, mode 1 = directed lists.
@@ -2285,47 +2294,40 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     // looked at (candidate-only pass); directed lists need no column at all. Callers that ask for the per-pair statistics
     // (|m12|, |m21|) or use other thresholds get every column's top-2 from the sweep itself, as before.
     const bool full_cols = mode == 0 && (stats_dev != nullptr || (long long)min_mutual < (long long)min_dir - 1);
-    MatchPlan pl = make_plan(ctx, npairs, full_cols);
+    const MatchPlan pl = make_plan(ctx, npairs, full_cols);
     // The row sweep of the lean form. EACHAM_MATCH_SWEEP_FORM forces the exact (1) or the bound form (2) at every dimension; screen (3)
     // and the default (0) run the screen sweep where the frames have the FP6 image (above 128-D) and the bound form up to 128-D.
     const int form = ctx->match_sweep_form;
     const bool screen_sweep = !full_cols && (form == 0 || form == 3) && frames_have_screen(ctx);
-    // behind the slots, under the screen sweep: the arrays of the call that its candidate list needs (seghead | segcount | one item
-    // counter per launch)
+    const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
+    // the arrays of the call behind the slots (under the screen sweep only), one item counter per launch: the launches are counted
+    // and the cut as match_openprep_kernel sees it is checked against them
     const LaunchCut cut = launch_cut(pl);
-    const size_t call_pairs = ((size_t)npairs + 63) & ~(size_t)63;
-    size_t call_ints = 0;
-    if (screen_sweep) {
-        int launches = 0;
-        for (int first = 0; first < npairs; ++launches) {
-            int start = 0;
-            if (launch_of(cut, first, &start) != launches || start != first)
-                return ctx->fail(EACHAM_ERR_INVALID, "internal: launch %d at pair %d is not where the cut has it", launches, first);
-            first += next_batch(pl, launches, first, npairs);
-        }
-        call_ints = 2 * call_pairs + (size_t)launches;
+    int launches = 0;
+    for (int first = 0; screen_sweep && first < npairs; ++launches) {
+        int start = 0;
+        if (launch_of(cut, first, &start) != launches || start != first)
+            return ctx->fail(EACHAM_ERR_INVALID, "internal: launch %d at pair %d is not where the cut has it", launches, first);
+        first += next_batch(pl, launches, first, npairs);
     }
-    rc = ensure_workspace(ctx, pl.total + call_ints * sizeof(int));
+    rc = ensure_workspace(ctx, pl.total + (screen_sweep ? call_bytes(npairs, launches) : 0));
     if (rc) return rc;
-    int* const seghead = (int*)((char*)ctx->ws + pl.total);
-    int* const segcount = seghead + call_pairs;
-    int* const launch_items = segcount + call_pairs;
     const size_t fin_smem = (size_t)(full_cols ? 2 : 1) * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024) {
         if (full_cols) EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_kernel<METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
         else EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize2_kernel<METRIC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
     }
-    // Two streams: the tile kernels run back to back on the context stream; finalize, scan and
-    // compaction of a batch run on stream2 beside the next batch's tile kernel (they are bound by
-    // HBM/L2, the tile kernel by the vector ALU), each batch in its own workspace slot.
+    // Two streams: the sweeps (and the screen form's exact pass) run back to back on the context stream; the tail, scan and
+    // compaction of a launch run on stream2 beside the next launch's sweep, each launch in its own workspace slot.
     hipStream_t st1 = ctx->stream, st2 = pl.slots == 2 || npairs <= pl.batch ? ctx->stream2 : ctx->stream;
+    const MatchCall c{ctx, pl, call_arrays(ctx->ws, pl, npairs, launches), st1, st2, ratio, min_dir, min_mutual, mode, fin_smem, screen_sweep, bound_sweep};
     EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, st1));        // inputs queued on the context stream
     EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_join, 0));
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(colprune_totals(ctx), 0, 2 * sizeof(unsigned long long), st2));
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(screen_tally(ctx), 0, 3 * sizeof(unsigned long long), screen_sweep ? st1 : st2));   // on the stream that adds to it first
     if (screen_sweep)   // segment heads, zeroed counters and the rows of the tally for every launch of the call: nothing of the list sits between two sweeps
-        match_openprep_kernel<<<(npairs + PREP_THREADS - 1) / PREP_THREADS, PREP_THREADS, 0, st1>>>(ctx->frame_table_dev, pairs_dev, npairs, cut, seghead, segcount,
-                                                                                                    launch_items, screen_tally(ctx));
+        match_openprep_kernel<<<(npairs + PREP_THREADS - 1) / PREP_THREADS, PREP_THREADS, 0, st1>>>(ctx->frame_table_dev, pairs_dev, npairs, cut, c.call.seghead,
+                                                                                                    c.call.segcount, c.call.launch_items, screen_tally(ctx));
     // The work behind a batch's sweep (rows / candidate columns / finalize / compaction) runs on the second stream beside the NEXT
     // batch's sweep — except the last batch's, which nothing hides: the job is cut into equal full batches and a short last one
     // (an eighth of a full one at the most; make_plan), so the exposed lists, exact pass and tail are those of ~1 200 pairs instead
@@ -2334,112 +2336,24 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     for (int first = 0, nb = 0; first < npairs; first += nb, ++b) {
         nb = next_batch(pl, b, first, npairs);
         const int slot = b % pl.slots;
-        char* ws = (char*)ctx->ws + (size_t)slot * pl.slot_bytes;
-        const int2* pb = pairs_dev + first;
+        const MatchLaunch l{pl.slot(ctx->ws, slot), pairs_dev + first, nb, first, b, counts_dev + first};
         if (b >= pl.slots) EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st1, ctx->ev_fin[slot], 0));  // slot free again
-        // The lean form sweeps rows with match_sweep_kernel. Its BOUND form + the exact pass over the rows it could not finish: up to
-        // 128-D, where the sweep is bound by its epilogue's VALU work (S200 at 128-D +5 %, the 1000-frame KITTI stand-in +12 %); at
-        // 256-D the sweep is bound by the matrix pipe and gains 4 % while the exact pass (one more stream of the train frame per pair
-        // beside the next sweep) costs the step 4-8 % (profiles/r05_match_bound_sweep_ab.txt)
-        // above it the int8 sweep is bound by the matrix pipe, where the bound form gains nothing: there the rows are screened on the FP6
-        // matrix cores instead (match_screen_kernel, half the matrix cycles), with the same exact pass behind
-        const bool bound_sweep = !full_cols && !screen_sweep && (form == 2 || ((form == 0 || form == 3) && ctx->ks_common <= 4));
-        uint4* rowres = (uint4*)(ws + pl.off_rowres);
-        int* n_pre = (int*)(ws + pl.off_nitems) + 8;   // item counter of the exact pass over the open rows of the bound form
-        // persistent workgroups over an item list (its length is only known on the device): one round of the chip
-        const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
-            with_ks(ctx->ks_common, [&](auto ks) {
-                constexpr int KS = decltype(ks)::value;
-                if (screen_sweep)
-                    match_screen_kernel<METRIC><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride, ratio,
-                                                                                          (unsigned long long*)(ws + pl.off_openmask), pl.mask_stride,
-                                                                                          OpenList{seghead + first, segcount + first, (uint2*)(ws + pl.off_rowcand),
-                                                                                                   (int2*)(ws + pl.off_items), launch_items + b});
-                else if (full_cols)
-                    match_tile_kernel<KS><<<nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, st1>>>(
-                        ctx->frame_table_dev, pb, pl.wgs_per_pair, pl.col_chunks, rowres, (uint2*)(ws + pl.off_colpart), pl.wb_stride, pl.row_stride);
-                else if (bound_sweep)
-                    match_sweep_kernel<KS, true><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
-                else
-                    match_sweep_kernel<KS, false><<<nb * pl.wgs_per_pair, WG_THREADS, 0, st1>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, rowres, pl.row_stride);
-            });
+            launch_sweep<METRIC>(c, l);
         }
         if (screen_sweep) {
-            // The exact pass over the rows the screen left open runs HERE, on the sweep's stream and ahead of ev_tile. Beside the next
-            // sweep it got in only as sweep workgroups retired (164 VGPRs x 3 waves fill a SIMD: 5.8 ms where it takes 1.0 ms alone) and
-            // held the slot the sweep after next waits for; behind its own sweep the next sweep starts behind it and the step is 4 %
-            // shorter (profiles/screen_exact_behind_sweep.txt). The sweep's tail has written the open rows of the whole launch as one
-            // candidate list, cut into items of 256 per run of pairs onto one train frame (the comment above match_openprep_kernel), so
-            // the exact pass follows the sweep directly: the exact sweep itself with gathered query rows, the train tile staged once in
-            // LDS for four waves, where match_colverify_kernel<8, true> fetched it per wave from L2 (profiles/open_rows_packed.txt).
-            // The list lives in the slot's rowcand area ({pair, row} is a uint2, one per stored row per pair at the most), which
-            // match_rows2_kernel first writes on the second stream behind ev_tile; {head, k} items: at most row_stride / 256 + 1
-            // per pair, the items area holds row_stride / 32. The slot-free wait above covers rowcand and items of this slot;
-            // the HBM-bound tail stays on the second stream.
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st1);
-            // a workgroup per item, the grid an upper bound of the dense list: workgroups past it leave at once. (Persistent workgroups
-            // over the list, one round of the chip, were slower at two and at three waves per SIMD: profiles/open_rows_reserved.txt)
-            const int ggrid = nb * ((pl.row_stride + GATHER_WIDTH - 1) / GATHER_WIDTH + 1);
-            match_sweep_kernel<SCREEN_EXACT_KS, false, true><<<ggrid, WG_THREADS, 0, st1>>>(
-                ctx->frame_table_dev, pb, 0, rowres, pl.row_stride,
-                GatherList<true>{(const uint2*)(ws + pl.off_rowcand), segcount + first, (const int2*)(ws + pl.off_items), launch_items + b});
+            launch_open_rows_exact(c, l);
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_tile[slot], st1));
         EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st2, ctx->ev_tile[slot], 0));
-        int* cnt = counts_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE, st2);
-            if (full_cols) {
-                match_finalize_kernel<METRIC><<<nb, FIN_THREADS, fin_smem, st2>>>(
-                    ctx->frame_table_dev, pb, rowres, (const uint2*)(ws + pl.off_colpart), pl.col_chunks, pl.wb_stride, pl.row_stride, ratio,
-                    min_dir, min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
-            } else {
-                uint2* rowcand = (uint2*)(ws + pl.off_rowcand);
-                int* candlist = (int*)(ws + pl.off_candlist);
-                uint2* colres = (uint2*)(ws + pl.off_colres);
-                int4* state = (int4*)(ws + pl.off_state);
-                int2* items = (int2*)(ws + pl.off_items);
-                int* n_items = (int*)(ws + pl.off_nitems);
-                int* n_aitems = n_items + 16;
-                int* bytile = (int*)(ws + pl.off_bytile);
-                int4* aitems = (int4*)(ws + pl.off_aitems);
-                int* openlist = (int*)(ws + pl.off_openlist);
-                const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
-                EACHAM_HIP_TRY(ctx, hipMemsetAsync(n_items, 0, 32 * sizeof(int), st2));
-                if (screen_sweep)   // the launch's open rows and items into the debug tally: off the sweeps' chain
-                    match_opentally_kernel<<<(nb + TALLY_THREADS - 1) / TALLY_THREADS, TALLY_THREADS, 0, st2>>>(seghead + first, segcount + first, nb, launch_items + b,
-                                                                                                           screen_tally(ctx));
-                with_ks(ctx->ks_common, [&](auto ks) {
-                    constexpr int KS = decltype(ks)::value;
-                    if (bound_sweep) {   // the rows the bound form left open: exact {v1, tile, v2} into rowres, before the rows kernel reads it (the screen form's ran behind its sweep)
-                        match_rowpick_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, candlist, state, items, n_pre);
-                        match_colverify_kernel<KS, true><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, nullptr, candlist, state, items, n_pre,
-                                                                                        pl.row_stride, 0, nullptr, rowres);
-                    }
-                    // (mutual matching behind the screen sweep: a pair its open count already fails leaves before it reads a row; L2 only)
-                    if (METRIC == METRIC_L2 && screen_sweep && mode == 0)
-                        match_rows2_kernel<METRIC_L2, true><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual,
-                                                                                  mode, rowcand, candlist, bytile, state, aitems, n_aitems,
-                                                                                  (const unsigned long long*)(ws + pl.off_openmask), pl.mask_stride);
-                    else
-                        match_rows2_kernel<METRIC><<<nb, FIN_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowres, pl.row_stride, ratio, min_dir, min_mutual, mode,
-                                                                        rowcand, candlist, bytile, state, aitems, n_aitems);
-                    match_argmin_kernel<KS, METRIC><<<agrid, 64, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, bytile, aitems, n_aitems, pl.row_stride,
-                                                                   mode == 0 ? colres : nullptr, state, ratio, ctx->match_colprune ? 1 : 0);
-                    if (mode == 0) {   // the candidates the arg-min pass could not settle (state[p].w of them): listed, then the column pass
-                        match_colpick_kernel<<<nb, FIN_THREADS, 0, st2>>>(candlist, colres, state, pl.row_stride, openlist, items, n_items, colprune_totals(ctx));
-                        match_colverify_kernel<KS><<<vgrid, WG_THREADS, 0, st2>>>(ctx->frame_table_dev, pb, rowcand, openlist, state, items, n_items,
-                                                                                  pl.row_stride, 3, colres);
-                    }
-                });
-                match_finalize2_kernel<METRIC><<<nb, FIN_THREADS, fin_smem, st2>>>(ctx->frame_table_dev, pb, rowcand, colres, state, pl.row_stride, ratio,
-                                                                          min_mutual, mode, (uint2*)(ws + pl.off_matches), cnt);
-            }
-            scan_counts_kernel<<<1, 1024, 0, st2>>>(cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-            compact_edges_kernel<<<nb, 256, 0, st2>>>((const uint2*)(ws + pl.off_matches), cnt, offsets_dev + first,
-                                                      pl.row_stride, edges_dev, edge_cap);
+            if (full_cols) launch_full_cols_tail<METRIC>(c, l, stats_dev ? stats_dev + first : nullptr);
+            else if ((rc = launch_lean_tail<METRIC>(c, l))) return rc;
+            scan_counts_kernel<<<1, 1024, 0, st2>>>(l.cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
+            compact_edges_kernel<<<nb, 256, 0, st2>>>(l.s.matches, l.cnt, offsets_dev + first, pl.row_stride, edges_dev, edge_cap);
         }
         EACHAM_HIP_TRY(ctx, hipEventRecord(ctx->ev_fin[slot], st2));
         EACHAM_HIP_TRY(ctx, hipGetLastError());
@@ -2741,15 +2655,15 @@ int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1
         const FrameHost& A = ctx->frames[f1];
         if (cap < A.n) return ctx->fail(EACHAM_ERR_CAPACITY, "%d rows but capacity %d", A.n, cap);
         if (A.n == 0) return EACHAM_OK;
-        MatchPlan pl = make_plan(ctx, 1, false);
+        const MatchPlan pl = make_plan(ctx, 1, false);
         rc = ensure_workspace(ctx, pl.total);
         if (rc) return rc;
+        uint4* const rowres = pl.slot(ctx->ws, 0).rowres;
         IoStage io(ctx, ctx->stream);
         const auto h_pair = io.in<int2>(pr, 1);
         IoDev d;
         rc = io.upload(d);
         if (rc) return rc;
-        uint4* rowres = (uint4*)((char*)ctx->ws + pl.off_rowres);
         match_screen_kernel<METRIC_L2><<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride, 0.0, nullptr, 0,
                                                                                         OpenList{});
         EACHAM_HIP_TRY(ctx, hipGetLastError());

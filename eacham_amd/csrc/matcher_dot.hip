@@ -13,6 +13,7 @@
 // comparison is a strict '>', so -inf and NaN similarities never win and never pass a threshold; ties resolve to the
 // lower index like every other path.
 #include "context.hpp"
+#include "match_plan.hpp"
 #include "match_tail.hpp"
 
 #include <algorithm>
@@ -23,6 +24,7 @@ typedef float v16f __attribute__((ext_vector_type(16)));
 typedef const float __attribute__((address_space(1)))* gfloat_t;
 
 constexpr int F_THREADS = 256, F_WAVES = 4;
+static_assert(PLAN_F32_WG_TILES == F_WAVES, "match_plan.hpp plans for these kernels");
 #define EACHAM_NEG_INF (-__builtin_inff())
 
 // ---- K1d: similarity tiles + fused row/column top-1 ---------------------------------------------------
@@ -226,13 +228,14 @@ void launch_match_tile_dot(eacham_ctx* ctx, const int2* pb, int nb, const MatchP
 }
 
 // finalize, scan of the counts and compaction of one launch's pairs [first, first + nb)
-int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const int2* pb, int nb, int first, bool is_last, int2* rr, int2* cp,
+int launch_match_dot_tail(eacham_ctx* ctx, const MatchPlanF32& pl, const F32Arrays& a, const int2* pb, int nb, int first, bool is_last,
                           float min_score, int min_dir, int min_mutual, int mode, int* counts_dev, long long* offsets_dev,
                           uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev) {
     const size_t fin_smem = (size_t)2 * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024)
         EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_dot_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
-    uint2* mt = (uint2*)((char*)ctx->ws + pl.off_matches);
+    int2 *rr = a.rowres_dot, *cp = a.colpart_dot;
+    uint2* mt = a.matches;
     {
         ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
         int* cnt = counts_dev + first;
@@ -252,17 +255,15 @@ int run_match_dot(eacham_ctx* ctx, const int2* pairs_dev, int npairs, float min_
     const MatchPlanF32 pl = plan_match_f32(ctx, npairs);
     int rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
-    char* ws = (char*)ctx->ws;
-    int2* rr = (int2*)(ws + pl.off_rowres);   // the plan's int4 slots, half used: one plan for both forms
-    int2* cp = (int2*)(ws + pl.off_colpart);
+    const F32Arrays a = pl.carve(ctx->ws);
     for (int first = 0; first < npairs; first += pl.batch) {
         const int nb = std::min(pl.batch, npairs - first);
         const int2* pb = pairs_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE);
-            launch_match_tile_dot(ctx, pb, nb, pl, rr, cp);
+            launch_match_tile_dot(ctx, pb, nb, pl, a.rowres_dot, a.colpart_dot);
         }
-        rc = launch_match_dot_tail(ctx, pl, pb, nb, first, first + nb == npairs, rr, cp, min_score, min_dir, min_mutual, mode, counts_dev,
+        rc = launch_match_dot_tail(ctx, pl, a, pb, nb, first, first + nb == npairs, min_score, min_dir, min_mutual, mode, counts_dev,
                                    offsets_dev, edges_dev, scores_dev, edge_cap, total_dev, stats_dev);
         if (rc) return rc;
     }

@@ -14,6 +14,7 @@
 // access is 1 KiB contiguous and LDS-DMA copies a tile unswizzled. Built lazily from the resident fp32 fragments on a frame's
 // first screened call, dropped with the frame.
 #include "context.hpp"
+#include "match_plan.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -535,23 +536,10 @@ int run_match_dot_screened(eacham_ctx* ctx, const int2* pairs_dev, const int2* p
                            int n_fallback, float min_score, int min_dir, int min_mutual, int* counts_dev, long long* offsets_dev,
                            uint2* edges_dev, float* scores_dev, long long edge_cap, long long* total_dev, int4* stats_dev) {
     const MatchPlanF32 pl = plan_match_f32(ctx, npairs);
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // behind the plan of the fp32 form (its {bits, index} arrays are what the finalize pass reads): the sweep's top-2 arrays
-    // and the lists of the open
-    const size_t off_rr16 = pl.total;
-    const size_t off_cp16 = align(off_rr16 + (size_t)pl.batch * pl.row_stride * sizeof(int4));
-    const size_t off_open = align(off_cp16 + (size_t)pl.batch * pl.wb_stride * pl.row_stride * sizeof(int4));
-    const size_t off_ocnt = align(off_open + (size_t)pl.batch * 2 * pl.row_stride * sizeof(int));
-    const size_t total = align(off_ocnt + (size_t)pl.batch * sizeof(int2));
-    int rc = ensure_workspace(ctx, total);
+    int rc = ensure_workspace(ctx, pl.total_screened);
     if (rc) return rc;
-    char* ws = (char*)ctx->ws;
-    int2* rr = (int2*)(ws + pl.off_rowres);
-    int2* cp = (int2*)(ws + pl.off_colpart);
-    int4* rr16 = (int4*)(ws + off_rr16);
-    int4* cp16 = (int4*)(ws + off_cp16);
-    int* open_idx = (int*)(ws + off_open);
-    int2* open_cnt = (int2*)(ws + off_ocnt);
+    const F32Arrays a = pl.carve(ctx->ws, true);   // (the {bits, index} arrays of the fp32 form are what the finalize pass reads)
+    int2 *rr = a.rowres_dot, *cp = a.colpart_dot;
     const int empty = (int)ctx->frames.size();
     const int D2 = ctx->ks_common;
     const float kappa = dot16_kappa(D2);
@@ -567,16 +555,16 @@ int run_match_dot_screened(eacham_ctx* ctx, const int2* pairs_dev, const int2* p
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE);
             if (fb_here < nb) {
-                launch_tile16<false>(ctx, grid, pb, fb, empty, pl, rr16, cp16, nullptr);
+                launch_tile16<false>(ctx, grid, pb, fb, empty, pl, a.rr16, a.cp16, nullptr);
                 dot_screen_classify_kernel<<<nb, CLS_T, 0, ctx->stream>>>(ctx->frame_table_dev, (const Frame16Dev*)ctx->table16_dev, pb, fb, empty,
-                                                                          rr16, cp16, pl.wb_stride, pl.row_stride, D2, kappa, min_score, rr, cp,
-                                                                          open_idx, open_cnt, dot16_tally(ctx));
-                dot_exact_rows_kernel<<<nb * EXACT_WGS, H_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, fb, empty, open_idx, open_cnt,
+                                                                          a.rr16, a.cp16, pl.wb_stride, pl.row_stride, D2, kappa, min_score, rr, cp,
+                                                                          a.open_idx, a.open_cnt, dot16_tally(ctx));
+                dot_exact_rows_kernel<<<nb * EXACT_WGS, H_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, fb, empty, a.open_idx, a.open_cnt,
                                                                                  pl.wb_stride, pl.row_stride, D2, rr, cp);
             }
             if (fb_here > 0) launch_match_tile_dot(ctx, fb, nb, pl, rr, cp);  // screened pairs name the empty frame there
         }
-        rc = launch_match_dot_tail(ctx, pl, pb, nb, first, first + nb == npairs, rr, cp, min_score, min_dir, min_mutual, 0, counts_dev,
+        rc = launch_match_dot_tail(ctx, pl, a, pb, nb, first, first + nb == npairs, min_score, min_dir, min_mutual, 0, counts_dev,
                                    offsets_dev, edges_dev, scores_dev, edge_cap, total_dev, stats_dev);
         if (rc) return rc;
     }
@@ -622,19 +610,24 @@ extern "C" int eacham_match_debug_dot_coarse(eacham_ctx* ctx, int f1, int f2, fl
         if (rc) return rc;
         if (nfb) return ctx->fail(EACHAM_ERR_UNSUPPORTED, "a frame of the pair holds a value that is not finite or beyond the fp16 range: it is not screened");
         const MatchPlanF32 pl = plan_match_f32(ctx, 1);
-        auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-        const size_t off_cp16 = align((size_t)pl.row_stride * sizeof(int4));
-        const size_t off_dump = align(off_cp16 + (size_t)pl.wb_stride * pl.row_stride * sizeof(int4));
-        const size_t off_pair = align(off_dump + (size_t)n1 * n2 * sizeof(float));
-        rc = ensure_workspace(ctx, off_pair + 256);
+        // one pair's sweep arrays, its n1 x n2 coarse scores and the pair itself (a null base: the bytes)
+        int4 *rr16, *cp16;
+        float* dump;
+        int2* pair;
+        auto carve = [&](void* base) {
+            Bump b(base);
+            rr16 = b.take<int4>((size_t)pl.row_stride), cp16 = b.take<int4>((size_t)pl.wb_stride * pl.row_stride);
+            dump = b.take<float>((size_t)n1 * n2), pair = b.take<int2>(1);
+            return b.off;
+        };
+        rc = ensure_workspace(ctx, carve(nullptr));
         if (rc) return rc;
-        char* ws = (char*)ctx->ws;
-        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(ws + off_pair, pr, sizeof(pr), hipMemcpyHostToDevice, ctx->stream));
-        launch_tile16<true>(ctx, pl.wgs_per_pair, (const int2*)(ws + off_pair), nullptr, 0, pl, (int4*)ws, (int4*)(ws + off_cp16),
-                            (float*)(ws + off_dump));
+        carve(ctx->ws);
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(pair, pr, sizeof(pr), hipMemcpyHostToDevice, ctx->stream));
+        launch_tile16<true>(ctx, pl.wgs_per_pair, pair, nullptr, 0, pl, rr16, cp16, dump);
         EACHAM_HIP_TRY(ctx, hipGetLastError());
         if (n1 > 0 && n2 > 0)
-            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(s_coarse, ws + off_dump, (size_t)n1 * n2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+            EACHAM_HIP_TRY(ctx, hipMemcpyAsync(s_coarse, dump, (size_t)n1 * n2 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
         // the bounds as the classify kernel computes them, from the stored norm bounds
         const FrameHost &A = ctx->frames[f1], &B = ctx->frames[f2];
         std::vector<float> na((size_t)std::max(n1, 1)), nb((size_t)std::max(n2, 1));

@@ -16,6 +16,7 @@
 // of 32 rows (D x 128 B) stream through a 2-slot LDS ring filled by LDS-DMA; the MFMA dominates
 // (D/2 instructions of 64 cycles per 32x32 tile), the (value, index) top-2 epilogue is minor.
 #include "context.hpp"
+#include "match_plan.hpp"
 #include "match_tail.hpp"
 
 #include <algorithm>
@@ -29,6 +30,7 @@ constexpr float PAD_F = 1.0e30f;      // norm of padding rows
 constexpr float INVALID_F = 1.0e29f;  // d2 at or above this marks "no such neighbour"
 constexpr float INIT_F = 3.0e38f;
 constexpr int F_THREADS = 256, F_WAVES = 4;
+static_assert(PLAN_F32_WG_TILES == F_WAVES, "match_plan.hpp plans for these kernels");
 
 // ---- upload ---------------------------------------------------------------------------------------
 __global__ void pack_f32_kernel(const float* __restrict__ src, int n, int dim, int D2, int npad, float* __restrict__ frag) {
@@ -275,53 +277,39 @@ MatchPlanF32 plan_match_f32(const eacham_ctx* ctx, int npairs) {
     int max_tiles = 4;
     for (const auto& f : ctx->frames)
         if (f.n >= 0) max_tiles = std::max(max_tiles, f.ntiles);
-    MatchPlanF32 pl;
-    pl.row_stride = max_tiles * 32, pl.wb_stride = max_tiles;
-    pl.wgs_per_pair = (max_tiles + F_WAVES - 1) / F_WAVES;
-    const size_t per_pair = (size_t)pl.row_stride * sizeof(int4) + (size_t)pl.wb_stride * pl.row_stride * sizeof(int4) +
-                            (size_t)pl.row_stride * sizeof(uint2) + sizeof(int);
-    pl.batch = (int)std::max<size_t>(1, std::min<size_t>(((size_t)1 << 30) / per_pair, (size_t)npairs));
-    auto align = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    pl.off_rowres = 0;
-    pl.off_colpart = align((size_t)pl.batch * pl.row_stride * sizeof(int4));
-    pl.off_matches = align(pl.off_colpart + (size_t)pl.batch * pl.wb_stride * pl.row_stride * sizeof(int4));
-    pl.total = align(pl.off_matches + (size_t)pl.batch * pl.row_stride * sizeof(uint2));
-    return pl;
+    return plan_match_f32(max_tiles, npairs);
 }
 
 int run_match_f32(eacham_ctx* ctx, const int2* pairs_dev, int npairs, double ratio, int min_dir, int min_mutual, int mode,
                   int* counts_dev, long long* offsets_dev, uint2* edges_dev, long long edge_cap, long long* total_dev,
                   int4* stats_dev) {
     const MatchPlanF32 pl = plan_match_f32(ctx, npairs);
-    const int row_stride = pl.row_stride, wb_stride = pl.wb_stride, wgs_per_pair = pl.wgs_per_pair, batch = pl.batch;
-    const size_t off_rowres = pl.off_rowres, off_colpart = pl.off_colpart, off_matches = pl.off_matches, total = pl.total;
-    int rc = ensure_workspace(ctx, total);
+    int rc = ensure_workspace(ctx, pl.total);
     if (rc) return rc;
-    char* ws = (char*)ctx->ws;
-    const size_t fin_smem = (size_t)2 * row_stride * sizeof(int);
+    const F32Arrays a = pl.carve(ctx->ws);
+    const size_t fin_smem = (size_t)2 * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024)
         EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)match_finalize_f32_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
-    for (int first = 0; first < npairs; first += batch) {
-        const int nb = std::min(batch, npairs - first);
+    for (int first = 0; first < npairs; first += pl.batch) {
+        const int nb = std::min(pl.batch, npairs - first);
         const int2* pb = pairs_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE);
-            int4* rr = (int4*)(ws + off_rowres);
-            int4* cp = (int4*)(ws + off_colpart);
+            const int grid = nb * pl.wgs_per_pair;
             switch (ctx->ks_common) {
-                case 32: match_tile_f32_kernel<32><<<nb * wgs_per_pair, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, wgs_per_pair, rr, cp, wb_stride, row_stride); break;
-                case 64: match_tile_f32_kernel<64><<<nb * wgs_per_pair, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, wgs_per_pair, rr, cp, wb_stride, row_stride); break;
-                default: match_tile_f32_kernel<128><<<nb * wgs_per_pair, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, wgs_per_pair, rr, cp, wb_stride, row_stride); break;
+                case 32: match_tile_f32_kernel<32><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, a.rowres, a.colpart, pl.wb_stride, pl.row_stride); break;
+                case 64: match_tile_f32_kernel<64><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, a.rowres, a.colpart, pl.wb_stride, pl.row_stride); break;
+                default: match_tile_f32_kernel<128><<<grid, F_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, pb, pl.wgs_per_pair, a.rowres, a.colpart, pl.wb_stride, pl.row_stride); break;
             }
         }
         int* cnt = counts_dev + first;
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_FINALIZE);
             match_finalize_f32_kernel<<<nb, FIN_THREADS, fin_smem, ctx->stream>>>(
-                ctx->frame_table_dev, pb, (const int4*)(ws + off_rowres), (const int4*)(ws + off_colpart), wb_stride, row_stride,
-                ratio, min_dir, min_mutual, mode, (uint2*)(ws + off_matches), cnt, stats_dev ? stats_dev + first : nullptr);
+                ctx->frame_table_dev, pb, a.rowres, a.colpart, pl.wb_stride, pl.row_stride, ratio, min_dir, min_mutual, mode, a.matches, cnt,
+                stats_dev ? stats_dev + first : nullptr);
             launch_scan_counts(ctx, cnt, nb, offsets_dev, total_dev, first, first + nb == npairs);
-            launch_compact_edges(ctx, nb, (const uint2*)(ws + off_matches), cnt, offsets_dev + first, row_stride, edges_dev, edge_cap);
+            launch_compact_edges(ctx, nb, a.matches, cnt, offsets_dev + first, pl.row_stride, edges_dev, edge_cap);
         }
         EACHAM_HIP_TRY(ctx, hipGetLastError());
     }

@@ -28,6 +28,7 @@
 //
 // Both directions: the sweep runs on (f1, f2) and on (f2, f1) — see DESIGN.md 3.7.
 #include "context.hpp"
+#include "match_plan.hpp"
 #include "match_tail.hpp"
 
 #include <algorithm>
@@ -274,25 +275,12 @@ int upload_frame_bits_wide(eacham_ctx* ctx, int frame_id, const unsigned char* p
 }
 
 namespace {
-struct HamWidePlan {
-    int row_stride, wgs_per_pair, batch;
-    size_t off_rowres, off_matches, total;
-};
-// per pair: two directions of row results and the match list. Where a batch ends decides nothing: every pair's arrays are its own.
+static_assert(PLAN_HW_WG_TILES == HW_WG_TILES, "match_plan.hpp plans for these kernels");
 HamWidePlan plan_ham_wide(const eacham_ctx* ctx, int npairs) {
     int max_tiles = HW_NSUB;
     for (const auto& f : ctx->frames)
         if (f.n >= 0) max_tiles = std::max(max_tiles, f.ntiles);
-    HamWidePlan pl;
-    pl.row_stride = 32 * max_tiles;
-    pl.wgs_per_pair = (max_tiles + HW_WG_TILES - 1) / HW_WG_TILES;
-    const size_t per_pair = (size_t)pl.row_stride * (2 * sizeof(float2) + sizeof(uint2));
-    const size_t budget = ctx->wide_budget_bytes ? ctx->wide_budget_bytes : (size_t)ctx->match_budget_mb << 20;
-    pl.batch = (int)std::min<size_t>(std::max<size_t>(budget / per_pair, 1), (size_t)std::max(npairs, 1));
-    pl.off_rowres = 0;
-    pl.off_matches = ((size_t)pl.batch * 2 * pl.row_stride * sizeof(float2) + 255) & ~(size_t)255;
-    pl.total = pl.off_matches + (size_t)pl.batch * pl.row_stride * sizeof(uint2);
-    return pl;
+    return eacham::plan_ham_wide(max_tiles, npairs, ctx->wide_budget_bytes ? ctx->wide_budget_bytes : (size_t)ctx->match_budget_mb << 20);
 }
 
 void launch_ham_wide_sweep(eacham_ctx* ctx, const int2* pb, int nb, int ndir, const HamWidePlan& pl, float2* rr) {
@@ -334,8 +322,9 @@ int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, doubl
     const size_t fin_smem = (size_t)2 * pl.row_stride * sizeof(int);
     if (fin_smem > 48 * 1024)
         EACHAM_HIP_TRY(ctx, hipFuncSetAttribute((const void*)ham_wide_finalize_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fin_smem));
-    float2* rr = (float2*)((char*)ctx->ws + pl.off_rowres);
-    uint2* mt = (uint2*)((char*)ctx->ws + pl.off_matches);
+    const HamWideArrays a = pl.carve(ctx->ws);
+    float2* rr = a.rowres;
+    uint2* mt = a.matches;
     long long batches = 0;
     for (int first = 0; first < npairs; first += pl.batch, ++batches) {
         const int nb = std::min(pl.batch, npairs - first);
@@ -383,7 +372,7 @@ int ham_wide_debug_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t*
     IoDev d;
     rc = io.upload(d);
     if (rc) return rc;
-    float2* rr = (float2*)((char*)ctx->ws + pl.off_rowres);
+    float2* rr = pl.carve(ctx->ws).rowres;
     launch_ham_wide_sweep(ctx, d(h_pair), 1, 1, pl, rr);
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     rc = io.finish();
