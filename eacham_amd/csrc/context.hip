@@ -300,7 +300,7 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
     if (const char* m = getenv("EACHAM_BA_SCHUR")) ctx->ba_schur_mode = !strcmp(m, "pairs") ? 2 : !strcmp(m, "groups") ? 1 : 0;
     if (const char* r = getenv("EACHAM_BA_GROUP_ROWS")) {
         const int v = atoi(r);
-        if (v >= 16 && v <= 508 && v % 4 == 0) ctx->ba_group_rows = v;   // (508: see the entry key of prep_grp_entries, ba.hip)
+        if (v >= 16 && v <= 508 && v % 4 == 0) ctx->ba_group_rows = v;   // (508: see the entry key of prep_grp_entries, ba_prepare.hip)
     }
     if (const char* o = getenv("EACHAM_BA_ORDERING"))
         ctx->ba_ordering = !strcmp(o, "natural") ? EACHAM_BA_ORDER_NATURAL : !strcmp(o, "rcm") ? EACHAM_BA_ORDER_RCM : !strcmp(o, "nd") ? EACHAM_BA_ORDER_ND : EACHAM_BA_ORDER_AUTO;

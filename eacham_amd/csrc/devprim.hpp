@@ -1,6 +1,6 @@
 // devprim.hpp — the data-parallel primitives under the device-side constructions: an exclusive prefix sum, a STABLE
 // least-significant-digit radix sort of (key, value) pairs and the search for the segment that owns an item, hand-written for
-// gfx950 (64-wide wavefronts: the in-tile ranks of the sort come from wave ballots). Five users: ba.hip (eacham_ba_prepare:
+// gfx950 (64-wide wavefronts: the in-tile ranks of the sort come from wave ballots). Five users: ba_prepare.hip (eacham_ba_prepare:
 // seven sorts, a dozen scans over int, long long and I3), tracks.hip, lmeds_batch.hip, graph_verify.hip, and, through
 // segment_of, triangulate.hip / pnp_batch.hip.
 //

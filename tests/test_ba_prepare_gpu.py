@@ -1,5 +1,5 @@
 """GPU: the two forms of RefineBA's graph construction (modules/sfm/reconstruction/BundleAdjuster.cpp:57-178) behind
-eacham_ba_prepare — host loops (local windows) and device sorts + scans (eacham_amd/csrc/devprim.hpp, ba.hip) — must build
+eacham_ba_prepare — host loops (local windows) and device sorts + scans (eacham_amd/csrc/devprim.hpp, ba_prepare.hip) — must build
 the SAME structure: every fp64 sum of the solver runs in the order of these lists, so the reduced system, the step and a
 whole Levenberg-Marquardt run are compared BIT FOR BIT between a context forced to one form and a context forced to the
 other (EACHAM_BA_PREPARE is read at eacham_ctx_create). Parity with the oracle is the business of tests/test_ba_gpu.py,
@@ -14,26 +14,30 @@ from eacham_amd import HipContext, ba, synth
 pytestmark = pytest.mark.gpu
 
 
-def _ctx_pair_with(**env):
-    """(host-built, device-built) contexts created under the given switches (they are read once, at eacham_ctx_create)."""
-    old = {k: os.environ.get(k) for k in ["EACHAM_BA_PREPARE", *env]}
-    host = None
+def _ctx_with(form, **env):
+    """A context forced to one form of the construction (host | device), created under the given switches (they are read
+    once, at eacham_ctx_create)."""
+    env = dict(env, EACHAM_BA_PREPARE=form)
+    old = {k: os.environ.get(k) for k in env}
     try:
         os.environ.update(env)
-        os.environ["EACHAM_BA_PREPARE"] = "host"
-        host = HipContext(0)
-        os.environ["EACHAM_BA_PREPARE"] = "device"
-        return host, HipContext(0)
-    except BaseException:
-        if host is not None:
-            host.close()
-        raise
+        return HipContext(0)
     finally:
         for k, v in old.items():
             if v is None:
                 os.environ.pop(k, None)
             else:
                 os.environ[k] = v
+
+
+def _ctx_pair_with(**env):
+    """(host-built, device-built) contexts created under the given switches."""
+    host = _ctx_with("host", **env)
+    try:
+        return host, _ctx_with("device", **env)
+    except BaseException:
+        host.close()
+        raise
 
 
 @pytest.fixture(scope="module", params=["groups", "pairs"])
@@ -172,7 +176,7 @@ def _group_rows(pb):
 @pytest.mark.parametrize("rows", [16, 64, 252, 480, 508, 512])
 def test_every_accepted_group_size_builds_the_same_structure(rows):
     """EACHAM_BA_GROUP_ROWS selects 16 to 508 rows per group (multiples of 4); 508 is the most the device form can pack
-    (9-bit row fields of its entry keys, ba.hip prep_grp_entries). At every accepted size both forms of the construction
+    (9-bit row fields of its entry keys, ba_prepare.hip prep_grp_entries). At every accepted size both forms of the construction
     choose the same structure and build it bit for bit alike; 512 is outside the range and ignored by both (the size the
     problem selects, 128 rows here, serves). At 16 rows a landmark of 8 observations (9 rows > 16 / 2) fits no group:
     both forms then take the pair lists."""
@@ -203,7 +207,7 @@ def test_every_accepted_group_size_builds_the_same_structure(rows):
 def test_long_runs_cut_into_slices_and_segments_by_both_entry_kernels(rows, repeat):
     """Five cameras and three observations per landmark: a 508-row group holds about 120 landmarks, so a block's run inside a
     group is several slices long and the diagonal blocks exceed 64 entries — lanes are sliced, segments are cut at GRP_SEG
-    lanes and some cross a row of GRP_ROW lanes. As it is the scene takes the sort-free entries kernel of ba.hip; with five
+    lanes and some cross a row of GRP_ROW lanes. As it is the scene takes the sort-free entries kernel of ba_prepare.hip; with five
     observations repeated (a camera sees a landmark twice) every group goes through the general, sorting one. Both must
     build the host form's structure at every group size; `_group_rows` holds the case to the groups (not the pair lists)."""
     A = _arrays(31, 5, 300, 3)
@@ -225,3 +229,61 @@ def test_long_runs_cut_into_slices_and_segments_by_both_entry_kernels(rows, repe
     finally:
         for ctx in pair:
             ctx.close()
+
+
+def _same_bytes_as_a_fresh_host_build(dev, pb, A, env, lam=1e-3):
+    """A problem prepared on the device-form context `dev` against the same problem on a FRESH context forced to the host form:
+    all thirty structure arrays, the plan's panels / tiles / levels and one damped step, equal as bytes."""
+    host = _ctx_with("host", **env)
+    try:
+        ref = ba.PreparedBA(host, A)
+        try:
+            for name in ba.PreparedBA.STRUCTURE:
+                x, y = ref.structure(name), pb.structure(name)
+                assert x.dtype == y.dtype and x.tobytes() == y.tobytes(), f"structure array {name} differs ({x.shape} vs {y.shape})"
+            want, got = ref.plan_info(), pb.plan_info()
+            for key in ("panels", "tiles", "levels"):
+                assert want[key] == got[key], (key, want, got)
+        finally:
+            ref.close()
+        a, b = ba.debug_step(host, A, lam), ba.debug_step(dev, A, lam)
+        for name, x, y in zip(["S", "g", "delta_c", "delta_l", "error", "lin_change"], a, b):
+            assert np.asarray(x, np.float64).tobytes() == np.asarray(y, np.float64).tobytes(), f"{name} differs from the host-built problem's"
+    finally:
+        host.close()
+
+
+@pytest.mark.parametrize("schur", ["groups", "pairs"])
+def test_device_built_problems_keep_their_bytes_under_reuse_of_both_arenas(schur):
+    """A device-built problem lives in two arenas of the context's pool (csrc/ba_prepare.hip: what (cameras, landmarks,
+    observations) size, then what the pair lists / groups and the plan size). On ONE context: two problems alive together, one
+    released, a refused problem (an observation names camera n_cams: the call leaves after the first arena was taken and must
+    give back what it holds), a third problem of the released one's size (it is carved out of the released blocks, which hold
+    the old problem's bytes), the first once more. Every prepared problem must be the host-built one byte for byte."""
+    from eacham_amd import EachamError, capi
+    env = {"EACHAM_BA_SCHUR": schur}
+    A, B, C = _arrays(41, 6, 90, 3), _arrays(42, 12, 300, 6, shuffle=True), _arrays(43, 6, 90, 3)
+    dev = _ctx_with("device", **env)
+    alive = []
+    try:
+        pa, pb = ba.PreparedBA(dev, A), ba.PreparedBA(dev, B)
+        alive += [pa, pb]
+        _same_bytes_as_a_fresh_host_build(dev, pa, A, env)
+        _same_bytes_as_a_fresh_host_build(dev, pb, B, env)
+        pa.close()
+        bad = _arrays(41, 6, 90, 3)
+        bad.obs_cam[11] = 6  # camera n_cams
+        with pytest.raises(EachamError) as e:
+            ba.PreparedBA(dev, bad)
+        assert e.value.code == capi.ERR_INVALID
+        pc = ba.PreparedBA(dev, C)
+        alive.append(pc)
+        _same_bytes_as_a_fresh_host_build(dev, pc, C, env)
+        pa2 = ba.PreparedBA(dev, A)
+        alive.append(pa2)
+        _same_bytes_as_a_fresh_host_build(dev, pa2, A, env)
+        _same_bytes_as_a_fresh_host_build(dev, pb, B, env)  # (untouched by what came and went beside it)
+    finally:
+        for p in alive:
+            p.close()
+        dev.close()
