@@ -60,7 +60,7 @@ struct FrameDev {
     const int* normb;  // int8: floor(|c|^2 / 2) + sum(c) per stored position (train role)
     const int* orig;   // int8: stored position -> caller's row (-1 = padding)
     const int* pos;    // int8: caller's row -> stored position
-    const int* meta;   // int8: {tiles of the even class, tiles in use}; written by the upload kernels
+    const int* meta;   // int8: {tiles of the even class, tiles in use, above 128-D: tiles that hold a real row}; written by the upload kernels
     const int4* screen;  // int8 frames above 128-D: the FP6 image of the screen sweep (matcher.hip, match_screen.hpp), at the same stored
                          // positions and tiles: [ntiles][4 k-steps]{64 x 16 B | 64 x 8 B} | |M|^2 / 2 as float [32 ntiles] | s_r [32 ntiles] | {E}; else null
     int n;             // real rows

@@ -204,13 +204,18 @@ __global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, i
     if (err) atomicAdd(&sr[j], err);
 }
 // U5: hm = |M|^2 / 2 as float in msq's place (the C-init of the row as a train row, added once as a query row; padding rows:
-// SCREEN_PAD, above every real value), eb[0] = the largest s_r of a real row.
-__global__ void finish_screen_kernel(int npad, const int* __restrict__ orig, int* __restrict__ msq, const int* __restrict__ sr, int* __restrict__ eb) {
+// SCREEN_PAD, above every real value), eb[0] = the largest s_r of a real row, meta[2] (zeroed) = the stored tiles up to the last
+// one that holds a real row: meta[1] without the tile that only rounds it up to whole wave-blocks. A class fills its tiles from
+// their first row on, so a tile holds a real row where its first row is one. The screen sweep runs over these tiles as a train
+// frame's: a tile of padding rows alone gives no subset a value below SCREEN_PAD, which the tail reads as no value at all.
+__global__ void finish_screen_kernel(int npad, const int* __restrict__ orig, int* __restrict__ msq, const int* __restrict__ sr, int* __restrict__ eb,
+                                     int* __restrict__ meta) {
     const int j = blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= npad) return;
     const bool real_row = orig[j] >= 0;
     reinterpret_cast<float*>(msq)[j] = real_row ? 0.5f * (float)msq[j] : SCREEN_PAD;
     if (real_row) atomicMax(eb, sr[j]);
+    if (real_row && (j & 31) == 0) atomicMax(&meta[2], (j >> 5) + 1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -958,6 +963,12 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // LDS reads. The call structure is its own: 8 MFMAs per tile are half the int8 sweep's, so a call covers TWO train tiles between
 // two barriers (six ring slots of 6 KiB, three calls per trip), the four waves stage three pieces each spread over the call, and
 // every wait inside a call is a counted one (see the call below; profiles/screen_two_tiles.txt).
+// The sweep covers the train frame's meta[2] tiles, those that hold a real row. The tile that rounds meta[1] up to whole wave-blocks
+// (the query side's unit) is padding alone: its distances are SCREEN_PAD in every subset, which the tail takes for no value, as it
+// takes the BIGF of a subset that met no tile. Left out, every word of rowres stays what it was, and a frame of 63 real tiles ends
+// on last() with no idle chains. An even count is made odd at the front: tile 0 is swept whole in the prologue (t0 = 1), into the
+// minima of the even tiles, and the calls start at tile 1 — the sixteen subsets are the same sets of train rows either way, so
+// every word of rowres stays what it was here too (profiles/screen_real_tiles.txt).
 // ------------------------------------------------------------------------------------------------
 typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v6i __attribute__((ext_vector_type(6)));
@@ -1009,7 +1020,7 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     const int2 pr = pairs[p];
     const FrameDev A = frames[pr.x], B = frames[pr.y];
     const int A_even = ((gint_t)A.meta)[0], A_tiles = ((gint_t)A.meta)[1];
-    const int T = ((gint_t)B.meta)[1];
+    const int T = ((gint_t)B.meta)[2];   // the train tiles that hold a real row (finish_screen_kernel): not the tile that rounds meta[1] up
     if (rb * (ROWS_WG / 32) >= A_tiles) return;  // workgroup-uniform
     const int wb = rb * WAVES + wave;
     const bool active = NSUB * wb < A_tiles;
@@ -1059,16 +1070,23 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         const gbytes_t row = reinterpret_cast<gbytes_t>(Bm2) + (size_t)128 * min(tile + (lane >> 5), TM);
         return *reinterpret_cast<gfloat_t>(row + hb_off);
     };
+    // An even tile count is peeled at the front, where nothing is in flight: t0 = 1, tile 0 is swept whole ahead of the calls and
+    // tile v lives in ring slot (v - t0) mod RING, so that what the calls cover is an odd number of tiles and ends on last() (cut
+    // at the back, the even count's last half call ran its chains on a tile that does not exist).
+    const int t0 = T > 0 && !(T & 1) ? 1 : 0;   // wave-uniform
     float hb_new = 0.0f;
     if (T > 0) {
-        // tiles 0 .. 2 NT: the first call stages the next two into the slot of tile 0 and the one still empty
+        // tiles 0 .. 2 NT + t0: the first call stages the next two into the slot of tile t0 and the one still empty (t0 = 1: tile 0's)
 #pragma unroll
-        for (int i = 0; i < ((2 * NT + 1) * PIECES + WAVES - 1) / WAVES; ++i) {
-            const int idx = wave + WAVES * i;
-            if (idx < (2 * NT + 1) * PIECES) stage_piece(idx / PIECES, idx / PIECES, idx % PIECES);
+        for (int i = 0; i < ((2 * NT + 2) * PIECES + WAVES - 1) / WAVES; ++i) {
+            const int idx = wave + WAVES * i, v = idx / PIECES;
+            if (v < 2 * NT + 1 + t0) stage_piece(v, v < t0 ? RING - 1 : v - t0, idx % PIECES);
         }
-        if (tid < 32 * (NT + 2)) sHb[tid >> 5][tid & 31] = Bm2[32 * min(tid >> 5, TM) + (tid & 31)];
-        if (wave == 0) hb_new = load_hb(NT + 2);   // stored at the head of the first call
+        if (tid < 32 * (NT + 2 + t0)) {
+            const int v = tid >> 5;
+            sHb[v < t0 ? RING - 1 : v - t0][tid & 31] = Bm2[32 * min(v, TM) + (tid & 31)];
+        }
+        if (wave == 0) hb_new = load_hb(NT + 2 + t0);   // stored at the head of the first call
     }
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
@@ -1136,6 +1154,24 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
                        "+v"(ci[2]), "+v"(ci[3]));
     };
     if (T > 0 && active) {
+        if (t0) {
+            // the peeled tile 0, whole: its chains, then its epilogue into the minima of the even tiles (the second half's: the calls
+            // start at tile 1, so xm[0] takes the odd tiles)
+            const v16f c0 = cinit_of(RING - 1);
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {
+                const ScreenFrag b0 = read_plain(RING - 1, ks);
+#pragma unroll
+                for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
+            }
+            // (plain minima, not consume(): its v_min3_f32 sits in an asm string, where nothing pads the wait states between the last
+            // MFMA and a reader of its accumulators; inside a call the chains ended half a call earlier)
+#pragma unroll
+            for (int s = 0; s < NSUB; ++s)
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+                    xm[1][s][g] = fminf(fminf(accA[s][4 * g], accA[s][4 * g + 1]), fminf(accA[s][4 * g + 2], accA[s][4 * g + 3]));
+        }
         const v16f c0 = cinit_of(0);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -1161,7 +1197,7 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         const int ph = idx / 16, eg = idx % 16;
         if (eg & 1) m[ph][eg >> 2] = fmin3(m[ph][eg >> 2], cur[ph][eg - 1], cur[ph][eg]);
     };
-    // One call covers NT = 2 train tiles between two barriers (t even, the tile whose chains accA holds; K3 = call mod 3 gives the ring
+    // One call covers NT = 2 train tiles between two barriers (t = t0 + 2 k, the tile whose chains accA holds; K3 = call mod 3 gives the ring
     // slots and the phase of the fragment ring, which advances NT KS = 8 steps per call). Half 0: epilogue of tile t from accA under the
     // chains of tile t + 1 into accB; half 1: epilogue of tile t + 1 from accB under the chains of tile t + 2 into accA — the roles
     // are back where they started, and xm is indexed by the half. Step i of the eight waits for fragment i, issues fragment i + 2
@@ -1248,7 +1284,7 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         asm volatile("s_waitcnt vmcnt(1)" : : : "memory");
         __builtin_amdgcn_s_barrier();
     };
-    // a last tile of even index has nothing to issue and nothing to stage: its epilogue alone, from accA
+    // the last tile (an even number of tiles behind t0) has nothing to issue and nothing to stage: its epilogue alone, from accA
     auto last = [&]() {
         if (active) {
 #pragma unroll
@@ -1256,21 +1292,21 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         }
     };
     if (T > 0) {
-        // tiles 1 .. TM have their chains inside a call, tiles 0 .. TM - 1 their epilogue: (TM + 1) / 2 calls. With TM odd the last
-        // call's second half consumes tile TM and runs chains on the ring's copy of it, never consumed; with TM even tile TM is left.
-        const int NC = (TM + 1) / 2;
+        // tiles t0 + 1 .. TM have their chains inside a call, tiles t0 .. TM - 1 their epilogue: TM - t0 of each, an even number (the
+        // front peel), so (TM - t0) / 2 calls and tile TM is left to last()
+        const int NC = (TM - t0) / 2;
         int c = 0;
         for (; c + 3 <= NC; c += 3) {
-            call(std::integral_constant<int, 0>{}, NT * c);
-            call(std::integral_constant<int, 1>{}, NT * (c + 1));
-            call(std::integral_constant<int, 2>{}, NT * (c + 2));
+            call(std::integral_constant<int, 0>{}, t0 + NT * c);
+            call(std::integral_constant<int, 1>{}, t0 + NT * (c + 1));
+            call(std::integral_constant<int, 2>{}, t0 + NT * (c + 2));
         }
-        if (c < NC) call(std::integral_constant<int, 0>{}, NT * c);
-        if (c + 1 < NC) call(std::integral_constant<int, 1>{}, NT * (c + 1));
+        if (c < NC) call(std::integral_constant<int, 0>{}, t0 + NT * c);
+        if (c + 1 < NC) call(std::integral_constant<int, 1>{}, t0 + NT * (c + 1));
         // nothing may land in a register or in this workgroup's LDS once the sweep is over
         asm volatile("s_waitcnt vmcnt(0)" : : : "memory");
         drain_lds();
-        if (!(TM & 1)) last();
+        last();
     }
     if (!active) return;
     // join the partner lane (the same query row against the other half of every tile's train rows) and the tile parities: the two
@@ -2090,8 +2126,9 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
     const int ntiles = n > 0 ? ((n + 31) / 32 + 1 + GROUP_TILES - 1) / GROUP_TILES * GROUP_TILES : 0;
     const int npad = ntiles * 32;
     {
-        // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[2]; binary frames only: + 6 unused (32-byte alignment) | the packed rows, 8 words each
-        const size_t ints = (size_t)6 * npad + 2 + (kind == FRAME_BITS ? 6 + (size_t)8 * n : 0);
+        // norm (ca) | normb (hb) | orig | pos | s2 | s1 | meta[8] (partition_kernel: two words; above 128-D finish_screen_kernel: the
+        // third; the rest unused, 32-byte alignment); binary frames only: | the packed rows, 8 words each
+        const size_t ints = (size_t)6 * npad + 8 + (kind == FRAME_BITS ? (size_t)8 * n : 0);
         EACHAM_HIP_TRY(ctx, hipMalloc((void**)&f.norm, ints * sizeof(int)));
         EACHAM_HIP_TRY(ctx, hipMemsetAsync(f.norm, 0, ints * sizeof(int), ctx->stream));
         f.normb = f.norm + npad;
@@ -2117,7 +2154,7 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
                 int* sr = msq + npad;
                 EACHAM_HIP_TRY(ctx, hipMemsetAsync(msq, 0, (size_t)npad * 8 + 16, ctx->stream));
                 quantize_screen_kernel<<<(npad * 2 * SCREEN_KS + 255) / 256, 256, 0, ctx->stream>>>(src_dev, dim, npad, f.orig, img, msq, sr);
-                finish_screen_kernel<<<(npad + 255) / 256, 256, 0, ctx->stream>>>(npad, f.orig, msq, sr, sr + npad);
+                finish_screen_kernel<<<(npad + 255) / 256, 256, 0, ctx->stream>>>(npad, f.orig, msq, sr, sr + npad, f.meta);
                 f.screen = (int4*)img;
             }
             EACHAM_HIP_TRY(ctx, hipGetLastError());
