@@ -1,8 +1,9 @@
 // match_screen.hpp — the FP6 (e2m3) grid of the 256-D screen sweep and its bound arithmetic, pure C++ usable from host and device
-// (matcher.hip quantises and bounds with it; tests/cpp/match_screen_driver.cpp executes it on the CPU).
+// (matcher.hip quantises and bounds with it; tests/cpp/match_screen_driver.cpp executes it on the CPU), and the lane map of the
+// sweep's 16x16x128 chains over the stored tile (tests/cpp/screen_shape16_driver.cpp executes that).
 //
-// What it serves: above 128-D the exact int8 row sweep is bound by the matrix pipe. v_mfma_scale_f32_32x32x64_f8f6f4 with e2m3
-// operands runs twice the K per instruction in the same cycles, so a sweep over QUANTISED descriptors costs the pipe half — and the
+// What it serves: above 128-D the exact int8 row sweep is bound by the matrix pipe. The block-scaled f8f6f4 MFMA with e2m3 operands
+// (v_mfma_scale_f32_32x32x64 / 16x16x128) runs twice the K in the same cycles, so a sweep over QUANTISED descriptors costs the pipe half — and the
 // result only needs exact distances for the rows that can pass the ratio test. A row is finished by the quantised sweep where the
 // bound below proves that it fails the test; every other row gets exact numbers from the int8 pass (match_colverify_kernel<KS, true>).
 //
@@ -77,6 +78,44 @@ EACHAM_SCREEN_HD inline int unpack32(const uint32_t in[6], int e) {
     if (sh > 26) v |= in[w + 1] << (32 - sh);
     return (int)(v & 63u);
 }
+
+// ---- the stored tile and the lane map of the 16x16x128 chains (match_screen_kernel) ----
+// A stored tile is 32 rows x 256 codes. Per K = 64 step ks, stored lane L = row + 32 h holds the 32 codes 64 ks + 32 h .. of `row`
+// (K block 2 ks + h of the row's eight), packed as above: words 0..3 at ks * STEP_BYTES + 16 L, words 4..5 at ks * STEP_BYTES +
+// HI_PLANE + 8 L. That is the operand image of v_mfma_scale_f32_32x32x64_f8f6f4, and the upload kernels write nothing else.
+// v_mfma_scale_f32_16x16x128_f8f6f4 wants of operand lane l the row l & 15 and the K block kg = l >> 4 of a K = 128 step. The sweep
+// cuts a tile into two row halves u and two steps S; the fragment of (u, S) gives lane l the stored fragment of row 16 u + (l & 15)
+// at ks = 2 S + (kg >> 1), h = kg & 1 — the K blocks of step S in their natural order. Any assignment of kg to the four (ks, h) of
+// the step would do as long as the query operand uses the same one (the sums are exact in any order), and none is better for the
+// LDS: the four candidates of a row lie multiples of 256 bytes apart in both planes. The 16-byte reads are conflict-free under all of
+// them (a group of 16 lanes covers the sixteen 16-byte slots of a bank row once); the 8-byte reads, served 32 lanes at a time, put
+// lanes l and l + 16 — one row, two K blocks — on one bank pair under all of them: two-way, 4 array cycles where the 32x32 form's
+// read took 2. A tile pays 4 x (4 + 4) + 2 x 4 (C-init) = 40 array cycles where it paid 4 x (4 + 2) + 4 x 4 = 40.
+constexpr int STEP_BYTES = 1536, HI_PLANE = 1024, TILE_ROWS = 32;
+struct FragSrc { int row, ks, h; };   // where a lane's fragment lies in the stored tile
+// train side: fragment (u, S) of a tile as operand lane `lane` reads it
+EACHAM_SCREEN_HD constexpr FragSrc frag16_src(int u, int S, int lane) { return FragSrc{16 * u + (lane & 15), 2 * S + (lane >> 5), (lane >> 4) & 1}; }
+// query side: sub-tile s4 (16 of the wave's 64 query rows), step S. The rows are those of stored tile query16_tile(s4) of the
+// wave-block, the K block of a lane the train side's
+EACHAM_SCREEN_HD constexpr int query16_tile(int s4) { return s4 >> 1; }
+EACHAM_SCREEN_HD constexpr FragSrc query16_src(int s4, int S, int lane) { return frag16_src(s4 & 1, S, lane); }
+EACHAM_SCREEN_HD constexpr int frag_lo_offset(FragSrc f) { return f.ks * STEP_BYTES + 16 * (f.row + TILE_ROWS * f.h); }
+EACHAM_SCREEN_HD constexpr int frag_hi_offset(FragSrc f) { return f.ks * STEP_BYTES + HI_PLANE + 8 * (f.row + TILE_ROWS * f.h); }
+EACHAM_SCREEN_HD constexpr int frag_kblock(FragSrc f) { return 2 * f.ks + f.h; }   // of the row's eight blocks of 32 codes
+// accumulator r (0..3) of the chain of row half u in output lane `lane`: the train row of the tile (the lane's query row is lane & 15
+// of the sub-tile). A lane's four are one group of four stored rows, row >> 2 = 4 u + (lane >> 4): one of the tile's eight subsets
+EACHAM_SCREEN_HD constexpr int acc16_row(int u, int lane, int r) { return 16 * u + 4 * (lane >> 4) + r; }
+// the kernel adds a lane's offset in fragment (0, 0) and the fragment's offset in lane 0: the map is the sum of the two
+EACHAM_SCREEN_HD constexpr bool frag16_separable() {
+    for (int u = 0; u < 2; ++u)
+        for (int S = 0; S < 2; ++S)
+            for (int l = 0; l < 64; ++l) {
+                if (frag_lo_offset(frag16_src(u, S, l)) != frag_lo_offset(frag16_src(0, 0, l)) + frag_lo_offset(frag16_src(u, S, 0))) return false;
+                if (frag_hi_offset(frag16_src(u, S, l)) != frag_hi_offset(frag16_src(0, 0, l)) + frag_hi_offset(frag16_src(u, S, 0)) - HI_PLANE) return false;
+            }
+    return true;
+}
+static_assert(frag16_separable(), "lane offset + fragment offset");
 
 // sqrt(s_a) + sqrt(E_B): how far a true distance can lie from the quantised one
 EACHAM_SCREEN_HD inline double slack(int s_a, int e_b) { return sqrt((double)s_a) + sqrt((double)e_b); }

@@ -171,7 +171,7 @@ constexpr float SCREEN_PAD = 8388608.0f;     // 2^23: exact in f32, above any n 
 constexpr int SCREEN_KS = 4;                 // K = 64 steps of a 256-D row
 constexpr int SCREEN_EXACT_KS = 8;           // int8 K = 32 steps of the same row: the exact pass behind the screen (frames_have_screen)
 constexpr int SCREEN_STEP_BYTES = 1536, SCREEN_TILE_BYTES = SCREEN_KS * SCREEN_STEP_BYTES;
-constexpr int SCREEN_CALL_TILES = 2;         // train tiles between two barriers of the screen sweep: 16 MFMAs per wave, the int8 sweep's ratio
+constexpr int SCREEN_CALL_TILES = 2;         // train tiles between two barriers of the screen sweep: 32 MFMAs of four passes per wave, the int8 sweep's matrix cycles per barrier
 __global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, int npad, const int* __restrict__ orig,
                                        char* __restrict__ image, int* __restrict__ msq, int* __restrict__ sr) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -940,14 +940,18 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // ------------------------------------------------------------------------------------------------
 // K1s: the SCREEN form of the row sweep above 128-D — match_sweep_kernel<8, true> on the FP6 image of the frames (match_screen.hpp).
 //
-// At 256-D the int8 sweep is bound by the matrix pipe (16 v_mfma_i32_32x32x32_i8 per wave-tile). v_mfma_scale_f32_32x32x64_f8f6f4
-// with e2m3 operands takes twice the K in the same cycles: 8 per wave-tile over the quantised rows. The train tile is the A operand,
+// At 256-D the int8 sweep is bound by the matrix pipe (16 v_mfma_i32_32x32x32_i8 per wave-tile). The block-scaled f8f6f4 instructions
+// with e2m3 operands take twice the K in the same cycles: half the matrix cycles per wave-tile over the quantised rows. They run in
+// the 16x16x128 shape (v_mfma_scale_f32_16x16x128_f8f6f4, 16 of four passes per wave-tile where the 32x32x64 shape took 8 of eight:
+// the same matrix cycles, under which the chip holds 1.61 GHz where it held 1.48; profiles/screen_shape16.txt). The stored
+// image is the 32x32x64 operand's; which of its fragments a lane reads is screen::frag16_src. The train tile is the A operand,
 // the wave's 64 query rows the B operand with their sign bits flipped; both scale operands are 2^3 (one register), so a product is the
 // integer -M_a M_b and, with |M_b|^2 / 2 as the C-init, an accumulator holds |M_b|^2 / 2 - M_a.M_b: every partial sum is a multiple of
 // 1/2 below 2^22, exact in f32 in any order. |M_a|^2 / 2 is added once after the sweep: n = |M_a - M_b|^2 is twice the sum.
-// The epilogue is the bound form's: four running minima per sub-tile (two v_min3_f32 per group and tile). Nothing here depends on the
-// parity of a norm, so there is no class boundary; the sixteen disjoint subsets of a query row are (tile parity, group of four
-// accumulators, lane half). Their smallest is n1, their second smallest u bounds the runner-up from above, and the tail turns them
+// The epilogue is the bound form's: running minima per chain (two v_min3_f32 per group of four train rows and tile). Nothing here
+// depends on the parity of a norm, so there is no class boundary; the sixteen disjoint subsets of a query row are (tile parity, group
+// of four stored train rows of the tile): a lane's four accumulators of a chain are one group (screen::acc16_row), the eight groups
+// of a tile lie in the four lanes of the query row's column, two row halves each. Their smallest is n1, their second smallest u bounds the runner-up from above, and the tail turns them
 // into L1 <= the true minimum and U2 >= the true runner-up (screen::lower_d2 / upper_d2 with the row's s and the train frame's E).
 // out: rowres[p][j] = {L1 - pa + 2, 0, U2 - pa + 2, n1}: the bound form's slot and encoding ((e.x + pa) - 2 decodes to L1), so
 // the rows that do not fail the ratio test on (L1, U2) are listed (match_rowpick_kernel's predicate), the gathered exact sweep
@@ -955,12 +959,12 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // A row without a real minimum, or whose minima fill one subset only, carries the bound form's padding values. The fourth word
 // (n1, ~0 without one) is read by eacham_match_debug_screen_pair only.
 // openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
-// predicate holds on the two words the tail is storing — two ballots over the h == 0 lanes, stored from one lane (256 B per pair
+// predicate holds on the two words the tail is storing — one ballot, every lane owning the row of its number, stored from one lane (256 B per pair
 // where its rowres is 32 KB: match_rows2_kernel<.., true> counts a pair's open rows from them). With the same word the tail
 // reserves room in the candidate list of the pair's segment — one returning add per wave with an open row — and writes its
 // candidates and, where its range holds a multiple of 256, the item that starts there (OpenList, match_openprep_kernel).
 // LDS-DMA ring, just-in-time fragment ring and double-buffered accumulators are match_sweep_kernel's; a fragment is 24 bytes, two
-// LDS reads. The call structure is its own: 8 MFMAs per tile are half the int8 sweep's, so a call covers TWO train tiles between
+// LDS reads. The call structure is its own: the matrix cycles of a tile are half the int8 sweep's, so a call covers TWO train tiles between
 // two barriers (six ring slots of 6 KiB, three calls per trip), the four waves stage three pieces each spread over the call, and
 // every wait inside a call is a counted one (see the call below; profiles/screen_two_tiles.txt).
 // The sweep covers the train frame's meta[2] tiles, those that hold a real row. The tile that rounds meta[1] up to whole wave-blocks
@@ -974,7 +978,6 @@ typedef int v2i __attribute__((ext_vector_type(2)));
 typedef int v6i __attribute__((ext_vector_type(6)));
 typedef int v8i __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-typedef float v16f __attribute__((ext_vector_type(16)));
 __device__ __forceinline__ void lds_read_frag64(v2i& dst, unsigned addr, int offset_bytes) {
     asm volatile("ds_read_b64 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(offset_bytes));
 }
@@ -1002,7 +1005,10 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
                                                                      int wgs_per_pair, uint4* __restrict__ rowres, int row_stride, double ratio,
                                                                      unsigned long long* __restrict__ openmask, int mask_stride,
                                                                      OpenList ol) {
-    constexpr int NSUB = 2, KS = SCREEN_KS;
+    constexpr int NSUB = 2;                   // stored (32-row) query tiles of a wave-block
+    constexpr int NQ = 4, NU = 2, NS = 2;     // per train tile: query sub-tiles of 16 rows x row halves u of the tile x K = 128 steps S
+    constexpr int KS = NU * NS;               // fragments of a tile = steps of a half, in the order f = u + NU S (see the call)
+    static_assert(KS == SCREEN_KS && 2 * NS == SCREEN_KS && screen::STEP_BYTES == SCREEN_STEP_BYTES, "match_screen.hpp maps this stored tile");
     constexpr int TILE_V4 = SCREEN_TILE_BYTES / 16;
     constexpr int ROWS_WAVE = 32 * NSUB, ROWS_WG = WAVES * ROWS_WAVE;
     constexpr float BIGF = 3.0e38f;
@@ -1014,7 +1020,6 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int h = lane >> 5;
     const int rb = blockIdx.x % wgs_per_pair;
     const int p = blockIdx.x / wgs_per_pair;
     const int2 pr = pairs[p];
@@ -1030,24 +1035,29 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     const gfloat_t Am2 = (gfloat_t)(Aimg + (size_t)A.ntiles * SCREEN_TILE_BYTES), Bm2 = (gfloat_t)(Bimg + (size_t)B.ntiles * SCREEN_TILE_BYTES);
     const int wbc = active ? wb : 0;
 
-    v6i a[NSUB][KS];   // this wave's 64 query rows, sign bits flipped: the B operand (a lane = a query row of the sub-tile)
+    // this wave's 64 query rows, sign bits flipped: the B operand (a lane = query row lane & 15 of the sub-tile, K block kg of the
+    // step: the stored fragment that screen::query16_src names, the train side's assignment of kg)
+    v6i a[NQ][NS];
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s)
+    for (int s = 0; s < NQ; ++s)
 #pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const gbytes_t tb = Aimg + (size_t)(NSUB * wbc + s) * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES;
-            const v4i lo = *(const v4i __attribute__((address_space(1)))*)(tb + 16 * lane);
-            const v2i hi = *(const v2i __attribute__((address_space(1)))*)(tb + 1024 + 8 * lane);
+        for (int S = 0; S < NS; ++S) {
+            const screen::FragSrc src = screen::query16_src(s, S, lane);
+            const gbytes_t tb = Aimg + (size_t)(NSUB * wbc + screen::query16_tile(s)) * SCREEN_TILE_BYTES;
+            const v4i lo = *(const v4i __attribute__((address_space(1)))*)(tb + screen::frag_lo_offset(src));
+            const v2i hi = *(const v2i __attribute__((address_space(1)))*)(tb + screen::frag_hi_offset(src));
             // the sign bit of code e is bit 6 e + 5: a pattern of period three words
-            a[s][ks] = v6i{lo[0] ^ 0x20820820, lo[1] ^ 0x08208208, lo[2] ^ (int)0x82082082u, lo[3] ^ 0x20820820, hi[0] ^ 0x08208208, hi[1] ^ (int)0x82082082u};
+            a[s][S] = v6i{lo[0] ^ 0x20820820, lo[1] ^ 0x08208208, lo[2] ^ (int)0x82082082u, lo[3] ^ 0x20820820, hi[0] ^ 0x08208208, hi[1] ^ (int)0x82082082u};
         }
-    float xm[2][NSUB][4];  // [tile parity][sub-tile][group]: the minimum over accumulators 4 g .. 4 g + 3 of the tiles of that parity
+    // [tile parity][sub-tile][row half]: the minimum over the lane's four accumulators of that chain (train rows 16 u + 4 kg .. + 3:
+    // one group of four stored rows) over the tiles of that parity
+    float xm[2][NQ][NU];
 #pragma unroll
     for (int q = 0; q < 2; ++q)
 #pragma unroll
-        for (int s = 0; s < NSUB; ++s)
+        for (int s = 0; s < NQ; ++s)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) xm[q][s][g] = BIGF;
+            for (int u = 0; u < NU; ++u) xm[q][s][u] = BIGF;
 
     static_assert(TILE_V4 % 64 == 0, "a tile is a whole number of 1 KiB pieces");
     constexpr int PIECES = TILE_V4 / 64;
@@ -1091,100 +1101,91 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
 
-    // C-init of a chain on the tile in ring slot `slot`: accumulator r is train row (r & 3) + 8 (r >> 2) + 4 h
-    // (the lane's address in slot 0 is one opaque register, slot and group immediate offsets: derived from h at every use it kept h
-    // and the lane alive through the sweep, spilled)
+    // C-init of the chains of row half u on the tile in ring slot `slot`: accumulator r is train row 16 u + 4 kg + r (screen::acc16_row)
+    // (the lane's address in slot 0 is one opaque register, slot and half immediate offsets: derived from the lane at every use it
+    // kept the lane alive through the sweep, spilled)
     typedef const v4f __attribute__((address_space(3)))* lds_v4f_t;
-    lds_v4f_t hb_lane = (lds_v4f_t)(const __attribute__((address_space(3))) void*)&sHb[0][4 * h];
+    lds_v4f_t hb_lane = (lds_v4f_t)(const __attribute__((address_space(3))) void*)&sHb[0][screen::acc16_row(0, lane, 0)];
     asm volatile("" : "+v"(hb_lane));
-    auto cinit_of = [&](int slot) {
-        v16f c;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const v4f q = hb_lane[8 * slot + 2 * g];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) c[4 * g + k] = q[k];
-        }
-        return c;
-    };
+    auto cinit_of = [&](int slot, int u) { return hb_lane[8 * slot + 4 * u]; };
     // (the scale is held in one register through the sweep: set up again inside a call it took the register of wave 0's load of the
     // constants, and the compiler put a vmcnt(0) in front of it that drained every wave's staging)
     int scale = SCALE;
     asm volatile("" : "+v"(scale));
-    auto mfma = [&](const ScreenFrag& b, const v6i& q, const v16f& c) {
+    auto mfma = [&](const ScreenFrag& b, const v6i& q, const v4f& c) {
         const v8i q8 = __builtin_shufflevector(q, q, 0, 1, 2, 3, 4, 5, -1, -1);
-        return __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, scale, 0, scale);
+        return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, scale, 0, scale);
     };
-    v16f accA[NSUB], accB[NSUB];
+    v4f accA[NU][NQ], accB[NU][NQ];   // a chain = (row half, query sub-tile): two MFMAs, one per step S
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s)
+    for (int u = 0; u < NU; ++u)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) accA[s][r] = 0.0f, accB[s][r] = 0.0f;
-    ScreenFrag bq[3];  // fragment ring: step i of the ks sequence lives in bq[i % 3]
+        for (int s = 0; s < NQ; ++s) accA[u][s] = v4f{0.0f, 0.0f, 0.0f, 0.0f}, accB[u][s] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    ScreenFrag bq[3];  // fragment ring: fragment i of the sequence lives in bq[i % 3]
     const char* sBb = reinterpret_cast<const char*>(&sB[0][0]);
-    auto read_plain = [&](int slot, int ks) {
-        ScreenFrag f;
-        f.lo = *reinterpret_cast<const v4i*>(sBb + slot * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 16 * lane);
-        f.hi = *reinterpret_cast<const v2i*>(sBb + slot * SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 1024 + 8 * lane);
-        return f;
+    // the whole tile in ring slot `slot` into accA with reads the compiler tracks (ahead of the calls)
+    auto tile_plain = [&](int slot) {
+#pragma unroll
+        for (int S = 0; S < NS; ++S)
+#pragma unroll
+            for (int u = 0; u < NU; ++u) {
+                const screen::FragSrc src = screen::frag16_src(u, S, lane);
+                ScreenFrag f;
+                f.lo = *reinterpret_cast<const v4i*>(sBb + slot * SCREEN_TILE_BYTES + screen::frag_lo_offset(src));
+                f.hi = *reinterpret_cast<const v2i*>(sBb + slot * SCREEN_TILE_BYTES + screen::frag_hi_offset(src));
+                const v4f c0 = cinit_of(slot, u);
+#pragma unroll
+                for (int s = 0; s < NQ; ++s) accA[u][s] = mfma(f, a[s][S], S ? accA[u][s] : c0);
+            }
     };
 #pragma unroll
     for (int i = 0; i < 3; ++i) bq[i].lo = v4i{0, 0, 0, 0}, bq[i].hi = v2i{0, 0};
-    // this lane's bytes in the two planes of slot 0, step 0: slot and step are immediate offsets of the reads
-    unsigned lds16 = lds_addr(sBb) + 16u * lane, lds8 = lds_addr(sBb) + 8u * lane;
+    // this lane's bytes in the two planes of slot 0, fragment (0, 0): slot and fragment are immediate offsets of the reads
+    unsigned lds16 = lds_addr(sBb) + (unsigned)screen::frag_lo_offset(screen::frag16_src(0, 0, lane));
+    unsigned lds8 = lds_addr(sBb) + (unsigned)(screen::frag_hi_offset(screen::frag16_src(0, 0, lane)) - screen::HI_PLANE);
     asm volatile("" : "+v"(lds16), "+v"(lds8));
+    // fragment f = u + NU S of the tile in ring slot `slot`: the immediates of its two reads
+    auto frag_lo_imm = [](int slot, int f) constexpr { return slot * SCREEN_TILE_BYTES + screen::frag_lo_offset(screen::frag16_src(f % NU, f / NU, 0)); };
+    auto frag_hi_imm = [](int slot, int f) constexpr { return slot * SCREEN_TILE_BYTES + screen::frag_hi_offset(screen::frag16_src(f % NU, f / NU, 0)); };
     // Inside the sweep every LDS operation is one the compiler does not track, so that every wait is a counted one placed here: the
     // fragments, the C-init of the chains after next (ci: read into registers of the accumulators just consumed, handed to the first
     // MFMAs as their C operand behind the wait of the half that issues its chains) and wave 0's store of the constants.
-    unsigned hb_rd = lds_addr(&sHb[0][4 * h]), hb_wr = lds_addr(&sHb[0][0]) + 4u * lane;
+    unsigned hb_rd = lds_addr(&sHb[0][screen::acc16_row(0, lane, 0)]), hb_wr = lds_addr(&sHb[0][0]) + 4u * lane;
     asm volatile("" : "+v"(hb_rd), "+v"(hb_wr));
-    // A lane's 16 constants depend on the tile and on its half h only, so ONE set serves both query sub-tiles: it is the C operand of
-    // both first chain steps, of which one writes accumulators of its own (D != C) and the other continues in ci's registers.
-    v4f ci[4];
+    // A lane's four constants of a row half depend on the tile, the half and kg only, so ONE set serves the four query sub-tiles: it
+    // is the C operand of the first step of all four chains, which write accumulators of their own (D != C; the last may go on in
+    // ci's registers).
+    v4f ci[NU];
 #pragma unroll
-    for (int g = 0; g < 4; ++g) ci[g] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int u = 0; u < NU; ++u) ci[u] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     auto cinit_issue = [&](int slot) {
 #pragma unroll
-        for (int g = 0; g < 4; ++g) lds_read_frag(ci[g], hb_rd, 128 * slot + 32 * g);
+        for (int u = 0; u < NU; ++u) lds_read_frag(ci[u], hb_rd, 128 * slot + 64 * u);
     };
     // lgkmcnt(0) on everything the sweep may have in flight (ahead of the first call, and behind the last)
     auto drain_lds = [&]() {
         asm volatile("s_waitcnt lgkmcnt(0)"
-                     : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi), "+v"(ci[0]), "+v"(ci[1]),
-                       "+v"(ci[2]), "+v"(ci[3]));
+                     : "+v"(bq[0].lo), "+v"(bq[0].hi), "+v"(bq[1].lo), "+v"(bq[1].hi), "+v"(bq[2].lo), "+v"(bq[2].hi), "+v"(ci[0]), "+v"(ci[1]));
     };
     if (T > 0 && active) {
         if (t0) {
             // the peeled tile 0, whole: its chains, then its epilogue into the minima of the even tiles (the second half's: the calls
             // start at tile 1, so xm[0] takes the odd tiles)
-            const v16f c0 = cinit_of(RING - 1);
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const ScreenFrag b0 = read_plain(RING - 1, ks);
-#pragma unroll
-                for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
-            }
+            tile_plain(RING - 1);
             // (plain minima, not consume(): its v_min3_f32 sits in an asm string, where nothing pads the wait states between the last
             // MFMA and a reader of its accumulators; inside a call the chains ended half a call earlier)
 #pragma unroll
-            for (int s = 0; s < NSUB; ++s)
+            for (int s = 0; s < NQ; ++s)
 #pragma unroll
-                for (int g = 0; g < 4; ++g)
-                    xm[1][s][g] = fminf(fminf(accA[s][4 * g], accA[s][4 * g + 1]), fminf(accA[s][4 * g + 2], accA[s][4 * g + 3]));
+                for (int u = 0; u < NU; ++u) xm[1][s][u] = fminf(fminf(accA[u][s][0], accA[u][s][1]), fminf(accA[u][s][2], accA[u][s][3]));
         }
-        const v16f c0 = cinit_of(0);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const ScreenFrag b0 = read_plain(0, ks);
-#pragma unroll
-            for (int s = 0; s < NSUB; ++s) accA[s] = mfma(b0, a[s][ks], ks ? accA[s] : c0);
-        }
+        tile_plain(0);
         // the constants and the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never consumed)
         cinit_issue(1);
 #pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            lds_read_frag(bq[ks].lo, lds16, SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES);
-            lds_read_frag64(bq[ks].hi, lds8, SCREEN_TILE_BYTES + ks * SCREEN_STEP_BYTES + 1024);
+        for (int f = 0; f < 2; ++f) {
+            lds_read_frag(bq[f].lo, lds16, frag_lo_imm(1, f));
+            lds_read_frag64(bq[f].hi, lds8, frag_hi_imm(1, f));
         }
         drain_lds();
     }
@@ -1192,26 +1193,30 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     // keys of a tile handled by step ks of the next tile's MFMAs: all 32 within the first KS - 1 steps, so that the accumulators are
     // free for the constants of the tile after next a step before the half ends
     auto key_lo = [](int ks) constexpr { return ks >= KS - 1 ? 32 : (32 * ks + KS - 2) / (KS - 1); };
-    // accumulators 4 g .. 4 g + 3 of sub-tile idx / 16 -> the running minimum of that group and tile parity, two at a time
-    auto consume = [&](const v16f(&cur)[NSUB], float(&m)[NSUB][4], const int idx) {
-        const int ph = idx / 16, eg = idx % 16;
-        if (eg & 1) m[ph][eg >> 2] = fmin3(m[ph][eg >> 2], cur[ph][eg - 1], cur[ph][eg]);
+    // the four accumulators of chain idx / 4 -> the running minimum of that chain and tile parity, two at a time. The chains of row
+    // half 0 come first: they ended a step before those of half 1
+    auto consume = [&](const v4f(&cur)[NU][NQ], float(&m)[NQ][NU], const int idx) {
+        const int u = idx / (4 * NQ), s = (idx / 4) % NQ, eg = idx % 4;
+        if (eg & 1) m[s][u] = fmin3(m[s][u], cur[u][s][eg - 1], cur[u][s][eg]);
     };
     // One call covers NT = 2 train tiles between two barriers (t = t0 + 2 k, the tile whose chains accA holds; K3 = call mod 3 gives the ring
     // slots and the phase of the fragment ring, which advances NT KS = 8 steps per call). Half 0: epilogue of tile t from accA under the
     // chains of tile t + 1 into accB; half 1: epilogue of tile t + 1 from accB under the chains of tile t + 2 into accA — the roles
-    // are back where they started, and xm is indexed by the half. Step i of the eight waits for fragment i, issues fragment i + 2
-    // (the last two are the first of tile t + 3) and, once per half, the C-init of the tile after next into ci: four ds_read_b128
-    // behind the last key of the tile being consumed, at step 2. One set of constants starts the chains of both query sub-tiles (a
-    // lane's sixteen depend on the tile and its half h alone), and ci's registers went to a chain at step 0 of the half.
+    // are back where they started, and xm is indexed by the half. A tile is 16 MFMAs of the 16x16x128 shape: its four fragments
+    // f = u + 2 S (row half u of the tile, K = 128 step S; screen::frag16_src) in the order (0,0) (1,0) (0,1) (1,1), each the A
+    // operand of four MFMAs, one per query sub-tile of 16 rows. The eight chains (u, sub-tile) of a tile are two MFMAs long, and the
+    // second comes two steps = eight MFMAs behind the first. Step i of the eight waits for fragment i, issues fragment i + 2 (the
+    // last two are the first of tile t + 3) and, once per half, the C-init of the tile after next into ci: two ds_read_b128 (one
+    // per row half: the constants of train rows 16 u + 4 kg .. + 3) behind the last key of the tile being consumed, at step 2. One
+    // set of constants starts the four chains of a row half at step u of the half.
     // The LDS queue of a wave is in order and every operation in it is issued here, so every wait is counted. A half issues
     //     step 0: F2    step 1: F3    step 2: F4, C    step 3: F5          (F_k: the two reads of the fragment of step k, F4 / F5 the
-    //                                                                       next half's steps 0 / 1; C: the four reads of the C-init)
+    //                                                                       next half's steps 0 / 1; C: the two reads of the C-init)
     // so that behind the fragment of step ks were issued
-    //     ks 0   the C-init (4, needed too: the chains start on it), the fragment of step 1 (2)   lgkmcnt(2)
+    //     ks 0   the C-init (2, needed too: the chains start on it), the fragment of step 1 (2)   lgkmcnt(2)
     //     ks 1   the fragment of step 2 (2)                                                        lgkmcnt(2)
     //     ks 2   the fragment of step 3 (2)                                                        lgkmcnt(2)
-    //     ks 3   the fragment of the next step 0 (2), the C-init (4)                               lgkmcnt(6)
+    //     ks 3   the fragment of the next step 0 (2), the C-init (2)                               lgkmcnt(4)
     // (wave 0's store of the constants at the head of the call is one more operation behind some of them: a wait that asks for more
     // than it needs). Nothing is drained at the barrier: the two fragments and the C-init in flight read slots that the next call
     // does not stage into.
@@ -1235,36 +1240,28 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         }
         auto half = [&](auto HHc) {
             constexpr int HH = decltype(HHc)::value;
-            v16f(&cur)[NSUB] = HH ? accB : accA;
-            v16f(&nxt)[NSUB] = HH ? accA : accB;
+            v4f(&cur)[NU][NQ] = HH ? accB : accA;
+            v4f(&nxt)[NU][NQ] = HH ? accA : accB;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const int i = HH * KS + ks, j = i + 2;
                 ScreenFrag& f = bq[(i + PH) % 3];
-                const int off = ((BASE + 1 + j / KS) % RING) * SCREEN_TILE_BYTES + (j % KS) * SCREEN_STEP_BYTES;
+                const int u = ks % NU, S = ks / NU;   // the fragment of this step
                 if (ks == 0) {
                     // the fragment of this step and, behind it, the C-init were issued at step 2 of the half before: younger is the fragment of step 1
-                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi), "+v"(ci[0]), "+v"(ci[1]), "+v"(ci[2]), "+v"(ci[3]));
+                    asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi), "+v"(ci[0]), "+v"(ci[1]));
                 } else if (ks < KS - 1) {
                     asm volatile("s_waitcnt lgkmcnt(2)" : "+v"(f.lo), "+v"(f.hi));   // issued two steps ago; younger: the fragment of the next step
                 } else {
-                    // issued at step 1; younger: the fragment of the next step 0 (2) and the C-init (4), both issued at step 2
-                    asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(f.lo), "+v"(f.hi));
+                    // issued at step 1; younger: the fragment of the next step 0 (2) and the C-init (2), both issued at step 2
+                    asm volatile("s_waitcnt lgkmcnt(4)" : "+v"(f.lo), "+v"(f.hi));
                 }
-                lds_read_frag(bq[(j + PH) % 3].lo, lds16, off);
-                lds_read_frag64(bq[(j + PH) % 3].hi, lds8, off + 1024);
-                if (ks == 0) {
-                    // both chains start on the one set of constants: the first sub-tile's writes registers of its own (D != C), the second
-                    // sub-tile's goes on in those of the constants, dead behind it
-                    v16f c0;
+                lds_read_frag(bq[(j + PH) % 3].lo, lds16, frag_lo_imm((BASE + 1 + j / KS) % RING, j % KS));
+                lds_read_frag64(bq[(j + PH) % 3].hi, lds8, frag_hi_imm((BASE + 1 + j / KS) % RING, j % KS));
+                // four MFMAs on four chains: the second step of a chain comes NU steps = eight MFMAs behind its first. The four chains
+                // of a row half start on its one set of constants
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) c0[r] = ci[r >> 2][r & 3];
-#pragma unroll
-                    for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][0], c0);
-                } else {
-#pragma unroll
-                    for (int s = 0; s < NSUB; ++s) nxt[s] = mfma(f, a[s][ks], nxt[s]);
-                }
+                for (int s = 0; s < NQ; ++s) nxt[u][s] = mfma(f, a[s][S], S ? nxt[u][s] : ci[u]);
 #pragma unroll
                 for (int idx = key_lo(ks); idx < key_lo(ks + 1); ++idx) {
                     consume(cur, xm[HH], idx);
@@ -1287,8 +1284,12 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     // the last tile (an even number of tiles behind t0) has nothing to issue and nothing to stage: its epilogue alone, from accA
     auto last = [&]() {
         if (active) {
+            // (plain minima, as for the peeled tile: the chains of row half 1 ended with the last MFMAs of the last call)
 #pragma unroll
-            for (int idx = 0; idx < 32; ++idx) consume(accA, xm[0], idx);
+            for (int s = 0; s < NQ; ++s)
+#pragma unroll
+                for (int u = 0; u < NU; ++u)
+                    xm[0][s][u] = fminf(xm[0][s][u], fminf(fminf(accA[u][s][0], accA[u][s][1]), fminf(accA[u][s][2], accA[u][s][3])));
         }
     };
     if (T > 0) {
@@ -1309,42 +1310,50 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         last();
     }
     if (!active) return;
-    // join the partner lane (the same query row against the other half of every tile's train rows) and the tile parities: the two
-    // smallest of the sixteen subset minima, then the bounds
+    // A query row's sixteen subset minima lie in the four lanes of its column (lane & 15 of its sub-tile, one per kg), four each
+    // (tile parity x row half): the two smallest of the four, joined across the lanes (xor 16, xor 32) as pairs. All four lanes end
+    // with the same two numbers, so lane 16 s + i keeps those of sub-tile s: every lane owns the row of the wave-block of its number,
+    // and the bounds are computed once for the 64 rows.
     const gint_t Asr = (gint_t)(Am2 + 32 * (size_t)A.ntiles);
     const int e_b = T > 0 ? ((gint_t)(Bm2 + 64 * (size_t)B.ntiles))[0] : 0;
     uint4* rr = rowres + (size_t)p * row_stride + ROWS_WAVE * wb;
-    const int lane_t = (int)((lds16 - lds_addr(sBb)) >> 4), cl_t = lane_t & 31, h_t = lane_t >> 5;   // (the lane, from what the sweep kept)
+    const int lane_t = (int)((hb_wr - lds_addr(&sHb[0][0])) >> 2);   // (the lane, from what the sweep kept)
     constexpr unsigned PAD_V = 2u * PADH;
-    unsigned long long open_rows = 0;   // bit 32 s + cl: that row of the wave-block goes to the exact pass
+    float v1 = BIGF, v2 = BIGF;
 #pragma unroll
-    for (int s = 0; s < NSUB; ++s) {
-        bool open = false;
-        const int j = ROWS_WAVE * wb + 32 * s + cl_t;
-        const float ma = Am2[j];
-        float v1 = BIGF, v2 = BIGF;
+    for (int s = 0; s < NQ; ++s) {
+        float m1 = BIGF, m2 = BIGF;
 #pragma unroll
         for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const float mine = xm[q][s][g], other = __shfl_xor(mine, 32);
-                v2 = fminf(v2, fmaxf(v1, mine)), v1 = fminf(v1, mine);
-                v2 = fminf(v2, fmaxf(v1, other)), v1 = fminf(v1, other);
+            for (int u = 0; u < NU; ++u) {
+                const float mine = xm[q][s][u];
+                m2 = fminf(m2, fmaxf(m1, mine)), m1 = fminf(m1, mine);
             }
-        if (h_t == 0) {
-            // a padding train row holds SCREEN_PAD or more, a subset that met no tile BIGF; real values stay below 2^21
-            const bool real_row = ma < 0.5f * SCREEN_PAD;
-            const bool real1 = real_row && v1 < 0.5f * SCREEN_PAD, real2 = real_row && v2 < 0.5f * SCREEN_PAD;
-            const unsigned pa = NSUB * wb + s >= A_even ? 1u : 0u;
-            const int s_a = Asr[j];
-            const unsigned n1 = real1 ? (unsigned)(2.0f * (v1 + ma)) : 0u, u = real2 ? (unsigned)(2.0f * (v2 + ma)) : 0u;
-            const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
-            const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
-            rr[32 * s + cl_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
-            // match_rowpick_kernel's predicate on the two words just stored (a padding row carries 0xffffffff in the first)
-            open = NSUB * wb + s < A_tiles && w1 < PAD_V && (w2 >= PAD_V || ratio_pass<METRIC>((int)(w1 + pa) - 2, (int)(w2 + pa) - 2, ratio));
+#pragma unroll
+        for (int x = 16; x <= 32; x *= 2) {
+            const float o1 = __shfl_xor(m1, x), o2 = __shfl_xor(m2, x);   // two sorted pairs: min of the firsts, then the next
+            m2 = fminf(fmaxf(m1, o1), fminf(m2, o2)), m1 = fminf(m1, o1);
         }
-        open_rows |= (__ballot(open) & 0xffffffffull) << (32 * s);
+        if ((lane_t >> 4) == s) v1 = m1, v2 = m2;
+    }
+    unsigned long long open_rows = 0;   // bit = row of the wave-block: that row goes to the exact pass
+    {
+        const int s = lane_t >> 5;      // the stored query tile of the row
+        const int j = ROWS_WAVE * wb + lane_t;
+        const float ma = Am2[j];
+        // a padding train row holds SCREEN_PAD or more, a subset that met no tile BIGF; real values stay below 2^21
+        const bool real_row = ma < 0.5f * SCREEN_PAD;
+        const bool real1 = real_row && v1 < 0.5f * SCREEN_PAD, real2 = real_row && v2 < 0.5f * SCREEN_PAD;
+        const unsigned pa = NSUB * wb + s >= A_even ? 1u : 0u;
+        const int s_a = Asr[j];
+        const unsigned n1 = real1 ? (unsigned)(2.0f * (v1 + ma)) : 0u, u = real2 ? (unsigned)(2.0f * (v2 + ma)) : 0u;
+        const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
+        const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
+        rr[lane_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
+        // match_rowpick_kernel's predicate on the two words just stored (a padding row carries 0xffffffff in the first)
+        const bool open = NSUB * wb + s < A_tiles && w1 < PAD_V && (w2 >= PAD_V || ratio_pass<METRIC>((int)(w1 + pa) - 2, (int)(w2 + pa) - 2, ratio));
+        open_rows = __ballot(open);
     }
     if (!openmask) return;   // (the debug entry: no list)
     if (lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
