@@ -99,6 +99,25 @@ EACHAM_SCREEN_HD constexpr FragSrc frag16_src(int u, int S, int lane) { return F
 // wave-block, the K block of a lane the train side's
 EACHAM_SCREEN_HD constexpr int query16_tile(int s4) { return s4 >> 1; }
 EACHAM_SCREEN_HD constexpr FragSrc query16_src(int s4, int S, int lane) { return frag16_src(s4 & 1, S, lane); }
+// A wave of the sweep owns QUERY_SUBTILES = 8 sub-tiles s8: two wave-blocks of 64 rows (the tail's unit: one openmask word, one row
+// per lane), four stored tiles. The two functions above serve all eight: query16_tile(s8) counts the stored tiles from the wave's
+// first, sub-tile s8 is sub-tile s8 & 3 of wave-block query16_block(s8) of the wave, and its 16 rows are the wave's rows 16 s8 ..
+constexpr int QUERY_SUBTILES = 8;
+EACHAM_SCREEN_HD constexpr int query16_block(int s8) { return s8 >> 2; }
+EACHAM_SCREEN_HD constexpr int query16_wave_row(int s8, int lane) { return TILE_ROWS * query16_tile(s8) + query16_src(s8, 0, lane).row; }
+constexpr bool query16_eight() {
+    for (int s8 = 0; s8 < QUERY_SUBTILES; ++s8)
+        for (int l = 0; l < 64; ++l) {
+            if (query16_tile(s8) != 2 * query16_block(s8) + query16_tile(s8 & 3) || query16_tile(s8) >= QUERY_SUBTILES / 2) return false;
+            if (query16_wave_row(s8, l) != 16 * s8 + (l & 15)) return false;
+            for (int S = 0; S < 2; ++S) {
+                const FragSrc f = query16_src(s8, S, l), g = query16_src(s8 & 3, S, l), t = frag16_src(0, S, l);
+                if (f.row != g.row || f.ks != g.ks || f.h != g.h || f.ks != t.ks || f.h != t.h) return false;
+            }
+        }
+    return true;
+}
+static_assert(query16_eight(), "eight sub-tiles = two wave-blocks of the four-sub-tile map, the train side's K blocks");
 EACHAM_SCREEN_HD constexpr int frag_lo_offset(FragSrc f) { return f.ks * STEP_BYTES + 16 * (f.row + TILE_ROWS * f.h); }
 EACHAM_SCREEN_HD constexpr int frag_hi_offset(FragSrc f) { return f.ks * STEP_BYTES + HI_PLANE + 8 * (f.row + TILE_ROWS * f.h); }
 EACHAM_SCREEN_HD constexpr int frag_kblock(FragSrc f) { return 2 * f.ks + f.h; }   // of the row's eight blocks of 32 codes

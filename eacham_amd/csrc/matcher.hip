@@ -171,7 +171,7 @@ constexpr float SCREEN_PAD = 8388608.0f;     // 2^23: exact in f32, above any n 
 constexpr int SCREEN_KS = 4;                 // K = 64 steps of a 256-D row
 constexpr int SCREEN_EXACT_KS = 8;           // int8 K = 32 steps of the same row: the exact pass behind the screen (frames_have_screen)
 constexpr int SCREEN_STEP_BYTES = 1536, SCREEN_TILE_BYTES = SCREEN_KS * SCREEN_STEP_BYTES;
-constexpr int SCREEN_CALL_TILES = 2;         // train tiles between two barriers of the screen sweep: 32 MFMAs of four passes per wave, the int8 sweep's matrix cycles per barrier
+constexpr int SCREEN_CALL_TILES = 2;         // train tiles between two barriers of the screen sweep: 64 MFMAs of four passes per wave (128 query rows)
 __global__ void quantize_screen_kernel(const float* __restrict__ src, int dim, int npad, const int* __restrict__ orig,
                                        char* __restrict__ image, int* __restrict__ msq, int* __restrict__ sr) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
@@ -945,7 +945,7 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // the 16x16x128 shape (v_mfma_scale_f32_16x16x128_f8f6f4, 16 of four passes per wave-tile where the 32x32x64 shape took 8 of eight:
 // the same matrix cycles, under which the chip holds 1.61 GHz where it held 1.48; profiles/screen_shape16.txt). The stored
 // image is the 32x32x64 operand's; which of its fragments a lane reads is screen::frag16_src. The train tile is the A operand,
-// the wave's 64 query rows the B operand with their sign bits flipped; both scale operands are 2^3 (one register), so a product is the
+// the wave's 128 query rows (eight sub-tiles of 16) the B operand with their sign bits flipped; both scale operands are 2^3 (one register), so a product is the
 // integer -M_a M_b and, with |M_b|^2 / 2 as the C-init, an accumulator holds |M_b|^2 / 2 - M_a.M_b: every partial sum is a multiple of
 // 1/2 below 2^22, exact in f32 in any order. |M_a|^2 / 2 is added once after the sweep: n = |M_a - M_b|^2 is twice the sum.
 // The epilogue is the bound form's: running minima per chain (two v_min3_f32 per group of four train rows and tile). Nothing here
@@ -961,10 +961,13 @@ __global__ __launch_bounds__(WG_THREADS, KS >= 4 ? 3 : 4) void match_sweep_kerne
 // openmask (null: none, the debug entry): openmask[p][wb] = one bit per row of wave-block wb, set where match_rowpick_kernel's
 // predicate holds on the two words the tail is storing — one ballot, every lane owning the row of its number, stored from one lane (256 B per pair
 // where its rowres is 32 KB: match_rows2_kernel<.., true> counts a pair's open rows from them). With the same word the tail
-// reserves room in the candidate list of the pair's segment — one returning add per wave with an open row — and writes its
+// reserves room in the candidate list of the pair's segment — one returning add per wave-block with an open row — and writes its
 // candidates and, where its range holds a multiple of 256, the item that starts there (OpenList, match_openprep_kernel).
-// LDS-DMA ring, just-in-time fragment ring and double-buffered accumulators are match_sweep_kernel's; a fragment is 24 bytes, two
-// LDS reads. The call structure is its own: the matrix cycles of a tile are half the int8 sweep's, so a call covers TWO train tiles between
+// LDS-DMA ring and just-in-time fragment ring are match_sweep_kernel's; a fragment is 24 bytes, two LDS reads, and feeds eight MFMAs.
+// A wave owns 128 query rows — two wave-blocks of 64, the unit of the tail, of openmask and of the candidate list — at two waves per
+// SIMD, with ONE set of accumulators (a second does not fit): per MFMA half the LDS reads, staged bytes, barriers and waits of the
+// 64-row form (profiles/screen_rows128.txt). A workgroup is 512 query rows; the host launches ceil(wgs_per_pair / 2) per pair.
+// The call structure is its own: a call covers TWO train tiles between
 // two barriers (six ring slots of 6 KiB, three calls per trip), the four waves stage three pieces each spread over the call, and
 // every wait inside a call is a counted one (see the call below; profiles/screen_two_tiles.txt).
 // The sweep covers the train frame's meta[2] tiles, those that hold a real row. The tile that rounds meta[1] up to whole wave-blocks
@@ -1001,12 +1004,14 @@ struct ScreenFrag { v4i lo; v2i hi; };   // a lane's 32 codes of one K = 64 step
 __device__ __forceinline__ v8i screen_operand(const ScreenFrag& f) { return v8i{f.lo[0], f.lo[1], f.lo[2], f.lo[3], f.hi[0], f.hi[1], 0, 0}; }
 
 template <int METRIC>   // of the ratio test in the tail (binary frames of 129..256 bits carry the FP6 image too)
-__global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
+__global__ __launch_bounds__(WG_THREADS, 2) void match_screen_kernel(const FrameDev* __restrict__ frames, const int2* __restrict__ pairs,
                                                                      int wgs_per_pair, uint4* __restrict__ rowres, int row_stride, double ratio,
                                                                      unsigned long long* __restrict__ openmask, int mask_stride,
                                                                      OpenList ol) {
-    constexpr int NSUB = 2;                   // stored (32-row) query tiles of a wave-block
-    constexpr int NQ = 4, NU = 2, NS = 2;     // per train tile: query sub-tiles of 16 rows x row halves u of the tile x K = 128 steps S
+    constexpr int WBS = 2, WB_TILES = 2;      // a wave owns two wave-blocks of 64 query rows (the tail's unit), two stored tiles each
+    constexpr int NSUB = WBS * WB_TILES;      // stored (32-row) query tiles of a wave
+    constexpr int NQ = screen::QUERY_SUBTILES, NU = 2, NS = 2;   // per train tile: query sub-tiles of 16 rows x row halves u of the tile x K = 128 steps S
+    static_assert(NQ == 2 * NSUB && screen::query16_block(NQ - 1) == WBS - 1, "match_screen.hpp maps the wave's eight sub-tiles");
     constexpr int KS = NU * NS;               // fragments of a tile = steps of a half, in the order f = u + NU S (see the call)
     static_assert(KS == SCREEN_KS && 2 * NS == SCREEN_KS && screen::STEP_BYTES == SCREEN_STEP_BYTES, "match_screen.hpp maps this stored tile");
     constexpr int TILE_V4 = SCREEN_TILE_BYTES / 16;
@@ -1027,15 +1032,14 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     const int A_even = ((gint_t)A.meta)[0], A_tiles = ((gint_t)A.meta)[1];
     const int T = ((gint_t)B.meta)[2];   // the train tiles that hold a real row (finish_screen_kernel): not the tile that rounds meta[1] up
     if (rb * (ROWS_WG / 32) >= A_tiles) return;  // workgroup-uniform
-    const int wb = rb * WAVES + wave;
-    const bool active = NSUB * wb < A_tiles;
+    const int wv = rb * WAVES + wave;            // this wave's 128 query rows: wave-blocks WBS wv and WBS wv + 1
+    const bool active = NSUB * wv < A_tiles;     // (A_tiles counts whole wave-blocks: the second may lie past the frame)
     typedef const __attribute__((address_space(1))) char* gbytes_t;
     typedef const float __attribute__((address_space(1)))* gfloat_t;
     const gbytes_t Aimg = (gbytes_t)A.screen, Bimg = (gbytes_t)B.screen;
     const gfloat_t Am2 = (gfloat_t)(Aimg + (size_t)A.ntiles * SCREEN_TILE_BYTES), Bm2 = (gfloat_t)(Bimg + (size_t)B.ntiles * SCREEN_TILE_BYTES);
-    const int wbc = active ? wb : 0;
 
-    // this wave's 64 query rows, sign bits flipped: the B operand (a lane = query row lane & 15 of the sub-tile, K block kg of the
+    // this wave's 128 query rows, sign bits flipped: the B operand (a lane = query row lane & 15 of the sub-tile, K block kg of the
     // step: the stored fragment that screen::query16_src names, the train side's assignment of kg)
     v6i a[NQ][NS];
 #pragma unroll
@@ -1043,7 +1047,8 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
 #pragma unroll
         for (int S = 0; S < NS; ++S) {
             const screen::FragSrc src = screen::query16_src(s, S, lane);
-            const gbytes_t tb = Aimg + (size_t)(NSUB * wbc + screen::query16_tile(s)) * SCREEN_TILE_BYTES;
+            const int qt = NSUB * wv + screen::query16_tile(s);   // (a tile past the frame: tile 0 in its place, its minima are never read)
+            const gbytes_t tb = Aimg + (size_t)(qt < A_tiles ? qt : 0) * SCREEN_TILE_BYTES;
             const v4i lo = *(const v4i __attribute__((address_space(1)))*)(tb + screen::frag_lo_offset(src));
             const v2i hi = *(const v2i __attribute__((address_space(1)))*)(tb + screen::frag_hi_offset(src));
             // the sign bit of code e is bit 6 e + 5: a pattern of period three words
@@ -1077,7 +1082,8 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     // the constants of tile `tile` + (lane / 32), clamped, one per lane of wave 0: loaded a call before they are stored to the ring
     auto load_hb = [&](int tile) {
         asm volatile("" : "+v"(hb_off));
-        const gbytes_t row = reinterpret_cast<gbytes_t>(Bm2) + (size_t)128 * min(tile + (lane >> 5), TM);
+        // (lane / 32 from the staging offset the sweep keeps: the lane itself would be one register more through the sweep, spilled)
+        const gbytes_t row = reinterpret_cast<gbytes_t>(Bm2) + (size_t)128 * min(tile + (int)(stage_off >> 9), TM);
         return *reinterpret_cast<gfloat_t>(row + hb_off);
     };
     // An even tile count is peeled at the front, where nothing is in flight: t0 = 1, tile 0 is swept whole ahead of the calls and
@@ -1116,14 +1122,14 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         const v8i q8 = __builtin_shufflevector(q, q, 0, 1, 2, 3, 4, 5, -1, -1);
         return __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(screen_operand(b), q8, c, 2, 2, 0, scale, 0, scale);
     };
-    v4f accA[NU][NQ], accB[NU][NQ];   // a chain = (row half, query sub-tile): two MFMAs, one per step S
+    v4f acc[NU][NQ];   // a chain = (row half, query sub-tile): two MFMAs, one per step S. ONE set: a second does not fit beside 128 rows
 #pragma unroll
     for (int u = 0; u < NU; ++u)
 #pragma unroll
-        for (int s = 0; s < NQ; ++s) accA[u][s] = v4f{0.0f, 0.0f, 0.0f, 0.0f}, accB[u][s] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int s = 0; s < NQ; ++s) acc[u][s] = v4f{0.0f, 0.0f, 0.0f, 0.0f};
     ScreenFrag bq[3];  // fragment ring: fragment i of the sequence lives in bq[i % 3]
     const char* sBb = reinterpret_cast<const char*>(&sB[0][0]);
-    // the whole tile in ring slot `slot` into accA with reads the compiler tracks (ahead of the calls)
+    // the whole tile in ring slot `slot` into acc with reads the compiler tracks (ahead of the calls)
     auto tile_plain = [&](int slot) {
 #pragma unroll
         for (int S = 0; S < NS; ++S)
@@ -1135,8 +1141,14 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
                 f.hi = *reinterpret_cast<const v2i*>(sBb + slot * SCREEN_TILE_BYTES + screen::frag_hi_offset(src));
                 const v4f c0 = cinit_of(slot, u);
 #pragma unroll
-                for (int s = 0; s < NQ; ++s) accA[u][s] = mfma(f, a[s][S], S ? accA[u][s] : c0);
+                for (int s = 0; s < NQ; ++s) acc[u][s] = mfma(f, a[s][S], S ? acc[u][s] : c0);
             }
+    };
+    // the chains of row half u into the minima m, plain (no v_min3_f32 in an asm string, where nothing pads the wait states between
+    // the last MFMA and a reader of its accumulators): ahead of the calls and behind them
+    auto consume_plain = [&](float(&m)[NQ][NU], int u) {
+#pragma unroll
+        for (int s = 0; s < NQ; ++s) m[s][u] = fminf(m[s][u], fminf(fminf(acc[u][s][0], acc[u][s][1]), fminf(acc[u][s][2], acc[u][s][3])));
     };
 #pragma unroll
     for (int i = 0; i < 3; ++i) bq[i].lo = v4i{0, 0, 0, 0}, bq[i].hi = v2i{0, 0};
@@ -1172,14 +1184,11 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
             // the peeled tile 0, whole: its chains, then its epilogue into the minima of the even tiles (the second half's: the calls
             // start at tile 1, so xm[0] takes the odd tiles)
             tile_plain(RING - 1);
-            // (plain minima, not consume(): its v_min3_f32 sits in an asm string, where nothing pads the wait states between the last
-            // MFMA and a reader of its accumulators; inside a call the chains ended half a call earlier)
-#pragma unroll
-            for (int s = 0; s < NQ; ++s)
-#pragma unroll
-                for (int u = 0; u < NU; ++u) xm[1][s][u] = fminf(fminf(accA[u][s][0], accA[u][s][1]), fminf(accA[u][s][2], accA[u][s][3]));
+            consume_plain(xm[1], 0), consume_plain(xm[1], 1);
         }
+        // tile t0: the chains of its row half 0 are consumed here, those of half 1 under the first step of the first call (or by last())
         tile_plain(0);
+        consume_plain(xm[0], 0);
         // the constants and the first fragments of tile 1 (the ring holds tile T - 1 again past the end: recomputed, never consumed)
         cinit_issue(1);
 #pragma unroll
@@ -1190,25 +1199,29 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         drain_lds();
     }
     __syncthreads();   // slot 0 is staged into again by the first call below
-    // keys of a tile handled by step ks of the next tile's MFMAs: all 32 within the first KS - 1 steps, so that the accumulators are
-    // free for the constants of the tile after next a step before the half ends
-    auto key_lo = [](int ks) constexpr { return ks >= KS - 1 ? 32 : (32 * ks + KS - 2) / (KS - 1); };
-    // the four accumulators of chain idx / 4 -> the running minimum of that chain and tile parity, two at a time. The chains of row
-    // half 0 come first: they ended a step before those of half 1
-    auto consume = [&](const v4f(&cur)[NU][NQ], float(&m)[NQ][NU], const int idx) {
-        const int u = idx / (4 * NQ), s = (idx / 4) % NQ, eg = idx % 4;
-        if (eg & 1) m[s][u] = fmin3(m[s][u], cur[u][s][eg - 1], cur[u][s][eg]);
+    // the four accumulators of chain (u, s) -> its running minimum of tile parity q: two v_min3_f32
+    auto consume = [&](float(&m)[NQ][NU], const int u, const int s) {
+        m[s][u] = fmin3(m[s][u], acc[u][s][0], acc[u][s][1]);
+        m[s][u] = fmin3(m[s][u], acc[u][s][2], acc[u][s][3]);
     };
-    // One call covers NT = 2 train tiles between two barriers (t = t0 + 2 k, the tile whose chains accA holds; K3 = call mod 3 gives the ring
-    // slots and the phase of the fragment ring, which advances NT KS = 8 steps per call). Half 0: epilogue of tile t from accA under the
-    // chains of tile t + 1 into accB; half 1: epilogue of tile t + 1 from accB under the chains of tile t + 2 into accA — the roles
-    // are back where they started, and xm is indexed by the half. A tile is 16 MFMAs of the 16x16x128 shape: its four fragments
-    // f = u + 2 S (row half u of the tile, K = 128 step S; screen::frag16_src) in the order (0,0) (1,0) (0,1) (1,1), each the A
-    // operand of four MFMAs, one per query sub-tile of 16 rows. The eight chains (u, sub-tile) of a tile are two MFMAs long, and the
-    // second comes two steps = eight MFMAs behind the first. Step i of the eight waits for fragment i, issues fragment i + 2 (the
-    // last two are the first of tile t + 3) and, once per half, the C-init of the tile after next into ci: two ds_read_b128 (one
-    // per row half: the constants of train rows 16 u + 4 kg .. + 3) behind the last key of the tile being consumed, at step 2. One
-    // set of constants starts the four chains of a row half at step u of the half.
+    // One call covers NT = 2 train tiles between two barriers (t = t0 + 2 k; K3 = call mod 3 gives the ring slots and the phase of
+    // the fragment ring, which advances NT KS = 8 steps per call). Half HH runs the chains of tile t + 1 + HH. A tile is 32 MFMAs of
+    // the 16x16x128 shape: its four fragments f = u + 2 S (row half u of the tile, K = 128 step S; screen::frag16_src) in the order
+    // (0,0) (1,0) (0,1) (1,1), each the A operand of EIGHT MFMAs, one per query sub-tile of 16 rows: a step. The sixteen chains
+    // (u, sub-tile) of a tile are two MFMAs long, and the second comes two steps = sixteen MFMAs behind the first.
+    // There is one set of accumulators, and each row half's has one step in which it is consumed:
+    //     step 0 (0,0)  writes acc[0] from ci[0]          consumes acc[1] of the tile BEFORE (ended in its step 3)  -> xm[HH]
+    //     step 1 (1,0)  writes acc[1] from ci[1]
+    //     step 2 (0,1)  ends the chains of acc[0]         issues the C-init of the next tile (ci is free from step 1 on)
+    //     step 3 (1,1)  ends the chains of acc[1]         consumes acc[0] of THIS tile (ended in step 2)            -> xm[1 - HH]
+    // (tile t + HH has parity HH behind t0, tile t + 1 + HH the other). A step goes in four groups of two MFMAs with a scheduling
+    // barrier behind each; group g consumes sub-tiles 2 g and 2 g + 1, whose chains ended with MFMAs 2 g and 2 g + 1 of the step
+    // before: at least 6 MFMAs lie between the MFMA that finished an accumulator and the v_min3_f32 that reads it, wherever the
+    // compiler puts the four inside their group. Ahead of the first call and behind the last there is no step to hide under:
+    // consume_plain().
+    // Step i of the eight waits for fragment i, issues fragment i + 2 (the last two are the first of tile t + 3) and, once per half,
+    // the C-init of the next tile into ci: two ds_read_b128 (one per row half: the constants of train rows 16 u + 4 kg .. + 3) at
+    // step 2. One set of constants starts the eight chains of a row half at step u of the half.
     // The LDS queue of a wave is in order and every operation in it is issued here, so every wait is counted. A half issues
     //     step 0: F2    step 1: F3    step 2: F4, C    step 3: F5          (F_k: the two reads of the fragment of step k, F4 / F5 the
     //                                                                       next half's steps 0 / 1; C: the two reads of the C-init)
@@ -1217,9 +1230,9 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
     //     ks 1   the fragment of step 2 (2)                                                        lgkmcnt(2)
     //     ks 2   the fragment of step 3 (2)                                                        lgkmcnt(2)
     //     ks 3   the fragment of the next step 0 (2), the C-init (2)                               lgkmcnt(4)
-    // (wave 0's store of the constants at the head of the call is one more operation behind some of them: a wait that asks for more
-    // than it needs). Nothing is drained at the barrier: the two fragments and the C-init in flight read slots that the next call
-    // does not stage into.
+    // (the issue order of a half is what it was with four MFMAs to a step, so the counts are; wave 0's store of the constants at
+    // the head of the call is one more operation behind some of them: a wait that asks for more than it needs). Nothing is drained
+    // at the barrier: the two fragments and the C-init in flight read slots that the next call does not stage into.
     // Staging: the call stages tiles t + 2 NT + 1 and t + 2 NT + 2 into the slots of tiles t - 1 and t (read for the last time
     // ahead of the previous barrier), three pieces per wave behind steps 0, 2 and 4, the earlier tile's first. The earlier tile is
     // read from step 6 of the NEXT call on, the later one a call after that: before the barrier a wave waits for all but the last
@@ -1240,8 +1253,6 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         }
         auto half = [&](auto HHc) {
             constexpr int HH = decltype(HHc)::value;
-            v4f(&cur)[NU][NQ] = HH ? accB : accA;
-            v4f(&nxt)[NU][NQ] = HH ? accA : accB;
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const int i = HH * KS + ks, j = i + 2;
@@ -1258,15 +1269,20 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
                 }
                 lds_read_frag(bq[(j + PH) % 3].lo, lds16, frag_lo_imm((BASE + 1 + j / KS) % RING, j % KS));
                 lds_read_frag64(bq[(j + PH) % 3].hi, lds8, frag_hi_imm((BASE + 1 + j / KS) % RING, j % KS));
-                // four MFMAs on four chains: the second step of a chain comes NU steps = eight MFMAs behind its first. The four chains
-                // of a row half start on its one set of constants
+                // eight MFMAs on eight chains, in groups of two: the second step of a chain comes NU steps = sixteen MFMAs behind its
+                // first. The eight chains of a row half start on its one set of constants
 #pragma unroll
-                for (int s = 0; s < NQ; ++s) nxt[u][s] = mfma(f, a[s][S], S ? nxt[u][s] : ci[u]);
+                for (int g = 0; g < NQ / 2; ++g) {
 #pragma unroll
-                for (int idx = key_lo(ks); idx < key_lo(ks + 1); ++idx) {
-                    consume(cur, xm[HH], idx);
-                    if (idx == 31) cinit_issue((BASE + HH + 2) % RING);   // both accumulator sets are free: the constants of the tile after next
+                    for (int s = 2 * g; s < 2 * g + 2; ++s) acc[u][s] = mfma(f, a[s][S], S ? acc[u][s] : ci[u]);
+#pragma unroll
+                    for (int s = 2 * g; s < 2 * g + 2; ++s) {
+                        if (ks == 0) consume(xm[HH], 1, s);           // the tile before, row half 1
+                        if (ks == KS - 1) consume(xm[1 - HH], 0, s);  // this tile, row half 0
+                    }
+                    if (g < NQ / 2 - 1) __builtin_amdgcn_sched_barrier(0);
                 }
+                if (ks == 2) cinit_issue((BASE + HH + 2) % RING);   // the constants of the next tile: ci[1] was last read by step 1's MFMAs
                 if (i % 2 == 0 && i / 2 < PPW) stage(i / 2);
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -1281,16 +1297,10 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         asm volatile("s_waitcnt vmcnt(1)" : : : "memory");
         __builtin_amdgcn_s_barrier();
     };
-    // the last tile (an even number of tiles behind t0) has nothing to issue and nothing to stage: its epilogue alone, from accA
+    // the last tile (an even number of tiles behind t0) has nothing to issue and nothing to stage: the epilogue of its row half 1 alone
+    // (plain minima, as for the peeled tile: those chains ended with the last MFMAs of the last call)
     auto last = [&]() {
-        if (active) {
-            // (plain minima, as for the peeled tile: the chains of row half 1 ended with the last MFMAs of the last call)
-#pragma unroll
-            for (int s = 0; s < NQ; ++s)
-#pragma unroll
-                for (int u = 0; u < NU; ++u)
-                    xm[0][s][u] = fminf(xm[0][s][u], fminf(fminf(accA[u][s][0], accA[u][s][1]), fminf(accA[u][s][2], accA[u][s][3])));
-        }
+        if (active) consume_plain(xm[0], 1);
     };
     if (T > 0) {
         // tiles t0 + 1 .. TM have their chains inside a call, tiles t0 .. TM - 1 their epilogue: TM - t0 of each, an even number (the
@@ -1310,64 +1320,74 @@ __global__ __launch_bounds__(WG_THREADS, 3) void match_screen_kernel(const Frame
         last();
     }
     if (!active) return;
+    // The tail runs per wave-block of 64 rows, the wave's two one after the other (the second only where it has a tile of the frame).
     // A query row's sixteen subset minima lie in the four lanes of its column (lane & 15 of its sub-tile, one per kg), four each
     // (tile parity x row half): the two smallest of the four, joined across the lanes (xor 16, xor 32) as pairs. All four lanes end
-    // with the same two numbers, so lane 16 s + i keeps those of sub-tile s: every lane owns the row of the wave-block of its number,
-    // and the bounds are computed once for the 64 rows.
+    // with the same two numbers, so lane 16 s + i keeps those of sub-tile s of the wave-block: every lane owns the row of the
+    // wave-block of its number, and the bounds are computed once for the 64 rows.
+    constexpr int ROWS_WB = 32 * WB_TILES;
     const gint_t Asr = (gint_t)(Am2 + 32 * (size_t)A.ntiles);
     const int e_b = T > 0 ? ((gint_t)(Bm2 + 64 * (size_t)B.ntiles))[0] : 0;
-    uint4* rr = rowres + (size_t)p * row_stride + ROWS_WAVE * wb;
     const int lane_t = (int)((hb_wr - lds_addr(&sHb[0][0])) >> 2);   // (the lane, from what the sweep kept)
     constexpr unsigned PAD_V = 2u * PADH;
-    float v1 = BIGF, v2 = BIGF;
+    auto tail = [&](auto Hc) {
+        constexpr int H = decltype(Hc)::value;
+        const int wb = WBS * wv + H;
+        if (WB_TILES * wb >= A_tiles) return;   // wave-uniform
+        uint4* rr = rowres + (size_t)p * row_stride + ROWS_WB * wb;
+        float v1 = BIGF, v2 = BIGF;
 #pragma unroll
-    for (int s = 0; s < NQ; ++s) {
-        float m1 = BIGF, m2 = BIGF;
+        for (int s = 0; s < NQ / WBS; ++s) {
+            static_assert(screen::query16_block(NQ / WBS * H) == H, "the sub-tiles of wave-block H");
+            float m1 = BIGF, m2 = BIGF;
 #pragma unroll
-        for (int q = 0; q < 2; ++q)
+            for (int q = 0; q < 2; ++q)
 #pragma unroll
-            for (int u = 0; u < NU; ++u) {
-                const float mine = xm[q][s][u];
-                m2 = fminf(m2, fmaxf(m1, mine)), m1 = fminf(m1, mine);
+                for (int u = 0; u < NU; ++u) {
+                    const float mine = xm[q][NQ / WBS * H + s][u];
+                    m2 = fminf(m2, fmaxf(m1, mine)), m1 = fminf(m1, mine);
+                }
+#pragma unroll
+            for (int x = 16; x <= 32; x *= 2) {
+                const float o1 = __shfl_xor(m1, x), o2 = __shfl_xor(m2, x);   // two sorted pairs: min of the firsts, then the next
+                m2 = fminf(fmaxf(m1, o1), fminf(m2, o2)), m1 = fminf(m1, o1);
             }
-#pragma unroll
-        for (int x = 16; x <= 32; x *= 2) {
-            const float o1 = __shfl_xor(m1, x), o2 = __shfl_xor(m2, x);   // two sorted pairs: min of the firsts, then the next
-            m2 = fminf(fmaxf(m1, o1), fminf(m2, o2)), m1 = fminf(m1, o1);
+            if ((lane_t >> 4) == s) v1 = m1, v2 = m2;
         }
-        if ((lane_t >> 4) == s) v1 = m1, v2 = m2;
-    }
-    unsigned long long open_rows = 0;   // bit = row of the wave-block: that row goes to the exact pass
-    {
-        const int s = lane_t >> 5;      // the stored query tile of the row
-        const int j = ROWS_WAVE * wb + lane_t;
-        const float ma = Am2[j];
-        // a padding train row holds SCREEN_PAD or more, a subset that met no tile BIGF; real values stay below 2^21
-        const bool real_row = ma < 0.5f * SCREEN_PAD;
-        const bool real1 = real_row && v1 < 0.5f * SCREEN_PAD, real2 = real_row && v2 < 0.5f * SCREEN_PAD;
-        const unsigned pa = NSUB * wb + s >= A_even ? 1u : 0u;
-        const int s_a = Asr[j];
-        const unsigned n1 = real1 ? (unsigned)(2.0f * (v1 + ma)) : 0u, u = real2 ? (unsigned)(2.0f * (v2 + ma)) : 0u;
-        const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
-        const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
-        rr[lane_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
-        // match_rowpick_kernel's predicate on the two words just stored (a padding row carries 0xffffffff in the first)
-        const bool open = NSUB * wb + s < A_tiles && w1 < PAD_V && (w2 >= PAD_V || ratio_pass<METRIC>((int)(w1 + pa) - 2, (int)(w2 + pa) - 2, ratio));
-        open_rows = __ballot(open);
-    }
-    if (!openmask) return;   // (the debug entry: no list)
-    if (lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
-    // the wave's open rows go into its segment's region of the candidate list (the comment above match_openprep_kernel)
-    const int c = __popcll(open_rows);
-    if (c == 0) return;      // wave-uniform: open_rows is a ballot
-    const int head = ol.seghead[p];
-    int pos = 0;
-    if (lane_t == 0) pos = atomicAdd(&ol.segcount[head], c);
-    pos = __shfl(pos, 0);
-    if ((open_rows >> lane_t) & 1)
-        ol.cands[(size_t)head * row_stride + pos + __popcll(open_rows & ((1ull << lane_t) - 1))] = make_uint2((unsigned)p, (unsigned)(ROWS_WAVE * wb + lane_t));
-    const int k = (pos + GATHER_WIDTH - 1) / GATHER_WIDTH;   // c <= 64: at most one multiple of the width in [pos, pos + c)
-    if (lane_t == 0 && GATHER_WIDTH * k < pos + c) ol.items[atomicAdd(ol.n_items, 1)] = make_int2(head, k);
+        unsigned long long open_rows = 0;   // bit = row of the wave-block: that row goes to the exact pass
+        {
+            const int s = lane_t >> 5;      // the stored query tile of the row
+            const int j = ROWS_WB * wb + lane_t;
+            const float ma = Am2[j];
+            // a padding train row holds SCREEN_PAD or more, a subset that met no tile BIGF; real values stay below 2^21
+            const bool real_row = ma < 0.5f * SCREEN_PAD;
+            const bool real1 = real_row && v1 < 0.5f * SCREEN_PAD, real2 = real_row && v2 < 0.5f * SCREEN_PAD;
+            const unsigned pa = WB_TILES * wb + s >= A_even ? 1u : 0u;
+            const int s_a = Asr[j];
+            const unsigned n1 = real1 ? (unsigned)(2.0f * (v1 + ma)) : 0u, u = real2 ? (unsigned)(2.0f * (v2 + ma)) : 0u;
+            const unsigned w1 = real1 ? (unsigned)screen::lower_d2(n1, s_a, e_b) - pa + 2u : 0xffffffffu;
+            const unsigned w2 = real2 ? (unsigned)screen::upper_d2(u, s_a, e_b) - pa + 2u : 0xffffffffu;
+            rr[lane_t] = make_uint4(w1, 0u, w2, real1 ? n1 : 0xffffffffu);
+            // match_rowpick_kernel's predicate on the two words just stored (a padding row carries 0xffffffff in the first)
+            const bool open = WB_TILES * wb + s < A_tiles && w1 < PAD_V && (w2 >= PAD_V || ratio_pass<METRIC>((int)(w1 + pa) - 2, (int)(w2 + pa) - 2, ratio));
+            open_rows = __ballot(open);
+        }
+        if (!openmask) return;   // (the debug entry: no list)
+        if (lane_t == 0) openmask[(size_t)p * mask_stride + wb] = open_rows;
+        // the wave-block's open rows go into its segment's region of the candidate list (the comment above match_openprep_kernel)
+        const int c = __popcll(open_rows);
+        if (c == 0) return;      // wave-uniform: open_rows is a ballot
+        const int head = ol.seghead[p];
+        int pos = 0;
+        if (lane_t == 0) pos = atomicAdd(&ol.segcount[head], c);
+        pos = __shfl(pos, 0);
+        if ((open_rows >> lane_t) & 1)
+            ol.cands[(size_t)head * row_stride + pos + __popcll(open_rows & ((1ull << lane_t) - 1))] = make_uint2((unsigned)p, (unsigned)(ROWS_WB * wb + lane_t));
+        const int k = (pos + GATHER_WIDTH - 1) / GATHER_WIDTH;   // c <= 64: at most one multiple of the width in [pos, pos + c)
+        if (lane_t == 0 && GATHER_WIDTH * k < pos + c) ol.items[atomicAdd(ol.n_items, 1)] = make_int2(head, k);
+    };
+    tail(std::integral_constant<int, 0>{});
+    tail(std::integral_constant<int, 1>{});
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2229,6 +2249,8 @@ struct MatchLaunch {
 // The row sweep, on st1. The full-column form sweeps with match_tile_kernel, the lean form with match_sweep_kernel: up to 128-D its
 // BOUND form (the sweep is bound by its epilogue's VALU work there) + an exact pass over the rows it could not finish; above, where
 // the matrix pipe binds, the rows are screened on the FP6 matrix cores (match_screen_kernel), the same exact pass behind
+// a workgroup of match_screen_kernel owns 512 query rows where the plan counts workgroups of 256
+static int screen_wgs_per_pair(const MatchPlan& pl) { return (pl.wgs_per_pair + 1) / 2; }
 template <int METRIC>
 static void launch_sweep(const MatchCall& c, const MatchLaunch& l) {
     const MatchPlan& pl = c.pl;
@@ -2236,8 +2258,8 @@ static void launch_sweep(const MatchCall& c, const MatchLaunch& l) {
     with_ks(c.ctx->ks_common, [&](auto ks) {
         constexpr int KS = decltype(ks)::value;
         if (c.screen_sweep)
-            match_screen_kernel<METRIC><<<l.nb * pl.wgs_per_pair, WG_THREADS, 0, c.st1>>>(
-                frames, l.pb, pl.wgs_per_pair, l.s.rowres, pl.row_stride, c.ratio, l.s.openmask, pl.mask_stride,
+            match_screen_kernel<METRIC><<<l.nb * screen_wgs_per_pair(pl), WG_THREADS, 0, c.st1>>>(
+                frames, l.pb, screen_wgs_per_pair(pl), l.s.rowres, pl.row_stride, c.ratio, l.s.openmask, pl.mask_stride,
                 OpenList{c.call.seghead + l.first, c.call.segcount + l.first, l.s.rowcand, l.s.items, c.call.launch_items + l.b});
         else if (pl.full_cols)
             match_tile_kernel<KS><<<l.nb * pl.wgs_per_pair * pl.col_chunks, WG_THREADS, 0, c.st1>>>(
@@ -2710,7 +2732,7 @@ int eacham_match_debug_screen_pair(eacham_ctx* ctx, int f1, int f2, uint32_t* n1
         IoDev d;
         rc = io.upload(d);
         if (rc) return rc;
-        match_screen_kernel<METRIC_L2><<<pl.wgs_per_pair, WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), pl.wgs_per_pair, rowres, pl.row_stride, 0.0, nullptr, 0,
+        match_screen_kernel<METRIC_L2><<<screen_wgs_per_pair(pl), WG_THREADS, 0, ctx->stream>>>(ctx->frame_table_dev, d(h_pair), screen_wgs_per_pair(pl), rowres, pl.row_stride, 0.0, nullptr, 0,
                                                                                         OpenList{});
         EACHAM_HIP_TRY(ctx, hipGetLastError());
         rc = io.finish();
