@@ -323,6 +323,7 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
         return EACHAM_ERR_HIP;
     };
     if (hipSetDevice(device_id) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) return bail();
+    if (hipDeviceGetAttribute(&ctx->cus, hipDeviceAttributeMultiprocessorCount, device_id) != hipSuccess || ctx->cus < 1) return bail();
     if (stream2_mode == 1 || stream2_mode == -1) {
         int prio_least = 0, prio_greatest = 0;
         if (hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest) != hipSuccess ||

@@ -120,6 +120,7 @@ struct ProfileSlot {
 
 struct eacham_ctx {
     int device = 0;
+    int cus = 256;   // compute units of the device (read at create): sizes the persistent grids that are a share of the chip
     hipStream_t stream = nullptr;
     hipStream_t stream2 = nullptr;   // finalize/compaction of batch i runs here beside the tile kernel of batch i+1
     hipEvent_t ev_tile[2] = {nullptr, nullptr}, ev_fin[2] = {nullptr, nullptr}, ev_join = nullptr;

@@ -187,6 +187,18 @@ EACHAM_PLAN_HD inline int launch_of(const LaunchCut& c, int i, int* start) {
     return c.n1 / c.len1 + (c.n2 - c.n1) / c.len2 + b;
 }
 
+// Workgroups of match_argmin_kernel (one wave each, persistent over an item list whose length only the device knows) for a launch of
+// nb pairs on a chip of `cus` CUs. 100 VGPRs: four of its waves fit a SIMD, sixteen a CU, and that round of the chip is what a launch
+// with the chip to itself gets (the job's last launch, a job of one launch, one stream). Beside the next launch's screen sweep it gets
+// half a round: its waves enter where a sweep workgroup retired (254 VGPRs on each of the CU's four SIMDs, room for eight of them)
+// and hold that slot until the list is done, so a full round can displace every sweep workgroup of the chip while the kernel, which
+// waits on gathered loads, is hardly faster for it: alone 323 us with sixteen waves per CU, 399 us with four (profiles/tail_placement.txt).
+inline int argmin_grid(int nb, int wgs_per_pair, int cus, bool beside_screen_sweep) {
+    const long long bound = std::max<long long>((long long)nb * wgs_per_pair, 1);
+    const long long cap = (long long)std::max(cus, 1) * (beside_screen_sweep ? 8 : 16);
+    return (int)std::min(bound, cap);
+}
+
 // Behind the slots, under the screen sweep: the arrays of the CALL that its candidate list needs (seghead | segcount | one item
 // counter per launch). Carved as ONE block of ints and indexed inside it: call_pairs is a multiple of 64 ints, so the three lie
 // where a carve each would put them, but the block ends with its last counter, not on the next 256 bytes (call_bytes).

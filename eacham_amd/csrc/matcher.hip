@@ -2244,6 +2244,7 @@ struct MatchLaunch {
     const int2* pb;
     int nb, first, b;
     int* cnt;
+    bool sweep_beside;   // the tail runs on the second stream beside the next launch's sweep
 };
 
 // The row sweep, on st1. The full-column form sweeps with match_tile_kernel, the lean form with match_sweep_kernel: up to 128-D its
@@ -2305,7 +2306,9 @@ static int launch_lean_tail(const MatchCall& c, const MatchLaunch& l) {
     int *n_items = &s.counters->n_items, *n_pre = &s.counters->n_pre, *n_aitems = &s.counters->n_aitems;
     // persistent workgroups over an item list (its length is only known on the device): one round of the chip
     const int vgrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 512);
-    const int agrid = std::min(std::max(nb * pl.wgs_per_pair, 1), 4096);   // one wave per item, persistent over the list
+    // one wave per item, persistent over the list: a round of the chip, half a round beside a screen sweep (argmin_grid, match_plan.hpp;
+    // the bound and exact forms keep the full round beside their sweeps: their lines are no faster with half, profiles/tail_placement.txt)
+    const int agrid = argmin_grid(nb, pl.wgs_per_pair, ctx->cus, c.screen_sweep && l.sweep_beside);
     EACHAM_HIP_TRY(ctx, hipMemsetAsync(s.counters, 0, sizeof(SlotCounters), st2));
     if (c.screen_sweep)   // the launch's open rows and items into the debug tally: off the sweeps' chain
         match_opentally_kernel<<<(nb + TALLY_THREADS - 1) / TALLY_THREADS, TALLY_THREADS, 0, st2>>>(c.call.seghead + l.first, c.call.segcount + l.first, nb,
@@ -2404,7 +2407,7 @@ static int run_match_metric(eacham_ctx* ctx, const int2* pairs_dev, int npairs, 
     for (int first = 0, nb = 0; first < npairs; first += nb, ++b) {
         nb = next_batch(pl, b, first, npairs);
         const int slot = b % pl.slots;
-        const MatchLaunch l{pl.slot(ctx->ws, slot), pairs_dev + first, nb, first, b, counts_dev + first};
+        const MatchLaunch l{pl.slot(ctx->ws, slot), pairs_dev + first, nb, first, b, counts_dev + first, st2 != st1 && first + nb < npairs};
         if (b >= pl.slots) EACHAM_HIP_TRY(ctx, hipStreamWaitEvent(st1, ctx->ev_fin[slot], 0));  // slot free again
         {
             ProfileScope ps(ctx, EACHAM_KERNEL_MATCH_TILE, st1);
