@@ -116,6 +116,12 @@ def lib() -> C.CDLL:
     L.eacham_solve_pnp.argtypes = [vp, i32, vp, vp, vp, i32, i32, vp, vp, vp]
     if hasattr(L, "eacham_lmeds_batch"):  # (absent from older builds selected with EACHAM_HIP_LIB; calling it on one raises AttributeError)
         L.eacham_lmeds_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "eacham_ransac_batch"):  # (likewise)
+        L.eacham_ransac_batch.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp, vp, f32, dbl, i32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "eacham_ransac_debug_last"):  # (likewise)
+        L.eacham_ransac_debug_last.argtypes = [vp, C.POINTER(i64), C.POINTER(dbl)]
+    if hasattr(L, "eacham_graph_verify_ransac"):  # (likewise)
+        L.eacham_graph_verify_ransac.argtypes = [vp, i32, vp, i32, i32, vp, i32, f32, dbl, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "eacham_two_view_batch"):  # (likewise)
         L.eacham_two_view_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, dbl, i32, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "eacham_pnp_hypotheses_batch"):  # (likewise)

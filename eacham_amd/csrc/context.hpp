@@ -184,6 +184,10 @@ struct eacham_ctx {
     // its cap, the read-backs of device words it made, and (profiling on) the device time between its upload and its copies back
     int tracks_rounds = 0, tracks_round_cap = 0, tracks_readbacks = 0;
     float tracks_ms = -1.f;
+    // the last threshold-RANSAC call (ransac_batch.hip; eacham_ransac_debug_last): the samples it solved over both passes and the host
+    // milliseconds it spent building the budget rows
+    long long ransac_solved = 0;
+    double ransac_table_ms = 0.0;
 
     // profiling
     bool profile = false;

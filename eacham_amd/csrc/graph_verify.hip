@@ -19,16 +19,22 @@
 //   gv_scatter_mask     the mask byte of packed match k of edge e to src_offsets[e] + k: the index space of the q / t the graph was made
 //                       from, which is what eacham_graph_tracks takes as `keep` (bytes that belong to no pair: zero)
 //
+// eacham_graph_verify_ransac is the same call with ransac_launch (ransac_batch.hip: threshold RANSAC in two passes) in lmeds_launch's
+// place: the checks, the gather, both draws, the packed sample list, the read-back below, the scatter and `retain` are ONE function,
+// gv_verify, which both entries hand their own staged arrays and their estimator's launch.
+//
 // READ-BACKS. The number of samples is known on the host — (pairs with n >= m) x iterations — except under the OpenCV stream for the
 // homography and the fundamental matrix, where checkSubset can make getSubset give up: then the total (8 bytes) is read back once through the pinned mirror.
 // The scratch is sized by the host-known bound either way; the launches cover exactly sample_ptr[npairs] samples.
 #include "context.hpp"
 #include "devprim.hpp"
+#include "ransac_launch.hpp"
 #include "solve_launch.hpp"
 #include "../../include/eacham/CvSampling.hpp"
 
 #include <climits>
 #include <exception>
+#include <memory>
 
 namespace eacham {
 namespace {
@@ -174,105 +180,181 @@ extern "C" int eacham_graph_set_keypoints(eacham_graph* g, const double* xy) {
     });
 }
 
+// What both verifications share, around the estimator of the call: the checks, the gather, the draw, the packed sample list, the
+// read-back of the sample total where only the device knows it, then — behind `launch` — the mask's scatter into the caller's match
+// index space and `retain`. declare(io, plan): the estimator's own staged arrays, before the upload; launch(d, plan, GvDev): its
+// kernels on the device arrays.
+struct GvDev {   // what gv_verify prepared on the device, as the estimator's launch finds it
+    long long S;                           // the samples sample_ptr[npairs] names
+    const double *a, *b, *K;               // gathered points (packed pair order), the staged K
+    const long long* sample_ptr;
+    const int* sample_idx;
+    unsigned char* packed_mask;            // the estimator's mask output: a byte per packed match
+    long long *total, *total_host;         // a device word and its pinned mirror, free for the estimator's own 8-byte read-backs
+};
+struct GvPlan {
+    int kind, P, m, maxm, iterations;
+    long long n_ok, max_n, NP, S_cap, slots;   // pairs with >= m matches, the largest of them, matches, n_ok x iterations, P x iterations
+    bool count_known;                          // every pair with >= m matches has exactly `iterations` samples
+};
+template <class Declare, class Launch>
+int gv_verify(eacham_graph* g, const char* what, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
+              uint8_t* masks, int32_t* n_samples, int32_t* samples, Declare declare, Launch launch) {
+    eacham_ctx* ctx = g->ctx;
+    if (!g->has_xy) return ctx->fail(EACHAM_ERR_INVALID, "%s: the graph has no keypoint coordinates (eacham_graph_set_keypoints)", what);
+    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: unknown kind %d", what, kind);
+    if (sampling != EACHAM_SAMPLING_OPENCV && sampling != EACHAM_SAMPLING_COUNTER)
+        return ctx->fail(EACHAM_ERR_INVALID, "%s: unknown sampling %d", what, sampling);
+    if (iterations < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative iterations", what);
+    const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4, fundamental = kind == EACHAM_SOLVE_FUNDAMENTAL7;
+    const int P = g->npairs, m = solve_sample_size(kind), maxm = solve_max_models(kind);
+    if (P == 0) return EACHAM_OK;
+    long long n_ok = 0, max_n = 0;   // pairs with a minimal sample's worth of matches; the largest of them
+    for (int p = 0; p < P; ++p)
+        if (g->pair_counts_h[p] >= m) ++n_ok, max_n = std::max<long long>(max_n, g->pair_counts_h[p]);
+    const long long NP = g->n_matches, S_cap = n_ok * iterations, slots = (long long)P * iterations;
+    if (NP > INT_MAX / 2 || P == INT_MAX || slots * m > INT_MAX || S_cap * maxm > INT_MAX)
+        return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %lld points / %d pairs x %d samples in one call", what, NP, P, iterations);
+    EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (retain && !g->keep_mask) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->keep_mask, std::max<size_t>((size_t)g->n_src, 16)));
+    const GvPlan plan{kind, P, m, maxm, iterations, n_ok, max_n, NP, S_cap, slots, !((homography || fundamental) && sampling == EACHAM_SAMPLING_OPENCV)};
+    hipStream_t st = ctx->stream;
+    IoStage io(ctx, st);
+    const auto h_total = io.out<long long>(nullptr, 1);   // first: offset 0, always inside the pinned mirror
+    const auto h_ons = io.out<int>(n_samples, (size_t)P), h_osamp = io.out<int>(samples, (size_t)slots * m);
+    const auto h_omask = io.out<unsigned char>(masks, (size_t)g->n_src);
+    const auto h_K = io.in<double>(K, 4);
+    const auto h_seeds = io.in<unsigned long long>(seeds, (size_t)P);
+    const auto h_a = io.scratch<double2>((size_t)NP), h_b = io.scratch<double2>((size_t)NP);
+    const auto h_cnt = io.scratch<long long>((size_t)P + 1), h_sp = io.scratch<long long>((size_t)P + 1);
+    const auto h_spws = io.scratch<long long>(prim::scan_ws_elems((size_t)P + 1));
+    const auto h_i = io.scratch<int>((size_t)S_cap * m);
+    const auto h_pmask = io.scratch<unsigned char>((size_t)NP);
+    declare(io, plan);
+    IoDev d;
+    if (int rc = io.upload(d)) return rc;
+    const double* d_a = (const double*)d(h_a);
+    const double* d_b = (const double*)d(h_b);
+    {   // (profiling: the gather, the draws and the mask's scatter count with the scorer's stage, as the estimators' kernels do)
+        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+        if (NP > 0)
+            gv_gather_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->pairs, g->n_edges, g->offsets, g->q, g->t, g->kp_offsets, (const double2*)g->xy,
+                                                               d(h_a), d(h_b));
+        if (sampling == EACHAM_SAMPLING_COUNTER) {
+            const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
+            const unsigned long long* d_seeds = seeds ? d(h_seeds) : nullptr;
+            if (homography) gv_draw_counter_kernel<4><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+            else if (fundamental) gv_draw_counter_kernel<7><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+            else gv_draw_counter_kernel<5><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
+        } else {
+            const unsigned grid = gv_blocks(P, GV_PAIR);
+            if (homography) gv_draw_opencv_kernel<4, 1><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+            else if (fundamental) gv_draw_opencv_kernel<7, 2><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+            else gv_draw_opencv_kernel<5, 0><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
+        }
+        prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
+        if (slots > 0) {
+            if (homography) gv_compact_kernel<4><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+            else if (fundamental) gv_compact_kernel<7><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+            else gv_compact_kernel<5><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+        }
+    }
+    EACHAM_HIP_TRY(ctx, hipGetLastError());
+    long long S = S_cap;
+    long long* total_host = (long long*)((char*)ctx->io_host + io.lay.off[h_total.k]);
+    if (!plan.count_known) {
+        EACHAM_HIP_TRY(ctx, hipMemcpyAsync(total_host, d(h_total), sizeof(long long), hipMemcpyDeviceToHost, st));
+        EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
+        S = *(volatile const long long*)total_host;
+        if (S < 0 || S > S_cap) return ctx->fail(EACHAM_ERR_HIP, "%s: %lld samples drawn, at most %lld possible", what, S, S_cap);
+    }
+    if (int rc = launch(d, plan, GvDev{S, d_a, d_b, d(h_K), d(h_sp), d(h_i), d(h_pmask), d(h_total), total_host})) return rc;
+    {
+        ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
+        if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemsetAsync(d(h_omask), 0, (size_t)g->n_src, st));
+        if (NP > 0) gv_scatter_mask_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->n_edges, g->offsets, g->src_offsets, d(h_pmask), d(h_omask));
+        EACHAM_HIP_TRY(ctx, hipGetLastError());
+        if (retain) {
+            g->has_keep = false;
+            if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(g->keep_mask, d(h_omask), (size_t)g->n_src, hipMemcpyDeviceToDevice, st));
+        }
+    }
+    if (int rc = io.finish()) return rc;
+    if (retain) g->has_keep = true;
+    return EACHAM_OK;
+}
+
 extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
                                    double* models, float* medians, float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner,
                                    int32_t* n_candidates, int32_t* n_samples, int32_t* samples) {
     if (!g) return EACHAM_ERR_INVALID;
     eacham_ctx* ctx = g->ctx;
     return verify_entry(ctx, "graph_verify", [&]() -> int {
-        if (!g->has_xy) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: the graph has no keypoint coordinates (eacham_graph_set_keypoints)");
-        if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
-            return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown kind %d", kind);
-        if (sampling != EACHAM_SAMPLING_OPENCV && sampling != EACHAM_SAMPLING_COUNTER)
-            return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: unknown sampling %d", sampling);
-        if (iterations < 0) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify: negative iterations");
-        const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4, fundamental = kind == EACHAM_SOLVE_FUNDAMENTAL7;
-        const int P = g->npairs, m = solve_sample_size(kind), maxm = solve_max_models(kind);
-        if (P == 0) return EACHAM_OK;
-        long long n_ok = 0, max_n = 0;   // pairs with a minimal sample's worth of matches; the largest of them
-        for (int p = 0; p < P; ++p)
-            if (g->pair_counts_h[p] >= m) ++n_ok, max_n = std::max<long long>(max_n, g->pair_counts_h[p]);
-        const long long NP = g->n_matches, S_cap = n_ok * iterations, slots = (long long)P * iterations;
-        if (NP > INT_MAX / 2 || P == INT_MAX || slots * m > INT_MAX || S_cap * maxm > INT_MAX)
-            return ctx->fail(EACHAM_ERR_CAPACITY, "graph_verify: %lld points / %d pairs x %d samples in one call", NP, P, iterations);
-        EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if (retain && !g->keep_mask) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->keep_mask, std::max<size_t>((size_t)g->n_src, 16)));
-        const bool need_rows = lmeds_needs_rows(max_n), count_known = !((homography || fundamental) && sampling == EACHAM_SAMPLING_OPENCV);
-        const long long cand_cap = S_cap * maxm;
-        const int score_grid = lmeds_score_grid(cand_cap, max_n);
-        hipStream_t st = ctx->stream;
-        IoStage io(ctx, st);
-        const auto h_total = io.out<long long>(nullptr, 1);   // first: offset 0, always inside the pinned mirror
-        const auto h_om = io.out<double>(models, 9 * (size_t)P);
-        const auto h_omed = io.out<float>(medians, (size_t)P), h_othr = io.out<float>(thresholds, (size_t)P);
-        const auto h_oinl = io.out<int>(inliers, (size_t)P), h_owin = io.out<int>(winner, 3 * (size_t)P), h_onc = io.out<int>(n_candidates, (size_t)P);
-        const auto h_ons = io.out<int>(n_samples, (size_t)P), h_osamp = io.out<int>(samples, (size_t)slots * m);
-        const auto h_omask = io.out<unsigned char>(masks, (size_t)g->n_src);
-        const auto h_K = io.in<double>(K, 4);
-        const auto h_seeds = io.in<unsigned long long>(seeds, (size_t)P);
-        const auto h_a = io.scratch<double2>((size_t)NP), h_b = io.scratch<double2>((size_t)NP);
-        const auto h_cnt = io.scratch<long long>((size_t)P + 1), h_sp = io.scratch<long long>((size_t)P + 1);
-        const auto h_spws = io.scratch<long long>(prim::scan_ws_elems((size_t)P + 1));
-        const auto h_i = io.scratch<int>((size_t)S_cap * m);
-        const auto h_m = io.scratch<double>(9 * (size_t)cand_cap);
-        const auto h_n = io.scratch<int>((size_t)S_cap), h_first = io.scratch<int>((size_t)S_cap), h_sprob = io.scratch<int>((size_t)S_cap);
-        const auto h_tot = io.scratch<int>(1), h_ws = io.scratch<int>(prim::scan_ws_elems((size_t)S_cap));
-        const auto h_cmed = io.scratch<float>((size_t)cand_cap);
-        const auto h_rows = io.scratch<float>(need_rows ? (size_t)score_grid * (size_t)max_n : 0);
-        const auto h_pmask = io.scratch<unsigned char>((size_t)NP);
-        IoDev d;
-        if (int rc = io.upload(d)) return rc;
-        const double* d_a = (const double*)d(h_a);
-        const double* d_b = (const double*)d(h_b);
-        {   // (profiling: the gather, the draws and the mask's scatter count with the scorer's stage, as the LMedS kernels do)
-            ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
-            if (NP > 0)
-                gv_gather_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->pairs, g->n_edges, g->offsets, g->q, g->t, g->kp_offsets, (const double2*)g->xy,
-                                                                   d(h_a), d(h_b));
-            if (sampling == EACHAM_SAMPLING_COUNTER) {
-                const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
-                const unsigned long long* d_seeds = seeds ? d(h_seeds) : nullptr;
-                if (homography) gv_draw_counter_kernel<4><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-                else if (fundamental) gv_draw_counter_kernel<7><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-                else gv_draw_counter_kernel<5><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-            } else {
-                const unsigned grid = gv_blocks(P, GV_PAIR);
-                if (homography) gv_draw_opencv_kernel<4, 1><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-                else if (fundamental) gv_draw_opencv_kernel<7, 2><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-                else gv_draw_opencv_kernel<5, 0><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-            }
-            prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
-            if (slots > 0) {
-                if (homography) gv_compact_kernel<4><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-                else if (fundamental) gv_compact_kernel<7><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-                else gv_compact_kernel<5><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-            }
-        }
-        EACHAM_HIP_TRY(ctx, hipGetLastError());
-        long long S = S_cap;
-        if (!count_known) {
-            const size_t at = io.lay.off[h_total.k];
-            EACHAM_HIP_TRY(ctx, hipMemcpyAsync((char*)ctx->io_host + at, d(h_total), sizeof(long long), hipMemcpyDeviceToHost, st));
-            EACHAM_HIP_TRY(ctx, hipStreamSynchronize(st));
-            S = *(volatile const long long*)((char*)ctx->io_host + at);
-            if (S < 0 || S > S_cap) return ctx->fail(EACHAM_ERR_HIP, "graph_verify: %lld samples drawn, at most %lld possible", S, S_cap);
-        }
-        const LmedsLaunch L{kind, P, S, max_n, score_grid, g->pair_ptr, d(h_sp), d_a, d_b, d(h_K), K != nullptr, d(h_i),
-                            d(h_m), d(h_n), d(h_first), d(h_sprob), d(h_tot), d(h_ws), d(h_cmed), d(h_rows),
-                            d(h_om), d(h_omed), d(h_othr), d(h_oinl), d(h_pmask), d(h_owin), d(h_onc)};
-        if (int rc = lmeds_launch(ctx, st, L)) return rc;
-        {
-            ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
-            if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemsetAsync(d(h_omask), 0, (size_t)g->n_src, st));
-            if (NP > 0) gv_scatter_mask_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->n_edges, g->offsets, g->src_offsets, d(h_pmask), d(h_omask));
-            EACHAM_HIP_TRY(ctx, hipGetLastError());
-            if (retain) {
-                g->has_keep = false;
-                if (g->n_src > 0) EACHAM_HIP_TRY(ctx, hipMemcpyAsync(g->keep_mask, d(h_omask), (size_t)g->n_src, hipMemcpyDeviceToDevice, st));
-            }
-        }
-        if (int rc = io.finish()) return rc;
-        if (retain) g->has_keep = true;
-        return EACHAM_OK;
+        IoArray<double> h_om{}, h_m{};
+        IoArray<float> h_omed{}, h_othr{}, h_cmed{}, h_rows{};
+        IoArray<int> h_oinl{}, h_owin{}, h_onc{}, h_n{}, h_first{}, h_sprob{}, h_tot{}, h_ws{};
+        int score_grid = 1;
+        return gv_verify(
+            g, "graph_verify", kind, K, sampling, iterations, seeds, retain, masks, n_samples, samples,
+            [&](IoStage& io, const GvPlan& pl) {
+                const size_t P = (size_t)pl.P;
+                const long long cand_cap = pl.S_cap * pl.maxm;
+                score_grid = lmeds_score_grid(cand_cap, pl.max_n);
+                h_om = io.out<double>(models, 9 * P);
+                h_omed = io.out<float>(medians, P), h_othr = io.out<float>(thresholds, P);
+                h_oinl = io.out<int>(inliers, P), h_owin = io.out<int>(winner, 3 * P), h_onc = io.out<int>(n_candidates, P);
+                h_m = io.scratch<double>(9 * (size_t)cand_cap);
+                h_n = io.scratch<int>((size_t)pl.S_cap), h_first = io.scratch<int>((size_t)pl.S_cap), h_sprob = io.scratch<int>((size_t)pl.S_cap);
+                h_tot = io.scratch<int>(1), h_ws = io.scratch<int>(prim::scan_ws_elems((size_t)pl.S_cap));
+                h_cmed = io.scratch<float>((size_t)cand_cap);
+                h_rows = io.scratch<float>(lmeds_needs_rows(pl.max_n) ? (size_t)score_grid * (size_t)pl.max_n : 0);
+            },
+            [&](const IoDev& d, const GvPlan& pl, const GvDev& v) -> int {
+                const LmedsLaunch L{kind, pl.P, v.S, pl.max_n, score_grid, g->pair_ptr, v.sample_ptr, v.a, v.b, v.K, K != nullptr, v.sample_idx,
+                                    d(h_m), d(h_n), d(h_first), d(h_sprob), d(h_tot), d(h_ws), d(h_cmed), d(h_rows),
+                                    d(h_om), d(h_omed), d(h_othr), d(h_oinl), v.packed_mask, d(h_owin), d(h_onc)};
+                return lmeds_launch(ctx, ctx->stream, L);
+            });
+    });
+}
+
+extern "C" int eacham_graph_verify_ransac(eacham_graph* g, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
+                                          float threshold, double confidence, int stage1, double* models, int32_t* inliers, uint8_t* masks,
+                                          int32_t* winner, int32_t* n_candidates, int32_t* n_used, int32_t* n_samples, int32_t* samples) {
+    if (!g) return EACHAM_ERR_INVALID;
+    eacham_ctx* ctx = g->ctx;
+    return verify_entry(ctx, "graph_verify_ransac", [&]() -> int {
+        if (!(threshold >= 0.f)) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify_ransac: the threshold is negative or not a number");
+        if (!(confidence > 0.0 && confidence < 1.0)) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify_ransac: confidence outside (0, 1)");
+        if (stage1 < 0) return ctx->fail(EACHAM_ERR_INVALID, "graph_verify_ransac: negative stage1");
+        if (stage1 == 0) stage1 = ransac_default_stage1();
+        IoArray<double> h_om{};
+        IoArray<int> h_oinl{}, h_owin{}, h_onc{}, h_onu{}, h_toff{}, h_tab{};
+        std::vector<int> tab_off, table;
+        std::unique_ptr<RansacScratch> sc;
+        bool single = false;
+        long long S1_cap = 0;
+        return gv_verify(
+            g, "graph_verify_ransac", kind, K, sampling, iterations, seeds, retain, masks, n_samples, samples,
+            [&](IoStage& io, const GvPlan& pl) {
+                const size_t P = (size_t)pl.P;
+                single = stage1 >= pl.iterations;
+                S1_cap = single ? pl.S_cap : pl.n_ok * stage1;   // (the budget rows are built here, on the host: the pairs' match counts are known)
+                ransac_build_table(ctx, confidence, pl.m, std::max(pl.iterations, 1), g->pair_counts_h.data(), pl.P, tab_off, table);
+                h_om = io.out<double>(models, 9 * P);
+                h_oinl = io.out<int>(inliers, P), h_owin = io.out<int>(winner, 3 * P), h_onc = io.out<int>(n_candidates, P), h_onu = io.out<int>(n_used, P);
+                h_toff = io.in<int>(tab_off.data(), P), h_tab = io.in<int>(table.data(), table.size());
+                sc.reset(new RansacScratch(io, pl.P, S1_cap, pl.m, pl.maxm, single));
+            },
+            [&](const IoDev& d, const GvPlan& pl, const GvDev& v) -> int {
+                RansacLaunch L{kind, pl.P, single ? v.S : S1_cap, stage1, single, threshold, g->pair_ptr, v.sample_ptr, v.a, v.b, v.K, K != nullptr, v.sample_idx,
+                               d(h_toff), d(h_tab)};
+                sc->bind(L, d);
+                L.s1_known = single || pl.count_known;
+                L.total2 = v.total, L.total2_host = v.total_host;
+                L.models = d(h_om), L.inliers = d(h_oinl), L.masks = v.packed_mask, L.winner = d(h_owin), L.n_candidates = d(h_onc), L.n_used = d(h_onu);
+                return ransac_launch(ctx, ctx->stream, L);
+            });
     });
 }

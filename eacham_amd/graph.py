@@ -65,6 +65,18 @@ class GraphVerify(NamedTuple):
     samples: np.ndarray | None  # [npairs, iterations, m] int32, -1 behind a pair's n_samples (want_samples)
 
 
+class GraphVerifyRansac(NamedTuple):
+    """eacham_graph_verify_ransac: the RansacBatch fields per caller pair, the mask in the caller's match index space, the samples drawn."""
+    models: np.ndarray        # [npairs, 9] float64: the winning model as solved (zeros: none)
+    inliers: np.ndarray       # [npairs] int32
+    masks: np.ndarray         # [n_src] uint8, indexed like the q / t the graph was made from
+    winner: np.ndarray        # [npairs, 3] int32: candidate, sample, root (-1 -1 -1: none)
+    n_candidates: np.ndarray  # [npairs] int32: candidates of the consumed samples
+    n_used: np.ndarray        # [npairs] int32: samples consumed
+    n_samples: np.ndarray     # [npairs] int32: the samples each pair drew
+    samples: np.ndarray | None  # [npairs, iterations, m] int32, -1 behind a pair's n_samples (want_samples)
+
+
 def lmeds_iterations(kind: str, max_iters: int | None = None, confidence: float | None = None) -> int:
     """The samples LMeDSPointSetRegistrator::run asks for, as twoview_detail::lmeds computes them: RANSACUpdateNumIters at an
     assumed outlier ratio of 0.45, at least 3, at most max_iters. Defaults: the reference's calls (essential 1000 / 0.99 -> 89,
@@ -150,6 +162,32 @@ class ResidentGraph:
             self._h, k, ptr(K4), sampling, its, ptr(sd), int(bool(retain)), ptr(models), ptr(med), ptr(thr), ptr(inl), ptr(masks), ptr(win),
             ptr(nc), ptr(ns), ptr(samples)))
         return GraphVerify(models, med, thr, inl, masks, win, nc, ns, samples)
+
+    def verify_ransac(self, kind: str, threshold: float, confidence: float, iterations: int, K=None, sampling: str = "opencv", seeds=None,
+                      retain: bool = False, want_samples: bool = False, stage1: int = 0) -> GraphVerifyRansac:
+        """eacham_graph_verify_ransac: threshold RANSAC (eacham_amd/ransac.py) for every pair of the graph, gathered, sampled and solved
+        on the device. threshold: squared, in the error's units; iterations: the samples drawn per pair (maxIters); stage1: 0 = the
+        library's default. retain=True keeps the mask on the device for tracks_verified()."""
+        from . import capi
+        homography, fundamental = kind.startswith("homography"), kind.startswith("fundamental")
+        if not homography and not fundamental and not kind.startswith("essential"):
+            raise ValueError(f"unknown kind {kind!r}")
+        k, m = (capi.SOLVE_HOMOGRAPHY4, 4) if homography else ((capi.SOLVE_FUNDAMENTAL7, 7) if fundamental else (capi.SOLVE_ESSENTIAL5, 5))
+        P, its = self._npairs, int(iterations)
+        K4 = None if K is None else np.ascontiguousarray(K, dtype=np.float64).reshape(4)
+        sd = None if seeds is None else np.ascontiguousarray(seeds, dtype=np.uint64)
+        if sd is not None and sd.size != P:
+            raise ValueError("one seed per pair")
+        models = np.zeros((P, 9), dtype=np.float64)
+        inl, nc, nu, ns = (np.zeros(P, dtype=np.int32) for _ in range(4))
+        win = np.zeros((P, 3), dtype=np.int32)
+        masks = np.zeros(self._n_src, dtype=np.uint8)
+        samples = np.zeros((P, max(its, 0), m), dtype=np.int32) if want_samples else None
+        ptr = lambda a: None if a is None or a.size == 0 else a.ctypes.data   # noqa: E731
+        self.ctx._check(self.ctx._L.eacham_graph_verify_ransac(
+            self._h, k, ptr(K4), SAMPLINGS[sampling], its, ptr(sd), int(bool(retain)), float(threshold), float(confidence), int(stage1),
+            ptr(models), ptr(inl), ptr(masks), ptr(win), ptr(nc), ptr(nu), ptr(ns), ptr(samples)))
+        return GraphVerifyRansac(models, inl, masks, win, nc, nu, ns, samples)
 
     def tracks_verified(self, min_len: int = 2, conflict_policy: int = 0, cap_obs=None, cap_tracks=None):
         """eacham_graph_tracks_verified: tracks() with the mask the last verify(retain=True) left on the device; nothing is uploaded."""

@@ -357,6 +357,11 @@ class HipContext:
         from . import lmeds
         return lmeds.lmeds_batch(self, kind, uv1, uv2, samples, K)
 
+    def ransac_batch(self, kind: str, uv1, uv2, samples, threshold: float, confidence: float, stage1: int = 0, K=None):
+        """eacham_ransac_batch: threshold RANSAC two-view estimation of a list of pairs in one call (eacham_amd/ransac.py)."""
+        from . import ransac
+        return ransac.ransac_batch(self, kind, uv1, uv2, samples, threshold, confidence, stage1, K)
+
     def two_view_batch(self, uv1, uv2, K, rules, transforms, max_repr_error: float, min_tri_angle: float, in_mask=None,
                        distance_thresh: float = 50.0, min_solution_matches: int = 20):
         """eacham_two_view_batch: candidate poses -> the winner and its kept points, for a list of pairs in one call (eacham_amd/twoview.py)."""

@@ -33,6 +33,7 @@
 #include <vector>
 
 #include "CvSampling.hpp"
+#include "RansacIters.hpp"
 #include "TriangulatorHip.hpp"
 
 namespace eacham {
@@ -131,17 +132,7 @@ struct LmedsTrace {
     Mat3 winner{};
 };
 
-// RANSACUpdateNumIters (ptsetreg.cpp): iterations after which a sample of m inliers has been drawn with probability p at
-// outlier ratio ep, capped by maxIters
-inline int ransac_update_num_iters(double p, double ep, int m, int maxIters) {
-    p = std::min(std::max(p, 0.0), 1.0);
-    ep = std::min(std::max(ep, 0.0), 1.0);
-    const double num = std::max(1.0 - p, std::numeric_limits<double>::min());
-    const double denom = 1.0 - std::pow(1.0 - ep, m);
-    if (denom < std::numeric_limits<double>::min()) return 0;
-    const double ln = std::log(num), ld = std::log(denom);
-    return ld >= 0 || -ln >= maxIters * (-ld) ? maxIters : (int)std::lround(ln / ld);
-}
+// ransac_update_num_iters (RANSACUpdateNumIters of ptsetreg.cpp): RansacIters.hpp
 
 // the LMedS loop: solve all samples, score all models, keep the smallest median, classify by sigma.
 // LMeDSPointSetRegistrator::run fixes its iteration count up front from the confidence at an assumed outlier ratio of 0.45
@@ -527,6 +518,129 @@ inline std::vector<RobustModel> FindHomographyBatch(Context& ctx, const std::vec
                                                     const std::vector<std::vector<double>>& uv2, int maxIters = 100, double confidence = 0.999,
                                                     Sampling sampling = Sampling::OpenCV, std::vector<LmedsTrace>* traces = nullptr) {
     return FindHomographyBatch(ctx, uv1, uv2, std::vector<uint64_t>(uv1.size(), 12345), maxIters, confidence, sampling, traces);
+}
+
+// ---- threshold RANSAC (cv::RANSAC, the default method of cv::findHomography / findEssentialMat / findFundamentalMat) --------------
+// One eacham_ransac_batch call for a list of pairs: per pair the registrator's own stream (lmeds_samples: cv::RNG((uint64)-1),
+// getSubset, the kind's checkSubset) drawn for the FULL maxIters, the device solves and counts only what every pair's budget asks
+// for. RobustModel: model = the winner as solved, mask / inliers = its errors against the threshold, iterations = the samples the
+// loop consumed (n_used), median stays NaN, ok = a model with more than m - 1 inliers was found.
+// n == m: RANSACPointSetRegistrator::run does not loop — the minimal solver's first model on all points, every point an inlier
+// (from memory of the 4.5.5 sources). eacham_ransac_batch does not special-case it; this adapter does, on the host.
+namespace twoview_detail {
+
+// The registrator's n == m shortcut: the minimal solver on all m points in their order, its first model, every point an inlier, no loop.
+inline RobustModel ransac_all_points(Context& ctx, int solve_kind, int m, const std::vector<double>& uv1, const std::vector<double>& uv2, const double* K4) {
+    RobustModel r;
+    std::vector<int32_t> all(m);
+    for (int k = 0; k < m; ++k) all[k] = k;
+    std::vector<double> models((size_t)(solve_kind == EACHAM_SOLVE_ESSENTIAL5 ? 10 : (solve_kind == EACHAM_SOLVE_FUNDAMENTAL7 ? 3 : 1)) * 9);
+    int32_t count = 0;
+    ctx.check(eacham_solve_minimal(ctx.get(), solve_kind, m, uv1.data(), uv2.data(), K4, 1, all.data(), models.data(), &count));
+    if (count > 0) {
+        for (int e = 0; e < 9; ++e) r.model[e] = models[e];
+        r.mask.assign(m, 1), r.inliers = m, r.ok = true;
+    }
+    return r;
+}
+
+inline std::vector<RobustModel> ransac_batch(Context& ctx, int solve_kind, int m, const std::vector<std::vector<double>>& uv1,
+                                             const std::vector<std::vector<double>>& uv2, const double* K4, int maxIters, float threshold_sq,
+                                             double confidence, const std::vector<uint64_t>& seeds, Sampling sampling, int stage1 = 0) {
+    const size_t P = uv1.size();
+    std::vector<RobustModel> out(P);
+    if (uv2.size() != P) throw std::invalid_argument("ransac_batch: uv1 and uv2 list different numbers of pairs");
+    if (seeds.size() != P) throw std::invalid_argument("ransac_batch: one seed per pair");
+    if (P == 0) return out;
+    std::vector<int64_t> point_ptr(P + 1, 0), sample_ptr(P + 1, 0);
+    std::vector<double> a, b;
+    std::vector<int32_t> idx;
+    for (size_t p = 0; p < P; ++p) {
+        const int n = (int)(uv1[p].size() / 2);
+        if (n > m && uv2[p].size() == uv1[p].size() && maxIters > 0) {
+            const std::vector<int32_t> s = lmeds_samples(n, m, maxIters, subset_check_of(solve_kind), uv1[p], uv2[p], seeds[p], sampling);
+            a.insert(a.end(), uv1[p].begin(), uv1[p].begin() + 2 * (size_t)n);
+            b.insert(b.end(), uv2[p].begin(), uv2[p].begin() + 2 * (size_t)n);
+            idx.insert(idx.end(), s.begin(), s.end());
+        } else if (n == m && uv2[p].size() == uv1[p].size() && maxIters > 0) {
+            out[p] = ransac_all_points(ctx, solve_kind, m, uv1[p], uv2[p], K4);
+        }
+        point_ptr[p + 1] = (int64_t)(a.size() / 2);
+        sample_ptr[p + 1] = (int64_t)(idx.size() / m);
+    }
+    std::vector<double> models(P * 9);
+    std::vector<int32_t> inl(P), win(P * 3), ncand(P), used(P);
+    std::vector<uint8_t> masks(a.size() / 2 + 1);
+    a.resize(a.size() + 2), b.resize(b.size() + 2), idx.resize(idx.size() + 1);   // (no null data() for a list without points or samples)
+    ctx.check(eacham_ransac_batch(ctx.get(), solve_kind, (int)P, point_ptr.data(), a.data(), b.data(), K4, sample_ptr.data(), idx.data(), threshold_sq,
+                                  confidence, stage1, models.data(), inl.data(), masks.data(), win.data(), ncand.data(), used.data()));
+    for (size_t p = 0; p < P; ++p) {
+        if (point_ptr[p + 1] == point_ptr[p]) continue;   // not in the call: left as it is (the shortcut's answer, or nothing)
+        RobustModel& r = out[p];
+        r.iterations = used[p];
+        if (win[3 * p] < 0) continue;
+        for (int e = 0; e < 9; ++e) r.model[e] = models[9 * p + e];
+        r.mask.assign(masks.begin() + point_ptr[p], masks.begin() + point_ptr[p + 1]);
+        r.inliers = inl[p];
+        r.ok = true;
+    }
+    return out;
+}
+
+// the squared thresholds as OpenCV forms them: pixels; for the essential matrix divided by (fx + fy) / 2 first (findEssentialMat, from memory)
+inline float ransac_threshold_sq(double pixels, const double* K4) {
+    const double t = K4 ? pixels / ((K4[0] + K4[1]) / 2.0) : pixels;
+    return (float)(t * t);
+}
+
+}  // namespace twoview_detail
+
+// cv::findEssentialMat(pts1, pts2, K, cv::RANSAC, 0.999, 1.0, 1000, mask) for every pair of a list; K4 = fx fy cx cy shared (NULL:
+// normalised points, the threshold is taken as given).
+inline std::vector<RobustModel> FindEssentialMatRansacBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                            const std::vector<std::vector<double>>& uv2, const double* K4, double threshold = 1.0,
+                                                            double prob = 0.999, int maxIters = 1000, Sampling sampling = Sampling::OpenCV,
+                                                            const std::vector<uint64_t>& seeds = {}, int stage1 = 0) {
+    return twoview_detail::ransac_batch(ctx, EACHAM_SOLVE_ESSENTIAL5, 5, uv1, uv2, K4, maxIters, twoview_detail::ransac_threshold_sq(threshold, K4), prob,
+                                        seeds.empty() ? std::vector<uint64_t>(uv1.size(), 12345) : seeds, sampling, stage1);
+}
+// cv::findFundamentalMat(pts1, pts2, cv::FM_RANSAC, 3.0, 0.99, 1000, mask) for every pair of a list: pixels in, no K, no refit.
+inline std::vector<RobustModel> FindFundamentalMatRansacBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                              const std::vector<std::vector<double>>& uv2, double threshold = 3.0,
+                                                              double confidence = 0.99, int maxIters = 1000, Sampling sampling = Sampling::OpenCV,
+                                                              const std::vector<uint64_t>& seeds = {}, int stage1 = 0) {
+    return twoview_detail::ransac_batch(ctx, EACHAM_SOLVE_FUNDAMENTAL7, 7, uv1, uv2, nullptr, maxIters, twoview_detail::ransac_threshold_sq(threshold, nullptr),
+                                        confidence, seeds.empty() ? std::vector<uint64_t>(uv1.size(), 12345) : seeds, sampling, stage1);
+}
+// cv::findHomography(pts1, pts2, cv::RANSAC, 3.0, mask, 2000, 0.995) for every pair of a list, then the refit of FindHomography on the
+// winner's inliers (the mask stays the winner's).
+inline std::vector<RobustModel> FindHomographyRansacBatch(Context& ctx, const std::vector<std::vector<double>>& uv1,
+                                                          const std::vector<std::vector<double>>& uv2, double threshold = 3.0, int maxIters = 2000,
+                                                          double confidence = 0.995, Sampling sampling = Sampling::OpenCV,
+                                                          const std::vector<uint64_t>& seeds = {}, int stage1 = 0) {
+    std::vector<RobustModel> r = twoview_detail::ransac_batch(ctx, EACHAM_SOLVE_HOMOGRAPHY4, 4, uv1, uv2, nullptr, maxIters,
+                                                              twoview_detail::ransac_threshold_sq(threshold, nullptr), confidence,
+                                                              seeds.empty() ? std::vector<uint64_t>(uv1.size(), 12345) : seeds, sampling, stage1);
+    for (size_t p = 0; p < r.size(); ++p)
+        if (r[p].ok && uv1[p].size() / 2 > 4) {
+            Mat3 H;
+            if (RefitHomography(uv1[p], uv2[p], r[p].mask, H)) r[p].model = H;
+        }
+    return r;
+}
+// The single-pair forms: the batch form with one problem.
+inline RobustModel FindEssentialMatRansac(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, const double* K4,
+                                          double threshold = 1.0, double prob = 0.999, int maxIters = 1000, Sampling sampling = Sampling::OpenCV,
+                                          uint64_t seed = 12345) {
+    return FindEssentialMatRansacBatch(ctx, {uv1}, {uv2}, K4, threshold, prob, maxIters, sampling, {seed})[0];
+}
+inline RobustModel FindFundamentalMatRansac(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, double threshold = 3.0,
+                                            double confidence = 0.99, int maxIters = 1000, Sampling sampling = Sampling::OpenCV, uint64_t seed = 12345) {
+    return FindFundamentalMatRansacBatch(ctx, {uv1}, {uv2}, threshold, confidence, maxIters, sampling, {seed})[0];
+}
+inline RobustModel FindHomographyRansac(Context& ctx, const std::vector<double>& uv1, const std::vector<double>& uv2, double threshold = 3.0,
+                                        int maxIters = 2000, double confidence = 0.995, Sampling sampling = Sampling::OpenCV, uint64_t seed = 12345) {
+    return FindHomographyRansacBatch(ctx, {uv1}, {uv2}, threshold, maxIters, confidence, sampling, {seed})[0];
 }
 
 // cv::decomposeEssentialMat: E = U diag(1, 1, 0) V^T -> R1 = U W V^T, R2 = U W^T V^T, t = U[:, 2] (|t| = 1)

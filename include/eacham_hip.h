@@ -577,6 +577,43 @@ int eacham_lmeds_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t*
                        const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, double* models, float* medians,
                        float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates);
 
+/* ---- Threshold RANSAC two-view estimation for a whole list of pairs -------------------------------------------------
+ * cv::findEssentialMat / cv::findHomography / cv::findFundamentalMat with cv::RANSAC for every edge of a match graph in ONE
+ * call. Inputs, layouts and host-side checks are those of eacham_lmeds_batch; the selection is RANSACPointSetRegistrator::run
+ * (OpenCV 4.5.5, from memory). threshold: already SQUARED, in the error's own units, as eacham_score_hypotheses takes it
+ * (essential with K: the K-normalised unit). Per problem, with n points, sample size m = 4 / 5 / 7 and S samples in order:
+ *     budget = S; best = -1; winner = none
+ *     for s = 0, 1, ... while s < budget:
+ *         for every root r of sample s, in root order (a degenerate sample has none):
+ *             cnt = #{ i : err(point i, model) <= threshold }
+ *             if cnt > max(best, m - 1):                   strictly more: the earlier candidate stays
+ *                 best = cnt; winner = (s, r)
+ *                 budget = ransac_update_num_iters(confidence, (double)(n - cnt) / n, m, budget)     (include/eacham/RansacIters.hpp)
+ *     n_used = samples whose roots were looked at
+ * The budget is tested per sample: a record in root 0 that drops the budget below s + 1 does not keep roots 1.. of the same
+ * sample from being counted, and they may win. ransac_update_num_iters is evaluated on the HOST only (an integer table per
+ * distinct n goes to the device): no device pow / log / lround decides anything.
+ * Outputs (each optional): models n_problems x 9 (the winner as solved), inliers (= best), masks (mask[i] = err_winner(i) <=
+ * threshold; point_ptr[n_problems] bytes), winner n_problems x 3 = {candidate index among the candidates of the n_used consumed
+ * samples, sample, root}, n_candidates = the candidates of the n_used consumed samples, n_used.
+ * The "NONE" RECORD — winner -1 -1 -1, a zero model, zero inliers, a zero mask, n_used = S, n_candidates as defined — goes to a
+ * problem with fewer than m points (then n_used = 0 and its samples are not looked at), with no samples, with no candidate, or
+ * with no count above m - 1. Its neighbours are not affected. n == m is NOT special-cased here: OpenCV's shortcut for it (the
+ * minimal solver's answer without a loop) belongs to the adapters of include/eacham/TwoViewHip.hpp.
+ * stage1: the samples of every problem that are solved and counted before the budgets are first looked at; only the ranks
+ * stage1 .. budget - 1 are solved after that (their number comes back in one 8-byte read). 0 = the library's default; any value
+ * >= the largest S is a single pass with no read-back. Every output is byte-identical for every stage1.
+ * Byte for byte the composition of eacham_solve_minimal, the inlier counts of eacham_score_hypotheses and the rule above.
+ * EACHAM_ERR_INVALID: as eacham_lmeds_batch, and a NaN or negative threshold, a confidence outside (0, 1), a negative stage1. */
+int eacham_ransac_batch(eacham_ctx* ctx, int kind, int n_problems, const int64_t* point_ptr, const double* a, const double* b,
+                        const double* K, const int64_t* sample_ptr, const int32_t* sample_idx, float threshold, double confidence,
+                        int stage1, double* models, int32_t* inliers, uint8_t* masks, int32_t* winner, int32_t* n_candidates,
+                        int32_t* n_used);
+/* Diagnostic: how the context's last eacham_ransac_batch / eacham_graph_verify_ransac ran (any pointer may be NULL). samples_solved =
+ * minimal samples handed to the solver over both passes (a single pass: all of them), table_ms = host milliseconds spent building
+ * the budget rows. */
+int eacham_ransac_debug_last(eacham_ctx* ctx, int64_t* samples_solved, double* table_ms);
+
 /* ---- PnP RANSAC for a whole list of problems ------------------------------------------------------------------------
  * cv::solvePnPRansac(..., SOLVEPNP_EPNP) (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:227-228) for
  * a list of (map points, pixels) problems: what eacham_solve_pnp + eacham_score_hypotheses(kind PNP) do for one frame per
@@ -763,6 +800,16 @@ int eacham_graph_set_keypoints(eacham_graph* graph, const double* xy);
 int eacham_graph_verify(eacham_graph* graph, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
                         double* models, float* medians, float* thresholds, int32_t* inliers, uint8_t* masks, int32_t* winner,
                         int32_t* n_candidates, int32_t* n_samples, int32_t* samples);
+/* eacham_graph_verify_ransac: the same gather, the same draws and the same mask layout, with eacham_ransac_batch as the estimator.
+ * kind, K, sampling, seeds, retain, masks, n_samples and samples are eacham_graph_verify's; iterations = the samples drawn per pair
+ * (the caller's maxIters: the threshold rule stops early by itself); threshold (squared), confidence and stage1, and the outputs
+ * models, inliers, winner, n_candidates and n_used, are eacham_ransac_batch's, per caller pair. The budget rows are built on the host
+ * from the pairs' match counts. A retained mask replaces an LMedS one and the other way round; eacham_graph_tracks_verified takes
+ * either. Byte for byte the host composition: gather, lmeds_samples / draw_samples per pair, eacham_ransac_batch.
+ * EACHAM_ERR_INVALID: as eacham_graph_verify, and a NaN or negative threshold, a confidence outside (0, 1), a negative stage1. */
+int eacham_graph_verify_ransac(eacham_graph* graph, int kind, const double* K, int sampling, int iterations, const uint64_t* seeds, int retain,
+                               float threshold, double confidence, int stage1, double* models, int32_t* inliers, uint8_t* masks,
+                               int32_t* winner, int32_t* n_candidates, int32_t* n_used, int32_t* n_samples, int32_t* samples);
 /* eacham_graph_tracks with the mask the last eacham_graph_verify(retain != 0) left in the graph as `keep`: nothing is uploaded.
  * Byte for byte eacham_graph_tracks(graph, masks of that verify call, ...). EACHAM_ERR_INVALID if no mask is retained. */
 int eacham_graph_tracks_verified(eacham_graph* graph, int min_len, int conflict_policy, int64_t cap_obs, int32_t cap_tracks,
