@@ -10,22 +10,11 @@ import pytest
 from eacham_amd import ba, synth
 from eacham_amd import capi, EachamError
 import oracle_api as O
+from ba_helpers import backward_error, rel, ctx_with as _ctx_with
 
 pytestmark = pytest.mark.gpu
 GOLD_DIR = os.path.join(os.path.dirname(__file__), "golden")
 POSE_POINT_RTOL = 1e-5  # north_star tolerance
-
-
-def rel(a, b):
-    return np.abs(np.asarray(a) - np.asarray(b)).max() / max(np.abs(np.asarray(b)).max(), 1e-300)
-
-
-def backward_error(S, g, x):
-    """Normwise backward error of x as a solution of S x = g, ||S x - g|| / (||S|| ||x|| + ||g||) in infinity norms, evaluated
-    in extended precision: it judges a step by the system alone, whatever algorithm produced it."""
-    S, g, x = (np.asarray(v, dtype=np.longdouble) for v in (S, g, x))
-    r = S @ x - g
-    return float(np.abs(r).max() / (np.abs(S).sum(axis=1).max() * np.abs(x).max() + np.abs(g).max()))
 
 
 def scene_arrays(seed=3, n_cams=6, n_lm=200, k=4, outliers=True, **kw):
@@ -468,21 +457,6 @@ def test_config4_damped_step_under_every_ordering(hip_ctx, config4):
         steps[name] = dc
     for name in ("nd", "auto"):
         assert rel(steps[name], steps["natural"]) < 1e-9
-
-
-def _ctx_with(**env):
-    """A context of its own created under the given environment switches (they are read once, at eacham_ctx_create)."""
-    from eacham_amd import HipContext
-    old = {k: os.environ.get(k) for k in env}
-    try:
-        os.environ.update(env)
-        return HipContext(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
 
 
 @pytest.mark.parametrize("prepare", ["host", "device"])

@@ -7,6 +7,7 @@ import pytest
 from eacham_amd import ba, synth
 import np_reference as R
 import oracle_api as O
+from ba_helpers import schur_step_equals_dense_step
 
 GOLD_DIR = os.path.join(os.path.dirname(__file__), "golden")
 GOLDEN = ["ba_golden.npz", "ba_golden_hard.npz", "ba_golden_policy.npz"]
@@ -79,15 +80,7 @@ def test_schur_complement_equals_dense_solve(lam):
     sc = small_scene(seed=9, n_cams=5, n_lm=60, k=3, pixel_noise=2.0)
     A = ba.BaArrays.from_scene(sc)
     A.obs_uv[::11] += 25.0
-    S, g, dc, dl, err, lin, ok = O.ba_step(A, lam, 0)
-    S2, g2, dc2, dl2, err2, lin2, ok2 = O.ba_step(A, lam, 1)
-    assert ok and ok2
-    scale = max(np.abs(dc2).max(), 1e-12)
-    assert np.abs(dc - dc2).max() < 1e-9 * scale and np.abs(dl - dl2).max() < 1e-9 * max(np.abs(dl2).max(), 1e-12)
-    assert np.isclose(lin, lin2, rtol=1e-9) and lin > 0 and np.isclose(err, err2, rtol=1e-12)  # OpenMP sum order
-    assert np.allclose(S, S.T, rtol=0, atol=1e-9 * np.abs(S).max())
-    # the reduced system reproduces the camera part of the step
-    assert np.allclose(np.linalg.solve(S, g), dc, rtol=1e-7, atol=1e-10)
+    schur_step_equals_dense_step(A, lam)   # (tests/test_ba_ragged_reference.py runs the same check on ragged problems)
 
 
 def replay_lambda_policy(out, policy):
