@@ -347,31 +347,6 @@ private:
         return EACHAM_OK;
     }
 };
-// lmeds_batch.hip: the launch sequence of eacham_lmeds_batch on device pointers — solve every sample, scan the root counts, score
-// every candidate (keys in LDS up to SC_MAX_LDS points, in error rows beyond, by max_n), select per problem. The host-pointer entry
-// and eacham_graph_verify (graph_verify.hip) both call it. S = the samples sample_ptr[P] names; the scratch arrays may be larger.
-struct LmedsLaunch {
-    int kind, P;                 // EACHAM_SOLVE_*, problems (> 0)
-    long long S, max_n;          // samples in this call; the largest problem with at least a minimal sample's worth of points
-    int score_grid;              // lmeds_score_grid(...): the workgroups of the scorer, and the rows `rows` holds beyond SC_MAX_LDS
-    const long long *point_ptr, *sample_ptr;
-    const double *a, *b, *K;     // K: device copy of fx fy cx cy; has_K says whether the caller gave one
-    bool has_K;
-    const int* sample_idx;
-    // scratch: 9 x S x maxm, S, S, S, 1, scan_ws_elems(S), S x maxm, need_rows ? score_grid x max_n : 0
-    double* cand_models;
-    int *n_models, *first, *sample_problem, *total, *scan_ws;
-    float *cand_medians, *rows;
-    // results, per problem (masks: per point, in the layout of a / b)
-    double* models;
-    float *medians, *thresholds;
-    int* inliers;
-    unsigned char* masks;
-    int *winner, *n_candidates;
-};
-int lmeds_score_grid(long long cand_cap, long long max_n);
-bool lmeds_needs_rows(long long max_n);
-int lmeds_launch(eacham_ctx* ctx, hipStream_t st, const LmedsLaunch& L);
 int sync_frame_table(eacham_ctx* ctx);
 // copies `pairs` into the workspace tail with every pair that names a missing frame redirected to the empty
 // stand-in entry frames[n_frames] (and flags it); returns the sanitised device pointer in *out

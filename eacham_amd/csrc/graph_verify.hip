@@ -21,15 +21,15 @@
 //
 // eacham_graph_verify_ransac is the same call with ransac_launch (ransac_batch.hip: threshold RANSAC in two passes) in lmeds_launch's
 // place: the checks, the gather, both draws, the packed sample list, the read-back below, the scatter and `retain` are ONE function,
-// gv_verify, which both entries hand their own staged arrays and their estimator's launch.
+// gv_verify, which both entries hand their own staged arrays and their estimator's launch. Each entry stages its estimator's scratch
+// with the struct the list call uses (lmeds_launch.hpp: LmedsScratch, ransac_launch.hpp: RansacScratch); the kernels that depend on
+// the kind are launched through with_solve_kind (solve_launch.hpp).
 //
 // READ-BACKS. The number of samples is known on the host — (pairs with n >= m) x iterations — except under the OpenCV stream for the
 // homography and the fundamental matrix, where checkSubset can make getSubset give up: then the total (8 bytes) is read back once through the pinned mirror.
 // The scratch is sized by the host-known bound either way; the launches cover exactly sample_ptr[npairs] samples.
-#include "context.hpp"
-#include "devprim.hpp"
+#include "lmeds_launch.hpp"
 #include "ransac_launch.hpp"
-#include "solve_launch.hpp"
 #include "../../include/eacham/CvSampling.hpp"
 
 #include <climits>
@@ -202,12 +202,10 @@ int gv_verify(eacham_graph* g, const char* what, int kind, const double* K, int 
               uint8_t* masks, int32_t* n_samples, int32_t* samples, Declare declare, Launch launch) {
     eacham_ctx* ctx = g->ctx;
     if (!g->has_xy) return ctx->fail(EACHAM_ERR_INVALID, "%s: the graph has no keypoint coordinates (eacham_graph_set_keypoints)", what);
-    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
-        return ctx->fail(EACHAM_ERR_INVALID, "%s: unknown kind %d", what, kind);
+    if (int rc = check_solve_kind(ctx, what, kind)) return rc;
     if (sampling != EACHAM_SAMPLING_OPENCV && sampling != EACHAM_SAMPLING_COUNTER)
         return ctx->fail(EACHAM_ERR_INVALID, "%s: unknown sampling %d", what, sampling);
     if (iterations < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative iterations", what);
-    const bool homography = kind == EACHAM_SOLVE_HOMOGRAPHY4, fundamental = kind == EACHAM_SOLVE_FUNDAMENTAL7;
     const int P = g->npairs, m = solve_sample_size(kind), maxm = solve_max_models(kind);
     if (P == 0) return EACHAM_OK;
     long long n_ok = 0, max_n = 0;   // pairs with a minimal sample's worth of matches; the largest of them
@@ -218,7 +216,7 @@ int gv_verify(eacham_graph* g, const char* what, int kind, const double* K, int 
         return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %lld points / %d pairs x %d samples in one call", what, NP, P, iterations);
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (retain && !g->keep_mask) EACHAM_HIP_TRY(ctx, hipMalloc((void**)&g->keep_mask, std::max<size_t>((size_t)g->n_src, 16)));
-    const GvPlan plan{kind, P, m, maxm, iterations, n_ok, max_n, NP, S_cap, slots, !((homography || fundamental) && sampling == EACHAM_SAMPLING_OPENCV)};
+    const GvPlan plan{kind, P, m, maxm, iterations, n_ok, max_n, NP, S_cap, slots, kind == EACHAM_SOLVE_ESSENTIAL5 || sampling != EACHAM_SAMPLING_OPENCV};
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
     const auto h_total = io.out<long long>(nullptr, 1);   // first: offset 0, always inside the pinned mirror
@@ -241,24 +239,18 @@ int gv_verify(eacham_graph* g, const char* what, int kind, const double* K, int 
         if (NP > 0)
             gv_gather_kernel<<<gv_blocks(NP, GV), GV, 0, st>>>(NP, g->pairs, g->n_edges, g->offsets, g->q, g->t, g->kp_offsets, (const double2*)g->xy,
                                                                d(h_a), d(h_b));
-        if (sampling == EACHAM_SAMPLING_COUNTER) {
-            const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
-            const unsigned long long* d_seeds = seeds ? d(h_seeds) : nullptr;
-            if (homography) gv_draw_counter_kernel<4><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-            else if (fundamental) gv_draw_counter_kernel<7><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-            else gv_draw_counter_kernel<5><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, d_seeds, d(h_osamp), d(h_ons), d(h_cnt));
-        } else {
-            const unsigned grid = gv_blocks(P, GV_PAIR);
-            if (homography) gv_draw_opencv_kernel<4, 1><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-            else if (fundamental) gv_draw_opencv_kernel<7, 2><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-            else gv_draw_opencv_kernel<5, 0><<<grid, GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp), d(h_ons), d(h_cnt));
-        }
-        prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
-        if (slots > 0) {
-            if (homography) gv_compact_kernel<4><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-            else if (fundamental) gv_compact_kernel<7><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-            else gv_compact_kernel<5><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
-        }
+        with_solve_kind(kind, [&](auto k) {
+            using Kind = decltype(k);
+            if (sampling == EACHAM_SAMPLING_COUNTER) {
+                const unsigned grid = gv_blocks((long long)P * std::max(iterations, 1), GV);
+                gv_draw_counter_kernel<Kind::M><<<grid, GV, 0, st>>>(P, iterations, g->pair_ptr, seeds ? d(h_seeds) : nullptr, d(h_osamp), d(h_ons), d(h_cnt));
+            } else {
+                gv_draw_opencv_kernel<Kind::M, Kind::CHECK><<<gv_blocks(P, GV_PAIR), GV_PAIR, 0, st>>>(P, iterations, g->pair_ptr, d_a, d_b, d(h_osamp),
+                                                                                                     d(h_ons), d(h_cnt));
+            }
+            prim::exclusive_scan<long long>(st, d(h_cnt), d(h_sp), P + 1, d(h_spws), d(h_total));
+            if (slots > 0) gv_compact_kernel<Kind::M><<<gv_blocks(slots, GV), GV, 0, st>>>(P, iterations, d(h_sp), d(h_osamp), d(h_i));
+        });
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     long long S = S_cap;
@@ -291,29 +283,23 @@ extern "C" int eacham_graph_verify(eacham_graph* g, int kind, const double* K, i
     if (!g) return EACHAM_ERR_INVALID;
     eacham_ctx* ctx = g->ctx;
     return verify_entry(ctx, "graph_verify", [&]() -> int {
-        IoArray<double> h_om{}, h_m{};
-        IoArray<float> h_omed{}, h_othr{}, h_cmed{}, h_rows{};
-        IoArray<int> h_oinl{}, h_owin{}, h_onc{}, h_n{}, h_first{}, h_sprob{}, h_tot{}, h_ws{};
-        int score_grid = 1;
+        IoArray<double> h_om{};
+        IoArray<float> h_omed{}, h_othr{};
+        IoArray<int> h_oinl{}, h_owin{}, h_onc{};
+        std::unique_ptr<LmedsScratch> sc;
         return gv_verify(
             g, "graph_verify", kind, K, sampling, iterations, seeds, retain, masks, n_samples, samples,
             [&](IoStage& io, const GvPlan& pl) {
                 const size_t P = (size_t)pl.P;
-                const long long cand_cap = pl.S_cap * pl.maxm;
-                score_grid = lmeds_score_grid(cand_cap, pl.max_n);
                 h_om = io.out<double>(models, 9 * P);
                 h_omed = io.out<float>(medians, P), h_othr = io.out<float>(thresholds, P);
                 h_oinl = io.out<int>(inliers, P), h_owin = io.out<int>(winner, 3 * P), h_onc = io.out<int>(n_candidates, P);
-                h_m = io.scratch<double>(9 * (size_t)cand_cap);
-                h_n = io.scratch<int>((size_t)pl.S_cap), h_first = io.scratch<int>((size_t)pl.S_cap), h_sprob = io.scratch<int>((size_t)pl.S_cap);
-                h_tot = io.scratch<int>(1), h_ws = io.scratch<int>(prim::scan_ws_elems((size_t)pl.S_cap));
-                h_cmed = io.scratch<float>((size_t)cand_cap);
-                h_rows = io.scratch<float>(lmeds_needs_rows(pl.max_n) ? (size_t)score_grid * (size_t)pl.max_n : 0);
+                sc.reset(new LmedsScratch(io, pl.S_cap, pl.maxm, pl.max_n));
             },
             [&](const IoDev& d, const GvPlan& pl, const GvDev& v) -> int {
-                const LmedsLaunch L{kind, pl.P, v.S, pl.max_n, score_grid, g->pair_ptr, v.sample_ptr, v.a, v.b, v.K, K != nullptr, v.sample_idx,
-                                    d(h_m), d(h_n), d(h_first), d(h_sprob), d(h_tot), d(h_ws), d(h_cmed), d(h_rows),
-                                    d(h_om), d(h_omed), d(h_othr), d(h_oinl), v.packed_mask, d(h_owin), d(h_onc)};
+                LmedsLaunch L{kind, pl.P, v.S, pl.max_n, g->pair_ptr, v.sample_ptr, v.a, v.b, CallK{v.K, K != nullptr}, v.sample_idx};
+                sc->bind(L, d);
+                L.models = d(h_om), L.medians = d(h_omed), L.thresholds = d(h_othr), L.inliers = d(h_oinl), L.masks = v.packed_mask, L.winner = d(h_owin), L.n_candidates = d(h_onc);
                 return lmeds_launch(ctx, ctx->stream, L);
             });
     });
@@ -348,8 +334,8 @@ extern "C" int eacham_graph_verify_ransac(eacham_graph* g, int kind, const doubl
                 sc.reset(new RansacScratch(io, pl.P, S1_cap, pl.m, pl.maxm, single));
             },
             [&](const IoDev& d, const GvPlan& pl, const GvDev& v) -> int {
-                RansacLaunch L{kind, pl.P, single ? v.S : S1_cap, stage1, single, threshold, g->pair_ptr, v.sample_ptr, v.a, v.b, v.K, K != nullptr, v.sample_idx,
-                               d(h_toff), d(h_tab)};
+                RansacLaunch L{kind, pl.P, single ? v.S : S1_cap, stage1, single, threshold, g->pair_ptr, v.sample_ptr, v.a, v.b, CallK{v.K, K != nullptr},
+                               v.sample_idx, d(h_toff), d(h_tab)};
                 sc->bind(L, d);
                 L.s1_known = single || pl.count_known;
                 L.total2 = v.total, L.total2_host = v.total_host;

@@ -14,16 +14,17 @@
 //                               or a barrier. A fixed grid strides over the device-side candidate total.
 //   rb_rule                     a thread per problem: ransac_rule_walk over the problem's samples in rank order, wherever a pass left
 //                               them; after pass 1 it only leaves the budget, at the end the budget, n_used, the winner and n_candidates
-//   rb_finish<KIND>             a workgroup per problem: the winner's model, its errors against the threshold (the mask bytes), the count
+//   rb_finish<KIND>             a workgroup per problem: the winner's place from win_at, then lb_select's tail (estimator_dev.hpp:
+//                               classify_winner) — the winner's model, its errors against the threshold (the mask bytes), the count
 // Pass 2 may solve samples the sequential loop would not reach (a record inside pass 2 shrinks the budget further): the rule only ever
 // reads a prefix of what was solved, so every output is the same for every stage1.
+// K, the candidate lookup and the kind dispatch are the shared ones (estimator_dev.hpp, solve_launch.hpp), and the entry's list checks
+// and input staging are eacham_lmeds_batch's (check_list_call, ListCall) behind the rule's own scalar checks.
+#include "estimator_dev.hpp"
 #include "ransac_launch.hpp"
 #include "ransac_rule.hpp"
-#include "score_dev.hpp"
-#include "solve_launch.hpp"
 
 #include <chrono>
-#include <climits>
 #include <cmath>
 #include <map>
 
@@ -72,29 +73,21 @@ __global__ __launch_bounds__(RB) void rb_count_kernel(const long long* __restric
                                                       const double* __restrict__ Kdev, int normalise, int n_samples, const int* __restrict__ first,
                                                       const int* __restrict__ total, const int* __restrict__ sample_problem,
                                                       const double* __restrict__ models, int max_models, float thr, int* __restrict__ counts) {
-    double K[4] = {1, 1, 0, 0};
-    if (Kdev) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) K[k] = Kdev[k];
-    }
+    double K[4];
+    load_K(Kdev, K);
     const int lane = threadIdx.x & 63, waves = RB / 64;
     const int ncand = *total;
     for (int c = blockIdx.x * waves + (threadIdx.x >> 6); c < ncand; c += gridDim.x * waves) {   // (c is uniform over the wave)
-        const int s = prim::segment_of(first, n_samples, c);
-        const long long base = point_ptr[sample_problem[s]];
-        const int n = (int)(point_ptr[sample_problem[s] + 1] - base);
-        const double* pm = models + 9 * ((size_t)s * max_models + (c - first[s]));
-        const double* pa = a + 2 * base;
-        const double* pb = b + 2 * base;
+        const Candidate cand(first, n_samples, models, max_models, c);
+        const Points q(point_ptr, a, b, sample_problem[cand.s]);
         double M[9];
-#pragma unroll
-        for (int k = 0; k < 9; ++k) M[k] = pm[k];
+        cand.load(M);
         int cnt = 0;
-        for (int i0 = 0; i0 < n; i0 += 64) {
+        for (int i0 = 0; i0 < q.n; i0 += 64) {
             const int i = i0 + lane;
             bool in = false;
-            if (i < n) {
-                const double xa[2] = {pa[2 * (size_t)i], pa[2 * (size_t)i + 1]}, xb[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
+            if (i < q.n) {
+                const double xa[2] = {q.pa[2 * (size_t)i], q.pa[2 * (size_t)i + 1]}, xb[2] = {q.pb[2 * (size_t)i], q.pb[2 * (size_t)i + 1]};
                 in = score_one<KIND>(xa, xb, M, K, normalise != 0) <= thr;
             }
             cnt += __popcll(__ballot(in));
@@ -135,7 +128,7 @@ __global__ __launch_bounds__(RB) void rb_rule_kernel(int P, int m, const long lo
     win_at[2 * (size_t)p + 1] = none ? 0 : (r.sample < src.c1 ? p1.first[src.s1 + r.sample] : p2.first[src.s2 + (r.sample - src.c1)]) + r.root;
 }
 
-// cand: the place of a pass-relative candidate's model: sample-major, max_models slots per sample
+// win_at: the winner's pass (-1: none) and its place in that pass's candidate list (n1 / n2 samples)
 template <int KIND>
 __global__ __launch_bounds__(SC_BLOCK) void rb_finish_kernel(const long long* __restrict__ point_ptr, const double* __restrict__ a,
                                                              const double* __restrict__ b, const double* __restrict__ Kdev, int normalise,
@@ -144,41 +137,13 @@ __global__ __launch_bounds__(SC_BLOCK) void rb_finish_kernel(const long long* __
                                                              int* __restrict__ out_inliers, unsigned char* __restrict__ out_masks) {
     __shared__ int wsum[SC_BLOCK / 64];
     const int p = blockIdx.x;
-    const long long base = point_ptr[p];
-    const int n = (int)(point_ptr[p + 1] - base);
     const int pass = win_at[2 * (size_t)p], at = win_at[2 * (size_t)p + 1];
-    const bool none = pass < 0;
-    double M[9], K[4] = {1, 1, 0, 0};
-#pragma unroll
-    for (int k = 0; k < 9; ++k) M[k] = 0.0;
-    if (!none) {
+    const double* pm = nullptr;   // pass < 0: no winner
+    if (pass >= 0) {
         const RbPass& w = pass == 0 ? p1 : p2;
-        const int s = prim::segment_of(w.first, pass == 0 ? n1 : n2, at);
-        const double* pm = w.models + 9 * ((size_t)s * max_models + (at - w.first[s]));
-#pragma unroll
-        for (int k = 0; k < 9; ++k) M[k] = pm[k];
-        if (Kdev) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) K[k] = Kdev[k];
-        }
+        pm = Candidate(w.first, pass == 0 ? n1 : n2, w.models, max_models, at).pm;
     }
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int k = 0; k < 9; ++k) out_models[9 * (size_t)p + k] = M[k];
-    }
-    const double* pa = a + 2 * base;
-    const double* pb = b + 2 * base;
-    int cnt = 0;
-    for (int i = threadIdx.x; i < n; i += SC_BLOCK) {
-        unsigned char in = 0;
-        if (!none) {
-            const double xa[2] = {pa[2 * (size_t)i], pa[2 * (size_t)i + 1]}, xb[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
-            in = score_one<KIND>(xa, xb, M, K, normalise != 0) <= thr;
-        }
-        out_masks[base + i] = in;
-        cnt += in;
-    }
-    const int tot = block_count(cnt, wsum);
+    const int tot = classify_winner<KIND>(pm, Kdev, normalise, Points(point_ptr, a, b, p), thr, out_models + 9 * (size_t)p, out_masks, wsum);
     if (threadIdx.x == 0) out_inliers[p] = tot;
 }
 
@@ -189,27 +154,19 @@ inline size_t rb_up(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 void rb_pass(hipStream_t st, const RansacLaunch& L, const long long* sp, const int* idx, int S, double* cand, int* n_models, int* first,
              int* sample_problem, int* total, int* scan_ws, int* counts) {
     const int maxm = solve_max_models(L.kind);
-    const double* d_K = L.has_K ? L.K : nullptr;
-    const int normalise = L.has_K && L.kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
-    solve_minimal_launch(st, MinimalLaunch{L.kind, SolveSeg{L.point_ptr, sp, L.P, sample_problem}, L.a, L.b, L.K, L.has_K, S, idx, cand, n_models});
+    solve_minimal_launch(st, MinimalLaunch{L.kind, SolveSeg{L.point_ptr, sp, L.P, sample_problem}, L.a, L.b, L.K.dev, L.K.given, S, idx, cand, n_models});
     prim::exclusive_scan<int>(st, n_models, first, S, scan_ws, total);
     const int grid = (int)std::max<long long>(1, std::min<long long>(((long long)S * maxm + RB / 64 - 1) / (RB / 64), RB_COUNT_GRID));
-    if (L.kind == EACHAM_SOLVE_ESSENTIAL5)
-        rb_count_kernel<0><<<grid, RB, 0, st>>>(L.point_ptr, L.a, L.b, d_K, normalise, S, first, total, sample_problem, cand, maxm, L.threshold, counts);
-    else if (L.kind == EACHAM_SOLVE_FUNDAMENTAL7)
-        rb_count_kernel<3><<<grid, RB, 0, st>>>(L.point_ptr, L.a, L.b, d_K, normalise, S, first, total, sample_problem, cand, maxm, L.threshold, counts);
-    else
-        rb_count_kernel<1><<<grid, RB, 0, st>>>(L.point_ptr, L.a, L.b, d_K, normalise, S, first, total, sample_problem, cand, maxm, L.threshold, counts);
+    with_solve_kind(L.kind, [&](auto k) {
+        rb_count_kernel<decltype(k)::SCORE><<<grid, RB, 0, st>>>(L.point_ptr, L.a, L.b, L.K.scorer(), L.K.normalise(L.kind), S, first, total,
+                                                                 sample_problem, cand, maxm, L.threshold, counts);
+    });
 }
 
-template <int M>
-void rb_compact(hipStream_t st, const RansacLaunch& L, long long n, const long long* sp, int skip, int* out) {
-    rb_compact_kernel<M><<<rb_blocks(n), RB, 0, st>>>(L.P, n, sp, L.sample_ptr, skip, L.sample_idx, out);
-}
 void rb_compact_any(hipStream_t st, const RansacLaunch& L, long long n, const long long* sp, int skip, int* out) {
-    if (L.kind == EACHAM_SOLVE_HOMOGRAPHY4) rb_compact<4>(st, L, n, sp, skip, out);
-    else if (L.kind == EACHAM_SOLVE_FUNDAMENTAL7) rb_compact<7>(st, L, n, sp, skip, out);
-    else rb_compact<5>(st, L, n, sp, skip, out);
+    with_solve_kind(L.kind, [&](auto k) {
+        rb_compact_kernel<decltype(k)::M><<<rb_blocks(n), RB, 0, st>>>(L.P, n, sp, L.sample_ptr, skip, L.sample_idx, out);
+    });
 }
 
 }  // namespace
@@ -238,8 +195,6 @@ void ransac_build_table(eacham_ctx* ctx, double confidence, int m, int cap, cons
 
 int ransac_launch(eacham_ctx* ctx, hipStream_t st, const RansacLaunch& L) {
     const int P = L.P, m = solve_sample_size(L.kind), maxm = solve_max_models(L.kind);
-    const double* d_K = L.has_K ? L.K : nullptr;
-    const int normalise = L.has_K && L.kind == EACHAM_SOLVE_ESSENTIAL5 ? 1 : 0;
     RbPass p1{L.single ? L.sample_ptr : L.sp1, L.n_models1, L.first1, L.counts1, L.cand1}, p2{nullptr, nullptr, nullptr, nullptr, nullptr};
     long long S1 = L.S1, S2 = 0;
     auto read_total = [&](long long& v) -> int {   // the 8-byte read-back of a pass's sample total
@@ -294,13 +249,10 @@ int ransac_launch(eacham_ctx* ctx, hipStream_t st, const RansacLaunch& L) {
     ctx->ransac_solved = S1 + S2;
     rb_rule_kernel<<<rb_blocks(P), RB, 0, st>>>(P, m, L.point_ptr, L.sample_ptr, p1, p2, L.tab_off, L.table, 1, L.budget, L.n_used, L.winner, L.n_candidates,
                                                L.win_at);
-#define EACHAM_RB_FINISH(KIND)                                                                                                                   \
-    rb_finish_kernel<KIND><<<P, SC_BLOCK, 0, st>>>(L.point_ptr, L.a, L.b, d_K, normalise, p1, p2, (int)S1, (int)S2, maxm, L.threshold, L.win_at, \
-                                                   L.models, L.inliers, L.masks)
-    if (L.kind == EACHAM_SOLVE_ESSENTIAL5) EACHAM_RB_FINISH(0);
-    else if (L.kind == EACHAM_SOLVE_FUNDAMENTAL7) EACHAM_RB_FINISH(3);
-    else EACHAM_RB_FINISH(1);
-#undef EACHAM_RB_FINISH
+    with_solve_kind(L.kind, [&](auto k) {
+        rb_finish_kernel<decltype(k)::SCORE><<<P, SC_BLOCK, 0, st>>>(L.point_ptr, L.a, L.b, L.K.scorer(), L.K.normalise(L.kind), p1, p2, (int)S1, (int)S2,
+                                                                     maxm, L.threshold, L.win_at, L.models, L.inliers, L.masks);
+    });
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     return EACHAM_OK;
 }
@@ -315,37 +267,21 @@ extern "C" int eacham_ransac_batch(eacham_ctx* ctx, int kind, int n_problems, co
                                    int32_t* n_used) {
     if (!ctx) return EACHAM_ERR_INVALID;
     std::lock_guard<std::mutex> lock(ctx->mu);
-    if (kind != EACHAM_SOLVE_HOMOGRAPHY4 && kind != EACHAM_SOLVE_ESSENTIAL5 && kind != EACHAM_SOLVE_FUNDAMENTAL7)
-        return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: unknown kind %d", kind);
+    if (int rc = check_solve_kind(ctx, "ransac_batch", kind)) return rc;
     if (!(threshold >= 0.f)) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: the threshold is negative or not a number");
     if (!(confidence > 0.0 && confidence < 1.0)) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: confidence outside (0, 1)");
     if (stage1 < 0) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: negative stage1");
-    if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: negative number of problems");
+    ListCall c;
+    std::vector<int> n_of;
+    if (int rc = check_list_call(ctx, "ransac_batch", kind, n_problems, point_ptr, sample_ptr, a, b, sample_idx, c, &n_of)) return rc;
     if (n_problems == 0) return EACHAM_OK;
-    if (!point_ptr || !sample_ptr) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: null offset table");
     const int P = n_problems, m = solve_sample_size(kind), maxm = solve_max_models(kind);
-    if (point_ptr[0] != 0 || sample_ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: an offset table does not start at 0");
-    for (int p = 0; p < P; ++p)
-        if (point_ptr[p + 1] < point_ptr[p] || sample_ptr[p + 1] < sample_ptr[p])
-            return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: problem %d: offset table not monotone", p);
-    const long long NP = point_ptr[P], S = sample_ptr[P];
-    if (NP > INT_MAX / 2 || S * m > INT_MAX || S * maxm > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "ransac_batch: %lld points / %lld samples in one call", NP, S);
-    if ((NP > 0 && (!a || !b)) || (S > 0 && !sample_idx)) return ctx->fail(EACHAM_ERR_INVALID, "ransac_batch: null array");
     if (stage1 == 0) stage1 = ransac_default_stage1();
-    long long max_S = 0, S1 = 0;
-    std::vector<int> n_of((size_t)P);
-    for (int p = 0; p < P; ++p) {
-        const long long n = point_ptr[p + 1] - point_ptr[p], Sp = sample_ptr[p + 1] - sample_ptr[p];
-        n_of[p] = (int)n;
-        max_S = std::max(max_S, Sp);
-        S1 += std::min<long long>(Sp, stage1);
-        if (n < m) continue;   // its samples are not looked at: the problem gets the "none" record
-        if (int rc = check_sample_idx(ctx, "ransac_batch", p, sample_idx + sample_ptr[p] * m, Sp * m, n)) return rc;
-    }
-    const bool single = stage1 >= max_S;
-    if (single) S1 = S;
+    const bool single = stage1 >= c.max_S;
+    long long S1 = single ? c.S : 0;   // pass 1: every problem's first min(S_p, stage1) samples
+    for (int p = 0; p < P && !single; ++p) S1 += std::min<long long>(sample_ptr[p + 1] - sample_ptr[p], stage1);
     std::vector<int> tab_off, table;
-    ransac_build_table(ctx, confidence, m, (int)std::max<long long>(max_S, 1), n_of.data(), P, tab_off, table);
+    ransac_build_table(ctx, confidence, m, (int)std::max<long long>(c.max_S, 1), n_of.data(), P, tab_off, table);
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
@@ -353,16 +289,15 @@ extern "C" int eacham_ransac_batch(eacham_ctx* ctx, int kind, int n_problems, co
     const auto h_om = io.out<double>(models, 9 * (size_t)P);
     const auto h_oinl = io.out<int>(inliers, (size_t)P), h_owin = io.out<int>(winner, 3 * (size_t)P), h_onc = io.out<int>(n_candidates, (size_t)P);
     const auto h_onu = io.out<int>(n_used, (size_t)P);
-    const auto h_omask = io.out<unsigned char>(masks, (size_t)NP);
-    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
-    const auto h_K = io.in<double>(K, 4);
+    const auto h_omask = io.out<unsigned char>(masks, (size_t)c.NP);
+    c.stage_tables(io, P, point_ptr, sample_ptr, K);
     const auto h_toff = io.in<int>(tab_off.data(), (size_t)P), h_tab = io.in<int>(table.data(), table.size());
-    const auto h_a = io.in<double>(a, 2 * (size_t)NP), h_b = io.in<double>(b, 2 * (size_t)NP);
-    const auto h_i = io.in<int>(sample_idx, (size_t)S * m);
+    c.stage_points(io, m, a, b, sample_idx);
     const RansacScratch sc(io, P, S1, m, maxm, single);
     IoDev d;
     if (int rc = io.upload(d)) return rc;
-    RansacLaunch L{kind, P, S1, stage1, single, threshold, d(h_pp), d(h_sp), d(h_a), d(h_b), d(h_K), K != nullptr, d(h_i), d(h_toff), d(h_tab)};
+    RansacLaunch L{kind, P, S1, stage1, single, threshold, d(c.point_ptr), d(c.sample_ptr), d(c.a), d(c.b), CallK{d(c.K), K != nullptr}, d(c.sample_idx),
+                   d(h_toff), d(h_tab)};
     sc.bind(L, d);
     L.total2 = d(h_total2), L.total2_host = (long long*)((char*)ctx->io_host + io.lay.off[h_total2.k]);
     L.models = d(h_om), L.inliers = d(h_oinl), L.masks = d(h_omask), L.winner = d(h_owin), L.n_candidates = d(h_onc), L.n_used = d(h_onu);

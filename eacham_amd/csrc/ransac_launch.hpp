@@ -1,9 +1,10 @@
 // ransac_launch.hpp — threshold RANSAC as the translation units share it: ransac_batch.hip defines the launch sequence, its host-pointer
-// entry and eacham_graph_verify_ransac (graph_verify.hip) stage its arrays and call it.
+// entry and eacham_graph_verify_ransac (graph_verify.hip) stage its arrays and call it. lmeds_launch.hpp is its LMedS counterpart.
 #pragma once
 
 #include "context.hpp"
 #include "devprim.hpp"
+#include "solve_launch.hpp"
 
 namespace eacham {
 
@@ -20,8 +21,8 @@ struct RansacLaunch {
     bool single;
     float threshold;
     const long long *point_ptr, *sample_ptr;
-    const double *a, *b, *K;     // K: device copy of fx fy cx cy; has_K says whether the caller gave one
-    bool has_K;
+    const double *a, *b;
+    CallK K;
     const int* sample_idx;
     const int *tab_off, *table;  // problem p's budget row begins at table[tab_off[p]] (ransac_budget_row; unread for a problem below m points)
     // scratch of pass 1: P + 1 three times, scan_ws_elems(P + 1); S1 x m (unless single), 9 x S1 x maxm, S1 x 3, 1, scan_ws_elems(S1), S1 x maxm

@@ -1,8 +1,9 @@
 // score_dev.hpp — the device functions of the hypothesis scoring that more than one translation unit runs: the error one
 // model assigns to one correspondence (OpenCV 4.5.5's estimator callbacks, no fused operations), the order-preserving key of
-// a float, the block-wide radix select, the median over it (block_median) and the block's inlier count (block_count). score.hip (eacham_score_hypotheses) and lmeds_batch.hip
-// (eacham_lmeds_batch) inline the same bodies, so a model's errors and median are the same bits through either entry point.
-// Every includer is compiled with -ffp-contract=off (csrc/Makefile).
+// a float, the block-wide radix select, the median over it (block_median) and the block's inlier count (block_count). score.hip
+// (eacham_score_hypotheses), pnp_batch.hip (the PnP rounds) and, through estimator_dev.hpp, lmeds_batch.hip and ransac_batch.hip
+// (the two-view estimators, under the list calls and under graph_verify.hip's) inline the same bodies, so a model's errors and
+// median are the same bits through every entry point. Every includer is compiled with -ffp-contract=off (csrc/Makefile).
 #pragma once
 
 #include <hip/hip_runtime.h>
