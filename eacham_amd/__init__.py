@@ -7,3 +7,4 @@ from .capi import EachamError  # noqa: F401
 from .matcher import FeatureMatcherDotHip, FeatureMatcherHammingHip, FeatureMatcherHip, HipContext, MIN_DIRECTED, MIN_MUTUAL, MIN_SCORE, RATIO  # noqa: F401
 from .graph import ResidentGraph  # noqa: F401
 from .tracks import Tracks, build_tracks  # noqa: F401
+from .guided import GuidedMatches, match_guided  # noqa: F401

@@ -23,6 +23,7 @@ KERNEL_BA_SOLVE = 4
 KERNEL_BA_ERROR = 5
 KERNEL_TRIANGULATE = 6
 KERNEL_SCORE = 7
+KERNEL_MATCH_GUIDED = 8
 SCORE_ESSENTIAL, SCORE_HOMOGRAPHY, SCORE_PNP, SCORE_FUNDAMENTAL = 0, 1, 2, 3
 SOLVE_HOMOGRAPHY4, SOLVE_ESSENTIAL5, SOLVE_FUNDAMENTAL7 = 0, 1, 2
 TWOVIEW_POSES, TWOVIEW_SOLUTIONS = 0, 1
@@ -143,6 +144,10 @@ def lib() -> C.CDLL:
         L.eacham_graph_set_keypoints.argtypes = [vp, vp]
         L.eacham_graph_verify.argtypes = [vp, i32, vp, i32, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.eacham_graph_tracks_verified.argtypes = [vp, i32, i32, i64, i32, C.POINTER(i32), C.POINTER(i64), vp, vp, vp, vp, vp]
+    if hasattr(L, "eacham_match_guided"):  # (likewise)
+        out = [vp, vp, vp, vp, vp, i64, C.POINTER(i64), vp]   # counts, offsets, q, t, d2, cap, total, stats
+        L.eacham_match_guided.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, f32, dbl, C.c_uint32, i32] + out
+        L.eacham_graph_match_guided.argtypes = [vp, i32, vp, vp, f32, dbl, C.c_uint32, i32] + out
     L.eacham_reprojection_errors.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp]
     L.eacham_profile_enable.argtypes = [vp, i32]
     L.eacham_profile_reset.argtypes = [vp]

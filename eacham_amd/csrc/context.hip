@@ -203,7 +203,7 @@ roctx_push_t g_roctx_push = nullptr;
 roctx_pop_t g_roctx_pop = nullptr;
 std::once_flag g_roctx_once;
 const char* const kStageNames[EACHAM_KERNEL_COUNT] = {"eacham.match.tile", "eacham.match.finalize", "eacham.ba.linearize", "eacham.ba.schur",
-                                                      "eacham.ba.solve", "eacham.ba.error", "eacham.triangulate", "eacham.score"};
+                                                      "eacham.ba.solve", "eacham.ba.error", "eacham.triangulate", "eacham.score", "eacham.match.guided"};
 void roctx_init() {
     const char* e = getenv("EACHAM_ROCTX");
     if (!e || !*e || *e == '0') return;
@@ -288,6 +288,7 @@ int eacham_ctx_create(int device_id, eacham_ctx** out_ctx) {
     ctx->device = device_id;
     ctx->match_no_overlap = getenv("EACHAM_NO_OVERLAP") != nullptr;
     if (const char* v = getenv("EACHAM_MATCH_COLPRUNE")) ctx->match_colprune = strcmp(v, "0") != 0;
+    if (const char* v = getenv("EACHAM_GUIDED_SCREEN")) ctx->guided_screen = strcmp(v, "0") != 0;
     if (const char* v = getenv("EACHAM_MATCH_SWEEP_FORM")) ctx->match_sweep_form = !strcmp(v, "exact") ? 1 : !strcmp(v, "bound") ? 2 : !strcmp(v, "screen") ? 3 : 0;
     if (const char* b = getenv("EACHAM_MATCH_BUDGET_MB")) {
         const int v = atoi(b);

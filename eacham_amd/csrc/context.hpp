@@ -176,6 +176,7 @@ struct eacham_ctx {
     int match_sweep_form = 0;         // EACHAM_MATCH_SWEEP_FORM=exact|bound|screen (diagnostic A/B, tests): the lean form's row sweep keeps every row's exact top-2 (1),
                                       // runs its bound form + the exact pass over the rows left open (2), or screens the rows on the FP6 image where the frames
                                       // have one, with the same exact pass (3); 0 = by descriptor dimension (bound up to 128-D, screen above)
+    bool guided_screen = true;        // EACHAM_GUIDED_SCREEN=0 (A/B, tests): match_guided.hip's exact gate runs its divisions for every element, no screen in front
     bool match_colprune = true;       // EACHAM_MATCH_COLPRUNE=0 (A/B, tests): no candidate column is settled from the sweep's row minima, all go to match_colverify_kernel
     int match_budget_mb = 1024;     // EACHAM_MATCH_BUDGET_MB (diagnostic: workspace budget of one batch of pairs), read at create
     bool match_no_overlap = false;  // EACHAM_NO_OVERLAP (diagnostic: finalize on the tile kernel's stream), read at create
@@ -223,6 +224,7 @@ struct eacham_graph {
     // what the geometric verification adds (graph_verify.hip: a PROBLEM is a caller pair, in the caller's order)
     int npairs = 0;                      // caller pairs, those without matches included
     std::vector<int> pair_counts_h;      // [npairs] the caller's counts
+    std::vector<int> pairs_h;            // [npairs x 2] the caller's pairs, those without matches included (match_guided.hip)
     long long* pair_ptr = nullptr;       // [npairs + 1] where each caller pair's matches begin in the packed lists (a pair without matches owns none)
     double* xy = nullptr;                // [n_kp x 2] pixel coordinates (eacham_graph_set_keypoints), an allocation of its own
     bool has_xy = false;
@@ -403,6 +405,7 @@ int run_match_ham_wide(eacham_ctx* ctx, const int2* pairs_dev, int npairs, doubl
                        int4* stats_dev, const int32_t* pairs_host, const int2** pairs_used);
 int ham_wide_debug_pair(eacham_ctx* ctx, int f1, int f2, int32_t* best, int32_t* h0, int32_t* h1, int cap);
 // matcher.hip
+int check_integer_flag(eacham_ctx* ctx);   // the sticky "a descriptor was not an integer" flag of the int8 uploads, read and cleared
 void launch_scan_counts(eacham_ctx* ctx, const int* counts, int n, long long* offsets, long long* total, int first, int is_last);
 void launch_compact_edges(eacham_ctx* ctx, int nb, const uint2* matches, const int* counts, const long long* offsets,
                           int row_stride, uint2* edges, long long edge_cap);

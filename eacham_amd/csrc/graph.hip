@@ -160,6 +160,7 @@ extern "C" int eacham_graph_create(eacham_ctx* ctx, int n_frames, const int32_t*
     g->kp_offsets_h.assign(kp_offsets, kp_offsets + n_frames + 1);
     g->npairs = npairs;
     g->pair_counts_h.assign(counts, counts + npairs);
+    if (npairs > 0) g->pairs_h.assign(pairs, pairs + 2 * (size_t)npairs);
     (void)hipSetDevice(ctx->device);
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 8)); return o; };

@@ -2193,7 +2193,7 @@ static int upload_frame(eacham_ctx* ctx, int frame_id, const float* src_dev, int
     return EACHAM_OK;
 }
 
-static int check_integer_flag(eacham_ctx* ctx) {
+int check_integer_flag(eacham_ctx* ctx) {
     if (ctx->kind_common == FRAME_F32) return EACHAM_OK;  // fp32 frames take any value
     int flag = 0;
     EACHAM_HIP_TRY(ctx, hipMemcpyAsync(&flag, &ctx->flag_dev->not_integer, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));

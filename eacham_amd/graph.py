@@ -118,6 +118,17 @@ class ResidentGraph:
         self._npairs = int(pairs.shape[0])
         ends = offsets[:counts.size] + counts    # (offsets may carry the CSR's closing entry)
         self._n_src = int(ends[counts > 0].max()) if (counts > 0).any() else 0   # the length of a `keep` mask
+        self._query_rows = int(sum(int(kpo[f + 1] - kpo[f]) for f in pairs[:, 0]))   # what a guided re-match of every pair can return at most
+
+    def match_guided(self, kind: str, models, max_error: float, ratio: float | None = None, max_d2: int = 0, cross_check: bool = True,
+                     K=None, cap: int | None = None):
+        """eacham_graph_match_guided: every pair of the graph matched again with only the candidates admitted whose error under
+        the pair's model (models [npairs, 9], as verify() / verify_ransac() returned them) is <= max_error; pairs and keypoints
+        are the graph's (set_keypoints). Returns eacham_amd.guided.GuidedMatches, the wire format a new ResidentGraph takes."""
+        from .guided import graph_match_guided
+        from .matcher import RATIO
+        return graph_match_guided(self.ctx, self._h, self._npairs, self._query_rows if cap is None else int(cap), kind, models, max_error,
+                                  RATIO if ratio is None else ratio, max_d2, cross_check, K)
 
     def set_keypoints(self, xy):
         """eacham_graph_set_keypoints: the pixel coordinates of every keypoint, frame-major ([total keypoints, 2], or a list of

@@ -203,6 +203,11 @@ class HipContext:
                                                         offsets.ctypes.data, q.ctypes.data, t.ctypes.data, cap, C.byref(total)))
         return [dict(zip(q[offsets[p]:offsets[p + 1]].tolist(), t[offsets[p]:offsets[p + 1]].tolist())) for p in range(npairs)]
 
+    def match_guided(self, kind: str, pairs, models, keypoints, max_error: float, **kw):
+        """eacham_match_guided on the resident int8 frames (eacham_amd/guided.py: match_guided has the arguments)."""
+        from .guided import match_guided
+        return match_guided(self, kind, pairs, models, keypoints, max_error, **kw)
+
     # ---- dot-product similarity (float frames), scores returned ----------------------------
     def match_pair_dot(self, f1: int, f2: int, min_score: float = MIN_SCORE):
         """(q, t, scores) of the directed match f1 -> f2: argmax of a.b per row, kept iff the similarity > min_score."""

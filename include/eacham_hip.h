@@ -815,6 +815,56 @@ int eacham_graph_verify_ransac(eacham_graph* graph, int kind, const double* K, i
 int eacham_graph_tracks_verified(eacham_graph* graph, int min_len, int conflict_policy, int64_t cap_obs, int32_t cap_tracks,
                                  int32_t* n_tracks, int64_t* n_obs, int64_t* track_ptr, uint32_t* obs_frame, uint32_t* obs_kp,
                                  uint8_t* track_flags, int32_t* node_track);
+/* ---- guided matching: verified pairs matched again under their two-view model --------------------------------------
+ * The step behind a verification (COLMAP's guided_matching, OpenCV's masked knnMatch): for every pair, match again with
+ * only the candidates admitted that agree with the pair's model. Descriptors are the context's resident int8 frames.
+ *
+ * ADMISSIBLE CANDIDATES. Pair p = (f1, f2) has the model M_p (9 doubles, row-major) of kind EACHAM_SCORE_ESSENTIAL |
+ * EACHAM_SCORE_HOMOGRAPHY | EACHAM_SCORE_FUNDAMENTAL. The candidate (row q of f1, row t of f2) is admissible iff
+ *     err(q, t) <= max_error
+ * where err is the float eacham_score_hypotheses gives the correspondence a = xy1[q], b = xy2[t] under M_p, bit for bit. K:
+ * 4 doubles or NULL for the essential kind (as there), ignored otherwise. max_error is in the error's own unit, as
+ * eacham_ransac_batch's threshold: squared pixels for H and F. +inf is legal and admits everything whose error is a number; a
+ * NaN error is never admissible. The admissible set is ONE bipartite mask per pair and serves both directions: for H it is the
+ * forward transfer error of M_p as given (f1 -> f2), also when f2's rows are the queries.
+ * A pair whose model is all zeros (the estimators' "none" record) has no admissible candidate, by rule.
+ *
+ * DIRECTED MATCH q -> t. Among the admissible t of q, the two nearest by exact squared L2 of the descriptors, ties to the
+ * lower train index:
+ *     no admissible candidate   no match
+ *     exactly one               matched (the runner-up counts as +inf)
+ *     two or more               eacham_match_pair's predicate: (float)(d0 / d1) < ratio, d = sqrtf(d2), the quotient promoted
+ *                               to double; 0 / 0 is NaN and rejected
+ * and in every case, if max_d2 > 0, d2(q, t0) <= max_d2 (max_d2 == 0: no bound). t -> q is the same on the transposed mask.
+ * FEWER THAN 2 TRAIN ROWS are legal here: a lone admissible row matches — unlike eacham_match_pair, whose result is empty
+ * then (the reference would read its second neighbour out of bounds); here the runner-up is defined.
+ *
+ * CROSS-CHECK. cross_check == 0: the result is m12. cross_check != 0: {(q, t) in m12 : m21[t] == q}, and ratio must be in
+ * (0, 1] as for eacham_match_all_pairs. There are no min_dir / min_mutual thresholds: the caller filters.
+ *
+ * eacham_match_guided: kp_offsets / xy in the layout of eacham_graph_create / eacham_graph_set_keypoints (kp_offsets[f] = the
+ * first row of frame f in xy, rows of 2 doubles; read for the frames the pairs name). A frame's keypoint count must equal its
+ * resident row count. Output: CSR over the caller's pairs, sorted by q — exactly the counts / offsets (npairs + 1) / q / t that
+ * eacham_graph_create and eacham_tracks_build take; out_d2 (optional) the uint32 squared distances; stats (optional) npairs x
+ * {|m12|, |m21|, |result|} (|m21| = 0 without the cross-check: that direction is not computed).
+ * eacham_graph_match_guided: pairs and keypoints are those the graph holds (eacham_graph_set_keypoints), models has npairs x 9
+ * entries as eacham_graph_verify[_ransac] wrote them. Byte for byte the list form's result; leaves no state in the graph.
+ *
+ * All checks run on the host before anything is launched or written.
+ * EACHAM_ERR_INVALID: a null required pointer, an unknown kind, a negative size, a NaN or negative max_error, a NaN ratio, a
+ * ratio outside (0, 1] with cross_check, a frame that is not resident, a keypoint count other than the frame's rows (the
+ * message names the frame), keypoints not set (graph form).
+ * EACHAM_ERR_UNSUPPORTED: the resident frames are not int8 frames (fp32, binary and wide binary frames are out of scope).
+ * EACHAM_ERR_CAPACITY: more than cap matches; *out_total holds what is needed and nothing else has been written.
+ * There is no device-pointer form and no sharded form. */
+int eacham_match_guided(eacham_ctx* ctx, int kind, const int32_t* pairs, int npairs, const double* models, const double* K,
+                        const int64_t* kp_offsets, const double* xy, float max_error, double ratio, uint32_t max_d2,
+                        int cross_check, int32_t* counts, int64_t* offsets, uint32_t* out_q, uint32_t* out_t, uint32_t* out_d2,
+                        int64_t cap, int64_t* out_total, int32_t* stats);
+int eacham_graph_match_guided(eacham_graph* graph, int kind, const double* models, const double* K, float max_error, double ratio,
+                              uint32_t max_d2, int cross_check, int32_t* counts, int64_t* offsets, uint32_t* out_q,
+                              uint32_t* out_t, uint32_t* out_d2, int64_t cap, int64_t* out_total, int32_t* stats);
+
 /* Diagnostic: how the context's last track-building call ran (any pointer may be NULL). rounds = hook-and-compress rounds until
  * one changed nothing (that one included; 0 if the call had no kept edge), round_cap = the bound it is held to,
  * 2 * ceil(log2(touched-node bound)) + 1 with the bound min(nodes, 2 x matches), readbacks = device-to-host read-backs of status words (one per batch of rounds, one
@@ -831,7 +881,8 @@ int eacham_tracks_debug_last(eacham_ctx* ctx, int32_t* rounds, int32_t* round_ca
 #define EACHAM_KERNEL_BA_ERROR 5
 #define EACHAM_KERNEL_TRIANGULATE 6     /* pair DLT + scoring and the per-track selection          */
 #define EACHAM_KERNEL_SCORE 7           /* hypothesis scoring (errors, inlier counts, medians)      */
-#define EACHAM_KERNEL_COUNT 8
+#define EACHAM_KERNEL_MATCH_GUIDED 8   /* guided matching: gated sweep + tail (eacham_match_guided)       */
+#define EACHAM_KERNEL_COUNT 9
 
 /* Enables (1) / disables (0) per-launch HIP-event timing of the kernels above. */
 int eacham_profile_enable(eacham_ctx* ctx, int on);
