@@ -384,6 +384,17 @@ class HipContext:
         from . import pnp
         return pnp.pnp_refit_batch(self, X, uv, K, models, has_model, threshold)
 
+    def solve_p3p(self, X, uv, K, samples, want_candidates: bool = True):
+        """eacham_solve_p3p: P3P on every row of `samples` (4 point indices per row: three solve, the fourth picks) (eacham_amd/pnp.py)."""
+        from . import pnp
+        return pnp.solve_p3p(self, X, uv, K, samples, want_candidates)
+
+    def pnp_hypotheses_batch_p3p(self, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True):
+        """eacham_pnp_hypotheses_batch_p3p: one PnP RANSAC round on four-point samples (P3P per sample, its inlier count) for a list of
+        problems, one launch (eacham_amd/pnp.py)."""
+        from . import pnp
+        return pnp.pnp_hypotheses_batch_p3p(self, X, uv, K, samples, threshold, want_models)
+
     def profile_enable(self, on: bool = True):
         self._check(self._L.eacham_profile_enable(self._h, int(on)))
 

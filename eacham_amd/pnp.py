@@ -2,7 +2,9 @@
 RecoverPosePnP's estimator (modules/sfm/reconstruction/ReconstructionManager.cpp:227-228) — for a whole list of (map points,
 pixels) problems: one call per RANSAC round of CHUNK samples for every problem still running, one call for all the refits, and
 the sequential rule replayed per problem on the host in between (pnp_ransac_batch, what SolvePnPRansacBatch of
-include/eacham/PnPHip.hpp does). Drawing the samples stays with the caller. Test / bench driver."""
+include/eacham/PnPHip.hpp does). Drawing the samples stays with the caller. Test / bench driver.
+The P3P form (eacham_solve_p3p / eacham_pnp_hypotheses_batch_p3p; SolvePnPRansacP3P[Batch] of include/eacham/PnPP3PHip.hpp) draws
+four-point samples: solve_p3p, pnp_hypotheses_batch_p3p[_raw] and pnp_ransac_batch(solver="p3p"); the refit stays EPnP."""
 from __future__ import annotations
 
 import ctypes as C
@@ -91,6 +93,54 @@ def pnp_hypotheses_batch(ctx, X, uv, K, samples, threshold: float = 16.0, want_m
     return pnp_hypotheses_batch_raw(ctx, point_ptr, A, B, K, _ptr([len(i) for i in I]), m, _cat(I, (0, m), np.int32), threshold, want_models)
 
 
+def pnp_hypotheses_batch_p3p_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_idx, threshold, want_models=True, n_problems=None):
+    """eacham_pnp_hypotheses_batch_p3p on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
+    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
+    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
+    point_ptr, sample_ptr = as_(point_ptr, np.int64), as_(sample_ptr, np.int64)
+    X, uv, sample_idx = as_(X, np.float64), as_(uv, np.float64), as_(sample_idx, np.int32)
+    K4 = None if K is None else _K4(K)
+    P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
+    S = max(int(sample_ptr[-1]), 0) if sample_ptr is not None and len(sample_ptr) and P > 0 else 0
+    if S > 1 << 28:   # (a table the library is about to refuse: nothing that size is allocated for it)
+        S = 0
+    models = np.zeros((S, 12), np.float64) if want_models else None
+    nm, cnt = np.zeros(S, np.int32), np.zeros(S, np.int32)
+    ctx._check(capi.lib().eacham_pnp_hypotheses_batch_p3p(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(sample_ptr), ptr(sample_idx),
+                                                          float(threshold), ptr(models), ptr(nm), ptr(cnt)))
+    return PnpHypotheses(_seg(models, sample_ptr) if want_models else None, _seg(nm, sample_ptr), _seg(cnt, sample_ptr), point_ptr, sample_ptr)
+
+
+def pnp_hypotheses_batch_p3p(ctx, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True) -> PnpHypotheses:
+    """One RANSAC round on four-point samples: pnp_hypotheses_batch with samples[p] = s_p x 4 rows (three points solve, the fourth picks
+    among the up-to-four poses) and ONE launch for the whole list."""
+    point_ptr, A, B = pack_points(X, uv)
+    I = [np.asarray(s, dtype=np.int32).reshape(-1, 4) for s in samples]
+    if len(I) != len(point_ptr) - 1:
+        raise ValueError("one [s_p, 4] index array per problem")
+    return pnp_hypotheses_batch_p3p_raw(ctx, point_ptr, A, B, K, _ptr([len(i) for i in I]), _cat(I, (0, 4), np.int32), threshold, want_models)
+
+
+def solve_p3p(ctx, X, uv, K, samples, want_candidates: bool = True):
+    """eacham_solve_p3p: every row of `samples` (4 indices into X / uv) -> (models [s, 12] = R | t, n_models [s]) and, when wanted,
+    (candidates [s, 4, 12] in root order, the slots behind the count zero, n_candidates [s])."""
+    vp = C.c_void_p
+    X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
+    uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
+    if len(X) != len(uv):
+        raise ValueError("point lists disagree")
+    idx = np.ascontiguousarray(samples, dtype=np.int32).reshape(-1, 4)
+    K4 = _K4(K)
+    s = idx.shape[0]
+    models, nm = np.zeros((s, 12), np.float64), np.zeros(s, np.int32)
+    cand = np.zeros((s, 4, 12), np.float64) if want_candidates else None
+    nc = np.zeros(s, np.int32) if want_candidates else None
+    ctx._check(capi.lib().eacham_solve_p3p(ctx.handle, len(X), vp(X.ctypes.data), vp(uv.ctypes.data), vp(K4.ctypes.data), s, vp(idx.ctypes.data),
+                                           vp(models.ctypes.data), vp(nm.ctypes.data), vp(cand.ctypes.data) if want_candidates else None,
+                                           vp(nc.ctypes.data) if want_candidates else None))
+    return (models, nm, cand, nc) if want_candidates else (models, nm)
+
+
 def pnp_refit_batch_raw(ctx, point_ptr, X, uv, K, models, has_model, threshold, n_problems=None):
     """eacham_pnp_refit_batch on arrays already in its wire form."""
     ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
@@ -135,15 +185,18 @@ def ransac_update_num_iters(p: float, ep: float, m: int, max_iters: int) -> int:
 
 
 def pnp_ransac_batch(ctx, X, uv, K, samples, max_iters: int, reprojection_error: float = 4.0, confidence: float = 0.999,
-                     hypotheses=None, refit=None):
+                     hypotheses=None, refit=None, solver: str = "epnp"):
     """cv::solvePnPRansac per problem over rounds of CHUNK samples. samples[p]: the stream problem p would draw, in order, s x 5
-    (rows past its end are not drawn: give at least as many as the loop consumes). Returns (results, turns): per problem a dict
+    (rows past its end are not drawn: give at least as many as the loop consumes). solver "p3p": SOLVEPNP_P3P, s x 4 rows, the
+    round is eacham_pnp_hypotheses_batch_p3p and a winner needs 4 inliers; the refit stays EPnP and is kept only where it has 5. Returns (results, turns): per problem a dict
     ok, iterations, winner (sample index, -1: none) and when ok: model, inliers, pose; turns = device calls made (rounds + 1).
     hypotheses / refit: the two calls (default: this context's batched entry points), same signatures as pnp_hypotheses_batch /
     pnp_refit_batch without the context."""
-    hypotheses = hypotheses or (lambda *a: pnp_hypotheses_batch(ctx, *a))
+    if solver not in ("epnp", "p3p"):
+        raise ValueError(f"unknown solver {solver!r}")
+    hypotheses = hypotheses or (lambda *a: (pnp_hypotheses_batch_p3p if solver == "p3p" else pnp_hypotheses_batch)(ctx, *a))
     refit = refit or (lambda *a: pnp_refit_batch(ctx, *a))
-    m = 5
+    m = 4 if solver == "p3p" else 5
     X = [np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in X]
     uv = [np.asarray(x, dtype=np.float64).reshape(-1, 2) for x in uv]
     S = [np.asarray(s, dtype=np.int32).reshape(-1, m) for s in samples]

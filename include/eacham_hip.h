@@ -653,6 +653,60 @@ int eacham_pnp_refit_batch(eacham_ctx* ctx, int n_problems, const int64_t* point
                            const double* image_points, const double* K, const double* models, const uint8_t* has_model,
                            float threshold, uint8_t* inlier_mask, int32_t* n_inliers, double* refit, int32_t* refit_ok);
 
+/* ---- P3P: the PnP RANSAC on its minimal sample ------------------------------------------------------------------------
+ * What cv::solvePnPRansac(..., cv::SOLVEPNP_P3P) draws: FOUR indices per sample — three correspondences give up to four poses,
+ * the fourth picks one. The refit of the winner's inliers stays EPnP (eacham_pnp_refit_batch, unchanged; from memory of OpenCV
+ * 4.5.5, unverified: parity is unpinned here as everywhere). The sample indices are an argument, so what is defined is "these
+ * four correspondences -> this pose". Layouts as eacham_solve_pnp: models = R (row-major) | t, 12 doubles, K = fx fy cx cy.
+ *
+ * THE SOLVER. A sample i0 i1 i2 i3 has object points X0..X3 and pixels x0..x3. fp64 throughout, only + - * / sqrt, fabs, fmax,
+ * fmin, every operation rounded on its own, every sum in the order written (tests/cpp/p3p_reference.c is the CPU restatement;
+ * the kernels give its bytes):
+ *   1. Bearings  y_k = ((u_k - cx) / fx, (v_k - cy) / fy, 1), f_k = y_k / sqrt(y_k . y_k), k = 0, 1, 2.
+ *   2. Triangle  A = |X1 - X2|^2, B = |X0 - X2|^2, C = |X0 - X1|^2; ca = f1 . f2, cb = f0 . f2, cg = f0 . f1.
+ *      DEGENERATE (n_models = 0, a zero model, no error): A, B or C zero or not finite; a bearing not finite; collinear object
+ *      points, |(X1 - X0) x (X2 - X0)|^2 <= 1e-20 B C.
+ *   3. Grunert's quartic in v = s2 / s0 (s_k: the depth along f_k). p = (A - C) / B, q = (A + C) / B, rA = A / B, rC = C / B:
+ *        A4 = (p - 1)^2 - 4 rC ca^2
+ *        A3 = 4 [ p (1 - p) cb - (1 - q) ca cg + 2 rC ca^2 cb ]
+ *        A2 = 2 [ p^2 - 1 + 2 p^2 cb^2 + 2 (1 - rC) ca^2 - 4 q ca cb cg + 2 (1 - rA) cg^2 ]
+ *        A1 = 4 [ -p (1 + p) cb + 2 rA cg^2 cb - (1 - q) ca cg ]
+ *        A0 = (1 + p)^2 - 4 rA cg^2
+ *   4. Its real roots by FUNDAMENTAL7's Durand-Kerner recipe carried to degree <= 4 (degree drop at 1e-14 cmax, monic, start
+ *      values r0 (0.4 + 0.9 i)^k, at most 200 sweeps stopped at a correction of 1e-11 bound, a root is real iff
+ *      |zi| <= 1e-7 (1 + |zr|), four Newton steps on the real polynomial, real roots ascending).
+ *   5. Per real root v, ascending: den = 2 (cg - v ca), skipped if 0; u = [(p - 1) v^2 - 2 p cb v + 1 + p] / den;
+ *      d = 1 + v^2 - 2 v cb, skipped unless > 0; s0 = sqrt(B / d), s1 = u s0, s2 = v s0; then TWO Newton steps on (s0, s1, s2)
+ *      for  s1^2 + s2^2 - 2 s1 s2 ca = A,  s0^2 + s2^2 - 2 s0 s2 cb = B,  s0^2 + s1^2 - 2 s0 s1 cg = C  (Cramer's rule, the
+ *      determinant expanded along the first row; skipped if it is 0 or a depth comes out not finite); skipped unless all three
+ *      depths are > 0. (Without the two steps a near-double root leaves errors of 1e-7 and an occasional missed pose.)
+ *   6. Pose. Q_k = s_k f_k. The frame of a triangle (P0, P1, P2): e1 = (P1 - P0) / |P1 - P0|, e3 = e1 x (P2 - P0) normalised,
+ *      e2 = e3 x e1, as the columns of F(P). R = F(Q) F(X)', t = Q0 - R X0.
+ *   7. The fourth point chooses: the candidate with the FIRST STRICTLY SMALLEST eacham_score_hypotheses(kind PNP) error of
+ *      (X3, x3), in root order; a NaN error never wins; no candidate, or only NaN errors: n_models = 0.
+ * DEVIATION FROM OPENCV: cv's p3p.cpp follows Gao et al. and solves its quartic in closed form; this is Grunert's elimination of
+ * the same three equations with an iterative root finder and a polish of the depths: the same solution set, not the same bits.
+ * Duplicate indices are legal: one among the first three gives a zero side (degenerate); a fourth equal to one of the three is fine.
+ *
+ * eacham_solve_p3p: every row of sample_idx (4 indices into the n_points points) -> models (n_samples x 12) and n_models (1, or
+ * 0 with a zero model). Optional (NULL = not wanted): candidates (n_samples x 4 x 12, every pose of step 5-6 in root order, the
+ * slots behind the count zero) and n_candidates.
+ * EACHAM_ERR_INVALID: a null required argument, a negative size, a sample index outside the points (checked on the host before
+ * anything is launched).
+ *
+ * eacham_pnp_hypotheses_batch_p3p: ONE RANSAC ROUND for every problem of a list in ONE launch — eacham_pnp_hypotheses_batch with
+ * the sample size fixed at 4 and the solver above: same tables, same outputs (models optional), same rules (a problem with no
+ * samples costs nothing; one with fewer than 4 points gets n_models = 0 for all its samples, which are then not looked at).
+ * Bit-identical, output by output, with eacham_solve_p3p on the problem's rows followed by eacham_score_hypotheses(kind PNP)
+ * per problem. Errors: those of eacham_pnp_hypotheses_batch (there is no sample_size to be wrong). */
+int eacham_solve_p3p(eacham_ctx* ctx, int n_points, const double* object_points, const double* image_points, const double* K,
+                     int n_samples, const int32_t* sample_idx, double* models, int32_t* n_models, double* candidates,
+                     int32_t* n_candidates);
+int eacham_pnp_hypotheses_batch_p3p(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                                    const double* image_points, const double* K, const int64_t* sample_ptr,
+                                    const int32_t* sample_idx, float threshold, double* models, int32_t* n_models,
+                                    int32_t* inlier_counts);
+
 /* ---- two-view motion and structure for a whole list of pairs ------------------------------------------------------
  * The second half of RecoverPoseTwoView (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:89-180)
  * for every edge of a match graph in ONE call: what eacham_two_view_points plus the host rules behind it
