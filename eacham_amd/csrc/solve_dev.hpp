@@ -312,7 +312,15 @@ __device__ static int essential5_wave(const double* p1, const double* p2, bool h
     for (int k = 0; k <= 10; ++k) cmax = fmax(cmax, fabs(S.poly[k]));
     if (!(cmax > 0.0)) return 0;
     int deg = 10;
-    while (deg > 0 && fabs(S.poly[deg]) <= 1e-14 * cmax) --deg;
+    for (; deg > 0; --deg) {  // a leading coefficient that puts a root beyond 1e14 counts as zero (solve_oracle.c, real_roots10)
+        double t = fabs(S.poly[deg]);
+        bool beyond = false;
+        for (int k = deg - 1; k >= 0; --k) {
+            t *= 1e14;
+            if (fabs(S.poly[k]) > t) beyond = true;
+        }
+        if (!beyond) break;
+    }
     if (deg == 0) return 0;
     const double lead = S.poly[deg];
     if (lane <= deg) S.mon[lane] = S.poly[lane] / lead;  /* monic */
@@ -325,8 +333,14 @@ __device__ static int essential5_wave(const double* p1, const double* p2, bool h
         double r0 = 1.0;
         const double a0 = fabs(S.mon[0]);
         if (a0 > 0.0) {
-            double y = a0 > 1.0 ? a0 : 1.0;
-            for (int it = 0; it < 80; ++it) {
+            double y = 1.0;  // the first power of two whose deg-th power reaches a0 (why not a0 itself: solve_oracle.c, real_roots10)
+            for (;;) {
+                double yp = 1.0;
+                for (int j = 0; j < deg; ++j) yp *= y;
+                if (!(yp < a0)) break;
+                y *= 2.0;
+            }
+            for (int it = 0; it < 24; ++it) {
                 double yp = 1.0;
                 for (int j = 0; j < deg - 1; ++j) yp *= y;
                 y = ((deg - 1) * y + a0 / yp) / deg;
@@ -345,20 +359,20 @@ __device__ static int essential5_wave(const double* p1, const double* p2, bool h
 #ifndef E5_EXP_DK_SWEEPS
 #define E5_EXP_DK_SWEEPS 200
 #endif
-    // one sweep: this lane's correction from the iterates the sweep starts with. `change <= 1e-11 bound` of the restatement = no
-    // lane's correction above it (a NaN correction is ignored by fmax there and by the comparison here); tolerance and sweep
-    // limit: see the CPU restatement (solve_oracle.c)
-    const double stop = 1e-11 * bound;
+    // one sweep: this lane's correction from the iterates the sweep starts with. The sweeps end when no lane's correction exceeds
+    // 1e-11 (1 + |zr| + |zi|) of the iterate it was computed from: every lane tests its own root (a NaN correction asks for no
+    // further sweep, there and here); why per root and not against the root bound, and the sweep limit: see the CPU
+    // restatement (solve_oracle.c, real_roots10)
     auto correct = [&](double pr, double pi, double dr, double di) {
         const double den = dr * dr + di * di;
-        double ch = 0.0;
+        bool more = false;
         if (mine && den > 0.0) {
             const double qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
+            more = fabs(qr) + fabs(qi) > 1e-11 * (1.0 + fabs(zr) + fabs(zi));
             zr -= qr;
             zi -= qi;
-            ch = fabs(qr) + fabs(qi);
         }
-        return __ballot(ch > stop) == 0ull;
+        return __ballot(more) == 0ull;
     };
     if (deg == 10) {  // the usual case: coefficients in registers, the other iterates by v_readlane with constant lanes
         double mm[10];
@@ -778,7 +792,8 @@ __device__ static int homography4_wave(const double* a, const double* b, double*
  * coordinate is not finite), when the cubic is all zero, or when no real root is left; a root whose model has no finite positive
  * norm is squeezed out.
  *
- * real_roots3: the Durand-Kerner recipe of essential5_wave / real_roots10 (solve_oracle.c) for degree <= 3, run sequentially:
+ * real_roots3: the Durand-Kerner recipe essential5_wave / real_roots10 (solve_oracle.c) had when this kind was added, for degree <= 3,
+ * run sequentially (the five-point solver has since changed its degree drop, start and stop test; this copy keeps the recipe below):
  * degree drop at 1e-14 cmax, monic, the start values r0 (0.4 + 0.9 i)^k with r0 = |m0|^(1/deg) by 80 Newton steps clamped to
  * [0.5, bound], at most 200 simultaneous sweeps stopped at a largest correction of 1e-11 bound, a root is real iff
  * |zi| <= 1e-7 (1 + |zr|), four Newton steps on the real polynomial, real roots ascending (equals in iterate order).

@@ -528,7 +528,7 @@ int eacham_score_hypotheses(eacham_ctx* ctx, int kind, int n_points, const doubl
  *                          eigen-solver on A'A (the homography's), which squares the condition number and needs the normalisation.
  *                       2. A model has unit Frobenius norm after denormalisation (as ESSENTIAL5's), not F[8] = 1.
  *                     Null space: f2 = eigenvector of the smallest eigenvalue, f1 = that of the second smallest, minus f2; the
- *                     cubic det(z f1 + f2) by run7Point's c[] expressions; its roots by ESSENTIAL5's Durand-Kerner recipe (degree
+ *                     cubic det(z f1 + f2) by run7Point's c[] expressions; its roots by a Durand-Kerner recipe of its own (degree
  *                     drop at 1e-14 cmax, a root is real iff |zi| <= 1e-7 (1 + |zr|), four Newton steps, real roots ascending).
  *                     A degenerate sample is no error: n_models = 0 and zero models when a normalisation scale is not finite (all
  *                     points of one image coincide), the cubic is all zero or no real root is left. */

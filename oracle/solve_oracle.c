@@ -227,7 +227,22 @@ static int real_roots10(const double* c, double* roots) {
     double cmax = 0.0;
     for (int k = 0; k <= 10; ++k) cmax = fmax(cmax, fabs(c[k]));
     if (!(cmax > 0.0)) return 0;
+#ifdef SOLVE_ORACLE_ROOTS_BEFORE
     while (deg > 0 && fabs(c[deg]) <= 1e-14 * cmax) --deg;
+#else
+    /* A leading coefficient counts as zero when it would put a root beyond 1e14: some |c[k]| above |c[deg]| 1e14^(deg - k)
+     * (the elementary symmetric functions of the roots). It used to be held against 1e-14 of the LARGEST coefficient, which
+     * large roots alone push up: roots of magnitude 40..400 gave |c[0] / c[10]| = 8e15 and the polynomial lost its degree. */
+    for (; deg > 0; --deg) {
+        double t = fabs(c[deg]);
+        int beyond = 0;
+        for (int k = deg - 1; k >= 0; --k) {
+            t *= 1e14;  /* (overflows to +inf at worst: nothing is above that) */
+            if (fabs(c[k]) > t) beyond = 1;
+        }
+        if (!beyond) break;
+    }
+#endif
     if (deg == 0) return 0;
     double m[11];  /* monic */
     for (int k = 0; k <= deg; ++k) m[k] = c[k] / c[deg];
@@ -235,14 +250,32 @@ static int real_roots10(const double* c, double* roots) {
     for (int k = 0; k < deg; ++k) bound = fmax(bound, fabs(m[k]));
     bound += 1.0;
     /* Durand-Kerner from the powers of 0.4 + 0.9 i scaled to the geometric mean of the root magnitudes |m0|^(1/deg)
-     * (Newton's iteration for the deg-th root: only + - * /, so that every build computes the same bits) */
+     * (Newton's iteration for the deg-th root: only + - * /, so that every build computes the same bits). The iteration starts
+     * from the first power of two whose deg-th power reaches |m0|. (It used to start from |m0| itself: far above the root a
+     * step only takes 1 / deg off, 80 steps had not arrived for |m0| > 1e4, and the sweeps below began on a circle of radius
+     * 1e10 and more — 1.8e12 for roots of magnitude 40 — and spent their 200 on walking in.) */
     double zr[10], zi[10];
     {
         double r0 = 1.0;
         const double a0 = fabs(m[0]);
         if (a0 > 0.0) {
+#ifdef SOLVE_ORACLE_ROOTS_BEFORE
             double y = a0 > 1.0 ? a0 : 1.0;
+#else
+            double y = 1.0;
+            for (;;) {
+                double yp = 1.0;
+                for (int j = 0; j < deg; ++j) yp *= y;
+                if (!(yp < a0)) break;  /* (an overflowing power ends the loop as well) */
+                y *= 2.0;
+            }
+#endif
+            /* from at most twice the root 12 steps arrive; from 1 down to a root in [0.5, 1) as many; a smaller root is clamped below */
+#ifdef SOLVE_ORACLE_ROOTS_BEFORE
             for (int it = 0; it < 80; ++it) {
+#else
+            for (int it = 0; it < 24; ++it) {
+#endif
                 double yp = 1.0;
                 for (int j = 0; j < deg - 1; ++j) yp *= y;
                 y = ((deg - 1) * y + a0 / yp) / deg;
@@ -262,12 +295,21 @@ static int real_roots10(const double* c, double* roots) {
      * the ten corrections are independent of each other — the device solver computes them on ten lanes of a wave
      * (eacham_amd/csrc/solve.hip) and this restatement defines the same arithmetic. (Until round 4 both used the
      * Gauss-Seidel form, a correction seeing the corrections before it: one more dependency per root, no better a result.)
-     * The sweeps stop at a correction of 1e-11 of the root bound, at most 200 of them: the real roots are polished by Newton's
-     * iteration on the real polynomial right below (quadratic: one step from 1e-11 is machine precision), and clustered roots,
-     * which converge linearly and never reach 1e-15 — 3.6 % of the samples of a two-view scene ran the old limit of 600 sweeps
-     * to its end — are not solutions anybody wants to wait for. */
+     * A sweep ends the iteration when no root's correction |qr| + |qi| exceeds 1e-11 (1 + |zr_k| + |zi_k|), measured on the iterate
+     * the correction was computed from; at most 200 sweeps. The test is PER ROOT and relative to that root. Until the five-point
+     * reference (tests/essential5_mp_reference.py) the largest correction was held against 1e-11 (1 + max |monic coefficient|):
+     * on a near-planar scene or a short baseline the roots span 1e0..1e4, that bound is 5e8..2e12, and the sweeps stopped at
+     * corrections of 5e-3..20 — roots of magnitude 2 still carried imaginary parts far above the real test below and were
+     * dropped (odd numbers of real roots, 2..3 of 64 samples of such scenes lost solutions; docs/HISTORY.md). The real roots
+     * are polished by Newton's iteration on the real polynomial right below (quadratic: one step from a relative 1e-11 is
+     * machine precision), and clustered roots, which converge linearly and never reach 1e-15 — 3.6 % of the samples of a
+     * two-view scene ran an old limit of 600 sweeps to its end — are not solutions anybody wants to wait for: the cap stays.
+     * Roots spread over 1e-2..1e4 take 120..170 sweeps from the start circle above (tests/test_essential5_reference.py).
+     * SOLVE_ORACLE_ROOTS_BEFORE compiles the former degree drop, start and stop test, for
+     * tests/golden/make_essential5_golden.py alone: it counts the samples of its fixture on which they lost solutions. */
     for (int it = 0; it < 200; ++it) {
-        double change = 0.0, nzr[10], nzi[10];
+        int more = 0;
+        double nzr[10], nzi[10];
         for (int k = 0; k < deg; ++k) {
             double pr = 1.0, pi = 0.0;  /* Horner on the monic polynomial */
             for (int j = deg - 1; j >= 0; --j) {
@@ -287,10 +329,14 @@ static int real_roots10(const double* c, double* roots) {
             const double qr = (pr * dr + pi * di) / den, qi = (pi * dr - pr * di) / den;
             nzr[k] = zr[k] - qr;
             nzi[k] = zi[k] - qi;
-            change = fmax(change, fabs(qr) + fabs(qi));
+#ifdef SOLVE_ORACLE_ROOTS_BEFORE
+            if (fabs(qr) + fabs(qi) > 1e-11 * bound) more = 1;
+#else
+            if (fabs(qr) + fabs(qi) > 1e-11 * (1.0 + fabs(zr[k]) + fabs(zi[k]))) more = 1;  /* (a NaN correction does not ask for more) */
+#endif
         }
         for (int k = 0; k < deg; ++k) zr[k] = nzr[k], zi[k] = nzi[k];
-        if (change <= 1e-11 * bound) break;
+        if (!more) break;
     }
     int n = 0;
     for (int k = 0; k < deg; ++k) {
