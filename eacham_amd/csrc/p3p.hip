@@ -8,18 +8,18 @@
 //                                                       state: 10 000 samples are 157 waves), optionally every candidate
 //   eacham_pnp_hypotheses_batch_p3p   p3p_count_kernel  a WAVE per sample, SOLVE_WAVES per workgroup (the shape of pb_count_kernel):
 //                                                       the sample's problem by prim::segment_of in sample_ptr, the solve on every
-//                                                       lane (identical values, so the candidates run in a row), then score_one<PNP>
-//                                                       over the problem's own points, a ballot and a popcount per 64 points, with the
-//                                                       model passed from the solve to the count in registers. One RANSAC round is
-//                                                       ONE launch and no scratch array, where EPnP's is three launches and two.
-// The refit of the winner's inliers stays EPnP (eacham_pnp_refit_batch, pnp_batch.hip), as in OpenCV.
+//                                                       lane (identical values, so the candidates run in a row), then the count
+//                                                       pb_count_kernel makes (pnp_count, pnp_dev.hpp) over the problem's own points,
+//                                                       with the model passed from the solve to the count in registers. One RANSAC
+//                                                       round is ONE launch and no scratch array, where EPnP's is three launches and two.
+// The entry's checks and staging are eacham_pnp_hypotheses_batch's (PnpHypCall, solve_launch.hpp). The refit of the winner's inliers
+// stays EPnP (eacham_pnp_refit_batch, pnp_batch.hip), as in OpenCV.
 #include "context.hpp"
 #include "devprim.hpp"
 #include "p3p_dev.hpp"
+#include "pnp_dev.hpp"
 #include "solve_dev.hpp"
 #include "solve_launch.hpp"
-
-#include <climits>
 
 namespace eacham {
 namespace {
@@ -76,36 +76,9 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void p3p_count_kernel(SolveSeg se
         int nc = 0;
         have = p3p_sample(X, x, K, M, nullptr, &nc);
     }
-    if (models && lane < 12) {   // (identical values in every lane: entry `lane` by selection)
-        double v = 0.0;
-#pragma unroll
-        for (int k = 0; k < 12; ++k)
-            if (k == lane) v = M[k];
-        models[12 * (size_t)s + lane] = v;
-    }
-    int c = 0;
-    if (have) {   // (wave-uniform)
-        for (int i0 = 0; i0 < n; i0 += 64) {   // (every lane takes every trip: the ballot sees the whole wave)
-            const int i = i0 + lane;
-            bool in = false;
-            if (i < n) {
-                const double P[3] = {pa[3 * (size_t)i], pa[3 * (size_t)i + 1], pa[3 * (size_t)i + 2]}, u[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
-                in = score_one<2>(P, u, M, K, false) <= threshold;
-            }
-            c += __popcll(__ballot(in));
-        }
-    }
+    if (models) pnp_write_model(lane, M, models + 12 * (size_t)s);   // (identical values in every lane)
+    const int c = have ? pnp_count(lane, pa, pb, n, M, K, threshold) : 0;   // (wave-uniform)
     if (lane == 0) n_models[s] = have, counts[s] = c;
-}
-
-// The table checks of eacham_pnp_hypotheses_batch (pnp_batch.hip), in its wording.
-int check_table(eacham_ctx* ctx, const char* call, const char* what, int n_problems, const int64_t* ptr) {
-    if (!ptr) return ctx->fail(EACHAM_ERR_INVALID, "%s: null %s", call, what);
-    if (ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: %s does not start at 0", call, what);
-    for (int p = 0; p < n_problems; ++p)
-        if (ptr[p + 1] < ptr[p]) return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: %s decreases", call, p, what);
-    if (ptr[n_problems] > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %s ends at %lld: more than 2^31 - 1 in one call", call, what, (long long)ptr[n_problems]);
-    return EACHAM_OK;
 }
 
 }  // namespace
@@ -152,34 +125,20 @@ extern "C" int eacham_pnp_hypotheses_batch_p3p(eacham_ctx* ctx, int n_problems, 
     const char* call = "pnp_hypotheses_batch_p3p";
     if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative number of problems", call);
     if (n_problems == 0) return EACHAM_OK;
-    const int P = n_problems, m = 4;
-    if (int rc = check_table(ctx, call, "point_ptr", P, point_ptr)) return rc;
-    if (int rc = check_table(ctx, call, "sample_ptr", P, sample_ptr)) return rc;
-    const long long NP = point_ptr[P], S = sample_ptr[P];
-    if (!K || (NP > 0 && (!object_points || !image_points)) || (S > 0 && (!sample_idx || !n_models || !inlier_counts)))
-        return ctx->fail(EACHAM_ERR_INVALID, "%s: null array", call);
-    for (int p = 0; p < P; ++p) {
-        const long long n = point_ptr[p + 1] - point_ptr[p];
-        if (n < m) continue;   // its samples are not looked at: each gets n_models = 0
-        if (int rc = check_sample_idx(ctx, call, p, sample_idx + sample_ptr[p] * m, (sample_ptr[p + 1] - sample_ptr[p]) * m, n)) return rc;
-    }
-    if (S == 0) return EACHAM_OK;
+    PnpHypCall c{n_problems, 4, point_ptr, object_points, image_points, K, sample_ptr, sample_idx, models, n_models, inlier_counts};
+    if (int rc = c.check(ctx, call)) return rc;
+    if (c.S == 0) return EACHAM_OK;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
-    const auto h_m = io.out<double>(models, models ? 12 * (size_t)S : 0);
-    const auto h_n = io.out<int>(n_models, (size_t)S), h_c = io.out<int>(inlier_counts, (size_t)S);
-    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
-    const auto h_K = io.in<double>(K, 4);
-    const auto h_a = io.in<double>(object_points, 3 * (size_t)NP), h_b = io.in<double>(image_points, 2 * (size_t)NP);
-    const auto h_i = io.in<int>(sample_idx, (size_t)S * m);
+    c.stage(io);
     IoDev d;
     if (int rc = io.upload(d)) return rc;
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
-        const unsigned gw = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
-        p3p_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(SolveSeg{d(h_pp), d(h_sp), P, nullptr}, d(h_a), d(h_b), d(h_K), (int)S, d(h_i), threshold,
-                                                         models ? d(h_m) : nullptr, d(h_n), d(h_c));
+        const unsigned gw = (unsigned)((c.S + SOLVE_WAVES - 1) / SOLVE_WAVES);
+        p3p_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(SolveSeg{d(c.h_pp), d(c.h_sp), c.P, nullptr}, d(c.h_a), d(c.h_b), d(c.h_K), (int)c.S,
+                                                         d(c.h_i), threshold, models ? d(c.h_m) : nullptr, d(c.h_n), d(c.h_c));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     return io.finish();

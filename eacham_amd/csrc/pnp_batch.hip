@@ -9,21 +9,22 @@
 //                   kernels eacham_solve_pnp launches, not a copy of them — on the sample's own problem, found by a binary search in
 //                   sample_ptr (left in sample_problem[])
 //   pb_count        a wave per sample: the first strictly smallest error of the three starts (pnp_first_smallest, solve_dev.hpp)
-//                   gives the model; score_one<PNP> over the problem's own points, a ballot and a popcount per 64 points,
-//                   gives its inlier count. The model passes from the choice to the count in registers.
+//                   gives the model; pnp_count (pnp_dev.hpp: score_one<PNP> over the problem's own points, a ballot and a popcount
+//                   per 64 points — the count p3p_count_kernel of p3p.hip makes too) gives its inlier count. The model passes
+//                   from the choice to the count in registers.
 // eacham_pnp_refit_batch — the tail of solvePnPRansac:
 //   pb_refit        a workgroup per problem: scores the model, writes the mask, compacts the inlier indices IN ASCENDING ORDER
 //                   into the problem's own row of a workspace (ballot prefix: EPnP's sums run in row order), then
 //                   pnp_refit_body (solve_dev.hpp: the function solve_pnp_big_kernel runs) on that row — for every size of the
 //                   inlier set: with at most 64 rows a lane holds one term and the partials are added in lane order, which is the
 //                   sequential sum of the at-most-64-point form term by term.
+// The hypotheses entry's checks and staging from the tables on are PnpHypCall's (solve_launch.hpp), shared with the P3P entry.
 #include "context.hpp"
-#include "score_dev.hpp"
+#include "pnp_dev.hpp"
 #include "solve_dev.hpp"
 #include "solve_launch.hpp"
 
 #include <algorithm>
-#include <climits>
 
 namespace eacham {
 namespace {
@@ -49,17 +50,7 @@ __global__ __launch_bounds__(64 * SOLVE_WAVES) void pb_count_kernel(const long l
         const double K[4] = {Kdev[0], Kdev[1], Kdev[2], Kdev[3]};
         const long long base = point_ptr[sample_problem[s]];
         const int n = (int)(point_ptr[sample_problem[s] + 1] - base);
-        const double* pa = obj + 3 * base;
-        const double* pb = img + 2 * base;
-        for (int i0 = 0; i0 < n; i0 += 64) {   // (every lane takes every trip: the ballot sees the whole wave)
-            const int i = i0 + lane;
-            bool in = false;
-            if (i < n) {
-                const double X[3] = {pa[3 * (size_t)i], pa[3 * (size_t)i + 1], pa[3 * (size_t)i + 2]}, x[2] = {pb[2 * (size_t)i], pb[2 * (size_t)i + 1]};
-                in = score_one<2>(X, x, M, K, false) <= threshold;
-            }
-            c += __popcll(__ballot(in));
-        }
+        c = pnp_count(lane, obj + 3 * base, img + 2 * base, n, M, K, threshold);
     }
     if (lane == 0) n_models[s] = which >= 0 ? 1 : 0, counts[s] = c;
 }
@@ -86,11 +77,7 @@ __global__ __launch_bounds__(PB_REFIT_BLOCK) void pb_refit_kernel(const long lon
     int m = 0;   // inliers so far = where the next trip's first inlier goes
     for (int i0 = 0; i0 < n; i0 += PB_REFIT_BLOCK) {   // (every thread takes every trip)
         const int i = i0 + (int)threadIdx.x;
-        bool in = false;
-        if (has && i < n) {
-            const double X[3] = {obj[3 * (size_t)i], obj[3 * (size_t)i + 1], obj[3 * (size_t)i + 2]}, x[2] = {img[2 * (size_t)i], img[2 * (size_t)i + 1]};
-            in = score_one<2>(X, x, M, K4, false) <= threshold;
-        }
+        const bool in = has && i < n && pnp_inlier(obj, img, i, M, K4, threshold);
         if (i < n) mask[base + i] = in;
         const unsigned long long b = __ballot(in);
         if (lane == 0) wcnt[wave] = __popcll(b);
@@ -114,16 +101,6 @@ __global__ __launch_bounds__(PB_REFIT_BLOCK) void pb_refit_kernel(const long lon
     }
 }
 
-// The checks both entry points share, before anything is launched. Returns EACHAM_OK with *total = ptr[n_problems].
-int check_table(eacham_ctx* ctx, const char* call, const char* what, int n_problems, const int64_t* ptr) {
-    if (!ptr) return ctx->fail(EACHAM_ERR_INVALID, "%s: null %s", call, what);
-    if (ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: %s does not start at 0", call, what);
-    for (int p = 0; p < n_problems; ++p)
-        if (ptr[p + 1] < ptr[p]) return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: %s decreases", call, p, what);
-    if (ptr[n_problems] > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %s ends at %lld: more than 2^31 - 1 in one call", call, what, (long long)ptr[n_problems]);
-    return EACHAM_OK;
-}
-
 }  // namespace
 }  // namespace eacham
 
@@ -139,27 +116,14 @@ extern "C" int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, cons
     if (n_problems < 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: negative number of problems", call);
     if (sample_size < 5 || sample_size > 64) return ctx->fail(EACHAM_ERR_INVALID, "%s: sample_size %d outside 5..64", call, sample_size);
     if (n_problems == 0) return EACHAM_OK;
-    const int P = n_problems, m = sample_size;
-    if (int rc = check_table(ctx, call, "point_ptr", P, point_ptr)) return rc;
-    if (int rc = check_table(ctx, call, "sample_ptr", P, sample_ptr)) return rc;
-    const long long NP = point_ptr[P], S = sample_ptr[P];
-    if (!K || (NP > 0 && (!object_points || !image_points)) || (S > 0 && (!sample_idx || !n_models || !inlier_counts)))
-        return ctx->fail(EACHAM_ERR_INVALID, "%s: null array", call);
-    for (int p = 0; p < P; ++p) {
-        const long long n = point_ptr[p + 1] - point_ptr[p];
-        if (n < m) continue;   // its samples are not looked at: each gets n_models = 0
-        if (int rc = check_sample_idx(ctx, call, p, sample_idx + sample_ptr[p] * m, (sample_ptr[p + 1] - sample_ptr[p]) * m, n)) return rc;
-    }
+    PnpHypCall c{n_problems, sample_size, point_ptr, object_points, image_points, K, sample_ptr, sample_idx, models, n_models, inlier_counts};
+    if (int rc = c.check(ctx, call)) return rc;
+    const long long S = c.S;
     if (S == 0) return EACHAM_OK;
     EACHAM_HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = ctx->stream;
     IoStage io(ctx, st);
-    const auto h_m = io.out<double>(models, models ? 12 * (size_t)S : 0);
-    const auto h_n = io.out<int>(n_models, (size_t)S), h_c = io.out<int>(inlier_counts, (size_t)S);
-    const auto h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
-    const auto h_K = io.in<double>(K, 4);
-    const auto h_a = io.in<double>(object_points, 3 * (size_t)NP), h_b = io.in<double>(image_points, 2 * (size_t)NP);
-    const auto h_i = io.in<int>(sample_idx, (size_t)S * m);
+    c.stage(io);
     const auto h_f = io.scratch<double>(PNP_FRAME * (size_t)S);   // the samples' frames between the front and the back half
     const auto h_t = io.scratch<double>(3 * 13 * (size_t)S);      // error + pose of the three starts
     const auto h_sprob = io.scratch<int>((size_t)S);
@@ -168,9 +132,9 @@ extern "C" int eacham_pnp_hypotheses_batch(eacham_ctx* ctx, int n_problems, cons
     {
         ProfileScope scope(ctx, EACHAM_KERNEL_SCORE);
         const unsigned gw = (unsigned)((S + SOLVE_WAVES - 1) / SOLVE_WAVES);
-        solve_pnp_launch(st, PnpLaunch{SolveSeg{d(h_pp), d(h_sp), P, d(h_sprob)}, d(h_a), d(h_b), d(h_K), m, (int)S, d(h_i), d(h_f), d(h_t)});
-        pb_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(d(h_pp), d(h_a), d(h_b), d(h_K), (int)S, d(h_sprob), d(h_t), threshold,
-                                                         models ? d(h_m) : nullptr, d(h_n), d(h_c));
+        solve_pnp_launch(st, PnpLaunch{SolveSeg{d(c.h_pp), d(c.h_sp), c.P, d(h_sprob)}, d(c.h_a), d(c.h_b), d(c.h_K), c.m, (int)S, d(c.h_i), d(h_f), d(h_t)});
+        pb_count_kernel<<<gw, 64 * SOLVE_WAVES, 0, st>>>(d(c.h_pp), d(c.h_a), d(c.h_b), d(c.h_K), (int)S, d(h_sprob), d(h_t), threshold,
+                                                         models ? d(c.h_m) : nullptr, d(c.h_n), d(c.h_c));
     }
     EACHAM_HIP_TRY(ctx, hipGetLastError());
     return io.finish();

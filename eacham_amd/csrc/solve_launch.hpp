@@ -2,7 +2,8 @@
 // template with a one-problem and a list instantiation, and eacham_solve_minimal / eacham_solve_pnp (solve.hip), lmeds_launch
 // (lmeds_batch.hip), rb_pass (ransac_batch.hip) and eacham_pnp_hypotheses_batch (pnp_batch.hip) go through the two functions below on
 // device pointers. With them, what the estimators above the solver share on the host: the kind dispatcher (with_solve_kind), the
-// call's K (CallK), and the entry check and input staging of the two list calls (check_list_call, ListCall).
+// call's K (CallK), the entry check and input staging of the two two-view list calls (check_list_call, ListCall) and of the two PnP
+// hypotheses calls (PnpHypCall, with the PnP calls' table check, check_table).
 #pragma once
 
 #include "context.hpp"
@@ -123,5 +124,55 @@ inline int check_list_call(eacham_ctx* ctx, const char* call, int kind, int n_pr
     }
     return EACHAM_OK;
 }
+
+// One offset table of a PnP list call (eacham_pnp_hypotheses_batch[_p3p], eacham_pnp_refit_batch): given, from 0, never decreasing, its
+// end within an int.
+inline int check_table(eacham_ctx* ctx, const char* call, const char* what, int n_problems, const int64_t* ptr) {
+    if (!ptr) return ctx->fail(EACHAM_ERR_INVALID, "%s: null %s", call, what);
+    if (ptr[0] != 0) return ctx->fail(EACHAM_ERR_INVALID, "%s: %s does not start at 0", call, what);
+    for (int p = 0; p < n_problems; ++p)
+        if (ptr[p + 1] < ptr[p]) return ctx->fail(EACHAM_ERR_INVALID, "%s: problem %d: %s decreases", call, p, what);
+    if (ptr[n_problems] > INT_MAX) return ctx->fail(EACHAM_ERR_CAPACITY, "%s: %s ends at %lld: more than 2^31 - 1 in one call", call, what, (long long)ptr[n_problems]);
+    return EACHAM_OK;
+}
+
+// eacham_pnp_hypotheses_batch / eacham_pnp_hypotheses_batch_p3p from the tables on: the caller's arguments (P > 0 problems, samples of m
+// points: the entry's own checks come first), check() — the tables, the null arrays, every sample index of a problem that has a
+// sample's worth of points, in that order and wording; it leaves the totals NP and S — and stage(): the nine arrays on the call's
+// IoStage in the order they always were, the three results, the tables and K, the points, the sample indices.
+struct PnpHypCall {
+    int P, m;
+    const int64_t* point_ptr;
+    const double *obj, *img, *K;
+    const int64_t* sample_ptr;
+    const int32_t* sample_idx;
+    double* models;   // may be null (not wanted)
+    int32_t *n_models, *counts;
+    long long NP = 0, S = 0;   // points and samples of the whole call
+    IoArray<double> h_m, h_K, h_a, h_b;
+    IoArray<int> h_n, h_c, h_i;
+    IoArray<long long> h_pp, h_sp;
+    int check(eacham_ctx* ctx, const char* call) {
+        if (int rc = check_table(ctx, call, "point_ptr", P, point_ptr)) return rc;
+        if (int rc = check_table(ctx, call, "sample_ptr", P, sample_ptr)) return rc;
+        NP = point_ptr[P], S = sample_ptr[P];
+        if (!K || (NP > 0 && (!obj || !img)) || (S > 0 && (!sample_idx || !n_models || !counts)))
+            return ctx->fail(EACHAM_ERR_INVALID, "%s: null array", call);
+        for (int p = 0; p < P; ++p) {
+            const long long n = point_ptr[p + 1] - point_ptr[p];
+            if (n < m) continue;   // its samples are not looked at: each gets n_models = 0
+            if (int rc = check_sample_idx(ctx, call, p, sample_idx + sample_ptr[p] * m, (sample_ptr[p + 1] - sample_ptr[p]) * m, n)) return rc;
+        }
+        return EACHAM_OK;
+    }
+    void stage(IoStage& io) {
+        h_m = io.out<double>(models, models ? 12 * (size_t)S : 0);
+        h_n = io.out<int>(n_models, (size_t)S), h_c = io.out<int>(counts, (size_t)S);
+        h_pp = io.in<long long>(point_ptr, (size_t)P + 1), h_sp = io.in<long long>(sample_ptr, (size_t)P + 1);
+        h_K = io.in<double>(K, 4);
+        h_a = io.in<double>(obj, 3 * (size_t)NP), h_b = io.in<double>(img, 2 * (size_t)NP);
+        h_i = io.in<int>(sample_idx, (size_t)S * m);
+    }
+};
 
 }  // namespace eacham

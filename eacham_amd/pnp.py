@@ -62,12 +62,14 @@ def _seg(x, t):
     return [x[int(t[p]):int(t[p + 1])] for p in range(len(t) - 1)]
 
 
-def pnp_hypotheses_batch_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_size, sample_idx, threshold, want_models=True, n_problems=None):
-    """eacham_pnp_hypotheses_batch on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
-    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
-    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
-    point_ptr, sample_ptr = as_(point_ptr, np.int64), as_(sample_ptr, np.int64)
-    X, uv, sample_idx = as_(X, np.float64), as_(uv, np.float64), as_(sample_idx, np.int32)
+_vp = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731  (a raw call's array, or its NULL)
+_as = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
+
+
+def _hypotheses_raw(entry, ctx, point_ptr, X, uv, K, sample_ptr, sample_size, sample_idx, threshold, want_models, n_problems):
+    """Either hypotheses entry on arrays already in its wire form; sample_size None: the entry has no such argument (P3P)."""
+    point_ptr, sample_ptr = _as(point_ptr, np.int64), _as(sample_ptr, np.int64)
+    X, uv, sample_idx = _as(X, np.float64), _as(uv, np.float64), _as(sample_idx, np.int32)
     K4 = None if K is None else _K4(K)
     P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
     S = max(int(sample_ptr[-1]), 0) if sample_ptr is not None and len(sample_ptr) and P > 0 else 0
@@ -75,9 +77,15 @@ def pnp_hypotheses_batch_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_size, 
         S = 0
     models = np.zeros((S, 12), np.float64) if want_models else None
     nm, cnt = np.zeros(S, np.int32), np.zeros(S, np.int32)
-    ctx._check(capi.lib().eacham_pnp_hypotheses_batch(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(sample_ptr), int(sample_size),
-                                                      ptr(sample_idx), float(threshold), ptr(models), ptr(nm), ptr(cnt)))
+    m = () if sample_size is None else (int(sample_size),)
+    ctx._check(getattr(capi.lib(), entry)(ctx.handle, P, _vp(point_ptr), _vp(X), _vp(uv), _vp(K4), _vp(sample_ptr), *m, _vp(sample_idx),
+                                          float(threshold), _vp(models), _vp(nm), _vp(cnt)))
     return PnpHypotheses(_seg(models, sample_ptr) if want_models else None, _seg(nm, sample_ptr), _seg(cnt, sample_ptr), point_ptr, sample_ptr)
+
+
+def pnp_hypotheses_batch_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_size, sample_idx, threshold, want_models=True, n_problems=None):
+    """eacham_pnp_hypotheses_batch on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
+    return _hypotheses_raw("eacham_pnp_hypotheses_batch", ctx, point_ptr, X, uv, K, sample_ptr, sample_size, sample_idx, threshold, want_models, n_problems)
 
 
 def pnp_hypotheses_batch(ctx, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True) -> PnpHypotheses:
@@ -95,20 +103,7 @@ def pnp_hypotheses_batch(ctx, X, uv, K, samples, threshold: float = 16.0, want_m
 
 def pnp_hypotheses_batch_p3p_raw(ctx, point_ptr, X, uv, K, sample_ptr, sample_idx, threshold, want_models=True, n_problems=None):
     """eacham_pnp_hypotheses_batch_p3p on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
-    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
-    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
-    point_ptr, sample_ptr = as_(point_ptr, np.int64), as_(sample_ptr, np.int64)
-    X, uv, sample_idx = as_(X, np.float64), as_(uv, np.float64), as_(sample_idx, np.int32)
-    K4 = None if K is None else _K4(K)
-    P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
-    S = max(int(sample_ptr[-1]), 0) if sample_ptr is not None and len(sample_ptr) and P > 0 else 0
-    if S > 1 << 28:   # (a table the library is about to refuse: nothing that size is allocated for it)
-        S = 0
-    models = np.zeros((S, 12), np.float64) if want_models else None
-    nm, cnt = np.zeros(S, np.int32), np.zeros(S, np.int32)
-    ctx._check(capi.lib().eacham_pnp_hypotheses_batch_p3p(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(sample_ptr), ptr(sample_idx),
-                                                          float(threshold), ptr(models), ptr(nm), ptr(cnt)))
-    return PnpHypotheses(_seg(models, sample_ptr) if want_models else None, _seg(nm, sample_ptr), _seg(cnt, sample_ptr), point_ptr, sample_ptr)
+    return _hypotheses_raw("eacham_pnp_hypotheses_batch_p3p", ctx, point_ptr, X, uv, K, sample_ptr, None, sample_idx, threshold, want_models, n_problems)
 
 
 def pnp_hypotheses_batch_p3p(ctx, X, uv, K, samples, threshold: float = 16.0, want_models: bool = True) -> PnpHypotheses:
@@ -124,7 +119,6 @@ def pnp_hypotheses_batch_p3p(ctx, X, uv, K, samples, threshold: float = 16.0, wa
 def solve_p3p(ctx, X, uv, K, samples, want_candidates: bool = True):
     """eacham_solve_p3p: every row of `samples` (4 indices into X / uv) -> (models [s, 12] = R | t, n_models [s]) and, when wanted,
     (candidates [s, 4, 12] in root order, the slots behind the count zero, n_candidates [s])."""
-    vp = C.c_void_p
     X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, 3)
     uv = np.ascontiguousarray(uv, dtype=np.float64).reshape(-1, 2)
     if len(X) != len(uv):
@@ -135,18 +129,14 @@ def solve_p3p(ctx, X, uv, K, samples, want_candidates: bool = True):
     models, nm = np.zeros((s, 12), np.float64), np.zeros(s, np.int32)
     cand = np.zeros((s, 4, 12), np.float64) if want_candidates else None
     nc = np.zeros(s, np.int32) if want_candidates else None
-    ctx._check(capi.lib().eacham_solve_p3p(ctx.handle, len(X), vp(X.ctypes.data), vp(uv.ctypes.data), vp(K4.ctypes.data), s, vp(idx.ctypes.data),
-                                           vp(models.ctypes.data), vp(nm.ctypes.data), vp(cand.ctypes.data) if want_candidates else None,
-                                           vp(nc.ctypes.data) if want_candidates else None))
+    ctx._check(capi.lib().eacham_solve_p3p(ctx.handle, len(X), _vp(X), _vp(uv), _vp(K4), s, _vp(idx), _vp(models), _vp(nm), _vp(cand), _vp(nc)))
     return (models, nm, cand, nc) if want_candidates else (models, nm)
 
 
 def pnp_refit_batch_raw(ctx, point_ptr, X, uv, K, models, has_model, threshold, n_problems=None):
     """eacham_pnp_refit_batch on arrays already in its wire form."""
-    ptr = lambda x: None if x is None else C.c_void_p(x.ctypes.data)   # noqa: E731
-    as_ = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
-    point_ptr, X, uv, models = as_(point_ptr, np.int64), as_(X, np.float64), as_(uv, np.float64), as_(models, np.float64)
-    has_model = as_(has_model, np.uint8)
+    point_ptr, X, uv, models = _as(point_ptr, np.int64), _as(X, np.float64), _as(uv, np.float64), _as(models, np.float64)
+    has_model = _as(has_model, np.uint8)
     K4 = None if K is None else _K4(K)
     P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
     npts = max(int(point_ptr[-1]), 0) if point_ptr is not None and len(point_ptr) and P > 0 else 0
@@ -154,8 +144,8 @@ def pnp_refit_batch_raw(ctx, point_ptr, X, uv, K, models, has_model, threshold, 
         npts = 0
     mask, ni = np.zeros(npts, np.uint8), np.zeros(max(P, 0), np.int32)
     refit, ok = np.zeros((max(P, 0), 12), np.float64), np.zeros(max(P, 0), np.int32)
-    ctx._check(capi.lib().eacham_pnp_refit_batch(ctx.handle, P, ptr(point_ptr), ptr(X), ptr(uv), ptr(K4), ptr(models), ptr(has_model),
-                                                 float(threshold), ptr(mask), ptr(ni), ptr(refit), ptr(ok)))
+    ctx._check(capi.lib().eacham_pnp_refit_batch(ctx.handle, P, _vp(point_ptr), _vp(X), _vp(uv), _vp(K4), _vp(models), _vp(has_model),
+                                                 float(threshold), _vp(mask), _vp(ni), _vp(refit), _vp(ok)))
     return PnpRefit(_seg(mask, point_ptr), ni, refit, ok, point_ptr)
 
 

@@ -14,6 +14,10 @@
 // default (Sampling::OpenCV, CvSampling.hpp: cv::RNG seeded (uint64)-1, getSubset; from memory of the 4.5.5 sources, unverified:
 // parity unpinned) or the counter-based generator seeded by the caller (Sampling::Counter); tests hold the result against the
 // ground truth under both.
+//
+// The loop is written ONCE for one problem and once for a list (pnp_detail::ransac_single / ransac_batch, over replay_chunk), for any
+// sample size m, the solver step handed in as a callable: SolvePnPRansac[Batch] are the EPnP instantiations (m = 5), PnPP3PHip.hpp
+// holds the P3P ones (m = 4). This header names no P3P entry point: a program that includes only it links without them.
 #pragma once
 
 #include <algorithm>
@@ -40,6 +44,31 @@ struct PnPTrace {
     int winner = -1;
 };
 
+// One (map points, pixels) problem of SolvePnPRansacBatch: object n x 3, image n x 2 (pixels).
+struct PnPProblem {
+    std::vector<double> object, image;
+};
+
+inline Vec3 RodriguesFromMatrix(const Mat3& R) {   // rotation matrix -> axis * angle
+    const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) * 0.5));
+    const double theta = std::acos(c);
+    Vec3 ax{R[7] - R[5], R[2] - R[6], R[3] - R[1]};
+    const double s = twoview_detail::norm(ax) * 0.5;   // sin(theta)
+    if (s > 1e-9) {
+        for (double& x : ax) x *= theta / (2.0 * s);
+        return ax;
+    }
+    if (c > 0.0) return {0.0, 0.0, 0.0};
+    // theta = pi: axis from the diagonal of (R + I) / 2
+    Vec3 v{std::sqrt(std::max(0.0, (R[0] + 1.0) * 0.5)), std::sqrt(std::max(0.0, (R[4] + 1.0) * 0.5)), std::sqrt(std::max(0.0, (R[8] + 1.0) * 0.5))};
+    if (R[1] + R[3] < 0.0) v[1] = -v[1];
+    if (R[2] + R[6] < 0.0) v[2] = -v[2];
+    if (v[0] == 0.0 && R[5] + R[7] < 0.0) v[2] = -v[2];
+    const double n = twoview_detail::norm(v);
+    for (double& x : v) x *= theta / (n > 0.0 ? n : 1.0);
+    return v;
+}
+
 namespace pnp_detail {
 
 const int kChunk = 256;   // samples solved and scored per launch
@@ -63,64 +92,57 @@ inline std::vector<int32_t> pnp_samples(int n, int m, int first, int count, CvRN
     return idx;
 }
 
-}  // namespace pnp_detail
-
-inline Vec3 RodriguesFromMatrix(const Mat3& R) {   // rotation matrix -> axis * angle
-    const double c = std::min(1.0, std::max(-1.0, (R[0] + R[4] + R[8] - 1.0) * 0.5));
-    const double theta = std::acos(c);
-    Vec3 ax{R[7] - R[5], R[2] - R[6], R[3] - R[1]};
-    const double s = twoview_detail::norm(ax) * 0.5;   // sin(theta)
-    if (s > 1e-9) {
-        for (double& x : ax) x *= theta / (2.0 * s);
-        return ax;
+// The sequential rule over one chunk's results (sample first + k is row k), in sample order and while the budget lasts: a model
+// with strictly more inliers than the best so far (and at least a sample's worth) replaces it and shrinks the budget.
+inline void replay_chunk(int n, int m, double confidence, int first, int cnt, const int32_t* ok, const int32_t* inl, const double* models,
+                         int& budget, int& best_inl, double* best_model, int& iterations, PnPTrace* trace) {
+    for (int k = 0; k < cnt && first + k < budget; ++k) {
+        iterations = first + k + 1;
+        if (!ok[k]) continue;
+        if (inl[k] > std::max(best_inl, m - 1)) {
+            best_inl = inl[k];
+            if (trace) trace->winner = first + k;
+            std::copy_n(&models[(size_t)k * 12], 12, best_model);
+            budget = twoview_detail::ransac_update_num_iters(confidence, (double)(n - inl[k]) / n, m, budget);
+        }
     }
-    if (c > 0.0) return {0.0, 0.0, 0.0};
-    // theta = pi: axis from the diagonal of (R + I) / 2
-    Vec3 v{std::sqrt(std::max(0.0, (R[0] + 1.0) * 0.5)), std::sqrt(std::max(0.0, (R[4] + 1.0) * 0.5)), std::sqrt(std::max(0.0, (R[8] + 1.0) * 0.5))};
-    if (R[1] + R[3] < 0.0) v[1] = -v[1];
-    if (R[2] + R[6] < 0.0) v[2] = -v[2];
-    if (v[0] == 0.0 && R[5] + R[7] < 0.0) v[2] = -v[2];
-    const double n = twoview_detail::norm(v);
-    for (double& x : v) x *= theta / (n > 0.0 ? n : 1.0);
-    return v;
 }
 
-// object: n x 3, image: n x 2 (pixels), K9: row-major 3 x 3 (no distortion — the reference passes zeros).
-inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
-                                int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999, uint64_t seed = 1,
-                                Sampling sampling = Sampling::OpenCV, PnPTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
+inline void set_pose(PnPResult& r, const double* pose) {   // R | t of the refit, or of the winner where there is none
+    for (int e = 0; e < 9; ++e) r.R[e] = pose[e];
+    for (int e = 0; e < 3; ++e) r.t[e] = pose[9 + e];
+    r.rvec = RodriguesFromMatrix(r.R);
+    r.ok = true;
+}
+
+// One problem, samples of m points. solve(ctx, n, object, image, K4, count, idx, models, ok) is the chunk's solver call: `count`
+// rows of m indices -> models [count][12] and ok [count]; it returns the library's error code.
+template <class Solve>
+inline PnPResult ransac_single(Context& ctx, int m, Solve&& solve, const std::vector<double>& object, const std::vector<double>& image,
+                               const double* K9, int iterations, float reprojectionError, double confidence, uint64_t seed, Sampling sampling,
+                               PnPTrace* trace, const std::vector<int32_t>* samples) {
     PnPResult out;
-    const int n = (int)(image.size() / 2), m = 5;
+    const int n = (int)(image.size() / 2);
     if (n < m || object.size() != (size_t)3 * n || iterations <= 0 || (samples && samples->size() < (size_t)m)) return out;
     const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
     const float thr = reprojectionError * reprojectionError;   // PnPRansacCallback::computeError returns squared pixels
-    const int chunk = pnp_detail::kChunk;
+    const int chunk = kChunk;
     std::vector<double> models((size_t)chunk * 12), best_model(12, 0.0);
     std::vector<int32_t> okv(chunk), inl(chunk);
-    int best_inl = -1, budget = iterations, done = 0;
+    int best_inl = -1, budget = iterations;
     CvRNG rng(0xffffffffffffffffull);   // RANSACPointSetRegistrator::run: RNG rng((uint64)-1), one stream for the whole call
     for (int first = 0; first < budget; first += chunk) {
         const int cnt = std::min(chunk, iterations - first);
         // sample s of the whole run is row (s - first) of this chunk: OpenCV's stream is drawn in sample order (a chunk draws ahead
         // of the budget, which only shrinks: the samples the sequential rule consumes are the stream's prefix); the counter-based
         // generator is indexed by the global sample number
-        const std::vector<int32_t> idx = pnp_detail::pnp_samples(n, m, first, cnt, rng, seed, sampling, samples);
+        const std::vector<int32_t> idx = pnp_samples(n, m, first, cnt, rng, seed, sampling, samples);
         if (trace) trace->samples.insert(trace->samples.end(), idx.begin(), idx.end());
-        ctx.check(eacham_solve_pnp(ctx.get(), n, object.data(), image.data(), K4, m, cnt, idx.data(), models.data(), okv.data()));
+        ctx.check(solve(ctx.get(), n, object.data(), image.data(), K4, cnt, idx.data(), models.data(), okv.data()));
         ctx.check(eacham_score_hypotheses(ctx.get(), EACHAM_SCORE_PNP, n, object.data(), image.data(), cnt, models.data(), K4, thr, nullptr,
                                           inl.data(), nullptr));
-        for (int k = 0; k < cnt && first + k < budget; ++k) {
-            done = first + k + 1;
-            if (!okv[k]) continue;
-            if (inl[k] > std::max(best_inl, m - 1)) {   // strictly more inliers (and at least a sample's worth) replaces the model
-                best_inl = inl[k];
-                if (trace) trace->winner = first + k;
-                std::copy(&models[(size_t)k * 12], &models[(size_t)k * 12] + 12, best_model.begin());
-                budget = twoview_detail::ransac_update_num_iters(confidence, (double)(n - inl[k]) / n, m, budget);
-            }
-        }
+        replay_chunk(n, m, confidence, first, cnt, okv.data(), inl.data(), models.data(), budget, best_inl, best_model.data(), out.iterations, trace);
     }
-    out.iterations = done;
     if (best_inl < m) return out;
     std::vector<float> err(n);
     int32_t cnt = 0;
@@ -132,34 +154,26 @@ inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object,
     out.inliers.assign(rows.begin(), rows.end());
     double refit[12];
     int32_t rok = 0;
-    ctx.check(eacham_solve_pnp(ctx.get(), n, object.data(), image.data(), K4, (int)rows.size(), 1, rows.data(), refit, &rok));
-    const double* pose = rok ? refit : best_model.data();   // (a collinear inlier set cannot be refitted: keep the winner)
-    for (int e = 0; e < 9; ++e) out.R[e] = pose[e];
-    for (int e = 0; e < 3; ++e) out.t[e] = pose[9 + e];
-    out.rvec = RodriguesFromMatrix(out.R);
-    out.ok = true;
+    if (rows.size() >= 5)   // the refit is EPnP, which needs five rows: a four-inlier winner (m = 4) keeps its own pose
+        ctx.check(eacham_solve_pnp(ctx.get(), n, object.data(), image.data(), K4, (int)rows.size(), 1, rows.data(), refit, &rok));
+    set_pose(out, rok ? refit : best_model.data());   // (a collinear inlier set cannot be refitted: keep the winner)
     return out;
 }
 
-// One (map points, pixels) problem of SolvePnPRansacBatch: object n x 3, image n x 2 (pixels).
-struct PnPProblem {
-    std::vector<double> object, image;
-};
-
-// SolvePnPRansac for a LIST of problems in rounds + 1 device calls, whatever the length of the list. In round r every problem
-// still running draws its rows [256 r, min(256 (r + 1), iterations)) from its OWN stream (Sampling::OpenCV: a CvRNG seeded
-// (uint64)-1 per problem, kept across the rounds; Sampling::Counter: seeds[p]) and ONE eacham_pnp_hypotheses_batch call solves and
-// counts them all; the sequential rule of SolvePnPRansac is then replayed per problem on the host over that problem's counts in
-// sample order (ransac_update_num_iters uses the host's log and pow: a device libm may round differently at a knife edge). A
-// problem leaves the list when its budget is within the samples already seen. After the last round ONE eacham_pnp_refit_batch
-// call serves every problem whose best count is >= 5; a failed refit keeps the winner. result[p] — and traces[p], when asked
-// for — equal what SolvePnPRansac returns for problem p alone with seeds[p] and the same arguments, field for field.
-inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9, int iterations = 10000,
-                                                  float reprojectionError = 4.0f, double confidence = 0.999,
-                                                  const std::vector<uint64_t>& seeds = {}, Sampling sampling = Sampling::OpenCV,
-                                                  std::vector<PnPTrace>* traces = nullptr) {
+// A LIST of problems in rounds + 1 device calls, whatever the length of the list. In round r every problem still running draws
+// its rows [256 r, min(256 (r + 1), iterations)) from its OWN stream (Sampling::OpenCV: a CvRNG seeded (uint64)-1 per problem,
+// kept across the rounds; Sampling::Counter: seeds[p]) and ONE call of round(ctx, P, point_ptr, object, image, K4, sample_ptr, idx,
+// thr, models, ok, counts) — an eacham_pnp_hypotheses_batch* entry with its sample size m bound — solves and counts them all; the
+// sequential rule is then replayed per problem on the host over that problem's counts (ransac_update_num_iters uses the host's log
+// and pow: a device libm may round differently at a knife edge). A problem leaves the list when its budget is within the samples
+// already seen. After the last round ONE eacham_pnp_refit_batch call (EPnP) serves every problem whose best count is >= m; where it
+// gives no pose — fewer than 5 inliers, a degenerate set — the winner's stays.
+template <class Round>
+inline std::vector<PnPResult> ransac_batch(Context& ctx, int m, Round&& round, const std::vector<PnPProblem>& problems, const double* K9,
+                                           int iterations, float reprojectionError, double confidence, const std::vector<uint64_t>& seeds,
+                                           Sampling sampling, std::vector<PnPTrace>* traces) {
     const size_t P = problems.size();
-    const int m = 5, chunk = pnp_detail::kChunk;
+    const int chunk = kChunk;
     std::vector<PnPResult> out(P);
     if (traces) traces->assign(P, PnPTrace{});
     const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
@@ -170,7 +184,7 @@ inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vecto
     std::vector<CvRNG> rng(P, CvRNG(0xffffffffffffffffull));
     for (size_t p = 0; p < P; ++p) {
         npts[p] = (int)(problems[p].image.size() / 2);
-        // (what SolvePnPRansac turns away takes part with its points and never with a sample)
+        // (what ransac_single turns away takes part with its points and never with a sample)
         budget[p] = npts[p] >= m && problems[p].object.size() == (size_t)3 * npts[p] && iterations > 0 ? iterations : 0;
         point_ptr[p + 1] = point_ptr[p] + npts[p];
         object.insert(object.end(), problems[p].object.begin(), problems[p].object.end());
@@ -184,7 +198,7 @@ inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vecto
         for (size_t p = 0; p < P; ++p) {
             const int cnt = first < budget[p] ? std::min(chunk, iterations - first) : 0;
             if (cnt > 0) {
-                const std::vector<int32_t> rows = pnp_detail::pnp_samples(npts[p], m, first, cnt, rng[p], p < seeds.size() ? seeds[p] : 1, sampling);
+                const std::vector<int32_t> rows = pnp_samples(npts[p], m, first, cnt, rng[p], p < seeds.size() ? seeds[p] : 1, sampling);
                 if (traces) (*traces)[p].samples.insert((*traces)[p].samples.end(), rows.begin(), rows.end());
                 idx.insert(idx.end(), rows.begin(), rows.end());
             }
@@ -193,21 +207,12 @@ inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vecto
         const size_t S = (size_t)sample_ptr[P];
         if (S == 0) break;
         models.resize(12 * S), okv.resize(S), inl.resize(S);
-        ctx.check(eacham_pnp_hypotheses_batch(ctx.get(), (int)P, point_ptr.data(), object.data(), image.data(), K4, sample_ptr.data(), m, idx.data(),
-                                              thr, models.data(), okv.data(), inl.data()));
+        ctx.check(round(ctx.get(), (int)P, point_ptr.data(), object.data(), image.data(), K4, sample_ptr.data(), idx.data(), thr, models.data(),
+                        okv.data(), inl.data()));
         for (size_t p = 0; p < P; ++p) {
             const size_t s0 = (size_t)sample_ptr[p];
-            const int cnt = (int)(sample_ptr[p + 1] - sample_ptr[p]), n = npts[p];
-            for (int k = 0; k < cnt && first + k < budget[p]; ++k) {
-                out[p].iterations = first + k + 1;
-                if (!okv[s0 + k]) continue;
-                if (inl[s0 + k] > std::max(best_inl[p], m - 1)) {
-                    best_inl[p] = inl[s0 + k];
-                    if (traces) (*traces)[p].winner = first + k;
-                    std::copy_n(&models[12 * (s0 + k)], 12, &best_model[12 * p]);
-                    budget[p] = twoview_detail::ransac_update_num_iters(confidence, (double)(n - inl[s0 + k]) / n, m, budget[p]);
-                }
-            }
+            replay_chunk(npts[p], m, confidence, first, (int)(sample_ptr[p + 1] - sample_ptr[p]), okv.data() + s0, inl.data() + s0,
+                         models.data() + 12 * s0, budget[p], best_inl[p], &best_model[12 * p], out[p].iterations, traces ? &(*traces)[p] : nullptr);
         }
     }
     std::vector<uint8_t> has(P, 0), mask((size_t)point_ptr[P], 0);
@@ -222,13 +227,33 @@ inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vecto
         if (!has[p]) continue;
         for (int i = 0; i < npts[p]; ++i)
             if (mask[(size_t)point_ptr[p] + i]) out[p].inliers.push_back(i);
-        const double* pose = rok[p] ? &refit[12 * p] : &best_model[12 * p];
-        for (int e = 0; e < 9; ++e) out[p].R[e] = pose[e];
-        for (int e = 0; e < 3; ++e) out[p].t[e] = pose[9 + e];
-        out[p].rvec = RodriguesFromMatrix(out[p].R);
-        out[p].ok = true;
+        set_pose(out[p], rok[p] ? &refit[12 * p] : &best_model[12 * p]);
     }
     return out;
+}
+
+}  // namespace pnp_detail
+
+// object: n x 3, image: n x 2 (pixels), K9: row-major 3 x 3 (no distortion — the reference passes zeros).
+inline PnPResult SolvePnPRansac(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
+                                int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999, uint64_t seed = 1,
+                                Sampling sampling = Sampling::OpenCV, PnPTrace* trace = nullptr, const std::vector<int32_t>* samples = nullptr) {
+    const auto solve = [](eacham_ctx* c, int n, const double* obj, const double* img, const double* K4, auto... rows) {
+        return eacham_solve_pnp(c, n, obj, img, K4, 5, rows...);   // (the sample size goes in front of the rows)
+    };
+    return pnp_detail::ransac_single(ctx, 5, solve, object, image, K9, iterations, reprojectionError, confidence, seed, sampling, trace, samples);
+}
+
+// SolvePnPRansac for a LIST of problems (pnp_detail::ransac_batch, the round one eacham_pnp_hypotheses_batch call). result[p] — and
+// traces[p], when asked for — equal what SolvePnPRansac returns for problem p alone with seeds[p] and the same arguments, field for field.
+inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9, int iterations = 10000,
+                                                  float reprojectionError = 4.0f, double confidence = 0.999,
+                                                  const std::vector<uint64_t>& seeds = {}, Sampling sampling = Sampling::OpenCV,
+                                                  std::vector<PnPTrace>* traces = nullptr) {
+    const auto round = [](eacham_ctx* c, int P, const int64_t* pp, const double* obj, const double* img, const double* K4, const int64_t* sp, auto... rest) {
+        return eacham_pnp_hypotheses_batch(c, P, pp, obj, img, K4, sp, 5, rest...);   // (the sample size goes in front of the rows)
+    };
+    return pnp_detail::ransac_batch(ctx, 5, round, problems, K9, iterations, reprojectionError, confidence, seeds, sampling, traces);
 }
 
 }  // namespace hip

@@ -116,6 +116,12 @@ def hyp_case():
     return _case(probs)
 
 
+def trip_edges():
+    """A problem on each side of the count loop's 64-point trip and of a 256-point one (63, 64, 65, 255, 256 and 257 points), without
+    outliers: some sample of each counts every point, the last included."""
+    return _case([problem(n, 4, 60 + k, outliers=0.0) for k, n in enumerate([63, 64, 65, 255, 256, 257])])
+
+
 def cpp_case():
     """EXACT pixels (the outliers apart), for the C++ adapters, which draw their own samples: 300 points with ~30 % outliers (ends
     inside the first chunk), 60 with ~70 %, exactly 4 points, 3 points (turned away), a planar scene. T = the true poses."""

@@ -86,7 +86,14 @@ def sample_counts():
     return _case([problem(60, c, 40 + k) for k, c in enumerate([3, 66, 129])])
 
 
-HYP_CASES = {"single": single, "mixed": mixed, "empties": empties, "structure": structure, "sample_counts": sample_counts}
+def trip_edges():
+    """A problem on each side of the count loop's 64-point trip (63, 64, 65 points) and of the refit's 256-point one (255, 256, 257),
+    without outliers: every point but point 0 (the camera centre) lies within 4 px of the true pose, the last one included."""
+    return _case([problem(n, 4, 110 + k, outliers=0.0) for k, n in enumerate([63, 64, 65, REFIT_BLOCK - 1, REFIT_BLOCK, REFIT_BLOCK + 1])])
+
+
+HYP_CASES = {"single": single, "mixed": mixed, "empties": empties, "structure": structure, "sample_counts": sample_counts,
+             "trip_edges": trip_edges}
 
 
 # ---- the round loop -------------------------------------------------------------------------------------------------------
@@ -133,6 +140,14 @@ def refit_case():
     c["models"] = np.array([p[3] for p in probs])
     c["has_model"] = np.array([1, 1, 0, 1, 1, 1, 1], dtype=np.uint8)
     c["collinear"] = (3, line)
+    return c
+
+
+def refit_edges():
+    """The problems of trip_edges under their true poses: n - 1 inliers, the last point of a trip and the first of the next among them."""
+    c = trip_edges()
+    probs = [problem(len(x), 0, 110 + k, outliers=0.0) for k, x in enumerate(c["X"])]
+    c.update(models=np.array([p[3] for p in probs]), has_model=np.ones(len(probs), dtype=np.uint8))
     return c
 
 

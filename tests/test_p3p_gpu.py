@@ -102,6 +102,12 @@ def test_a_round_equals_the_single_call_and_the_scorer(hip_ctx):
     assert lean.models is None
     for p in range(len(c["X"])):
         assert np.array_equal(lean.n_models[p], got.n_models[p]) and np.array_equal(lean.inlier_counts[p], got.inlier_counts[p])
+    e = PC.trip_edges()                                                                                  # 63 .. 65 and 255 .. 257 points
+    got = hip_ctx.pnp_hypotheses_batch_p3p(e["X"], e["uv"], e["K"], e["samples"], PC.THR)
+    assert_same_hypotheses(got, device_compose(hip_ctx, e), "trip edges, device composition")
+    cpu = R.compose_hypotheses(R.solve_p3p, lambda x, u, m, k, t: R.score(x, u, m, k, t)[1], e["X"], e["uv"], e["K"], e["samples"], PC.THR)
+    assert_same_hypotheses(got, cpu, "trip edges, restatement")
+    assert [int(g.max()) for g in got.inlier_counts] == [63, 64, 65, 255, 256, 257] == [len(u) for u in e["uv"]]
 
 
 def test_the_ransac_loop_equals_the_loop_over_the_restatement(hip_ctx):

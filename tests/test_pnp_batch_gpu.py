@@ -52,6 +52,8 @@ def test_a_round_equals_the_composition_of_the_existing_calls(hip_ctx, name):
     if name == "structure":
         assert got.n_models[0].tolist() == [1, 0, 1] and not got.models[0][1].any() and got.inlier_counts[0][1] == 0
         assert got.n_models[1].all() and not got.n_models[2].any() and not got.inlier_counts[2].any()
+    if name == "trip_edges":                     # some model of each problem counts every point but the camera centre, the last included
+        assert [int(c.max()) for c in got.inlier_counts] == [62, 63, 64, 254, 255, 256]
     if name == "empties":
         assert len(got.n_models[1]) == 0 and got.n_models[0].any() and got.n_models[2].any()
 
@@ -90,6 +92,10 @@ def test_the_refit_equals_the_composition_of_the_existing_calls(hip_ctx):
     assert np.array_equal(np.nonzero(got.masks[p])[0], line) and got.n_inliers[p] == 10 and got.refit_ok[p] == 0 and not got.refit[p].any()
     assert got.refit_ok.tolist() == [1, 1, 0, 0, 0, 1, 1] and got.n_inliers[0] > 64 >= got.n_inliers[1] >= 5
     assert not got.masks[2].any() and got.n_inliers[2] == 0 and got.n_inliers[4] < 5
+    e = PC.refit_edges()                                                         # 63 .. 65 and 255 .. 257 points
+    want = REF.compose_refit(*device_calls(hip_ctx), e["X"], e["uv"], e["K"], e["models"], e["has_model"], PC.THR)
+    assert_same_refit(hip_ctx.pnp_refit_batch(e["X"], e["uv"], e["K"], e["models"], e["has_model"], PC.THR), want, "trip edges")
+    assert [w["n_inliers"] for w in want] == [62, 63, 64, 254, 255, 256] and all(w["refit_ok"] and w["mask"][-1] for w in want)
 
 
 @pytest.mark.parametrize("count", [5, 63, 64, 65, 129])

@@ -145,6 +145,11 @@ def test_the_cases_hold_what_they_are_for(sequential):
     assert rf[4]["n_inliers"] < 5 and not rf[4]["refit_ok"]
     assert rf[5]["refit_ok"] and rf[5]["mask"][:PC.REFIT_BLOCK].any() and rf[5]["mask"][PC.REFIT_BLOCK:].any()
     assert rf[6]["refit_ok"] and rf[6]["n_inliers"] > 64
+    e = PC.refit_edges()
+    h = compose_hypotheses(O.solve_pnp, oracle_score, e["X"], e["uv"], e["K"], e["samples"], thr)
+    rf = compose_refit(O.solve_pnp, oracle_score, e["X"], e["uv"], e["K"], e["models"], e["has_model"], thr)
+    assert [len(u) for u in e["uv"]] == [63, 64, 65, 255, 256, 257] and [int(x[2].max()) for x in h] == [62, 63, 64, 254, 255, 256]
+    assert [r["n_inliers"] for r in rf] == [62, 63, 64, 254, 255, 256] and all(r["refit_ok"] and r["mask"][-1] for r in rf)
 
 
 def test_the_python_round_loop_is_the_same_rule():
