@@ -384,6 +384,13 @@ class HipContext:
         from . import pnp
         return pnp.pnp_refit_batch(self, X, uv, K, models, has_model, threshold)
 
+    def pnp_refine_batch(self, X, uv, K, poses, has_pose, use_masks=None, max_tries: int = 20, threshold: float = 16.0,
+                         want_recount: bool = True):
+        """eacham_pnp_refine_batch: Levenberg-Marquardt on the reprojection error of one pose per problem over the rows its mask names,
+        and the recount under the refined pose, for a list of problems in one launch (eacham_amd/pnp.py)."""
+        from . import pnp
+        return pnp.pnp_refine_batch(self, X, uv, K, poses, has_pose, use_masks, max_tries, threshold, want_recount)
+
     def solve_p3p(self, X, uv, K, samples, want_candidates: bool = True):
         """eacham_solve_p3p: P3P on every row of `samples` (4 point indices per row: three solve, the fourth picks) (eacham_amd/pnp.py)."""
         from . import pnp

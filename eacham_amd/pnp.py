@@ -4,7 +4,9 @@ pixels) problems: one call per RANSAC round of CHUNK samples for every problem s
 the sequential rule replayed per problem on the host in between (pnp_ransac_batch, what SolvePnPRansacBatch of
 include/eacham/PnPHip.hpp does). Drawing the samples stays with the caller. Test / bench driver.
 The P3P form (eacham_solve_p3p / eacham_pnp_hypotheses_batch_p3p; SolvePnPRansacP3P[Batch] of include/eacham/PnPP3PHip.hpp) draws
-four-point samples: solve_p3p, pnp_hypotheses_batch_p3p[_raw] and pnp_ransac_batch(solver="p3p"); the refit stays EPnP."""
+four-point samples: solve_p3p, pnp_hypotheses_batch_p3p[_raw] and pnp_ransac_batch(solver="p3p"); the refit stays EPnP.
+The polish (eacham_pnp_refine_batch; RefinePnP[Batch] and SolvePnPRansac[P3P]Refined[Batch] of the two headers) is
+pnp_refine_batch[_raw]: Levenberg-Marquardt on the reprojection error of one pose per problem over the rows a mask names, a PnpRefine."""
 from __future__ import annotations
 
 import ctypes as C
@@ -32,6 +34,19 @@ class PnpRefit(NamedTuple):
     refit: np.ndarray         # [P, 12] float64 (zeros where refit_ok is 0)
     refit_ok: np.ndarray      # [P] int32
     point_ptr: np.ndarray
+
+
+class PnpRefine(NamedTuple):
+    refined: np.ndarray       # [P, 12] float64 = R | t (the input pose where status is NOT_REFINED; zeros without a pose)
+    cost: np.ndarray          # [P, 2] float64: sum of squared pixels over the used rows before, after
+    tries: np.ndarray         # [P] int32
+    status: np.ndarray        # [P] int32: REFINE_CONVERGED, REFINE_CAP, REFINE_NOT_REFINED
+    masks: list | None        # P arrays of uint8: err <= threshold under the refined pose; None: not asked for
+    n_inliers: np.ndarray | None
+    point_ptr: np.ndarray
+
+
+REFINE_CONVERGED, REFINE_CAP, REFINE_NOT_REFINED = 0, 1, 2   # EACHAM_PNP_REFINE_*
 
 
 def _K4(K):
@@ -157,6 +172,44 @@ def pnp_refit_batch(ctx, X, uv, K, models, has_model, threshold: float = 16.0) -
     if not (len(models) == len(has_model) == len(point_ptr) - 1):
         raise ValueError("one model and one has_model byte per problem")
     return pnp_refit_batch_raw(ctx, point_ptr, A, B, K, models, has_model, threshold)
+
+
+def pnp_refine_batch_raw(ctx, point_ptr, X, uv, K, poses, has_pose, use_mask=None, max_tries=20, threshold=16.0, want_recount=True,
+                         n_problems=None):
+    """eacham_pnp_refine_batch on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
+    point_ptr, X, uv, poses = _as(point_ptr, np.int64), _as(X, np.float64), _as(uv, np.float64), _as(poses, np.float64)
+    has_pose, use_mask = _as(has_pose, np.uint8), _as(use_mask, np.uint8)
+    K4 = None if K is None else _K4(K)
+    P = (len(point_ptr) - 1 if point_ptr is not None else 0) if n_problems is None else int(n_problems)
+    npts = max(int(point_ptr[-1]), 0) if point_ptr is not None and len(point_ptr) and P > 0 else 0
+    if npts > 1 << 28:
+        npts = 0
+    Pz = max(P, 0)
+    refined, cost = np.zeros((Pz, 12), np.float64), np.zeros((Pz, 2), np.float64)
+    tries, status = np.zeros(Pz, np.int32), np.zeros(Pz, np.int32)
+    mask = np.zeros(npts, np.uint8) if want_recount else None
+    ni = np.zeros(Pz, np.int32) if want_recount else None
+    ctx._check(capi.lib().eacham_pnp_refine_batch(ctx.handle, P, _vp(point_ptr), _vp(X), _vp(uv), _vp(K4), _vp(poses), _vp(has_pose), _vp(use_mask),
+                                                  int(max_tries), float(threshold), _vp(refined), _vp(cost), _vp(tries), _vp(status), _vp(mask), _vp(ni)))
+    return PnpRefine(refined, cost, tries, status, _seg(mask, point_ptr) if want_recount else None, ni, point_ptr)
+
+
+def pnp_refine_batch(ctx, X, uv, K, poses, has_pose, use_masks=None, max_tries: int = 20, threshold: float = 16.0,
+                     want_recount: bool = True) -> PnpRefine:
+    """cv::solvePnPRefineLM per problem: Levenberg-Marquardt on the reprojection error of poses[p] (12 doubles; has_pose[p] = 0: none)
+    over the rows of problem p with a non-zero byte in use_masks[p] (None: every row), at most max_tries tries; then the recount of
+    err <= threshold (squared pixels) over all of the problem's points under the refined pose."""
+    point_ptr, A, B = pack_points(X, uv)
+    poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(-1, 12)
+    has_pose = np.ascontiguousarray(has_pose, dtype=np.uint8).reshape(-1)
+    if not (len(poses) == len(has_pose) == len(point_ptr) - 1):
+        raise ValueError("one pose and one has_pose byte per problem")
+    use = None
+    if use_masks is not None:
+        use = _cat([np.asarray(m, dtype=np.uint8).reshape(-1) for m in use_masks], (0,), np.uint8)
+        if len(use_masks) != len(poses) or len(use) != len(B):
+            raise ValueError("one use byte per point")
+    return pnp_refine_batch_raw(ctx, point_ptr, A, B, K, poses, has_pose, use, max_tries, threshold, want_recount)
 
 
 def ransac_update_num_iters(p: float, ep: float, m: int, max_iters: int) -> int:

@@ -256,5 +256,87 @@ inline std::vector<PnPResult> SolvePnPRansacBatch(Context& ctx, const std::vecto
     return pnp_detail::ransac_batch(ctx, 5, round, problems, K9, iterations, reprojectionError, confidence, seeds, sampling, traces);
 }
 
+// ---- the polish: cv::solvePnPRefineLM on the inliers (eacham_pnp_refine_batch, include/eacham_hip.h states the loop) --------------
+// SolvePnPRansac[Batch] end on EPnP's algebraic fit, as cv::solvePnPRansac(..., SOLVEPNP_EPNP) does; the calls below add what
+// SOLVEPNP_ITERATIVE and COLMAP add after it: Levenberg-Marquardt on the reprojection error over the winner's inliers, for the whole
+// list in ONE device call. The functions above, their defaults and their results are unchanged.
+
+// A PnPResult whose pose has been polished. `inliers` keeps its meaning (the rows within the threshold of the RANSAC winner: the
+// rows the polish ran on); a result that is not ok, or whose status is NOT_REFINED (fewer than 3 inliers, a point behind the
+// camera), keeps the pose it came with.
+struct PnPRefined : PnPResult {
+    double cost_before = 0.0, cost_after = 0.0;   // sum of squared pixel residuals over the inliers
+    int tries = 0;
+    int status = EACHAM_PNP_REFINE_NOT_REFINED;   // EACHAM_PNP_REFINE_CONVERGED / _CAP / _NOT_REFINED
+};
+
+namespace pnp_detail {
+
+// One eacham_pnp_refine_batch call for the list: problem p is refined from poses[p] (R, t; skipped unless ok) over poses[p].inliers.
+inline std::vector<PnPRefined> refine_batch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9,
+                                            const std::vector<PnPResult>& poses, int maxTries) {
+    const size_t P = problems.size();
+    std::vector<PnPRefined> out(P);
+    if (P == 0 || poses.size() != P) return out;
+    const double K4[4] = {K9[0], K9[4], K9[2], K9[5]};
+    std::vector<int64_t> point_ptr(P + 1, 0);
+    std::vector<double> object, image, in(12 * P, 0.0);
+    std::vector<uint8_t> has(P, 0);
+    for (size_t p = 0; p < P; ++p) {
+        static_cast<PnPResult&>(out[p]) = poses[p];
+        const int n = (int)(problems[p].image.size() / 2);
+        point_ptr[p + 1] = point_ptr[p] + n;
+        object.insert(object.end(), problems[p].object.begin(), problems[p].object.end());
+        object.resize((size_t)3 * point_ptr[p + 1], 0.0);
+        image.insert(image.end(), problems[p].image.begin(), problems[p].image.begin() + 2 * (size_t)n);
+        has[p] = poses[p].ok && problems[p].object.size() == (size_t)3 * n;
+        for (int e = 0; e < 9; ++e) in[12 * p + e] = poses[p].R[e];
+        for (int e = 0; e < 3; ++e) in[12 * p + 9 + e] = poses[p].t[e];
+    }
+    std::vector<uint8_t> use((size_t)point_ptr[P], 0);
+    for (size_t p = 0; p < P; ++p)
+        for (const int i : poses[p].inliers)
+            if (i >= 0 && i < point_ptr[p + 1] - point_ptr[p]) use[(size_t)point_ptr[p] + i] = 1;
+    std::vector<double> refined(12 * P), cost(2 * P);
+    std::vector<int32_t> tries(P), status(P);
+    ctx.check(eacham_pnp_refine_batch(ctx.get(), (int)P, point_ptr.data(), object.data(), image.data(), K4, in.data(), has.data(), use.data(), maxTries,
+                                      0.f, refined.data(), cost.data(), tries.data(), status.data(), nullptr, nullptr));
+    for (size_t p = 0; p < P; ++p) {
+        out[p].cost_before = cost[2 * p], out[p].cost_after = cost[2 * p + 1], out[p].tries = tries[p], out[p].status = status[p];
+        if (has[p] && status[p] != EACHAM_PNP_REFINE_NOT_REFINED) set_pose(out[p], &refined[12 * p]);
+    }
+    return out;
+}
+
+}  // namespace pnp_detail
+
+// The polish for a LIST: poses[p] is what a SolvePnPRansac* call returned for problems[p] (or any pose R, t with ok set and the rows
+// to use in `inliers`). result[p] equals what RefinePnP returns for problem p alone, field for field.
+inline std::vector<PnPRefined> RefinePnPBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9,
+                                              const std::vector<PnPResult>& poses, int maxTries = 20) {
+    return pnp_detail::refine_batch(ctx, problems, K9, poses, maxTries);
+}
+
+// The polish for one problem: Levenberg-Marquardt from `pose` (R, t) over the rows pose.inliers of object / image.
+inline PnPRefined RefinePnP(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
+                            const PnPResult& pose, int maxTries = 20) {
+    return pnp_detail::refine_batch(ctx, {PnPProblem{object, image}}, K9, {pose}, maxTries)[0];
+}
+
+// SolvePnPRansac, then the polish on its inliers (arguments and defaults of SolvePnPRansac; maxTries = the cap of the LM loop).
+inline PnPRefined SolvePnPRansacRefined(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
+                                        int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999, uint64_t seed = 1,
+                                        Sampling sampling = Sampling::OpenCV, int maxTries = 20) {
+    return RefinePnP(ctx, object, image, K9, SolvePnPRansac(ctx, object, image, K9, iterations, reprojectionError, confidence, seed, sampling), maxTries);
+}
+
+// SolvePnPRansacBatch, then ONE more device call for every polish. result[p] equals SolvePnPRansacRefined on problem p with seeds[p].
+inline std::vector<PnPRefined> SolvePnPRansacRefinedBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9,
+                                                          int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999,
+                                                          const std::vector<uint64_t>& seeds = {}, Sampling sampling = Sampling::OpenCV,
+                                                          int maxTries = 20) {
+    return RefinePnPBatch(ctx, problems, K9, SolvePnPRansacBatch(ctx, problems, K9, iterations, reprojectionError, confidence, seeds, sampling), maxTries);
+}
+
 }  // namespace hip
 }  // namespace eacham

@@ -33,5 +33,23 @@ inline std::vector<PnPResult> SolvePnPRansacP3PBatch(Context& ctx, const std::ve
                                     sampling, traces);
 }
 
+// SolvePnPRansacP3P, then the polish of PnPHip.hpp (RefinePnP: Levenberg-Marquardt on the reprojection error) on its inliers. EPnP's
+// refit needs five rows, the polish three: under this call a frame registered from exactly FOUR correspondences, or a winner with four
+// inliers, comes back polished where SolvePnPRansacP3P returns the raw minimal pose.
+inline PnPRefined SolvePnPRansacP3PRefined(Context& ctx, const std::vector<double>& object, const std::vector<double>& image, const double* K9,
+                                           int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999, uint64_t seed = 1,
+                                           Sampling sampling = Sampling::OpenCV, int maxTries = 20) {
+    return RefinePnP(ctx, object, image, K9, SolvePnPRansacP3P(ctx, object, image, K9, iterations, reprojectionError, confidence, seed, sampling), maxTries);
+}
+
+// SolvePnPRansacP3PBatch, then ONE more device call for every polish. result[p] equals SolvePnPRansacP3PRefined on problem p with seeds[p].
+inline std::vector<PnPRefined> SolvePnPRansacP3PRefinedBatch(Context& ctx, const std::vector<PnPProblem>& problems, const double* K9,
+                                                             int iterations = 10000, float reprojectionError = 4.0f, double confidence = 0.999,
+                                                             const std::vector<uint64_t>& seeds = {}, Sampling sampling = Sampling::OpenCV,
+                                                             int maxTries = 20) {
+    return RefinePnPBatch(ctx, problems, K9, SolvePnPRansacP3PBatch(ctx, problems, K9, iterations, reprojectionError, confidence, seeds, sampling),
+                          maxTries);
+}
+
 }  // namespace hip
 }  // namespace eacham

@@ -653,6 +653,54 @@ int eacham_pnp_refit_batch(eacham_ctx* ctx, int n_problems, const int64_t* point
                            const double* image_points, const double* K, const double* models, const uint8_t* has_model,
                            float threshold, uint8_t* inlier_mask, int32_t* n_inliers, double* refit, int32_t* refit_ok);
 
+/* ---- PnP pose refinement for a whole list of problems ---------------------------------------------------------------
+ * cv::solvePnPRefineLM (the polish of SOLVEPNP_ITERATIVE; from memory of OpenCV 4.5.5, unverified: the idea, not the bits): where
+ * eacham_pnp_refit_batch ends on EPnP's algebraic fit, this minimises the REPROJECTION error of a pose over the rows the caller
+ * names, by Levenberg-Marquardt, for n_problems problems in ONE launch with the whole loop on the device. Tables and layouts as
+ * eacham_pnp_refit_batch: problem p owns the rows point_ptr[p] .. point_ptr[p+1] of object_points / image_points; K = fx fy cx cy.
+ * poses: 12 doubles R | t per problem, has_pose: one byte per problem. use_mask: one byte per point in the layout of image_points
+ * (optional, NULL = every point); the USED rows of a problem are those with a non-zero byte. threshold (squared pixels) serves the
+ * recount only. Outputs per problem: refined (12 doubles), cost (2 doubles: the sum of squared pixel residuals over the used rows
+ * before and after), tries, status; optional (NULL = not wanted, each on its own): inlier_mask (bytes, layout of image_points) and
+ * n_inliers, the recount err <= threshold of eacham_score_hypotheses(kind PNP) over ALL of the problem's points under `refined`
+ * — what eacham_pnp_refit_batch writes for that pose (all zero where has_pose is 0).
+ *
+ * THE LOOP. fp64 throughout, only + - * /, every operation rounded on its own, every sum in the order written
+ * (tests/cpp/pnp_refine_reference.c is the CPU restatement; the kernel gives its bytes):
+ *   1. A row (X, (u, v)) under M = R | t:  x y z = R X + t (each ((m0 X0 + m1 X1) + m2 X2) + t),  iz = 1 / z,  xn = x iz,  yn = y iz,
+ *      r = ((fx xn + cx) - u, (fy yn + cy) - v). The perturbation d = [w, v] acts in the camera frame, X_c' ~ X_c + w x X_c + v, so with
+ *      a = fx iz, b = fy iz:   Ju = (-(fx xn yn), fx (1 + xn xn), -(fx yn), a, 0, -(a xn)),
+ *                              Jv = (-(fy (1 + yn yn)), fy xn yn, fy xn, 0, b, -(b yn)).
+ *   2. Sums. 28 numbers: H = J'J (upper triangle, row by row, 21), g = J'r (6), cost = r'r. A row adds
+ *      H_ij += (Ju_i Ju_j + Jv_i Jv_j), g_i += (Ju_i r_0 + Jv_i r_1), cost += (r_0 r_0 + r_1 r_1). THE ORDER: 64 partial sums start at
+ *      zero; partial l takes the used rows i of the problem (i local to it) with i mod 64 = l, in ascending i; then the partials are
+ *      folded in halves, s[l] += s[l + off] for l < off, off = 32, 16, 8, 4, 2, 1, and s[0] is the sum.
+ *   3. A try at damping lambda (1e-3 at the start): A = H with A_ii = H_ii + lambda H_ii; A = L D L' without pivoting (column by
+ *      column, each entry minus its products L_ik D_k L_jk in ascending k, then divided by the pivot); a pivot that is not > 0 fails
+ *      the try. Else L y = -g, z = y / D, L' d = z (back substitution, products subtracted in ascending k).
+ *   4. If max |d_k| <= 1e-10 the loop ends CONVERGED (tested before the step is taken, whatever came before). Else the candidate is
+ *      R' = C(w) R, t' = C(w) t + v with the Cayley map of the bundle adjuster's Pose3 chart,
+ *      C(w) = ((4 - |w|^2) I + 2 w w' + 4 [w]x) / (4 + |w|^2), and step 2 at the candidate gives cost', H', g'.
+ *   5. The candidate is ACCEPTED iff no used row has !(z > 0) under it and cost' < cost: the pose, H, g and the cost become the
+ *      candidate's and lambda <- max(lambda / 10, 1e-12); if cost - cost' <= 1e-9 cost' the loop ends CONVERGED. A failed or
+ *      rejected try: lambda <- min(10 lambda, 1e12).
+ *   6. After max_tries tries (every solve attempted counts, also the one that finds the small step) the loop ends CAP.
+ * NOT_REFINED (no error; refined = the input pose, or zero where has_pose is 0; both costs equal: the sum at the input pose, a NaN
+ * as 0x7ff8000000000000, 0 without a pose; tries = 0): has_pose = 0, fewer than 3 used rows, a used row with !(z > 0) at the start,
+ * a start cost that is not finite (a NaN or infinity in the pose, K or a used row). Rows that are not used are never read by the
+ * loop. A problem's outputs depend on its own rows only: not on its neighbours, the length of the list or its place in it.
+ *
+ * EACHAM_ERR_INVALID (checked on the host before anything is launched or written; the message names the problem): a negative
+ * size, an offset table that is null / does not start at 0 / decreases, a null required array, max_tries < 1, a NaN or negative
+ * threshold while inlier_mask or n_inliers is asked for. EACHAM_ERR_CAPACITY: more than 2^31 - 1 points in one call. */
+#define EACHAM_PNP_REFINE_CONVERGED 0
+#define EACHAM_PNP_REFINE_CAP 1          /* max_tries reached */
+#define EACHAM_PNP_REFINE_NOT_REFINED 2
+int eacham_pnp_refine_batch(eacham_ctx* ctx, int n_problems, const int64_t* point_ptr, const double* object_points,
+                            const double* image_points, const double* K, const double* poses, const uint8_t* has_pose,
+                            const uint8_t* use_mask, int max_tries, float threshold, double* refined, double* cost, int32_t* tries,
+                            int32_t* status, uint8_t* inlier_mask, int32_t* n_inliers);
+
 /* ---- P3P: the PnP RANSAC on its minimal sample ------------------------------------------------------------------------
  * What cv::solvePnPRansac(..., cv::SOLVEPNP_P3P) draws: FOUR indices per sample — three correspondences give up to four poses,
  * the fourth picks one. The refit of the winner's inliers stays EPnP (eacham_pnp_refit_batch, unchanged; from memory of OpenCV
