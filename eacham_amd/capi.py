@@ -133,6 +133,8 @@ def lib() -> C.CDLL:
         L.eacham_pnp_hypotheses_batch_p3p.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, f32, vp, vp, vp]
     if hasattr(L, "eacham_pnp_refine_batch"):  # (likewise)
         L.eacham_pnp_refine_batch.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, "eacham_triangulate_refine_tracks"):  # (likewise)
+        L.eacham_triangulate_refine_tracks.argtypes = [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, vp, vp, vp, vp]
     L.eacham_graph_best_pair.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     if hasattr(L, "eacham_graph_create"):
         L.eacham_graph_create.argtypes = [vp, i32, vp, i32, vp, vp, vp, vp, vp, C.POINTER(vp)]

@@ -391,6 +391,15 @@ class HipContext:
         from . import pnp
         return pnp.pnp_refine_batch(self, X, uv, K, poses, has_pose, use_masks, max_tries, threshold, want_recount)
 
+    def refine_tracks(self, transforms, track_ptr, obs_frame, obs_uv, K, points, has_point, use_mask=None, max_tries: int = 20,
+                      max_repr_error: float = 4.0, want_recount: bool = True):
+        """eacham_triangulate_refine_tracks: Levenberg-Marquardt on the reprojection error of one 3-D point per track over the
+        observations its mask names, the cameras fixed, and the recount at the refined point, for a list of tracks in one launch
+        (eacham_amd/triangulate.py)."""
+        from . import triangulate
+        return triangulate.refine_tracks(self, transforms, track_ptr, obs_frame, obs_uv, K, points, has_point, use_mask, max_tries,
+                                         max_repr_error, want_recount)
+
     def solve_p3p(self, X, uv, K, samples, want_candidates: bool = True):
         """eacham_solve_p3p: P3P on every row of `samples` (4 point indices per row: three solve, the fourth picks) (eacham_amd/pnp.py)."""
         from . import pnp

@@ -58,6 +58,80 @@ def triangulate_tracks(ctx: HipContext, transforms, track_ptr, obs_frame, obs_uv
     return points, status, masks
 
 
+REFINE_CONVERGED, REFINE_CAP, REFINE_NOT_REFINED = 0, 1, 2   # EACHAM_TRI_REFINE_*
+
+
+@dataclass
+class TrackRefine:
+    """What eacham_triangulate_refine_tracks returns for a list of n tracks."""
+    refined: np.ndarray            # [n, 3] float64 (the input point where status is NOT_REFINED; zeros without a point)
+    cost: np.ndarray               # [n, 2] float64: sum of squared pixels over the used observations before, after
+    tries: np.ndarray              # [n] int32
+    status: np.ndarray             # [n] int32: REFINE_CONVERGED, REFINE_CAP, REFINE_NOT_REFINED
+    masks: np.ndarray | None       # [n_obs] uint8: is_inlier at the refined point, every observation; None: not asked for
+    n_inliers: np.ndarray | None   # [n] int32
+
+
+_vp = lambda x: None if x is None else x.ctypes.data   # noqa: E731  (a raw call's array, or its NULL)
+_as = lambda x, dt: None if x is None else np.ascontiguousarray(x, dtype=dt)   # noqa: E731
+
+
+def refine_tracks_raw(ctx: HipContext, transforms, n_frames, n_tracks, track_ptr, obs_frame, obs_uv, K, points, has_point, use_mask=None,
+                      max_tries=20, max_repr_error=4.0, want_recount=True) -> TrackRefine:
+    """eacham_triangulate_refine_tracks on arrays already in its wire form (nothing is checked here: the library's own checks answer)."""
+    T, tp, of, uv = _as(transforms, np.float64), _as(track_ptr, np.int64), _as(obs_frame, np.uint32), _as(obs_uv, np.float64)
+    P3, has, use = _as(points, np.float64), _as(has_point, np.uint8), _as(use_mask, np.uint8)
+    K4 = None if K is None else _K4(K)
+    n = max(int(n_tracks), 0)
+    n_obs = max(int(tp[-1]), 0) if tp is not None and len(tp) and n > 0 else 0
+    if n_obs > 1 << 28:   # (a table the library is about to refuse: nothing that size is allocated for it)
+        n_obs = 0
+    refined, cost = np.zeros((n, 3), np.float64), np.zeros((n, 2), np.float64)
+    tries, status = np.zeros(n, np.int32), np.zeros(n, np.int32)
+    masks = np.zeros(n_obs, np.uint8) if want_recount else None
+    ni = np.zeros(n, np.int32) if want_recount else None
+    ctx._check(capi.lib().eacham_triangulate_refine_tracks(
+        ctx.handle, _vp(T), int(n_frames), int(n_tracks), _vp(tp), _vp(of), _vp(uv), _vp(K4), _vp(P3), _vp(has), _vp(use), int(max_tries),
+        float(max_repr_error), _vp(refined), _vp(cost), _vp(tries), _vp(status), _vp(masks), _vp(ni)))
+    return TrackRefine(refined, cost, tries, status, masks, ni)
+
+
+def refine_tracks(ctx: HipContext, transforms, track_ptr, obs_frame, obs_uv, K, points, has_point, use_mask=None, max_tries: int = 20,
+                  max_repr_error: float = 4.0, want_recount: bool = True) -> TrackRefine:
+    """Levenberg-Marquardt on the reprojection error of points[t] (has_point[t] = 0: none) over the observations of track t with a
+    non-zero byte in use_mask (one byte per observation; None: every observation), the cameras fixed, at most max_tries tries; then
+    the recount of triangulate_tracks' inlier predicate over all of the track's observations at the refined point. The layouts are
+    triangulate_tracks'; see include/eacham_hip.h."""
+    T = np.ascontiguousarray(transforms, dtype=np.float64).reshape(-1, 16)
+    tp = np.ascontiguousarray(track_ptr, dtype=np.int64).reshape(-1)
+    of = np.ascontiguousarray(obs_frame, dtype=np.uint32).reshape(-1)
+    uv = np.ascontiguousarray(obs_uv, dtype=np.float64).reshape(-1, 2)
+    n = tp.size - 1
+    if n < 0 or of.size != uv.shape[0] or int(tp[-1]) != of.size:
+        raise ValueError("track_ptr / observation arrays disagree")
+    P3 = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+    has = np.ascontiguousarray(has_point, dtype=np.uint8).reshape(-1)
+    if not (len(P3) == len(has) == n):
+        raise ValueError("one point and one has_point byte per track")
+    use = None
+    if use_mask is not None:
+        use = np.ascontiguousarray(use_mask, dtype=np.uint8).reshape(-1)
+        if use.size != of.size:
+            raise ValueError("one use byte per observation")
+    return refine_tracks_raw(ctx, T, T.shape[0], n, tp, of, uv, K, P3, has, use, max_tries, max_repr_error, want_recount)
+
+
+def triangulate_tracks_refined(ctx: HipContext, transforms, track_ptr, obs_frame, obs_uv, K, max_repr_error: float, min_tri_angle: float,
+                               max_tries: int = 20, want_recount: bool = True):
+    """triangulate_tracks, then refine_tracks on the tracks TriangulateFrame would add (status == STATUS_ADD) over their masks.
+    Returns (points, status, masks) exactly as triangulate_tracks gives them, and the TrackRefine (NOT_REFINED, a zero point and a
+    zero recount for every other track)."""
+    points, status, masks = triangulate_tracks(ctx, transforms, track_ptr, obs_frame, obs_uv, K, max_repr_error, min_tri_angle)
+    has = (status == STATUS_ADD).astype(np.uint8)
+    return points, status, masks, refine_tracks(ctx, transforms, track_ptr, obs_frame, obs_uv, K, points, has, masks, max_tries,
+                                                max_repr_error, want_recount)
+
+
 def TriangulatePointRansac(ctx: HipContext, data: list, maxReprError: float, minTriAngle: float):
     """One track; returns (ok, point3d, inliers) as the reference's (return, point3d&, inliers&)."""
     m = len(data)

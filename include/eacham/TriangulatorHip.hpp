@@ -67,6 +67,109 @@ inline bool TriangulatePointRansac(Context& ctx, const std::vector<EstimatorData
     return (status & 1) != 0;
 }
 
+// ---- the polish: Levenberg-Marquardt on a track's point over its inlier views (eacham_triangulate_refine_tracks; include/eacham_hip.h
+// states the loop) ----
+// TriangulatePointRansac / eacham_triangulate_tracks end on the two-view DLT point of the last pair tried, as the reference does; the
+// calls below add what COLMAP and OpenCV's sfm module add after it: the point that minimises the reprojection error over ALL of the
+// track's inlier views, the cameras held fixed, for a whole list of tracks in ONE device call. Opt-in: the functions above and
+// TriangulateFrame below, their defaults and their results are unchanged.
+
+// A list of tracks in the layout of eacham_triangulate_tracks (trackPtr: int64_t, as eacham_tracks_build writes it).
+struct TrackList {
+    std::vector<double> transforms;   // nFrames x 16, row-major world->camera
+    std::vector<int64_t> trackPtr;    // nTracks + 1 offsets into obsFrame / obsUv
+    std::vector<uint32_t> obsFrame;   // row of `transforms` per observation
+    std::vector<double> obsUv;        // pixel (x, y) per observation
+    int tracks() const { return trackPtr.empty() ? 0 : (int)trackPtr.size() - 1; }
+    int frames() const { return (int)(transforms.size() / 16); }
+};
+
+struct RefinedTracks {
+    std::vector<double> points;               // nTracks x 3 (the input point where status is NOT_REFINED; zero without a point)
+    std::vector<double> costBefore, costAfter;   // sum of squared pixel residuals over the used observations
+    std::vector<int32_t> tries, status;       // EACHAM_TRI_REFINE_CONVERGED / _CAP / _NOT_REFINED
+    std::vector<uint8_t> inliers;             // per observation: the inlier predicate of eacham_triangulate_tracks at the refined point
+    std::vector<int32_t> nInliers;
+};
+
+// points: nTracks x 3 starts, hasPoint: one byte per track, useMask: one byte per observation (empty: every observation is used).
+inline RefinedTracks RefineTrackPoints(Context& ctx, const TrackList& tl, const double* K, const std::vector<double>& points,
+                                       const std::vector<uint8_t>& hasPoint, const std::vector<uint8_t>& useMask, float maxReprError,
+                                       int maxTries = 20) {
+    const int n = tl.tracks();
+    const size_t nObs = tl.obsFrame.size();
+    if (points.size() != 3 * (size_t)n || hasPoint.size() != (size_t)n || tl.obsUv.size() != 2 * nObs ||
+        (n > 0 && (size_t)tl.trackPtr[n] != nObs) || (!useMask.empty() && useMask.size() != nObs))
+        throw std::runtime_error("RefineTrackPoints: array sizes disagree");
+    const double K4[4] = {K[0], K[4], K[2], K[5]};
+    RefinedTracks out;
+    out.points.assign(3 * (size_t)n, 0.0);
+    out.costBefore.assign(n, 0.0), out.costAfter.assign(n, 0.0);
+    out.tries.assign(n, 0), out.status.assign(n, EACHAM_TRI_REFINE_NOT_REFINED);
+    out.inliers.assign(nObs, 0), out.nInliers.assign(n, 0);
+    std::vector<double> cost(2 * (size_t)n + 2);
+    ctx.check(eacham_triangulate_refine_tracks(ctx.get(), tl.transforms.data(), tl.frames(), n, tl.trackPtr.data(), tl.obsFrame.data(),
+                                               tl.obsUv.data(), K4, points.data(), hasPoint.data(), useMask.empty() ? nullptr : useMask.data(),
+                                               maxTries, maxReprError, out.points.data(), cost.data(), out.tries.data(), out.status.data(),
+                                               out.inliers.data(), out.nInliers.data()));
+    for (int t = 0; t < n; ++t) out.costBefore[t] = cost[2 * (size_t)t], out.costAfter[t] = cost[2 * (size_t)t + 1];
+    return out;
+}
+
+// eacham_triangulate_tracks on the list, then ONE more device call: the polish of the tracks TriangulateFrame would add
+// (status == 3) over their inlier masks. points / status / masks are eacham_triangulate_tracks' own outputs, untouched.
+struct TriangulatedTracks {
+    std::vector<double> points;     // nTracks x 3: the point of the last pair tried
+    std::vector<int32_t> status;    // bit 0: TriangulatePointRansac's return, bit 1: every observation an inlier
+    std::vector<uint8_t> masks;     // per observation
+    RefinedTracks refined;          // NOT_REFINED, a zero point and a zero recount where status != 3
+};
+
+inline TriangulatedTracks TriangulateTracksRefined(Context& ctx, const TrackList& tl, const double* K, float maxReprError, float minTriAngle,
+                                                   int maxTries = 20) {
+    const int n = tl.tracks();
+    const size_t nObs = tl.obsFrame.size();
+    std::vector<int32_t> ptr32(tl.trackPtr.size());
+    for (size_t k = 0; k < ptr32.size(); ++k) {
+        if (tl.trackPtr[k] < 0 || tl.trackPtr[k] > INT32_MAX) throw std::runtime_error("TriangulateTracksRefined: track offset out of range");
+        ptr32[k] = (int32_t)tl.trackPtr[k];
+    }
+    if (ptr32.empty()) ptr32.push_back(0);
+    const double K4[4] = {K[0], K[4], K[2], K[5]};
+    TriangulatedTracks out;
+    out.points.assign(3 * (size_t)n, 0.0), out.status.assign(n, 0), out.masks.assign(nObs, 0);
+    if (n == 0) return out;
+    ctx.check(eacham_triangulate_tracks(ctx.get(), tl.transforms.data(), tl.frames(), n, ptr32.data(), tl.obsFrame.data(), tl.obsUv.data(), K4,
+                                        maxReprError, minTriAngle, out.points.data(), out.status.data(), out.masks.data()));
+    std::vector<uint8_t> has(n);
+    for (int t = 0; t < n; ++t) has[t] = out.status[t] == 3;
+    out.refined = RefineTrackPoints(ctx, tl, K, out.points, has, out.masks, maxReprError, maxTries);
+    return out;
+}
+
+// The polish for one track, beside TriangulatePointRansac: Levenberg-Marquardt from point3d over the observations `inliers` names
+// (empty: every observation). point3d is replaced by the refined point; returns the status (EACHAM_TRI_REFINE_*), and the costs
+// before and after when asked for.
+inline int RefinePoint(Context& ctx, const std::vector<EstimatorData>& data, const double* K, double* point3d, const std::vector<bool>& inliers,
+                       const float maxReprError, int maxTries = 20, double* costBefore = nullptr, double* costAfter = nullptr) {
+    const size_t m = data.size();
+    if (!inliers.empty() && inliers.size() != m) throw std::runtime_error("RefinePoint: one inlier flag per observation");
+    TrackList tl;
+    tl.trackPtr = {0, (int64_t)m};
+    std::vector<uint8_t> use;
+    for (size_t i = 0; i < m; ++i) {
+        tl.transforms.insert(tl.transforms.end(), data[i].transform, data[i].transform + 16);
+        tl.obsFrame.push_back((uint32_t)i);
+        tl.obsUv.push_back(data[i].point2d[0]), tl.obsUv.push_back(data[i].point2d[1]);
+        if (!inliers.empty()) use.push_back(inliers[i] ? 1 : 0);
+    }
+    const RefinedTracks r = RefineTrackPoints(ctx, tl, K, {point3d[0], point3d[1], point3d[2]}, {1}, use, maxReprError, maxTries);
+    for (int k = 0; k < 3; ++k) point3d[k] = r.points[k];
+    if (costBefore) *costBefore = r.costBefore[0];
+    if (costAfter) *costAfter = r.costAfter[0];
+    return r.status[0];
+}
+
 // ---- two-view structure for candidate relative poses --------------------------------------------
 // The per-match loops of ReconstructionManager::RecoverPoseTwoView
 // (/root/reference/modules/sfm/reconstruction/ReconstructionManager.cpp:118-143 over the solutions of

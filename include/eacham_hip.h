@@ -701,6 +701,59 @@ int eacham_pnp_refine_batch(eacham_ctx* ctx, int n_problems, const int64_t* poin
                             const uint8_t* use_mask, int max_tries, float threshold, double* refined, double* cost, int32_t* tries,
                             int32_t* status, uint8_t* inlier_mask, int32_t* n_inliers);
 
+/* ---- track point refinement for a whole list of tracks ---------------------------------------------------------------
+ * The non-linear step that COLMAP and OpenCV's sfm module run after triangulation, the counterpart of eacham_pnp_refine_batch with
+ * the roles swapped: where eacham_triangulate_tracks ends on the two-view DLT point of the LAST pair tried, this minimises the
+ * REPROJECTION error of a track's 3-D point over the observations the caller names, the cameras held fixed, by
+ * Levenberg-Marquardt, for n_tracks tracks in ONE launch with the whole loop on the device. Layouts as
+ * eacham_triangulate_tracks: transforms = n_frames row-major 4 x 4 world->camera matrices T, obs_frame = the row of `transforms`
+ * per observation, obs_uv = its pixel (u, v), K = fx fy cx cy; track t owns the observations track_ptr[t] .. track_ptr[t+1], and
+ * track_ptr is int64_t as eacham_tracks_build writes it. points: 3 doubles per track (the start), has_point: one byte per track.
+ * use_mask: one byte per observation (optional, NULL = every observation); the USED observations of a track are those with a
+ * non-zero byte (eacham_triangulate_tracks' masks serve as they are). max_repr_error (pixels) serves the recount only. Outputs per
+ * track: refined (3 doubles), cost (2 doubles: the sum of squared pixel residuals over the used observations before and after),
+ * tries, status; optional (NULL = not wanted, each on its own): inlier_mask (one byte per observation) and n_inliers, the recount
+ * over ALL of the track's observations at `refined` with the predicate of eacham_triangulate_tracks: the float reprojection error
+ * (float)sqrt(du du + dv dv) < max_repr_error and the depth >= DBL_EPSILON (all zero where has_point is 0).
+ *
+ * THE LOOP. fp64 throughout, only + - * /, every operation rounded on its own, every sum in the order written
+ * (tests/cpp/tri_refine_reference.c is the CPU restatement; the kernel gives its bytes):
+ *   1. An observation (T, (u, v)) at the point X:  x y z = T X (each ((T_i0 X0 + T_i1 X1) + T_i2 X2) + T_i3, i = 0, 1, 2),
+ *      iz = 1 / z,  xn = x iz,  yn = y iz,  r = ((fx xn + cx) - u, (fy yn + cy) - v). The derivative by X, with a = fx iz, b = fy iz:
+ *      Ju_j = a (T_0j - xn T_2j),  Jv_j = b (T_1j - yn T_2j),  j = 0, 1, 2.
+ *   2. Sums. 10 numbers: H = J'J (upper triangle, row by row, 6), g = J'r (3), cost = r'r. An observation adds
+ *      H_ij += (Ju_i Ju_j + Jv_i Jv_j), g_i += (Ju_i r_0 + Jv_i r_1), cost += (r_0 r_0 + r_1 r_1). THE ORDER: 8 partial sums start at
+ *      zero; partial l takes the used observations i of the track (i local to it, counted over all of its observations, used or
+ *      not) with i mod 8 = l, in ascending i; then the partials are folded in halves, s[l] += s[l + off] for l < off,
+ *      off = 4, 2, 1, and s[0] is the sum.
+ *   3. A try at damping lambda (1e-3 at the start): A = H with A_ii = H_ii + lambda H_ii; A = L D L' without pivoting (column by
+ *      column, each entry minus its products L_ik D_k L_jk in ascending k, then divided by the pivot); a pivot that is not > 0 fails
+ *      the try. Else L y = -g, z = y / D, L' d = z (back substitution, products subtracted in ascending k).
+ *   4. If max |d_k| <= 1e-10 (1 + max |X_k|) the loop ends CONVERGED (tested before the step is taken, whatever came before).
+ *      Else the candidate is X' = X + d, and step 2 at the candidate gives cost', H', g'.
+ *   5. The candidate is ACCEPTED iff no used observation has !(z > 0) at it and cost' < cost: the point, H, g and the cost become
+ *      the candidate's and lambda <- max(lambda / 10, 1e-12); if cost - cost' <= 1e-9 cost' the loop ends CONVERGED. A failed or
+ *      rejected try: lambda <- min(10 lambda, 1e12).
+ *   6. After max_tries tries (every solve attempted counts, also the one that finds the small step) the loop ends CAP.
+ * NOT_REFINED (no error; refined = the input point, or zero where has_point is 0; both costs equal: the sum at the input point, a
+ * NaN as 0x7ff8000000000000, 0 without a point; tries = 0): has_point = 0, fewer than 2 used observations, a used observation with
+ * !(z > 0) at the start, a start cost that is not finite (a NaN or infinity in the point, K, a used pixel or its transform).
+ * Observations that are not used are never read by the loop. A track's outputs depend on its own observations only: not on its
+ * neighbours, the length of the list or its place in it.
+ *
+ * EACHAM_ERR_INVALID (checked on the host before anything is launched or written; the message names the problem): a negative
+ * size, a track_ptr that is null / does not start at 0 / decreases, a null required array, max_tries < 1, an obs_frame entry
+ * >= n_frames (the message names the track), a NaN or negative max_repr_error while inlier_mask or n_inliers is asked for.
+ * EACHAM_ERR_CAPACITY: more than 2^31 - 1 observations in one call. */
+#define EACHAM_TRI_REFINE_CONVERGED 0
+#define EACHAM_TRI_REFINE_CAP 1          /* max_tries reached */
+#define EACHAM_TRI_REFINE_NOT_REFINED 2
+int eacham_triangulate_refine_tracks(eacham_ctx* ctx, const double* transforms, int n_frames, int n_tracks,
+                                     const int64_t* track_ptr, const uint32_t* obs_frame, const double* obs_uv, const double* K,
+                                     const double* points, const uint8_t* has_point, const uint8_t* use_mask, int max_tries,
+                                     float max_repr_error, double* refined, double* cost, int32_t* tries, int32_t* status,
+                                     uint8_t* inlier_mask, int32_t* n_inliers);
+
 /* ---- P3P: the PnP RANSAC on its minimal sample ------------------------------------------------------------------------
  * What cv::solvePnPRansac(..., cv::SOLVEPNP_P3P) draws: FOUR indices per sample — three correspondences give up to four poses,
  * the fourth picks one. The refit of the winner's inliers stays EPnP (eacham_pnp_refit_batch, unchanged; from memory of OpenCV
